@@ -14,8 +14,10 @@
  *  - `stream` is a hipStream_t (0 = default stream); every call is asynchronous on it.
  *  - activations are NDHWC ("channels last"): element (n,z,y,x,c) of a view lives at
  *    data[(((n*d + z)*h + y)*w + x)*ld + c]; ld >= c allows concat-by-offset views.
- *  - dtype: SEGMI_F32 (exact-f32 MFMA path, parity mode) or SEGMI_BF16 (bf16 storage,
- *    f32 accumulation).
+ *  - dtype: SEGMI_F32 (exact-f32 MFMA path, parity mode), SEGMI_BF16 (bf16 storage,
+ *    f32 accumulation) or SEGMI_F16 (IEEE fp16 storage, f32 accumulation).  Every entry point
+ *    that takes SEGMI_BF16 takes SEGMI_F16 with the same semantics and the same kernel family;
+ *    "bf16" below stands for either 16-bit format unless it says otherwise.
  */
 #ifndef SEGMI_H_
 #define SEGMI_H_
@@ -28,7 +30,7 @@ extern "C" {
 
 #define SEGMI_VERSION 1
 
-enum { SEGMI_F32 = 0, SEGMI_BF16 = 1 };
+enum { SEGMI_F32 = 0, SEGMI_BF16 = 1, SEGMI_F16 = 2 };
 enum { SEGMI_OK = 0, SEGMI_EINVAL = -1, SEGMI_EUNSUPPORTED = -2, SEGMI_ELAUNCH = -3 };
 
 /* NDHWC activation view */
@@ -369,6 +371,38 @@ int segmi_adabelief_step(float* param, const float* grad, float* exp_avg, float*
                          int64_t n, double lr, double beta1, double beta2, double eps,
                          double weight_decay, int weight_decouple, int64_t step,
                          float grad_scale, void* stream);
+
+/* ---------------------------------------------------------------- dynamic loss scaling - */
+/* fp16 training with torch.amp.GradScaler semantics, every piece of state in device memory (no host
+ * synchronisation per step).  amp: f32[3] = {scale, found_inf, skipped steps}; growth_tracker: int32[1]; step: int64[1],
+ * the optimiser's count of APPLIED updates (a skipped step does not advance it, as GradScaler skips
+ * optimizer.step()).  Per step: segmi_softmax_dice_bwd_amp (dlogits scaled by amp[0]) -> backward
+ * (+ gradient all-reduce) -> segmi_amp_check_finite over the whole f32 gradient arena -> a *_step_amp
+ * update -> segmi_amp_update_scale.
+ * segmi_amp_check_finite: amp[1] = 1 when any grad[i] is Inf or NaN (it never clears it).
+ * *_step_amp: as the plain updates with the gradient multiplied by grad_scale and by 1/amp[0] (formed in
+ *   double, rounded to f32 once), bias corrections / SGD's first-step rule from step[0] + 1; when amp[1] != 0
+ *   params and moments are left bit-untouched.
+ * segmi_amp_update_scale: torch._amp_update_scale_ (found_inf: scale *= backoff, tracker = 0; else
+ *   tracker + 1, and at growth_interval scale *= growth when that stays finite, tracker = 0); a skipped step
+ *   adds 1 to amp[2], an applied one adds 1 to step[0] (step nullable); then amp[1] = 0 for the next step. */
+int segmi_softmax_dice_bwd_amp(int dtype, const segmi_act* logits, const float* labels,
+                               const float* coef, const float* amp, const segmi_act* dlogits,
+                               float* scratch, float* bias_grad, void* stream);
+int segmi_amp_check_finite(const float* grad, int64_t n, float* amp, void* stream);
+int segmi_amp_update_scale(float* amp, int32_t* growth_tracker, int64_t* step, double growth_factor,
+                           double backoff_factor, int growth_interval, void* stream);
+int segmi_adam_step_amp(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                        float* max_exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
+                        double eps, double weight_decay, const float* amp, const int64_t* step,
+                        float grad_scale, void* stream);
+int segmi_sgd_step_amp(float* param, const float* grad, float* momentum_buf, int64_t n, double lr,
+                       double momentum, double weight_decay, const float* amp, const int64_t* step,
+                       float grad_scale, void* stream);
+int segmi_adabelief_step_amp(float* param, const float* grad, float* exp_avg, float* exp_avg_var,
+                             int64_t n, double lr, double beta1, double beta2, double eps,
+                             double weight_decay, int weight_decouple, const float* amp,
+                             const int64_t* step, float grad_scale, void* stream);
 
 /* ---------------------------------------------------------------- sliding window ------- */
 /* MONAI sliding_window_inference, monai_unet.py:354-356,637-639,665.

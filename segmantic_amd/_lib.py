@@ -18,6 +18,7 @@ import torch  # noqa: F401,E402
 
 SEGMI_F32 = 0
 SEGMI_BF16 = 1
+SEGMI_F16 = 2
 
 _LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libsegmi.so"
 
@@ -138,6 +139,12 @@ SIGNATURES = {
     "segmi_adam_step": (_i, [_P, _P, _P, _P, _P, _i64, _d, _d, _d, _d, _d, _i64, _f, _P]),
     "segmi_sgd_step": (_i, [_P, _P, _P, _i64, _d, _d, _d, _i, _f, _P]),
     "segmi_adabelief_step": (_i, [_P, _P, _P, _P, _i64, _d, _d, _d, _d, _d, _i, _i64, _f, _P]),
+    "segmi_softmax_dice_bwd_amp": (_i, [_i, _AP, _P, _P, _P, _AP, _P, _P, _P]),
+    "segmi_amp_check_finite": (_i, [_P, _i64, _P, _P]),
+    "segmi_amp_update_scale": (_i, [_P, _P, _P, _d, _d, _i, _P]),
+    "segmi_adam_step_amp": (_i, [_P, _P, _P, _P, _P, _i64, _d, _d, _d, _d, _d, _P, _P, _f, _P]),
+    "segmi_sgd_step_amp": (_i, [_P, _P, _P, _i64, _d, _d, _d, _P, _P, _f, _P]),
+    "segmi_adabelief_step_amp": (_i, [_P, _P, _P, _P, _i64, _d, _d, _d, _d, _d, _i, _P, _P, _f, _P]),
     "segmi_sw_gather": (_i, [_i, _AP, _i, _P, _i, _i, _AP, _P]),
     "segmi_sw_scatter_add": (_i, [_i, _AP, _P, _i, _P, _AP, _P, _P]),
     "segmi_sw_finalize": (_i, [_AP, _P, _i, _P, _i, _P]),

@@ -204,7 +204,7 @@ int segmi_warp_crop_patches(const segmi_act* image, const float* label, const in
                   "warp_crop_patches: bad arguments");
   SEGMI_CHECK_ARG(count > 0 && count <= kMaxCrops && out_image->n >= count && out_image->c == image->c,
                   "warp_crop_patches: 1..%d crops per call", kMaxCrops);
-  SEGMI_CHECK_ARG(dst_dtype == SEGMI_F32 || dst_dtype == SEGMI_BF16, "warp_crop_patches: bad dtype");
+  SEGMI_CHECK_ARG(dtype_ok(dst_dtype), "warp_crop_patches: bad dtype");
   WarpList wl{};
   wl.n = count;
   for (int i = 0; i < count; ++i) {
@@ -220,6 +220,10 @@ int segmi_warp_crop_patches(const segmi_act* image, const float* label, const in
   if (dst_dtype == SEGMI_F32)
     hipLaunchKernelGGL(warp_crop_kernel<float>, grid, 256, 0, st, (const float*)image->data, label, wl,
                        image->d, image->h, image->w, image->c, image->ld, (float*)out_image->data,
+                       out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
+  else if (dst_dtype == SEGMI_F16)
+    hipLaunchKernelGGL(warp_crop_kernel<f16_t>, grid, 256, 0, st, (const float*)image->data, label, wl,
+                       image->d, image->h, image->w, image->c, image->ld, (f16_t*)out_image->data,
                        out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
   else
     hipLaunchKernelGGL(warp_crop_kernel<bf16_t>, grid, 256, 0, st, (const float*)image->data, label, wl,

@@ -37,8 +37,10 @@ void set_error(const char* fmt, ...);
 
 // ------------------------------------------------------------------ types
 typedef unsigned short bf16_t;  // raw storage
+struct alignas(2) f16_t { unsigned short bits; };  // raw IEEE binary16 storage (a distinct type: never arithmetic)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -58,6 +60,53 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_cv));
 }
 
+// fp16: RNE conversions (fptrunc -> v_cvt_pk_f16_f32 / v_cvt_f16_f32, never the round-toward-zero
+// v_cvt_pkrtz), NaN and Inf kept, |x| > 65504 (after rounding) -> Inf, subnormals kept (no flush)
+typedef _Float16 f16x2_cv __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float f16_to_f32(f16_t v) {
+  return (float)__builtin_bit_cast(_Float16, v.bits);
+}
+__device__ __forceinline__ f16_t f32_to_f16(float f) {
+  return f16_t{__builtin_bit_cast(unsigned short, (_Float16)f)};
+}
+__device__ __forceinline__ unsigned pack_f16x2(float lo, float hi) {
+  const f32x2_cv f{lo, hi};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, f16x2_cv));
+}
+
+// The 16-bit storage formats on one interface, for the kernels that handle packed pairs themselves:
+// pack2 rounds two f32 into one dword (low half = first element), lo / hi widen one half back to f32.
+template <typename T> struct H16;
+template <> struct H16<bf16_t> {
+  static constexpr int dtype = SEGMI_BF16;
+  __device__ static __forceinline__ unsigned pack2(float lo, float hi) { return pack_bf16x2(lo, hi); }
+  __device__ static __forceinline__ float lo(unsigned u) { return __uint_as_float(u << 16); }
+  __device__ static __forceinline__ float hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
+};
+template <> struct H16<f16_t> {
+  static constexpr int dtype = SEGMI_F16;
+  __device__ static __forceinline__ unsigned pack2(float lo, float hi) { return pack_f16x2(lo, hi); }
+  __device__ static __forceinline__ float lo(unsigned u) {
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xffffu));
+  }
+  __device__ static __forceinline__ float hi(unsigned u) {
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16));
+  }
+};
+// raw bits of one 16-bit element
+__device__ __forceinline__ unsigned raw16(bf16_t v) { return v; }
+__device__ __forceinline__ unsigned raw16(f16_t v) { return v.bits; }
+
+// the type a kernel moves one element as when it only copies bits (f16_t: its raw 16 bits)
+template <typename T> struct RawOf { typedef T type; };
+template <> struct RawOf<f16_t> { typedef unsigned short type; };
+
+// SEGMI_* dtype of a storage type
+template <typename T> struct DtypeOf;
+template <> struct DtypeOf<float> { static constexpr int value = SEGMI_F32; };
+template <> struct DtypeOf<bf16_t> { static constexpr int value = SEGMI_BF16; };
+template <> struct DtypeOf<f16_t> { static constexpr int value = SEGMI_F16; };
+
 template <typename T> struct Elem;
 template <> struct Elem<float> {
   static constexpr int KG = 4;  // elements per 16-byte lane fragment
@@ -69,17 +118,25 @@ template <> struct Elem<bf16_t> {
   __device__ static float ld(const bf16_t* p) { return bf16_to_f32(*p); }
   __device__ static void st(bf16_t* p, float v) { *p = f32_to_bf16(v); }
 };
+template <> struct Elem<f16_t> {
+  static constexpr int KG = 8;
+  __device__ static float ld(const f16_t* p) { return f16_to_f32(*p); }
+  __device__ static void st(f16_t* p, float v) { *p = f32_to_f16(v); }
+};
 
 // 16-byte fragment, generic over dtype
 typedef u32x4 frag_t;
 
 // D[m][n] += sum_k A[m][k] B[k][n] with the 16-byte-per-lane k-slot convention of DESIGN.md:
-// bf16: one v_mfma_f32_16x16x32_bf16 (lane l holds k = 8*(l>>4)+j, j<8)
+// bf16: one v_mfma_f32_16x16x32_bf16 (lane l holds k = 8*(l>>4)+j, j<8); fp16: v_mfma_f32_16x16x32_f16, same slots
 // f32 : four v_mfma_f32_16x16x4_f32, MFMA j consuming element j (k-slot 4*(l>>4)+j)
 template <typename T> __device__ __forceinline__ f32x4 mma16(frag_t a, frag_t b, f32x4 c);
 template <> __device__ __forceinline__ f32x4 mma16<bf16_t>(frag_t a, frag_t b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
                                                  __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+template <> __device__ __forceinline__ f32x4 mma16<f16_t>(frag_t a, frag_t b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 template <> __device__ __forceinline__ f32x4 mma16<float>(frag_t a, frag_t b, f32x4 c) {
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[0]), __uint_as_float(b[0]), c, 0, 0, 0);
@@ -100,6 +157,12 @@ template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, f32x4 v) {
   o[1] = pack_bf16x2(v[2], v[3]);
   *reinterpret_cast<u32x2*>(p) = o;
 }
+template <> __device__ __forceinline__ void store4<f16_t>(f16_t* p, f32x4 v) {
+  u32x2 o;
+  o[0] = pack_f16x2(v[0], v[1]);
+  o[1] = pack_f16x2(v[2], v[3]);
+  *reinterpret_cast<u32x2*>(p) = o;
+}
 template <typename T> __device__ __forceinline__ f32x4 load4(const T* p);
 template <> __device__ __forceinline__ f32x4 load4<float>(const float* p) {
   return *reinterpret_cast<const f32x4*>(p);
@@ -112,6 +175,10 @@ template <> __device__ __forceinline__ f32x4 load4<bf16_t>(const bf16_t* p) {
   v[2] = __uint_as_float(o[1] << 16);
   v[3] = __uint_as_float(o[1] & 0xffff0000u);
   return v;
+}
+template <> __device__ __forceinline__ f32x4 load4<f16_t>(const f16_t* p) {
+  u32x2 o = *reinterpret_cast<const u32x2*>(p);
+  return f32x4{H16<f16_t>::lo(o[0]), H16<f16_t>::hi(o[0]), H16<f16_t>::lo(o[1]), H16<f16_t>::hi(o[1])};
 }
 
 // "Use" a value without emitting an instruction: the compiler must complete the load that
@@ -175,22 +242,23 @@ __device__ __forceinline__ f32x2 bn_bwd_apply_elem2g(f32x2 a, f32x2 d, f32x2 mea
   return gm_is * __builtin_elementwise_fma(-xh, c1, dz - c0);
 }
 
-// BatchNorm-apply + PReLU of the PRODUCER layer on 8 bf16 channels of one voxel, done while the
+// BatchNorm-apply + PReLU of the PRODUCER layer on 8 16-bit channels of one voxel, done while the
 // consumer stages its input (segmi_in_affine): z = fma(x, scale, shift); z = z > 0 ? z : alpha * z,
-// rounded to bf16 exactly as bn_act_fwd stores it, so a consumer that transforms on the fly sees
+// rounded to T exactly as bn_act_fwd stores it, so a consumer that transforms on the fly sees
 // the very bits the separate pass would have written.  sc / sh: the 8 channels of this 16-byte chunk.
-__device__ __forceinline__ frag_t bn_prelu_bf16x8(const frag_t raw, const float (&sc)[8], const float (&sh)[8],
-                                                  const float alpha, const bool has_alpha) {
+template <typename T>
+__device__ __forceinline__ frag_t bn_prelu_h8(const frag_t raw, const float (&sc)[8], const float (&sh)[8],
+                                              const float alpha, const bool has_alpha) {
   frag_t o;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    float z0 = fmaf(__uint_as_float(raw[q] << 16), sc[2 * q], sh[2 * q]);
-    float z1 = fmaf(__uint_as_float(raw[q] & 0xffff0000u), sc[2 * q + 1], sh[2 * q + 1]);
+    float z0 = fmaf(H16<T>::lo(raw[q]), sc[2 * q], sh[2 * q]);
+    float z1 = fmaf(H16<T>::hi(raw[q]), sc[2 * q + 1], sh[2 * q + 1]);
     if (has_alpha) {
       z0 = z0 > 0.f ? z0 : alpha * z0;
       z1 = z1 > 0.f ? z1 : alpha * z1;
     }
-    o[q] = pack_bf16x2(z0, z1);
+    o[q] = H16<T>::pack2(z0, z1);
   }
   return o;
 }
@@ -199,16 +267,17 @@ __device__ __forceinline__ frag_t bn_prelu_bf16x8(const frag_t raw, const float 
 // z > 0 ? z : alpha*z == max(z, alpha*z) bit for bit (signed zeros and NaN included), which is a
 // packed multiply and one max per element instead of multiply + compare + select.  Callers pick it
 // behind a wave-uniform branch.
-__device__ __forceinline__ frag_t bn_prelu01_bf16x8(const frag_t raw, const float (&sc)[8], const float (&sh)[8],
-                                                    const float alpha) {
+template <typename T>
+__device__ __forceinline__ frag_t bn_prelu01_h8(const frag_t raw, const float (&sc)[8], const float (&sh)[8],
+                                                const float alpha) {
   frag_t o;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const f32x2_cv x = {__uint_as_float(raw[q] << 16), __uint_as_float(raw[q] & 0xffff0000u)};
+    const f32x2_cv x = {H16<T>::lo(raw[q]), H16<T>::hi(raw[q])};
     const f32x2_cv s = {sc[2 * q], sc[2 * q + 1]}, h = {sh[2 * q], sh[2 * q + 1]};
     const f32x2_cv z = __builtin_elementwise_fma(x, s, h);       // one rounding per element, as fmaf
     const f32x2_cv az = z * alpha;
-    o[q] = pack_bf16x2(fmaxf(z[0], az[0]), fmaxf(z[1], az[1]));
+    o[q] = H16<T>::pack2(fmaxf(z[0], az[0]), fmaxf(z[1], az[1]));
   }
   return o;
 }
@@ -243,19 +312,22 @@ static inline bool act_ok(const segmi_act* a) {
          a->ld >= a->c;
 }
 static inline int dtype_size(int dtype) { return dtype == SEGMI_F32 ? 4 : 2; }
+static inline bool dtype_ok(int dtype) { return dtype == SEGMI_F32 || dtype == SEGMI_BF16 || dtype == SEGMI_F16; }
+// the 16-bit storage formats: every kernel family, fast path and shape gate treats them alike
+static inline bool dtype_h16(int dtype) { return dtype == SEGMI_BF16 || dtype == SEGMI_F16; }
 
 // ------------------------------------------------------------------ fragment-pack geometry
 // k-slot enumeration shared by the pack kernels and the MFMA kernels.
-//  KG   = elements per 16-byte fragment (8 bf16 / 4 f32)
+//  KG   = elements per 16-byte fragment (8 bf16 / fp16, 4 f32)
 //  CK   = channels staged per chunk (16 or 32); SPT = CK / KG slots per tap
 //  slot q = tap * SPT + sub ; k-step s covers slots 4s..4s+3, lane group g = lane>>4 owns 4s+g
 struct PackGeom {
   int KG, CK, SPT, ntaps, nslots, nsteps, nchunks, ntiles;
 };
 // f32 always stages 16 channels per chunk (64-B rows keep the halo tile within LDS);
-// bf16 stages 32 when the channel count allows it.
+// bf16 / fp16 stage 32 when the channel count allows it.
 static inline int pick_ck(int dtype, int cin) {
-  return (dtype == SEGMI_BF16 && cin % 32 == 0) ? 32 : 16;
+  return (dtype_h16(dtype) && cin % 32 == 0) ? 32 : 16;
 }
 static inline PackGeom pack_geom(int dtype, int cin, int cout, int ntaps) {
   PackGeom g;

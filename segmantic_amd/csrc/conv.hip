@@ -10,11 +10,23 @@
 namespace segmi {
 
 int conv_s2_bnbwd_bf16(const ConvBnBwdParams& p, hipStream_t st);
+int conv_s2_bnbwd_f16(const ConvBnBwdParams& p, hipStream_t st);
 
 int conv_mfma_f32(const ConvParams& p, int ksize, int stride, hipStream_t st);
 int conv_mfma_bf16(const ConvParams& p, int ksize, int stride, hipStream_t st);
+int conv_mfma_f16(const ConvParams& p, int ksize, int stride, hipStream_t st);
 int convt_mfma_f32(const ConvTParams& p, hipStream_t st);
 int convt_mfma_bf16(const ConvTParams& p, hipStream_t st);
+int convt_mfma_f16(const ConvTParams& p, hipStream_t st);
+// the MFMA families by storage format
+static inline int conv_mfma_dt(int dtype, const ConvParams& p, int ksize, int stride, hipStream_t st) {
+  if (dtype == SEGMI_F32) return conv_mfma_f32(p, ksize, stride, st);
+  return dtype == SEGMI_F16 ? conv_mfma_f16(p, ksize, stride, st) : conv_mfma_bf16(p, ksize, stride, st);
+}
+static inline int convt_mfma_dt(int dtype, const ConvTParams& p, hipStream_t st) {
+  if (dtype == SEGMI_F32) return convt_mfma_f32(p, st);
+  return dtype == SEGMI_F16 ? convt_mfma_f16(p, st) : convt_mfma_bf16(p, st);
+}
 int bn_stats_launch(int dtype, const segmi_act* x, float* partials, hipStream_t st, const BiasFin* bias_fin = nullptr);
 int bn_stats_rows_for(const segmi_act* x);
 int stats_reserve_rows();
@@ -163,7 +175,7 @@ int segmi_conv3d_stats_rows(int dtype, const segmi_act* in, const segmi_act* out
 int segmi_conv3d_pair_ok(int dtype, const segmi_act* in, const segmi_act* out_a,
                          const segmi_act* out_b) {
   if (!act_ok(in) || !act_ok(out_a) || !act_ok(out_b)) return 0;
-  if (dtype != SEGMI_F32 && dtype != SEGMI_BF16) return 0;
+  if (!dtype_ok(dtype)) return 0;
   return !mfma_ok(in->c, out_a->c) && small_fwd_eligible(dtype, in, out_a, 3) &&
          small_fwd_eligible(dtype, in, out_b, 3) && out_a->c == out_b->c && out_a->n == out_b->n &&
          out_a->d == out_b->d && out_a->h == out_b->h && out_a->w == out_b->w;
@@ -199,7 +211,7 @@ int segmi_conv3d_fwd_pair(int dtype, const segmi_act* in, const segmi_act* out_a
 
 int segmi_conv3d_split_act_ok(int dtype, const segmi_act* in, const segmi_act* out, int ksize,
                               int stride) {
-  if (!act_ok(in) || !act_ok(out) || (dtype != SEGMI_F32 && dtype != SEGMI_BF16)) return 0;
+  if (!act_ok(in) || !act_ok(out) || !dtype_ok(dtype)) return 0;
   // the tile kernel must take the layer (it is the one that honours act_tiles): k3 stride 2 MFMA
   return mfma_ok(in->c, out->c) && ksize == 3 && stride == 2 && !conv_ks_ok(dtype, in->c, ksize, stride) &&
          !conv_ring_ok(dtype, in->c, ksize, stride, out);
@@ -238,14 +250,14 @@ int segmi_conv3d_fwd_split_act(int dtype, const segmi_act* in, const segmi_act* 
     SEGMI_CHECK_ARG(!stats_fin, "conv3d_fwd_split_act: stats_fin needs stats_partials");
   }
   hipStream_t st = (hipStream_t)stream;
-  return dtype == SEGMI_F32 ? conv_mfma_f32(p, ksize, stride, st) : conv_mfma_bf16(p, ksize, stride, st);
+  return conv_mfma_dt(dtype, p, ksize, stride, st);
 }
 
 const char* segmi_conv3d_fwd_kernel_name(int dtype, const segmi_act* in, const segmi_act* out,
                                          int ksize, int stride) {
   static thread_local char buf[96];
   if (!act_ok(in) || !act_ok(out)) return "invalid";
-  const char* dt = dtype == SEGMI_BF16 ? "bf16" : "f32";
+  const char* dt = dtype == SEGMI_BF16 ? "bf16" : dtype == SEGMI_F16 ? "f16" : "f32";
   if (mfma_ok(in->c, out->c)) {
     const int ck = pick_ck(dtype, in->c);
     if (conv_ring_ok(dtype, in->c, ksize, stride, out)) {
@@ -269,14 +281,14 @@ const char* segmi_conv3d_fwd_kernel_name(int dtype, const segmi_act* in, const s
 
 int segmi_conv3d_in_affine_ok(int dtype, const segmi_act* in, const segmi_act* out, int ksize,
                               int stride) {
-  if (!act_ok(in) || !act_ok(out) || dtype != SEGMI_BF16 || !mfma_ok(in->c, out->c)) return 0;
-  // forward: the bf16 z-marching ring; weight gradient: the MFMA kernel (any channel blocking)
+  if (!act_ok(in) || !act_ok(out) || !dtype_h16(dtype) || !mfma_ok(in->c, out->c)) return 0;
+  // forward: the bf16 / fp16 z-marching ring; weight gradient: the MFMA kernel (any channel blocking)
   return ksize == 3 && stride == 1 && conv_ring_ok(dtype, in->c, ksize, stride, out) ? 1 : 0;
 }
 
 int segmi_conv3d_bn_bwd_sums_ok(int dtype, const segmi_act* in, const segmi_act* out, int ksize,
                                 int stride) {
-  if (!act_ok(in) || !act_ok(out) || dtype != SEGMI_BF16) return 0;
+  if (!act_ok(in) || !act_ok(out) || !dtype_h16(dtype)) return 0;
   // the ring kernels' MODE 4: 16 -> 16 (conv_ring3 / conv_ring2<bf16, 16, 1>) and 32 -> 32 (conv_ring2<bf16, 32, 2>)
   return ((in->c == 16 && out->c == 16) || (in->c == 32 && out->c == 32)) && ksize == 3 && stride == 1 &&
                  conv_ring_ok(dtype, in->c, ksize, stride, out) ? 1 : 0;
@@ -284,7 +296,7 @@ int segmi_conv3d_bn_bwd_sums_ok(int dtype, const segmi_act* in, const segmi_act*
 
 int segmi_bn_act_bwd_apply_conv_ok(int dtype, const segmi_act* dy, const segmi_act* x, const segmi_act* dx,
                                    const segmi_act* out) {
-  if (dtype != SEGMI_BF16 || !act_ok(dy) || !act_ok(x) || !act_ok(dx) || !act_ok(out)) return 0;
+  if (!dtype_h16(dtype) || !act_ok(dy) || !act_ok(x) || !act_ok(dx) || !act_ok(out)) return 0;
   const segmi_act* a3[3] = {dy, x, dx};
   for (const segmi_act* a : a3) {
     if (a->n != dy->n || a->d != dy->d || a->h != dy->h || a->w != dy->w || a->c != 16) return 0;
@@ -316,7 +328,7 @@ int segmi_bn_act_bwd_apply_conv(int dtype, const segmi_act* dy, const segmi_act*
   p.N = dy->n; p.Di = dy->d; p.Hi = dy->h; p.Wi = dy->w; p.Do = out->d; p.Ho = out->h; p.Wo = out->w;
   p.Cout = out->c; p.ldy = dy->ld; p.ldx = x->ld; p.lddx = dx->ld; p.ldo = out->ld;
   p.ntiles_total = out->c / 16;
-  return conv_s2_bnbwd_bf16(p, (hipStream_t)stream);
+  return dtype == SEGMI_F16 ? conv_s2_bnbwd_f16(p, (hipStream_t)stream) : conv_s2_bnbwd_bf16(p, (hipStream_t)stream);
 }
 
 int segmi_conv3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, const void* packed,
@@ -338,7 +350,7 @@ int segmi_conv3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, const
   if (in_tf)
     SEGMI_CHECK_ARG(in_tf->scale && in_tf->shift && segmi_conv3d_in_affine_ok(dtype, in, out, ksize, stride),
                     "conv3d: this layer cannot take an input transform (ask segmi_conv3d_in_affine_ok)");
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "conv3d: bad dtype %d", dtype);
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "conv3d: bad dtype %d", dtype);
   SEGMI_CHECK_ARG(act_ok(in) && act_ok(out), "conv3d: bad activation view");
   SEGMI_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2),
                   "conv3d: unsupported ksize/stride %d/%d", ksize, stride);
@@ -384,8 +396,7 @@ int segmi_conv3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, const
       }
     }
     if (stats_fin) { p.fin_on = 1; p.bfin = bn_fin_from(stats_fin, out->c); }
-    return dtype == SEGMI_F32 ? conv_mfma_f32(p, ksize, stride, st)
-                              : conv_mfma_bf16(p, ksize, stride, st);
+    return conv_mfma_dt(dtype, p, ksize, stride, st);
   }
   SEGMI_CHECK_ARG(w_src, "conv3d: direct path (channels not multiples of 16) needs w_src");
   SEGMI_CHECK_ARG(w_kind == 0 || w_kind == 1, "conv3d: bad w_kind %d", w_kind);
@@ -407,6 +418,7 @@ int segmi_conv3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, const
   const int64_t total = act_voxels(out) * out->c;
   int blocks = (int)(cdiv64(total, 256) > 8192 ? 8192 : cdiv64(total, 256));
   if (dtype == SEGMI_F32) hipLaunchKernelGGL(conv_direct_kernel<float>, blocks, 256, 0, st, p);
+  else if (dtype == SEGMI_F16) hipLaunchKernelGGL(conv_direct_kernel<f16_t>, blocks, 256, 0, st, p);
   else hipLaunchKernelGGL(conv_direct_kernel<bf16_t>, blocks, 256, 0, st, p);
   SEGMI_LAUNCH_CHECK("conv3d_fwd(direct)");
   if (stats_partials) {
@@ -432,7 +444,7 @@ int segmi_convT3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, cons
                       void* stream) {
   SEGMI_CHECK_ARG(!stats_fin || (stats_partials && bn_fin_ok(stats_fin)),
                   "convT3d: stats_fin needs stats_partials and its output pointers");
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "convT3d: bad dtype %d", dtype);
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "convT3d: bad dtype %d", dtype);
   SEGMI_CHECK_ARG(act_ok(in) && act_ok(out), "convT3d: bad activation view");
   SEGMI_CHECK_ARG(in->n == out->n, "convT3d: batch mismatch");
   const int di[3] = {in->d, in->h, in->w}, dout[3] = {out->d, out->h, out->w};
@@ -463,7 +475,7 @@ int segmi_convT3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, cons
     p.nchunks = in->c / pick_ck(dtype, in->c);
     p.ntiles_total = out->c / 16;
     if (stats_fin) { p.fin_on = 1; p.bfin = bn_fin_from(stats_fin, out->c); }
-    return dtype == SEGMI_F32 ? convt_mfma_f32(p, st) : convt_mfma_bf16(p, st);
+    return convt_mfma_dt(dtype, p, st);
   }
   SEGMI_CHECK_ARG(w_src, "convT3d: direct path (channels not multiples of 16) needs w_src");
   DirectParams p{};
@@ -475,6 +487,7 @@ int segmi_convT3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, cons
   const int64_t total = act_voxels(out) * out->c;
   int blocks = (int)(cdiv64(total, 256) > 8192 ? 8192 : cdiv64(total, 256));
   if (dtype == SEGMI_F32) hipLaunchKernelGGL(convt_direct_kernel<float>, blocks, 256, 0, st, p);
+  else if (dtype == SEGMI_F16) hipLaunchKernelGGL(convt_direct_kernel<f16_t>, blocks, 256, 0, st, p);
   else hipLaunchKernelGGL(convt_direct_kernel<bf16_t>, blocks, 256, 0, st, p);
   SEGMI_LAUNCH_CHECK("convT3d_fwd(direct)");
   if (stats_partials) {

@@ -34,9 +34,8 @@ struct ConvBnBwdParams {
   int tz, ty, tx, ntiles_total;
 };
 
-template <int NT>
+template <typename T, int NT>
 __global__ __launch_bounds__(256, 3) void conv_s2_bnbwd_kernel(ConvBnBwdParams p) {
-  using T = bf16_t;
   constexpr int S = 2, KS = 3, TD = 2, TH = 4, TW = 16;
   using G = ConvGeom<T, 16, KS, S, TD, TH, TW>;
   static_assert(G::SPT == 2 && G::ROWB == 32 && G::CPR == 2, "16 bf16 channels per voxel row");
@@ -125,10 +124,10 @@ __global__ __launch_bounds__(256, 3) void conv_s2_bnbwd_kernel(ConvBnBwdParams p
       frag_t val;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const f32x2 a{__uint_as_float(xx[k][q] << 16), __uint_as_float(xx[k][q] & 0xffff0000u)};
-        const f32x2 d{__uint_as_float(dz[k][q] << 16), __uint_as_float(dz[k][q] & 0xffff0000u)};
+        const f32x2 a{H16<T>::lo(xx[k][q]), H16<T>::hi(xx[k][q])};
+        const f32x2 d{H16<T>::lo(dz[k][q]), H16<T>::hi(dz[k][q])};
         const f32x2 o2 = bn_bwd_apply_elem2g<HA>(a, d, m2[q], i2[q], g2[q], b2[q], c02[q], c12[q], gi2[q], alpha);
-        val[q] = cd[k] >= 0 ? pack_bf16x2(o2[0], o2[1]) : 0u;      // zero padding stays zero
+        val[q] = cd[k] >= 0 ? H16<T>::pack2(o2[0], o2[1]) : 0u;      // zero padding stays zero
       }
       __builtin_amdgcn_raw_buffer_store_b128(val, rs_dx, ((cd[k] >= 0) & ((cd[k] & 1) != 0)) ? (cd[k] >> 1) * p.lddx * 2 : kOob, 0, 0);
       *reinterpret_cast<frag_t*>(smem + v * G::ROWB + half * 16) = val;
@@ -205,16 +204,16 @@ __global__ __launch_bounds__(256, 3) void conv_s2_bnbwd_kernel(ConvBnBwdParams p
   }
 }
 
-template <int NT>
+template <typename T, int NT>
 static int launch_conv_s2_bnbwd(ConvBnBwdParams p, hipStream_t st) {
-  using G = ConvGeom<bf16_t, 16, 3, 2, 2, 4, 16>;
+  using G = ConvGeom<T, 16, 3, 2, 2, 4, 16>;
   p.tz = cdiv(p.Do, 2);
   p.ty = cdiv(p.Ho, 4);
   p.tx = cdiv(p.Wo, 16);
   const int64_t nb = (int64_t)p.N * p.tz * p.ty * p.tx;
   SEGMI_CHECK_ARG(nb < (1ll << 31), "bn_act_bwd_apply_conv: too many tiles");
   static_assert(G::LDS_BYTES <= kBnBwdLds, "halo tile fits");
-  hipLaunchKernelGGL(conv_s2_bnbwd_kernel<NT>, dim3((unsigned)nb), 256, kBnBwdLds, st, p);
+  hipLaunchKernelGGL((conv_s2_bnbwd_kernel<T, NT>), dim3((unsigned)nb), 256, kBnBwdLds, st, p);
   SEGMI_LAUNCH_CHECK("bn_act_bwd_apply_conv");
   return SEGMI_OK;
 }

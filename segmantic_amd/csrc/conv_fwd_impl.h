@@ -371,7 +371,7 @@ static int launch_conv_nt(const ConvParams& p, hipStream_t st) {
 
 template <typename T>
 static int launch_conv_mfma_t(const ConvParams& p, int ksize, int stride, hipStream_t st) {
-  constexpr int dt = sizeof(T) == 4 ? SEGMI_F32 : SEGMI_BF16;
+  constexpr int dt = DtypeOf<T>::value;
   const int ck = pick_ck(dt, p.Cin);
   if constexpr (sizeof(T) == 2) {
     if (ck == 32) {

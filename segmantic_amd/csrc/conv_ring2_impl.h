@@ -42,7 +42,7 @@ namespace segmi {
 // BatchNorm, 3 both.
 template <typename T, int CK, int NT, int MODE>
 __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvParams p) {
-  static_assert(sizeof(T) == 2, "bf16 only");
+  static_assert(sizeof(T) == 2, "16-bit storage only");
   using G = RingGeom<T, CK>;
   constexpr int J = G::SPT == 2 ? 5 : 9;     // k-steps per kd
   constexpr int NIT = 6 * J;                 // (input plane, k-step) iterations per step
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
     float sc[8], sh[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { sc[e] = tfs[tf_ch + e]; sh[e] = tfs[CK + tf_ch + e]; }
-    return bn_prelu_bf16x8(v, sc, sh, in_alpha, in_act);
+    return bn_prelu_h8<T>(v, sc, sh, in_alpha, in_act);
   };
   const bool in_act01 = in_act && in_alpha >= 0.f && in_alpha <= 1.f;
   if (in_tf) __syncthreads();
@@ -380,9 +380,9 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
           *reinterpret_cast<f32x4*>(&sc[e]) = *reinterpret_cast<const f32x4*>(tb + tfo + e * 4);
           *reinterpret_cast<f32x4*>(&sh[e]) = *reinterpret_cast<const f32x4*>(tb + CK * 4 + tfo + e * 4);
         }
-        if (in_act01) commit([&](frag_t v) { return bn_prelu01_bf16x8(v, sc, sh, in_alpha); });
-        else if (in_act) commit([&](frag_t v) { return bn_prelu_bf16x8(v, sc, sh, in_alpha, true); });
-        else commit([&](frag_t v) { return bn_prelu_bf16x8(v, sc, sh, 0.f, false); });
+        if (in_act01) commit([&](frag_t v) { return bn_prelu01_h8<T>(v, sc, sh, in_alpha); });
+        else if (in_act) commit([&](frag_t v) { return bn_prelu_h8<T>(v, sc, sh, in_alpha, true); });
+        else commit([&](frag_t v) { return bn_prelu_h8<T>(v, sc, sh, 0.f, false); });
       }
     }
     // every staging register is dead from here on; say so on ALL control-flow paths (touch_v)
@@ -474,8 +474,8 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
           }
           if (resp) v += Raw4<T>::cvt(resv[rz][ro][jt]);
           u32x2 o;
-          o[0] = pack_bf16x2(v[0], v[1]);
-          o[1] = pack_bf16x2(v[2], v[3]);
+          o[0] = H16<T>::pack2(v[0], v[1]);
+          o[1] = H16<T>::pack2(v[2], v[3]);
           __builtin_amdgcn_raw_buffer_store_b64(o, rs_out, valid ? opoff + o_off[ro] + jt * 32 : kOob, 0, 0);
           if constexpr (BSUM) {
             // the sums are taken of the STORED gradient (bf16-rounded), as the separate pass reads it; lanes
@@ -568,7 +568,7 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
 template <typename T, int CK, int NT, int MODE>
 static int launch_conv_ring2_k(ConvParams p, hipStream_t st) {
   using G = RingGeom<T, CK>;
-  constexpr int dt = SEGMI_BF16;
+  constexpr int dt = DtypeOf<T>::value;
   p.tz = conv_ring_zsplit(dt, p.Cin, 3, 1, p.N, p.Do, p.Ho, p.Wo);
   static const int dbg = getenv("SEGMI_RING2_DBG") ? atoi(getenv("SEGMI_RING2_DBG")) : 0;
   p.dbg = dbg;
@@ -619,16 +619,17 @@ static int launch_conv_ring2_cfg(const ConvParams& p, hipStream_t st) {
   }
 }
 
-// bf16 ring layers: 16 -> 16*m and 32 -> 32*m
+// bf16 / fp16 ring layers: 16 -> 16*m and 32 -> 32*m
+template <typename T>
 static int launch_conv_ring2(const ConvParams& p, hipStream_t st) {
-  const int ck = pick_ck(SEGMI_BF16, p.Cin);
+  const int ck = pick_ck(DtypeOf<T>::value, p.Cin);
   const int nt = p.Cout / 16;
   if (ck == 32) {
     const bool sums = p.bpart && !p.alpha && !p.stats;
-    if (nt % 2 == 0 && !sums) return launch_conv_ring2_cfg<bf16_t, 32, 2>(p, st);
-    return launch_conv_ring2_cfg<bf16_t, 32, 1>(p, st);
+    if (nt % 2 == 0 && !sums) return launch_conv_ring2_cfg<T, 32, 2>(p, st);
+    return launch_conv_ring2_cfg<T, 32, 1>(p, st);
   }
-  return launch_conv_ring2_cfg<bf16_t, 16, 1>(p, st);
+  return launch_conv_ring2_cfg<T, 16, 1>(p, st);
 }
 
 }  // namespace segmi

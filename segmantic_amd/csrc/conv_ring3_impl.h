@@ -76,10 +76,9 @@ __device__ __forceinline__ void ring3_dma16(const __amdgpu_buffer_rsrc_t rs, uns
 
 // MODE as ring2: bit 0 = PReLU, bit 1 = BatchNorm statistics; 4 = plain + the BatchNorm-backward sums of the layer
 // the output gradient flows into (ConvParams::bpart).
-template <int MODE>
+template <typename T, int MODE>
 __global__ __launch_bounds__(256, 2) void conv_ring3_kernel(ConvParams p) {
   using G = Ring3Geom;
-  using T = bf16_t;
   constexpr int J = 5;                       // k-steps per kd (two taps per k-step, the 10th half-k-step is a zero weight)
   constexpr int NIT = 6 * J;
   constexpr unsigned kOob = 0x80000000u;     // + any soffset < 2^31: out of range, no 32-bit wrap
@@ -215,8 +214,8 @@ __global__ __launch_bounds__(256, 2) void conv_ring3_kernel(ConvParams p) {
         return keep ? a : (unsigned)(G::DUMP_OFF + tid * 16);
       });
     };
-    if (in_act01) with_dst([&](frag_t v) { return bn_prelu01_bf16x8(v, sc, sh, in_alpha); });
-    else with_dst([&](frag_t v) { return bn_prelu_bf16x8(v, sc, sh, in_alpha, in_act); });
+    if (in_act01) with_dst([&](frag_t v) { return bn_prelu01_h8<T>(v, sc, sh, in_alpha); });
+    else with_dst([&](frag_t v) { return bn_prelu_h8<T>(v, sc, sh, in_alpha, in_act); });
   };
 
   // ---- prologue: planes z0 - 1, z0 -> positions 2, 3 of group 2; planes z0 + 1 .. z0 + 4 -> group 0
@@ -250,7 +249,7 @@ __global__ __launch_bounds__(256, 2) void conv_ring3_kernel(ConvParams p) {
                         (unsigned)x < (unsigned)p.Wi;
         if (ok) {
           frag_t* q = reinterpret_cast<frag_t*>(smem + dst0 + 16u * i);
-          *q = bn_prelu_bf16x8(*q, sc, sh, in_alpha, in_act);
+          *q = bn_prelu_h8<T>(*q, sc, sh, in_alpha, in_act);
         }
       }
       transform_group(0u, p.Di - (z0 + 1));
@@ -318,7 +317,7 @@ __global__ __launch_bounds__(256, 2) void conv_ring3_kernel(ConvParams p) {
     // ---- the next group: planes z0 + zb + 5 .. + 8, straight into the ring
     if (more && !(p.dbg & 2)) dma_group(g_next, z0 + zb + 5);
     // residual rows of this step's outputs (external residual: the gradient sums of the backward chain)
-    typedef Raw4<T>::type raw4_t;
+    typedef typename Raw4<T>::type raw4_t;
     raw4_t resv[4][2];
     if (res_ext) {
 #pragma unroll
@@ -429,8 +428,8 @@ __global__ __launch_bounds__(256, 2) void conv_ring3_kernel(ConvParams p) {
         }
         if (resp) v += Raw4<T>::cvt(resv[zi][ro]);
         u32x2 o;
-        o[0] = pack_bf16x2(v[0], v[1]);
-        o[1] = pack_bf16x2(v[2], v[3]);
+        o[0] = H16<T>::pack2(v[0], v[1]);
+        o[1] = H16<T>::pack2(v[2], v[3]);
         __builtin_amdgcn_raw_buffer_store_b64(o, rs_out, (p.dbg & 4) ? kOob : o_off[ro], opoff, 0);
         if constexpr (BSUM) {
           // the sums are taken of the STORED gradient (bf16-rounded), as the separate pass reads it
@@ -507,10 +506,10 @@ static inline bool conv_ring3_ok(const ConvParams& p) {
   return conv_ring3_shape_ok(p.Cin, p.Cout, p.in, p.out, p.Di, p.Hi, p.Wi, p.ldi, p.Do, p.Ho, p.Wo, p.ldo, p.ldr, p.ldbx);
 }
 
-template <int MODE>
+template <typename T, int MODE>
 static int launch_conv_ring3_k(ConvParams p, hipStream_t st) {
   using G = Ring3Geom;
-  p.tz = conv_ring_zsplit(SEGMI_BF16, p.Cin, 3, 1, p.N, p.Do, p.Ho, p.Wo);
+  p.tz = conv_ring_zsplit(DtypeOf<T>::value, p.Cin, 3, 1, p.N, p.Do, p.Ho, p.Wo);
   // diagnostics (timing probes, WRONG results): SEGMI_RING3_DBG bits: 2 = no staging DMA in the step loop, 4 = stores
   // dropped, 8 = no MFMA loop, 16 = no input transform
   static const int dbg3 = getenv("SEGMI_RING3_DBG") ? atoi(getenv("SEGMI_RING3_DBG")) : 0;
@@ -530,7 +529,7 @@ static int launch_conv_ring3_k(ConvParams p, hipStream_t st) {
   constexpr bool kStats = (MODE & 2) != 0, kBsum = MODE == 4;
   p.fin_on = p.fin_on && (kStats || kBsum);
   (void)fin_tail_arm(p, grid, 256, (kBsum ? 3 : 2) * p.Cout, G::LDS_BYTES);   // LDS: the ring is larger than the tail's need
-  auto kern = conv_ring3_kernel<MODE>;
+  auto kern = conv_ring3_kernel<T, MODE>;
   static bool attr_done = false;
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -542,13 +541,14 @@ static int launch_conv_ring3_k(ConvParams p, hipStream_t st) {
   return SEGMI_OK;
 }
 
+template <typename T>
 static int launch_conv_ring3(const ConvParams& p, hipStream_t st) {
-  if (p.bpart && !p.alpha && !p.stats && p.Cout == 16) return launch_conv_ring3_k<4>(p, st);
+  if (p.bpart && !p.alpha && !p.stats && p.Cout == 16) return launch_conv_ring3_k<T, 4>(p, st);
   switch ((p.alpha ? 1 : 0) | (p.stats ? 2 : 0)) {
-    case 0: return launch_conv_ring3_k<0>(p, st);
-    case 1: return launch_conv_ring3_k<1>(p, st);
-    case 2: return launch_conv_ring3_k<2>(p, st);
-    default: return launch_conv_ring3_k<3>(p, st);
+    case 0: return launch_conv_ring3_k<T, 0>(p, st);
+    case 1: return launch_conv_ring3_k<T, 1>(p, st);
+    case 2: return launch_conv_ring3_k<T, 2>(p, st);
+    default: return launch_conv_ring3_k<T, 3>(p, st);
   }
 }
 

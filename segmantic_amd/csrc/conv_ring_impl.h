@@ -55,6 +55,13 @@ template <> struct Raw4<bf16_t> {
                  __uint_as_float(o[1] << 16), __uint_as_float(o[1] & 0xffff0000u)};
   }
 };
+template <> struct Raw4<f16_t> {
+  typedef u32x2 type;
+  __device__ static type ld(const f16_t* p) { return *reinterpret_cast<const u32x2*>(p); }
+  __device__ static f32x4 cvt(type o) {
+    return f32x4{H16<f16_t>::lo(o[0]), H16<f16_t>::hi(o[0]), H16<f16_t>::lo(o[1]), H16<f16_t>::hi(o[1])};
+  }
+};
 
 
 // Plan: columns = N * ceil(H/8) * ceil(W/16); each column is cut into `zsplit` z-segments so that
@@ -64,7 +71,7 @@ template <> struct Raw4<bf16_t> {
 static inline int conv_ring_zsplit(int dtype, int cin, int ksize, int stride, int N, int Do, int Ho,
                                    int Wo) {
   if (!(ksize == 3 && stride == 1 && cin == pick_ck(dtype, cin) && Wo > 8)) return 0;
-  if (dtype != SEGMI_BF16) return 0;
+  if (!dtype_h16(dtype)) return 0;
   // the kernel addresses one sample with 32-bit "plane index x plane size" products (bytes for the
   // input, elements for the others); rows may be strided views (ld up to 4 x cin in this engine: skip
   // buffers, padded class axis).  Larger samples take the tile / K-split kernels (64-bit addressing)

@@ -68,7 +68,8 @@ __global__ __launch_bounds__(256) void conv_small_fwd_kernel(SmallConvParams p) 
   constexpr int RPI = 256 / HW < HH ? 256 / HW : HH;   // rows staged per iteration (<= one row wrap)
   constexpr int NIT = (NROWS + RPI - 1) / RPI;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* xs = reinterpret_cast<T*>(smem);                  // [CIN][HD][HH][XW], halo x = 0 at column 3
+  typedef typename RawOf<T>::type R;                  // staging moves raw bits
+  R* xs = reinterpret_cast<R*>(smem);                  // [CIN][HD][HH][XW], halo x = 0 at column 3
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, r = lane & 15;
@@ -86,13 +87,13 @@ __global__ __launch_bounds__(256) void conv_small_fwd_kernel(SmallConvParams p) 
   // the halo rows with running (ci, hz, hy) counters and a running 32-bit element offset from the
   // wave-uniform tile origin; all loads are issued before the first LDS store.
   const bool win = p.nwin > 0;                         // (windows: single channel, ldi = 1)
-  const T* tile = win ? (const T*)p.in + p.woff[n] + (int64_t)iz0 * p.wsz + (int64_t)iy0 * p.wsy + ix0
-                      : (const T*)p.in + ((((int64_t)n * p.Di + iz0) * p.Hi + iy0) * p.Wi + ix0) * p.ldi;
+  const R* tile = win ? (const R*)p.in + p.woff[n] + (int64_t)iz0 * p.wsz + (int64_t)iy0 * p.wsy + ix0
+                      : (const R*)p.in + ((((int64_t)n * p.Di + iz0) * p.Hi + iy0) * p.Wi + ix0) * p.ldi;
   const int hx = tid % HW;
   const bool xlive = tid < RPI * HW && (unsigned)(ix0 + hx) < (unsigned)p.Wi;
-  T stg[NIT];
+  R stg[NIT];
 #pragma unroll
-  for (int k = 0; k < NIT; ++k) stg[k] = (T)0;
+  for (int k = 0; k < NIT; ++k) stg[k] = (R)0;
   // single-channel dense rows: the halo row [ix0 - 3, ix0 - 3 + XW) starts on a multiple of 4
   // elements (ix0 = TW*S*tx - 1, TW*S % 4 == 0), so it is XW/4 aligned 4-element loads -- 6 loads per
   // thread for the stride-2 first layer instead of 22 two-byte ones
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(256) void conv_small_fwd_kernel(SmallConvParams p) 
       // element group instead (always there, aligned) and drop it.
       const bool ok = (gi < NGRP) & ((unsigned)(iz0 + hz) < (unsigned)p.Di) & ((unsigned)(iy0 + hy) < (unsigned)p.Hi) &
                       ((unsigned)x0 < (unsigned)p.Wi);
-      const T* src = ok ? tile + hz * sz + hy * sy + (4 * gq - 3) : (const T*)p.in;
+      const R* src = ok ? tile + hz * sz + hy * sy + (4 * gq - 3) : (const R*)p.in;
       vstg[k] = *reinterpret_cast<const Vec4*>(src);      // (zeroed where !ok when it goes to LDS: no use of the value here)
       vok |= ok ? (1u << k) : 0u;
     }
@@ -129,9 +130,9 @@ __global__ __launch_bounds__(256) void conv_small_fwd_kernel(SmallConvParams p) 
     for (int k = 0; k < NIT; ++k) {
       {
         const bool ok = xlive & (row < NROWS) & ((unsigned)(iz0 + hz) < (unsigned)p.Di) & ((unsigned)(iy0 + hy) < (unsigned)p.Hi);
-        const T* src = ok ? tile + off : (const T*)p.in;          // (no branch around the load, as above)
-        const T got = *src;
-        stg[k] = ok ? got : (T)0;
+        const R* src = ok ? tile + off : (const R*)p.in;          // (no branch around the load, as above)
+        const R got = *src;
+        stg[k] = ok ? got : (R)0;
       }
       row += RPI;
       hy += RPI;
@@ -162,8 +163,8 @@ __global__ __launch_bounds__(256) void conv_small_fwd_kernel(SmallConvParams p) 
       lk[s][j] = lane_vox + (g == 0 ? o0 : g == 1 ? o1 : g == 2 ? o2 : o3);
     }
     if constexpr (ES == 2) {
-      wf[s] = frag_t{pack_bf16x2(wv[0], wv[1]), pack_bf16x2(wv[2], wv[3]), pack_bf16x2(wv[4], wv[5]),
-                     pack_bf16x2(wv[6], wv[7])};
+      wf[s] = frag_t{H16<T>::pack2(wv[0], wv[1]), H16<T>::pack2(wv[2], wv[3]), H16<T>::pack2(wv[4], wv[5]),
+                     H16<T>::pack2(wv[6], wv[7])};
     } else {
       wf[s] = frag_t{__float_as_uint(wv[0]), __float_as_uint(wv[1]), __float_as_uint(wv[2]),
                      __float_as_uint(wv[3])};
@@ -175,8 +176,8 @@ __global__ __launch_bounds__(256) void conv_small_fwd_kernel(SmallConvParams p) 
         wv[j] = k < 27 * CIN ? p.w2[(co0 + r) * 27 * CIN + k] : 0.f;
       }
       if constexpr (ES == 2) {
-        wf2[s] = frag_t{pack_bf16x2(wv[0], wv[1]), pack_bf16x2(wv[2], wv[3]), pack_bf16x2(wv[4], wv[5]),
-                        pack_bf16x2(wv[6], wv[7])};
+        wf2[s] = frag_t{H16<T>::pack2(wv[0], wv[1]), H16<T>::pack2(wv[2], wv[3]), H16<T>::pack2(wv[4], wv[5]),
+                        H16<T>::pack2(wv[6], wv[7])};
       } else {
         wf2[s] = frag_t{__float_as_uint(wv[0]), __float_as_uint(wv[1]), __float_as_uint(wv[2]),
                         __float_as_uint(wv[3])};
@@ -349,7 +350,8 @@ __global__ __launch_bounds__(256) void conv_small_wgrad_kernel(SmallWgradParams 
   static_assert(NV * YROWB / 16 % 256 == 0, "dY tile staging");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ysm = smem;                                        // [NV][16] T
-  T* xsm = reinterpret_cast<T*>(smem + NV * YROWB);         // [CIN][3][ROWS][16] T
+  typedef typename RawOf<T>::type R;                        // staging moves raw bits
+  R* xsm = reinterpret_cast<R*>(smem + NV * YROWB);         // [CIN][3][ROWS][16] T
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, i16 = lane & 15;
@@ -373,10 +375,10 @@ __global__ __launch_bounds__(256) void conv_small_wgrad_kernel(SmallWgradParams 
 #pragma unroll
   for (int nt = 0; nt < NTL; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const T* x = (const T*)p.x;
+  const R* x = (const R*)p.x;
   const char* yb = (const char*)p.dy;
   frag_t ry[NLY];
-  T rx[NLX];
+  R rx[NLX];
   auto fetch = [&](int tile) {
     int t = tile;
     const int txi = t % p.tx; t /= p.tx;
@@ -401,7 +403,7 @@ __global__ __launch_bounds__(256) void conv_small_wgrad_kernel(SmallWgradParams 
       const int ci = i % CIN, r = i / CIN;
       const int hx = r % HWX, hy = (r / HWX) % HH, hz = r / (HWX * HH);
       const int z = oz0 * S - 1 + hz, y = oy0 * S - 1 + hy, xx = ox0 * S - 1 + hx;
-      rx[k] = (T)0;
+      rx[k] = (R)0;
       if (i < NXE && (unsigned)z < (unsigned)p.Dx && (unsigned)y < (unsigned)p.Hx &&
           (unsigned)xx < (unsigned)p.Wx)
         rx[k] = x[((((int64_t)n * p.Dx + z) * p.Hx + y) * p.Wx + xx) * p.ldx + ci];
@@ -416,7 +418,7 @@ __global__ __launch_bounds__(256) void conv_small_wgrad_kernel(SmallWgradParams 
       if (i >= NXE) continue;
       const int ci = i % CIN, r = i / CIN;
       const int hx = r % HWX, row = r / HWX;
-      T* pr = xsm + (ci * 3 * ROWS + row) * 16;
+      R* pr = xsm + (ci * 3 * ROWS + row) * 16;
       // P[kw][vx] = halo[S*vx + kw]  <=>  hx = S*vx + kw
 #pragma unroll
       for (int kw = 0; kw < 3; ++kw) {
@@ -557,6 +559,9 @@ int conv_small_fwd(int dtype, const segmi_act* in, const segmi_act* out, const f
   if (dtype == SEGMI_F32)
     return stride == 2 ? launch_small_fwd_cin<float, 2>(p, in->c, st)
                        : launch_small_fwd_cin<float, 1>(p, in->c, st);
+  if (dtype == SEGMI_F16)
+    return stride == 2 ? launch_small_fwd_cin<f16_t, 2>(p, in->c, st)
+                       : launch_small_fwd_cin<f16_t, 1>(p, in->c, st);
   return stride == 2 ? launch_small_fwd_cin<bf16_t, 2>(p, in->c, st)
                      : launch_small_fwd_cin<bf16_t, 1>(p, in->c, st);
 }
@@ -607,6 +612,9 @@ int conv_small_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float* 
   if (dtype == SEGMI_F32)
     return stride == 2 ? launch_small_wgrad_cin<float, 2>(p, x->c, grid, st)
                        : launch_small_wgrad_cin<float, 1>(p, x->c, grid, st);
+  if (dtype == SEGMI_F16)
+    return stride == 2 ? launch_small_wgrad_cin<f16_t, 2>(p, x->c, grid, st)
+                       : launch_small_wgrad_cin<f16_t, 1>(p, x->c, grid, st);
   return stride == 2 ? launch_small_wgrad_cin<bf16_t, 2>(p, x->c, grid, st)
                      : launch_small_wgrad_cin<bf16_t, 1>(p, x->c, grid, st);
 }

@@ -366,7 +366,7 @@ static int launch_convt_nt(const ConvTParams& p, hipStream_t st) {
 
 template <typename T>
 static int launch_convt_mfma_t(ConvTParams p, hipStream_t st) {
-  constexpr int dt = sizeof(T) == 4 ? SEGMI_F32 : SEGMI_BF16;
+  constexpr int dt = DtypeOf<T>::value;
   const int ck = pick_ck(dt, p.Cin);
   const PackGeom g = pack_geom(dt, p.Cin, p.Cout, 1);
   int64_t off = 0;

@@ -34,7 +34,7 @@ static inline bool convt_ps_ok(int dtype, int cin, int cout, int wi) {
   const int ck = dtype == SEGMI_F32 ? 16 : 32;
   if (cin % ck || cout % 16 || wi < 16) return false;
   const int nch = cin / ck, nt = cout / 16;
-  return (nt == 1 && nch <= 2) || (nt == 2 && nch == 1 && dtype == SEGMI_BF16);
+  return (nt == 1 && nch <= 2) || (nt == 2 && nch == 1 && dtype_h16(dtype));
 }
 
 // partial-statistics rows the MFMA transposed-conv path writes (one per workgroup)
@@ -80,6 +80,20 @@ template <> struct Vec8<bf16_t> {
     u32x4 o;
     o[0] = pack_bf16x2(a[0], a[1]); o[1] = pack_bf16x2(a[2], a[3]);
     o[2] = pack_bf16x2(b[0], b[1]); o[3] = pack_bf16x2(b[2], b[3]);
+    *reinterpret_cast<u32x4*>(p) = o;
+  }
+};
+template <> struct Vec8<f16_t> {
+  __device__ static void load(const f16_t* p, f32x4& a, f32x4& b) {
+    using H = H16<f16_t>;
+    const u32x4 o = *reinterpret_cast<const u32x4*>(p);
+    a = f32x4{H::lo(o[0]), H::hi(o[0]), H::lo(o[1]), H::hi(o[1])};
+    b = f32x4{H::lo(o[2]), H::hi(o[2]), H::lo(o[3]), H::hi(o[3])};
+  }
+  __device__ static void store(f16_t* p, f32x4 a, f32x4 b) {
+    u32x4 o;
+    o[0] = pack_f16x2(a[0], a[1]); o[1] = pack_f16x2(a[2], a[3]);
+    o[2] = pack_f16x2(b[0], b[1]); o[3] = pack_f16x2(b[2], b[3]);
     *reinterpret_cast<u32x4*>(p) = o;
   }
 };

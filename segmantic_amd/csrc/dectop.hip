@@ -36,8 +36,8 @@
 namespace segmi {
 
 struct DecTopParams {
-  const void* in;       // [N, Dc, Hc, Wc, 32] bf16
-  void* out;            // [N, 2Dc, 2Hc, 2Wc, 16] bf16
+  const void* in;       // [N, Dc, Hc, Wc, 32] bf16 / fp16
+  void* out;            // [N, 2Dc, 2Hc, 2Wc, 16] bf16 / fp16
   const void* up_frag;  // [27][64][16 B]: tap (kd*3+kh)*3+kw, lane (g, co): W_T[ci = 8g .. 8g+7][co][tap] * bn_scale[co]
   const float* up_bias; // folded: b * bn_scale + bn_shift
   const float* up_alpha;
@@ -75,10 +75,9 @@ constexpr int NTILE = (NBASE + 15) / 16;    // 16-voxel tiles per coarse plane (
 // planes are 2c .. 2c + 3: the fine ring holds one plane more (11) and runs one plane ahead of round 2's.
 // Per step and producer wave: ~95 MFMAs, 28 neighbour reads, 28 emits of ~20 instructions (was: 121 MFMAs,
 // ~100 reads, 36 emits inside ~2000 instructions).
-template <bool A01>
+template <typename T, bool A01>
 __global__ __launch_bounds__(512, 1) void dectop_kernel(DecTopParams p) {
   using namespace dectop;
-  using T = bf16_t;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const catl = smem + OFF_CAT;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -218,8 +217,8 @@ __global__ __launch_bounds__(512, 1) void dectop_kernel(DecTopParams p) {
         }
         const bool keep = (pz ? zin1 : zin0) && (m & (16u << (py * 2 + px))) != 0;
         u32x2 o;
-        o[0] = keep ? pack_bf16x2(vv[0], vv[1]) : 0u;
-        o[1] = keep ? pack_bf16x2(vv[2], vv[3]) : 0u;
+        o[0] = keep ? H16<T>::pack2(vv[0], vv[1]) : 0u;
+        o[1] = keep ? H16<T>::pack2(vv[2], vv[3]) : 0u;
         const bool wr = (m & (1u << (py * 2 + px))) != 0;
         const int dst = wr ? (pz ? pl1 : pl0) + waddr + (py * HW + px) * ROWB : OFF_DUMP;
         *reinterpret_cast<u32x2*>(smem + dst) = o;
@@ -365,10 +364,26 @@ static inline int dectop_tz(int n, int Do, int Ho, int Wo) {
   return zs < 1 ? 1 : zs;
 }
 
+template <typename T>
+static int launch_dectop(const DecTopParams& p, unsigned grid, hipStream_t st) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dectop_kernel<T, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, dectop::LDS_BYTES);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dectop_kernel<T, false>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, dectop::LDS_BYTES);
+    attr_done = true;
+  }
+  if (p.alpha01) hipLaunchKernelGGL((dectop_kernel<T, true>), grid, 512, dectop::LDS_BYTES, st, p);
+  else hipLaunchKernelGGL((dectop_kernel<T, false>), grid, 512, dectop::LDS_BYTES, st, p);
+  SEGMI_LAUNCH_CHECK("dectop_fwd");
+  return SEGMI_OK;
+}
+
 extern "C" {
 
 int segmi_dectop_ok(int dtype, const segmi_act* in, const segmi_act* out) {
-  if (!act_ok(in) || !act_ok(out) || dtype != SEGMI_BF16) return 0;
+  if (!act_ok(in) || !act_ok(out) || !dtype_h16(dtype)) return 0;
   if (in->c != 32 || out->c != 16 || in->n != out->n) return 0;
   if (out->d != 2 * in->d || out->h != 2 * in->h || out->w != 2 * in->w) return 0;
   if (out->d % dectop::TD || out->h % dectop::TH || out->w % dectop::TW) return 0;
@@ -392,19 +407,9 @@ int segmi_dectop_fwd(int dtype, const segmi_act* in, const segmi_act* out, const
   static const int dbg = getenv("SEGMI_DECTOP_DBG") ? atoi(getenv("SEGMI_DECTOP_DBG")) : 0;
   p.dbg = dbg;
   p.alpha01 = up_alpha_in_unit_range ? 1 : 0;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dectop_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, dectop::LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dectop_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, dectop::LDS_BYTES);
-    attr_done = true;
-  }
   const unsigned grid = (unsigned)(p.N * p.ty * p.tx * p.tz);
-  if (p.alpha01) hipLaunchKernelGGL(dectop_kernel<true>, grid, 512, dectop::LDS_BYTES, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(dectop_kernel<false>, grid, 512, dectop::LDS_BYTES, (hipStream_t)stream, p);
-  SEGMI_LAUNCH_CHECK("dectop_fwd");
-  return SEGMI_OK;
+  if (dtype == SEGMI_F16) return launch_dectop<f16_t>(p, grid, (hipStream_t)stream);
+  return launch_dectop<bf16_t>(p, grid, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -61,6 +61,7 @@ struct DiceParams {
   int64_t vox;       // voxels per batch item
   int chunks;
   float grad_scale;
+  const float* amp;  // nullable: {scale, found_inf} in device memory; scale replaces grad_scale
   float* bias_part;  // [n * chunks][k] per-workgroup channel sums of the written gradient (nullable)
   // finalisation by the last workgroup of the launch (fin_tail.h): forward -> DiceFin over `partials`,
   // backward -> ChanSumFin over `bias_part`
@@ -91,8 +92,8 @@ __device__ __forceinline__ void load_logits(const T* p, int k, float (&v)[KMAX])
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            if (j + 2 * e < KMAX) v[j + 2 * e] = __uint_as_float(f[e] << 16);
-            if (j + 2 * e + 1 < KMAX) v[j + 2 * e + 1] = __uint_as_float(f[e] & 0xffff0000u);
+            if (j + 2 * e < KMAX) v[j + 2 * e] = H16<T>::lo(f[e]);
+            if (j + 2 * e + 1 < KMAX) v[j + 2 * e + 1] = H16<T>::hi(f[e]);
           }
         }
       }
@@ -215,6 +216,7 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(DiceParams p) {
   for (int j = 0; j < KMAX; ++j) gsum[j] = 0.f;
   const bool vec_in = logits_vec_ok<T>(lg, p.k, p.ld);
   const bool vec_out = (FULL || p.k % 4 == 0) && p.ldd % 4 == 0 && ((uintptr_t)dl % (4 * sizeof(T))) == 0;
+  const float grad_scale = p.amp ? p.amp[0] : p.grad_scale;
   for (int64_t v = v0 + tid; v < v1; v += 256) {
     float x[KMAX];
     if (vec_in) load_logits<T, KMAX, true>(lg + v * p.ld, FULL ? KMAX : p.k, x);
@@ -237,7 +239,7 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(DiceParams p) {
         if (FULL || j < p.k) {
           f32x4 g4;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) g4[e] = (j + e < KMAX) ? p.grad_scale * x[j + e] * (dp[j + e] - dot) : 0.f;
+          for (int e = 0; e < 4; ++e) g4[e] = (j + e < KMAX) ? grad_scale * x[j + e] * (dp[j + e] - dot) : 0.f;
           store4<T>(o + j, g4);
 #pragma unroll
           for (int e = 0; e < 4; ++e)
@@ -248,7 +250,7 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(DiceParams p) {
 #pragma unroll
       for (int j = 0; j < KMAX; ++j)
         if (FULL || j < p.k) {
-          const float gv = p.grad_scale * x[j] * (dp[j] - dot);
+          const float gv = grad_scale * x[j] * (dp[j] - dot);
           Elem<T>::st(o + j, gv);
           gsum[j] += gv;
         }
@@ -276,42 +278,75 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(DiceParams p) {
 }
 
 // ---------------------------------------------------------------- optimisers
+// one element of each update, shared by the plain kernels and the loss-scaled (_amp) ones
+__device__ __forceinline__ void adam_elem(int64_t i, float* __restrict__ p, const float* __restrict__ g,
+                                          float* __restrict__ m, float* __restrict__ v, float* __restrict__ vmax,
+                                          float omb1, float beta2, float omb2, float eps, float wd,
+                                          float step_size, float bc2_sqrt, float grad_scale) {
+  float gi = g[i] * grad_scale;
+  const float pi = p[i];
+  if (wd != 0.f) gi = fmaf(wd, pi, gi);
+  float mi = m[i];
+  mi = mi + omb1 * (gi - mi);                   // exp_avg.lerp_(grad, 1 - beta1)
+  float vi = v[i] * beta2;
+  vi = fmaf(omb2 * gi, gi, vi);                 // mul_(beta2).addcmul_(g, g, 1 - beta2)
+  m[i] = mi;
+  v[i] = vi;
+  float vv = vi;
+  if (vmax) { vv = fmaxf(vmax[i], vi); vmax[i] = vv; }
+  const float denom = sqrtf(vv) / bc2_sqrt + eps;
+  p[i] = pi - step_size * (mi / denom);
+}
+
+__device__ __forceinline__ void sgd_elem(int64_t i, float* __restrict__ p, const float* __restrict__ g,
+                                         float* __restrict__ buf, float lr, float momentum, float wd, int first,
+                                         float grad_scale) {
+  float gi = g[i] * grad_scale;
+  const float pi = p[i];
+  if (wd != 0.f) gi = fmaf(wd, pi, gi);
+  if (momentum != 0.f) {
+    const float b = first ? gi : fmaf(buf[i], momentum, gi);
+    buf[i] = b;
+    gi = b;
+  }
+  p[i] = pi - lr * gi;
+}
+
+__device__ __forceinline__ void adabelief_elem(int64_t i, float* __restrict__ p, const float* __restrict__ g,
+                                               float* __restrict__ m, float* __restrict__ s, float decay,
+                                               float beta1, float omb1, float beta2, float omb2, float eps,
+                                               float wd, int decouple, float step_size, float bc2_sqrt,
+                                               float grad_scale) {
+  float gi = g[i] * grad_scale;
+  float pi = p[i];
+  if (wd != 0.f) {
+    if (decouple) pi *= decay;             // p.mul_(1 - lr * weight_decay)
+    else gi = fmaf(wd, pi, gi);
+  }
+  const float mi = fmaf(omb1, gi, m[i] * beta1);     // mul_(beta1).add_(g, alpha=1 - beta1)
+  const float r = gi - mi;
+  float si = fmaf(omb2 * r, r, s[i] * beta2);        // mul_(beta2).addcmul_(r, r, value=1 - beta2)
+  si += eps;  // exp_avg_var.add_(eps) is in place in adabelief_pytorch
+  m[i] = mi;
+  s[i] = si;
+  const float denom = sqrtf(si) / bc2_sqrt + eps;
+  p[i] = pi - step_size * (mi / denom);
+}
+
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                             float* __restrict__ m, float* __restrict__ v,
                             float* __restrict__ vmax, int64_t n, float omb1, float beta2,
                             float omb2, float eps, float wd, float step_size, float bc2_sqrt,
                             float grad_scale) {
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float gi = g[i] * grad_scale;
-    const float pi = p[i];
-    if (wd != 0.f) gi = fmaf(wd, pi, gi);
-    float mi = m[i];
-    mi = mi + omb1 * (gi - mi);                   // exp_avg.lerp_(grad, 1 - beta1)
-    float vi = v[i] * beta2;
-    vi = fmaf(omb2 * gi, gi, vi);                 // mul_(beta2).addcmul_(g, g, 1 - beta2)
-    m[i] = mi;
-    v[i] = vi;
-    float vv = vi;
-    if (vmax) { vv = fmaxf(vmax[i], vi); vmax[i] = vv; }
-    const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    p[i] = pi - step_size * (mi / denom);
-  }
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    adam_elem(i, p, g, m, v, vmax, omb1, beta2, omb2, eps, wd, step_size, bc2_sqrt, grad_scale);
 }
 
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
                            float* __restrict__ buf, int64_t n, float lr, float momentum,
                            float wd, int first, float grad_scale) {
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float gi = g[i] * grad_scale;
-    const float pi = p[i];
-    if (wd != 0.f) gi = fmaf(wd, pi, gi);
-    if (momentum != 0.f) {
-      const float b = first ? gi : fmaf(buf[i], momentum, gi);
-      buf[i] = b;
-      gi = b;
-    }
-    p[i] = pi - lr * gi;
-  }
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    sgd_elem(i, p, g, buf, lr, momentum, wd, first, grad_scale);
 }
 
 __global__ void adabelief_kernel(float* __restrict__ p, const float* __restrict__ g,
@@ -319,22 +354,92 @@ __global__ void adabelief_kernel(float* __restrict__ p, const float* __restrict_
                                  float decay, float beta1, float omb1, float beta2,
                                  float omb2, float eps, float wd, int decouple,
                                  float step_size, float bc2_sqrt, float grad_scale) {
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float gi = g[i] * grad_scale;
-    float pi = p[i];
-    if (wd != 0.f) {
-      if (decouple) pi *= decay;             // p.mul_(1 - lr * weight_decay)
-      else gi = fmaf(wd, pi, gi);
-    }
-    const float mi = fmaf(omb1, gi, m[i] * beta1);     // mul_(beta1).add_(g, alpha=1 - beta1)
-    const float r = gi - mi;
-    float si = fmaf(omb2 * r, r, s[i] * beta2);        // mul_(beta2).addcmul_(r, r, value=1 - beta2)
-    si += eps;  // exp_avg_var.add_(eps) is in place in adabelief_pytorch
-    m[i] = mi;
-    s[i] = si;
-    const float denom = sqrtf(si) / bc2_sqrt + eps;
-    p[i] = pi - step_size * (mi / denom);
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    adabelief_elem(i, p, g, m, s, decay, beta1, omb1, beta2, omb2, eps, wd, decouple, step_size, bc2_sqrt,
+                   grad_scale);
+}
+
+// ---------------------------------------------------------------- dynamic loss scaling
+// amp = {scale, found_inf, skipped steps} in device memory (segmi.h).  The gated updates read found_inf and the optimiser's
+// count of applied steps there: a step with a non-finite gradient leaves every parameter and moment untouched
+// (torch's GradScaler skips optimizer.step()); otherwise the gradient is unscaled by 1/scale (formed in double and
+// rounded to f32 once, as GradScaler's inv_scale) on top of grad_scale, and the bias corrections use step + 1.
+__device__ __forceinline__ float amp_inv_scale(const float* amp) { return (float)(1.0 / (double)amp[0]); }
+
+__global__ void adam_amp_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                float* __restrict__ v, float* __restrict__ vmax, int64_t n, double lr,
+                                double beta1, double beta2, float eps, float wd, const float* __restrict__ amp,
+                                const int64_t* __restrict__ step, float grad_scale) {
+  if (amp[1] != 0.f) return;
+  const double t = (double)(*step + 1);
+  const float step_size = (float)(lr / (1.0 - pow(beta1, t)));
+  const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
+  const float gs = grad_scale * amp_inv_scale(amp);
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    adam_elem(i, p, g, m, v, vmax, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, wd, step_size,
+              bc2_sqrt, gs);
+}
+
+__global__ void sgd_amp_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                               int64_t n, float lr, float momentum, float wd, const float* __restrict__ amp,
+                               const int64_t* __restrict__ step, float grad_scale) {
+  if (amp[1] != 0.f) return;
+  const int first = *step == 0;
+  const float gs = grad_scale * amp_inv_scale(amp);
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    sgd_elem(i, p, g, buf, lr, momentum, wd, first, gs);
+}
+
+__global__ void adabelief_amp_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                     float* __restrict__ s, int64_t n, double lr, double beta1, double beta2,
+                                     float eps, double wd, int decouple, const float* __restrict__ amp,
+                                     const int64_t* __restrict__ step, float grad_scale) {
+  if (amp[1] != 0.f) return;
+  const double t = (double)(*step + 1);
+  const float step_size = (float)(lr / (1.0 - pow(beta1, t)));
+  const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
+  const float gs = grad_scale * amp_inv_scale(amp);
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    adabelief_elem(i, p, g, m, s, (float)(1.0 - lr * wd), (float)beta1, (float)(1.0 - beta1), (float)beta2,
+                   (float)(1.0 - beta2), eps, (float)wd, decouple, step_size, bc2_sqrt, gs);
+}
+
+// found_inf |= any non-finite element of g (never cleared here: segmi_amp_update_scale clears it)
+__global__ __launch_bounds__(256) void amp_check_kernel(const float* __restrict__ g, int64_t n, float* amp) {
+  bool bad = false;
+  const int64_t n4 = ((uintptr_t)g % 16) == 0 ? n / 4 : 0;
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const f32x4 v = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bad |= (__float_as_uint(v[e]) & 0x7f800000u) == 0x7f800000u;
   }
+  for (int64_t i = 4 * n4 + blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    bad |= (__float_as_uint(g[i]) & 0x7f800000u) == 0x7f800000u;
+  if (__syncthreads_or(bad) && threadIdx.x == 0) amp[1] = 1.f;
+}
+
+// torch._amp_update_scale_ on {scale, found_inf} + growth tracker; a skipped step is counted in amp[2]; when the step
+// was applied, the optimiser's step count advances; found_inf is cleared for the next step
+__global__ void amp_update_kernel(float* amp, int32_t* tracker, int64_t* step, float growth, float backoff,
+                                  int interval) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float scale = amp[0];
+  if (amp[1] != 0.f) {
+    amp[0] = scale * backoff;
+    *tracker = 0;
+    amp[2] += 1.f;
+  } else {
+    const int successful = *tracker + 1;
+    if (successful >= interval) {
+      const float grown = scale * growth;
+      if (__builtin_isfinite(grown)) amp[0] = grown;
+      *tracker = 0;
+    } else {
+      *tracker = successful;
+    }
+    if (step) *step += 1;
+  }
+  amp[1] = 0.f;
 }
 
 static inline int opt_blocks(int64_t n) {
@@ -365,6 +470,10 @@ static int dice_dispatch(bool fwd, const DiceParams& p, hipStream_t st) {
   SEGMI_LAUNCH_CHECK("softmax_dice");
   return SEGMI_OK;
 }
+static int dice_dispatch_dt(int dtype, bool fwd, const DiceParams& p, hipStream_t st) {
+  if (dtype == SEGMI_F32) return dice_dispatch<float>(fwd, p, st);
+  return dtype == SEGMI_F16 ? dice_dispatch<f16_t>(fwd, p, st) : dice_dispatch<bf16_t>(fwd, p, st);
+}
 
 }  // namespace segmi
 
@@ -386,7 +495,7 @@ int segmi_dice_chunks(const segmi_act* logits) {
 int segmi_softmax_dice_fwd(int dtype, const segmi_act* logits, const float* labels,
                            float* partials, float* coef, float* loss, float smooth_nr,
                            float smooth_dr, void* stream) {
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "softmax_dice_fwd: bad dtype");
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_dice_fwd: bad dtype");
   SEGMI_CHECK_ARG(act_ok(logits) && labels && partials && coef && loss, "softmax_dice_fwd: bad arguments");
   DiceParams p{};
   p.logits = logits->data; p.labels = labels; p.partials = partials;
@@ -398,13 +507,12 @@ int segmi_softmax_dice_fwd(int dtype, const segmi_act* logits, const float* labe
   // (fin_tail.h): rows = chunks, one row = [n][3][k]
   p.ft = fin_tail_make(p.chunks, p.n * 3 * p.k, (unsigned)p.chunks * (unsigned)p.n);
   p.dfin = DiceFin{p.n, p.k, smooth_nr, smooth_dr, coef, loss};
-  return dtype == SEGMI_F32 ? dice_dispatch<float>(true, p, st) : dice_dispatch<bf16_t>(true, p, st);
+  return dice_dispatch_dt(dtype, true, p, st);
 }
 
-int segmi_softmax_dice_bwd(int dtype, const segmi_act* logits, const float* labels,
-                           const float* coef, float grad_scale, const segmi_act* dlogits,
-                           float* scratch, float* bias_grad, void* stream) {
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "softmax_dice_bwd: bad dtype");
+static int dice_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef, float grad_scale,
+                    const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad, void* stream) {
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_dice_bwd: bad dtype");
   SEGMI_CHECK_ARG(act_ok(logits) && act_ok(dlogits) && labels && coef &&
                       logits->n == dlogits->n && logits->d == dlogits->d &&
                       logits->h == dlogits->h && logits->w == dlogits->w &&
@@ -415,6 +523,7 @@ int segmi_softmax_dice_bwd(int dtype, const segmi_act* logits, const float* labe
   p.vox = (int64_t)logits->d * logits->h * logits->w;
   p.chunks = dice_real_chunks(logits);
   p.grad_scale = grad_scale;
+  p.amp = amp;
   SEGMI_CHECK_ARG(!bias_grad || scratch, "softmax_dice_bwd: bias_grad needs the scratch buffer");
   p.bias_part = bias_grad ? scratch : nullptr;
   hipStream_t st = (hipStream_t)stream;
@@ -422,7 +531,20 @@ int segmi_softmax_dice_bwd(int dtype, const segmi_act* logits, const float* labe
     p.ft = fin_tail_make(p.n * p.chunks, p.k, (unsigned)p.chunks * (unsigned)p.n);
     p.cfin = ChanSumFin{p.k, bias_grad};
   }
-  return dtype == SEGMI_F32 ? dice_dispatch<float>(false, p, st) : dice_dispatch<bf16_t>(false, p, st);
+  return dice_dispatch_dt(dtype, false, p, st);
+}
+
+int segmi_softmax_dice_bwd(int dtype, const segmi_act* logits, const float* labels,
+                           const float* coef, float grad_scale, const segmi_act* dlogits,
+                           float* scratch, float* bias_grad, void* stream) {
+  return dice_bwd(dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
+}
+
+int segmi_softmax_dice_bwd_amp(int dtype, const segmi_act* logits, const float* labels,
+                               const float* coef, const float* amp, const segmi_act* dlogits,
+                               float* scratch, float* bias_grad, void* stream) {
+  SEGMI_CHECK_ARG(amp, "softmax_dice_bwd_amp: amp state missing");
+  return dice_bwd(dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
 }
 
 int segmi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
@@ -466,6 +588,57 @@ int segmi_adabelief_step(float* param, const float* grad, float* exp_avg, float*
                      (float)weight_decay, weight_decouple, (float)(lr / bc1), (float)sqrt(bc2),
                      grad_scale);
   SEGMI_LAUNCH_CHECK("adabelief");
+  return SEGMI_OK;
+}
+
+int segmi_amp_check_finite(const float* grad, int64_t n, float* amp, void* stream) {
+  SEGMI_CHECK_ARG(grad && amp && n > 0, "amp_check_finite: bad arguments");
+  hipLaunchKernelGGL(amp_check_kernel, opt_blocks(n), 256, 0, (hipStream_t)stream, grad, n, amp);
+  SEGMI_LAUNCH_CHECK("amp_check_finite");
+  return SEGMI_OK;
+}
+
+int segmi_amp_update_scale(float* amp, int32_t* growth_tracker, int64_t* step, double growth_factor,
+                           double backoff_factor, int growth_interval, void* stream) {
+  SEGMI_CHECK_ARG(amp && growth_tracker && growth_interval > 0, "amp_update_scale: bad arguments");
+  hipLaunchKernelGGL(amp_update_kernel, 1, 64, 0, (hipStream_t)stream, amp, growth_tracker, step,
+                     (float)growth_factor, (float)backoff_factor, growth_interval);
+  SEGMI_LAUNCH_CHECK("amp_update_scale");
+  return SEGMI_OK;
+}
+
+int segmi_adam_step_amp(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                        float* max_exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
+                        double eps, double weight_decay, const float* amp, const int64_t* step,
+                        float grad_scale, void* stream) {
+  SEGMI_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n > 0 && amp && step, "adam_amp: bad arguments");
+  hipLaunchKernelGGL(adam_amp_kernel, opt_blocks(n), 256, 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, max_exp_avg_sq, n, lr, beta1, beta2, (float)eps, (float)weight_decay, amp, step,
+                     grad_scale);
+  SEGMI_LAUNCH_CHECK("adam_amp");
+  return SEGMI_OK;
+}
+
+int segmi_sgd_step_amp(float* param, const float* grad, float* momentum_buf, int64_t n, double lr,
+                       double momentum, double weight_decay, const float* amp, const int64_t* step,
+                       float grad_scale, void* stream) {
+  SEGMI_CHECK_ARG(param && grad && n > 0 && (momentum == 0.0 || momentum_buf) && amp && step,
+                  "sgd_amp: bad arguments");
+  hipLaunchKernelGGL(sgd_amp_kernel, opt_blocks(n), 256, 0, (hipStream_t)stream, param, grad, momentum_buf, n,
+                     (float)lr, (float)momentum, (float)weight_decay, amp, step, grad_scale);
+  SEGMI_LAUNCH_CHECK("sgd_amp");
+  return SEGMI_OK;
+}
+
+int segmi_adabelief_step_amp(float* param, const float* grad, float* exp_avg, float* exp_avg_var,
+                             int64_t n, double lr, double beta1, double beta2, double eps,
+                             double weight_decay, int weight_decouple, const float* amp,
+                             const int64_t* step, float grad_scale, void* stream) {
+  SEGMI_CHECK_ARG(param && grad && exp_avg && exp_avg_var && n > 0 && amp && step, "adabelief_amp: bad arguments");
+  hipLaunchKernelGGL(adabelief_amp_kernel, opt_blocks(n), 256, 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_var, n, lr, beta1, beta2, (float)eps, weight_decay, weight_decouple, amp, step,
+                     grad_scale);
+  SEGMI_LAUNCH_CHECK("adabelief_amp");
   return SEGMI_OK;
 }
 

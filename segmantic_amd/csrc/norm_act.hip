@@ -162,12 +162,15 @@ int bn_stats_launch(int dtype, const segmi_act* x, float* partials, hipStream_t 
   }
   if (v4) {
     if (dtype == SEGMI_F32) hipLaunchKernelGGL((bn_stats_kernel<float, 4>), rows, 256, lds, st, p);
+    else if (dtype == SEGMI_F16) hipLaunchKernelGGL((bn_stats_kernel<f16_t, 4>), rows, 256, lds, st, p);
     else hipLaunchKernelGGL((bn_stats_kernel<bf16_t, 4>), rows, 256, lds, st, p);
   } else if (x->c <= 256) {
     if (dtype == SEGMI_F32) hipLaunchKernelGGL((bn_stats_kernel<float, 1>), rows, 256, lds, st, p);
+    else if (dtype == SEGMI_F16) hipLaunchKernelGGL((bn_stats_kernel<f16_t, 1>), rows, 256, lds, st, p);
     else hipLaunchKernelGGL((bn_stats_kernel<bf16_t, 1>), rows, 256, lds, st, p);
   } else {
     if (dtype == SEGMI_F32) hipLaunchKernelGGL(bn_stats_wide_kernel<float>, rows, 256, 0, st, p);
+    else if (dtype == SEGMI_F16) hipLaunchKernelGGL(bn_stats_wide_kernel<f16_t>, rows, 256, 0, st, p);
     else hipLaunchKernelGGL(bn_stats_wide_kernel<bf16_t>, rows, 256, 0, st, p);
   }
   SEGMI_LAUNCH_CHECK("bn_stats");
@@ -637,6 +640,9 @@ using namespace segmi;
     if (dtype == SEGMI_F32) {                                                                 \
       if (v4) hipLaunchKernelGGL((KERN<float, 4>), grid, 256, lds, st, p);                    \
       else hipLaunchKernelGGL((KERN<float, 1>), grid, 256, lds, st, p);                       \
+    } else if (dtype == SEGMI_F16) {                                                          \
+      if (v4) hipLaunchKernelGGL((KERN<f16_t, 4>), grid, 256, lds, st, p);                    \
+      else hipLaunchKernelGGL((KERN<f16_t, 1>), grid, 256, lds, st, p);                       \
     } else {                                                                                  \
       if (v4) hipLaunchKernelGGL((KERN<bf16_t, 4>), grid, 256, lds, st, p);                   \
       else hipLaunchKernelGGL((KERN<bf16_t, 1>), grid, 256, lds, st, p);                      \
@@ -648,7 +654,7 @@ extern "C" {
 int segmi_bn_stats_rows(const segmi_act* x) { return x ? bn_stats_rows_for(x) + kReserveRows : 0; }
 
 int segmi_bn_stats(int dtype, const segmi_act* x, float* stats_partials, void* stream) {
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "bn_stats: bad dtype");
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "bn_stats: bad dtype");
   SEGMI_CHECK_ARG(act_ok(x) && stats_partials, "bn_stats: bad arguments");
   return bn_stats_launch(dtype, x, stats_partials, (hipStream_t)stream, nullptr);
 }
@@ -681,7 +687,7 @@ int segmi_bn_eval_affine(int c, const float* gamma, const float* beta,
 int segmi_bn_act_fwd(int dtype, const segmi_act* x, const segmi_act* y, const float* scale,
                      const float* shift, const float* prelu_alpha, const segmi_act* residual,
                      float dropout_p, uint32_t dropout_seed, void* stream) {
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "bn_act_fwd: bad dtype");
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "bn_act_fwd: bad dtype");
   SEGMI_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "bn_act_fwd: dropout_p must be in [0, 1)");
   SEGMI_CHECK_ARG(act_ok(x) && act_ok(y) && same_shape(x, y), "bn_act_fwd: shape mismatch");
   if (residual) SEGMI_CHECK_ARG(act_ok(residual) && same_shape(x, residual), "bn_act_fwd: residual shape");
@@ -712,7 +718,7 @@ int segmi_bn_act_bwd_reduce(int dtype, const segmi_act* dy, const segmi_act* x,
                             float dropout_p, uint32_t dropout_seed, const segmi_bn_bwd_fin* fin,
                             void* stream) {
   SEGMI_CHECK_ARG(!fin || (fin->count > 0 && fin->coef), "bn_act_bwd_reduce: fin needs count and coef");
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "bn_act_bwd_reduce: bad dtype");
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "bn_act_bwd_reduce: bad dtype");
   SEGMI_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "bn_act_bwd_reduce: dropout_p must be in [0, 1)");
   SEGMI_CHECK_ARG(act_ok(dy) && act_ok(x) && same_shape(x, dy) && mean && invstd && red_partials,
                   "bn_act_bwd_reduce: bad arguments");
@@ -753,7 +759,7 @@ int segmi_bn_act_bwd_apply(int dtype, const segmi_act* dy, const segmi_act* x,
                            const segmi_act* dx, const float* mean, const float* invstd,
                            const float* gamma, const float* beta, const float* prelu_alpha,
                            const float* coef, float dropout_p, uint32_t dropout_seed, void* stream) {
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "bn_act_bwd_apply: bad dtype");
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "bn_act_bwd_apply: bad dtype");
   SEGMI_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "bn_act_bwd_apply: dropout_p must be in [0, 1)");
   SEGMI_CHECK_ARG(act_ok(dy) && act_ok(x) && act_ok(dx) && same_shape(x, dy) && same_shape(x, dx) &&
                       mean && invstd && coef, "bn_act_bwd_apply: bad arguments");
@@ -789,8 +795,9 @@ static int fused_capacity(int dtype, size_t lds) {
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
   int per_cu = 0, cus = 0;
-  const void* fn = dtype == SEGMI_F32 ? reinterpret_cast<const void*>(bn_act_bwd_fused_kernel<float>)
-                                      : reinterpret_cast<const void*>(bn_act_bwd_fused_kernel<bf16_t>);
+  const void* fn = dtype == SEGMI_F32   ? reinterpret_cast<const void*>(bn_act_bwd_fused_kernel<float>)
+                   : dtype == SEGMI_F16 ? reinterpret_cast<const void*>(bn_act_bwd_fused_kernel<f16_t>)
+                                        : reinterpret_cast<const void*>(bn_act_bwd_fused_kernel<bf16_t>);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kFusedThreads, lds) != hipSuccess) per_cu = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
   (void)hipGetLastError();
@@ -829,7 +836,7 @@ static int fused_tmo_init() {
   return SEGMI_OK;
 }
 int segmi_bn_act_bwd_fused_ok(int dtype, const segmi_act* dy, const segmi_act* x, const segmi_act* dx) {
-  if (!act_ok(dy) || !act_ok(x) || !act_ok(dx) || (dtype != SEGMI_F32 && dtype != SEGMI_BF16)) return 0;
+  if (!act_ok(dy) || !act_ok(x) || !act_ok(dx) || !dtype_ok(dtype)) return 0;
   if (!same_shape(x, dy) || !same_shape(x, dx)) return 0;
   if (!(vec4_ok(x, dtype) && vec4_ok(dy, dtype) && vec4_ok(dx, dtype)) || x->c > 256) return 0;
   if (act_voxels(x) * x->c * dtype_size(dtype) > (32ll << 20)) return 0;
@@ -871,12 +878,13 @@ int segmi_bn_act_bwd_fused(int dtype, const segmi_act* dy, const segmi_act* x, c
   p.tmo = g_fused_tmo_dev;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == SEGMI_F32) hipLaunchKernelGGL(bn_act_bwd_fused_kernel<float>, rows, kFusedThreads, lds, st, p);
+  else if (dtype == SEGMI_F16) hipLaunchKernelGGL(bn_act_bwd_fused_kernel<f16_t>, rows, kFusedThreads, lds, st, p);
   else hipLaunchKernelGGL(bn_act_bwd_fused_kernel<bf16_t>, rows, kFusedThreads, lds, st, p);
   SEGMI_LAUNCH_CHECK("bn_act_bwd_fused");
   return SEGMI_OK;
 }
 int segmi_bn_act_bwd_fused_wgs(int dtype, const segmi_act* x, int max_wgs) {
-  if (!act_ok(x) || x->c % 4 != 0 || x->c > 256 || (dtype != SEGMI_F32 && dtype != SEGMI_BF16)) return 0;
+  if (!act_ok(x) || x->c % 4 != 0 || x->c > 256 || !dtype_ok(dtype)) return 0;
   return fused_wgs(dtype, x, max_wgs);
 }
 unsigned segmi_fused_timeouts(int reset) {
@@ -907,6 +915,12 @@ int segmi_cast_copy(int src_dtype, const segmi_act* src, int dst_dtype, const se
     hipLaunchKernelGGL((cast_copy_kernel<bf16_t, float>), grid, 256, 0, st, (const bf16_t*)src->data, (float*)dst->data, nvox, src->c, src->ld, dst->ld);
   else if (src_dtype == SEGMI_BF16 && dst_dtype == SEGMI_BF16)
     hipLaunchKernelGGL((cast_copy_kernel<bf16_t, bf16_t>), grid, 256, 0, st, (const bf16_t*)src->data, (bf16_t*)dst->data, nvox, src->c, src->ld, dst->ld);
+  else if (src_dtype == SEGMI_F32 && dst_dtype == SEGMI_F16)
+    hipLaunchKernelGGL((cast_copy_kernel<float, f16_t>), grid, 256, 0, st, (const float*)src->data, (f16_t*)dst->data, nvox, src->c, src->ld, dst->ld);
+  else if (src_dtype == SEGMI_F16 && dst_dtype == SEGMI_F32)
+    hipLaunchKernelGGL((cast_copy_kernel<f16_t, float>), grid, 256, 0, st, (const f16_t*)src->data, (float*)dst->data, nvox, src->c, src->ld, dst->ld);
+  else if (src_dtype == SEGMI_F16 && dst_dtype == SEGMI_F16)
+    hipLaunchKernelGGL((cast_copy_kernel<f16_t, f16_t>), grid, 256, 0, st, (const f16_t*)src->data, (f16_t*)dst->data, nvox, src->c, src->ld, dst->ld);
   else SEGMI_CHECK_ARG(false, "cast_copy: bad dtypes");
   SEGMI_LAUNCH_CHECK("cast_copy");
   return SEGMI_OK;
@@ -918,6 +932,8 @@ int segmi_nchw_to_ndhwc(const float* src, int dst_dtype, const segmi_act* dst, v
   const int grid = ew_blocks((int64_t)dst->n * vox * dst->c);
   if (dst_dtype == SEGMI_F32)
     hipLaunchKernelGGL(nchw_to_ndhwc_kernel<float>, grid, 256, 0, (hipStream_t)stream, src, (float*)dst->data, dst->n, dst->c, vox, dst->ld);
+  else if (dst_dtype == SEGMI_F16)
+    hipLaunchKernelGGL(nchw_to_ndhwc_kernel<f16_t>, grid, 256, 0, (hipStream_t)stream, src, (f16_t*)dst->data, dst->n, dst->c, vox, dst->ld);
   else
     hipLaunchKernelGGL(nchw_to_ndhwc_kernel<bf16_t>, grid, 256, 0, (hipStream_t)stream, src, (bf16_t*)dst->data, dst->n, dst->c, vox, dst->ld);
   SEGMI_LAUNCH_CHECK("nchw_to_ndhwc");
@@ -930,6 +946,8 @@ int segmi_ndhwc_to_nchw(int src_dtype, const segmi_act* src, float* dst, void* s
   const int grid = ew_blocks((int64_t)src->n * vox * src->c);
   if (src_dtype == SEGMI_F32)
     hipLaunchKernelGGL(ndhwc_to_nchw_kernel<float>, grid, 256, 0, (hipStream_t)stream, (const float*)src->data, dst, src->n, src->c, vox, src->ld);
+  else if (src_dtype == SEGMI_F16)
+    hipLaunchKernelGGL(ndhwc_to_nchw_kernel<f16_t>, grid, 256, 0, (hipStream_t)stream, (const f16_t*)src->data, dst, src->n, src->c, vox, src->ld);
   else
     hipLaunchKernelGGL(ndhwc_to_nchw_kernel<bf16_t>, grid, 256, 0, (hipStream_t)stream, (const bf16_t*)src->data, dst, src->n, src->c, vox, src->ld);
   SEGMI_LAUNCH_CHECK("ndhwc_to_nchw");

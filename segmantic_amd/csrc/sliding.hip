@@ -258,10 +258,10 @@ __global__ __launch_bounds__(256) void sw_blend_kernel(
             if constexpr (G == 8) {
               f32x4 p0, p1;
               const u32x4 o = *reinterpret_cast<const u32x4*>(pp);
-              p0[0] = __uint_as_float(o[0] << 16); p0[1] = __uint_as_float(o[0] & 0xffff0000u);
-              p0[2] = __uint_as_float(o[1] << 16); p0[3] = __uint_as_float(o[1] & 0xffff0000u);
-              p1[0] = __uint_as_float(o[2] << 16); p1[1] = __uint_as_float(o[2] & 0xffff0000u);
-              p1[2] = __uint_as_float(o[3] << 16); p1[3] = __uint_as_float(o[3] & 0xffff0000u);
+              p0[0] = H16<T>::lo(o[0]); p0[1] = H16<T>::hi(o[0]);
+              p0[2] = H16<T>::lo(o[1]); p0[3] = H16<T>::hi(o[1]);
+              p1[0] = H16<T>::lo(o[2]); p1[1] = H16<T>::hi(o[2]);
+              p1[2] = H16<T>::lo(o[3]); p1[3] = H16<T>::hi(o[3]);
 #pragma unroll
               for (int j = 0; j < 4; ++j) { a[j] += wt * p0[j]; a[4 + j] += wt * p1[j]; }
             } else if constexpr (G == 4) {
@@ -424,10 +424,10 @@ __global__ __launch_bounds__(256) void sw_blend2_kernel(
       if (ok[c]) {
         if constexpr (G == 8) {
           const u32x4 o = pv[c];
-          a[0] += wt[c] * __uint_as_float(o[0] << 16); a[1] += wt[c] * __uint_as_float(o[0] & 0xffff0000u);
-          a[2] += wt[c] * __uint_as_float(o[1] << 16); a[3] += wt[c] * __uint_as_float(o[1] & 0xffff0000u);
-          a[4] += wt[c] * __uint_as_float(o[2] << 16); a[5] += wt[c] * __uint_as_float(o[2] & 0xffff0000u);
-          a[6] += wt[c] * __uint_as_float(o[3] << 16); a[7] += wt[c] * __uint_as_float(o[3] & 0xffff0000u);
+          a[0] += wt[c] * H16<T>::lo(o[0]); a[1] += wt[c] * H16<T>::hi(o[0]);
+          a[2] += wt[c] * H16<T>::lo(o[1]); a[3] += wt[c] * H16<T>::hi(o[1]);
+          a[4] += wt[c] * H16<T>::lo(o[2]); a[5] += wt[c] * H16<T>::hi(o[2]);
+          a[6] += wt[c] * H16<T>::lo(o[3]); a[7] += wt[c] * H16<T>::hi(o[3]);
         } else {
 #pragma unroll
           for (int j = 0; j < 4; ++j) a[j] += wt[c] * pv[c][j];
@@ -498,6 +498,9 @@ int segmi_sw_gather(int dtype_src, const segmi_act* image, int img_index,
     else if (dtype_src == SEGMI_F32 && dst_dtype == SEGMI_BF16) GATHER4(float, bf16_t);
     else if (dtype_src == SEGMI_BF16 && dst_dtype == SEGMI_BF16) GATHER4(bf16_t, bf16_t);
     else if (dtype_src == SEGMI_BF16 && dst_dtype == SEGMI_F32) GATHER4(bf16_t, float);
+    else if (dtype_src == SEGMI_F32 && dst_dtype == SEGMI_F16) GATHER4(float, f16_t);
+    else if (dtype_src == SEGMI_F16 && dst_dtype == SEGMI_F16) GATHER4(f16_t, f16_t);
+    else if (dtype_src == SEGMI_F16 && dst_dtype == SEGMI_F32) GATHER4(f16_t, float);
     else SEGMI_CHECK_ARG(false, "sw_gather: bad dtypes");
 #undef GATHER4
     SEGMI_LAUNCH_CHECK("sw_gather");
@@ -507,6 +510,9 @@ int segmi_sw_gather(int dtype_src, const segmi_act* image, int img_index,
   else if (dtype_src == SEGMI_F32 && dst_dtype == SEGMI_BF16) GATHER(float, bf16_t);
   else if (dtype_src == SEGMI_BF16 && dst_dtype == SEGMI_BF16) GATHER(bf16_t, bf16_t);
   else if (dtype_src == SEGMI_BF16 && dst_dtype == SEGMI_F32) GATHER(bf16_t, float);
+  else if (dtype_src == SEGMI_F32 && dst_dtype == SEGMI_F16) GATHER(float, f16_t);
+  else if (dtype_src == SEGMI_F16 && dst_dtype == SEGMI_F16) GATHER(f16_t, f16_t);
+  else if (dtype_src == SEGMI_F16 && dst_dtype == SEGMI_F32) GATHER(f16_t, float);
   else SEGMI_CHECK_ARG(false, "sw_gather: bad dtypes");
 #undef GATHER
   SEGMI_LAUNCH_CHECK("sw_gather");
@@ -516,7 +522,7 @@ int segmi_sw_gather(int dtype_src, const segmi_act* image, int img_index,
 int segmi_sw_scatter_add(int dtype, const segmi_act* pred, const int32_t* starts_host,
                          int nwin, const float* importance, const segmi_act* acc, float* cnt,
                          void* stream) {
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "sw_scatter_add: bad dtype");
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "sw_scatter_add: bad dtype");
   SEGMI_CHECK_ARG(act_ok(pred) && act_ok(acc) && starts_host && acc->n == 1, "sw_scatter_add: bad arguments");
   SEGMI_CHECK_ARG(nwin > 0 && nwin <= kMaxWin && pred->n >= nwin && pred->c == acc->c, "sw_scatter_add: windows / channels");
   WinList wl{};
@@ -540,6 +546,8 @@ int segmi_sw_scatter_add(int dtype, const segmi_act* pred, const int32_t* starts
     const int g4 = grid_for((int64_t)bd * bh * bw * (acc->c / 4));
     if (dtype == SEGMI_F32)
       hipLaunchKernelGGL(sw_scatter4_kernel<float>, g4, 256, 0, st, (const float*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
+    else if (dtype == SEGMI_F16)
+      hipLaunchKernelGGL(sw_scatter4_kernel<f16_t>, g4, 256, 0, st, (const f16_t*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
     else
       hipLaunchKernelGGL(sw_scatter4_kernel<bf16_t>, g4, 256, 0, st, (const bf16_t*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
     SEGMI_LAUNCH_CHECK("sw_scatter_add");
@@ -548,6 +556,8 @@ int segmi_sw_scatter_add(int dtype, const segmi_act* pred, const int32_t* starts
   const int grid = grid_for((int64_t)bd * bh * bw * acc->c);
   if (dtype == SEGMI_F32)
     hipLaunchKernelGGL(sw_scatter_kernel<float>, grid, 256, 0, st, (const float*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
+  else if (dtype == SEGMI_F16)
+    hipLaunchKernelGGL(sw_scatter_kernel<f16_t>, grid, 256, 0, st, (const f16_t*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
   else
     hipLaunchKernelGGL(sw_scatter_kernel<bf16_t>, grid, 256, 0, st, (const bf16_t*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
   SEGMI_LAUNCH_CHECK("sw_scatter_add");
@@ -570,6 +580,10 @@ static int argmax_launch(int dtype, const segmi_act* lg, const float* cnt, int w
       if (label_bytes == 1) ARGMAX4(float, uint8_t);
       else if (label_bytes == 2) ARGMAX4(float, int16_t);
       else ARGMAX4(float, int32_t);
+    } else if (dtype == SEGMI_F16) {
+      if (label_bytes == 1) ARGMAX4(f16_t, uint8_t);
+      else if (label_bytes == 2) ARGMAX4(f16_t, int16_t);
+      else ARGMAX4(f16_t, int32_t);
     } else {
       if (label_bytes == 1) ARGMAX4(bf16_t, uint8_t);
       else if (label_bytes == 2) ARGMAX4(bf16_t, int16_t);
@@ -587,6 +601,10 @@ static int argmax_launch(int dtype, const segmi_act* lg, const float* cnt, int w
     if (label_bytes == 1) ARGMAX(float, uint8_t);
     else if (label_bytes == 2) ARGMAX(float, int16_t);
     else ARGMAX(float, int32_t);
+  } else if (dtype == SEGMI_F16) {
+    if (label_bytes == 1) ARGMAX(f16_t, uint8_t);
+    else if (label_bytes == 2) ARGMAX(f16_t, int16_t);
+    else ARGMAX(f16_t, int32_t);
   } else {
     if (label_bytes == 1) ARGMAX(bf16_t, uint8_t);
     else if (label_bytes == 2) ARGMAX(bf16_t, int16_t);
@@ -606,7 +624,7 @@ int segmi_sw_finalize(const segmi_act* acc, const float* cnt, int write_logits, 
 }
 
 int segmi_argmax(int dtype, const segmi_act* logits, void* labels, int label_bytes, void* stream) {
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "argmax: bad dtype");
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "argmax: bad dtype");
   SEGMI_CHECK_ARG(act_ok(logits) && labels, "argmax: bad arguments");
   SEGMI_CHECK_ARG(label_bytes == 1 || label_bytes == 2 || label_bytes == 4, "argmax: label_bytes");
   return argmax_launch(dtype, logits, nullptr, 0, labels, label_bytes, (hipStream_t)stream);
@@ -617,7 +635,7 @@ int segmi_sw_blend(int dtype, const void* cache, int k, int ldp, const int32_t* 
                    int win_hi, int rd, int rh, int rw, const float* importance, int d, int h, int w,
                    float* out_logits, int ldo, float* out_count, void* labels, int label_bytes,
                    int normalize, void* stream) {
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "sw_blend: bad dtype");
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "sw_blend: bad dtype");
   SEGMI_CHECK_ARG(cache && starts_z && starts_y && starts_x && k > 0 && ldp >= k && rd > 0 &&
                       rh > 0 && rw > 0 && d > 0 && h > 0 && w > 0,
                   "sw_blend: bad arguments");
@@ -672,7 +690,11 @@ int segmi_sw_blend(int dtype, const void* cache, int k, int ldp, const int32_t* 
                          rh, rw, ldp, normalize);                                                 \
   } while (0)
   if (vec) {
-    if (dtype == SEGMI_BF16) {
+    if (dtype == SEGMI_F16) {
+      if (label_bytes == 1) BLEND(f16_t, uint8_t, 8);
+      else if (label_bytes == 2) BLEND(f16_t, uint16_t, 8);
+      else BLEND(f16_t, int32_t, 8);
+    } else if (dtype == SEGMI_BF16) {
       if (label_bytes == 1) BLEND(bf16_t, uint8_t, 8);
       else if (label_bytes == 2) BLEND(bf16_t, uint16_t, 8);
       else BLEND(bf16_t, int32_t, 8);
@@ -684,7 +706,10 @@ int segmi_sw_blend(int dtype, const void* cache, int k, int ldp, const int32_t* 
   } else {
     // scalar lanes: one channel each; labels (if wanted) come from a second pass over the logits
     SEGMI_CHECK_ARG(!labels || out_logits, "sw_blend: the scalar path labels from the written logits");
-    if (dtype == SEGMI_BF16) hipLaunchKernelGGL((sw_blend_kernel<bf16_t, int32_t, 1>), grid, 256, 0, st,
+    if (dtype == SEGMI_F16) hipLaunchKernelGGL((sw_blend_kernel<f16_t, int32_t, 1>), grid, 256, 0, st,
+        (const f16_t*)cache, sc, win_lo, win_hi, importance, out_logits, out_count, (int32_t*)nullptr,
+        d, h, w, k, ldo, rd, rh, rw, ldp, normalize);
+    else if (dtype == SEGMI_BF16) hipLaunchKernelGGL((sw_blend_kernel<bf16_t, int32_t, 1>), grid, 256, 0, st,
         (const bf16_t*)cache, sc, win_lo, win_hi, importance, out_logits, out_count, (int32_t*)nullptr,
         d, h, w, k, ldo, rd, rh, rw, ldp, normalize);
     else hipLaunchKernelGGL((sw_blend_kernel<float, int32_t, 1>), grid, 256, 0, st,
@@ -736,6 +761,8 @@ int segmi_crop_patches(const segmi_act* image, const float* label, const int32_t
   hipStream_t st = (hipStream_t)stream;
   if (dst_dtype == SEGMI_F32)
     hipLaunchKernelGGL(crop_kernel<float>, grid, 256, 0, st, (const float*)image->data, label, cl, image->d, image->h, image->w, image->c, image->ld, (float*)out_image->data, out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
+  else if (dst_dtype == SEGMI_F16)
+    hipLaunchKernelGGL(crop_kernel<f16_t>, grid, 256, 0, st, (const float*)image->data, label, cl, image->d, image->h, image->w, image->c, image->ld, (f16_t*)out_image->data, out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
   else
     hipLaunchKernelGGL(crop_kernel<bf16_t>, grid, 256, 0, st, (const float*)image->data, label, cl, image->d, image->h, image->w, image->c, image->ld, (bf16_t*)out_image->data, out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
   SEGMI_LAUNCH_CHECK("crop_patches");

@@ -24,6 +24,7 @@ namespace segmi {
 
 int wgrad_mfma_f32(const WgradParams& p, int ksize, int stride, int ct, int gx, hipStream_t st);
 int wgrad_mfma_bf16(const WgradParams& p, int ksize, int stride, int ct, int gx, hipStream_t st);
+int wgrad_mfma_f16(const WgradParams& p, int ksize, int stride, int ct, int gx, hipStream_t st);
 int bn_stats_launch(int dtype, const segmi_act* x, float* partials, hipStream_t st, const BiasFin* bias_fin = nullptr);
 int bn_stats_rows_for(const segmi_act* x);
 bool conv_small_ok(int cin, int cout, int ksize);
@@ -219,10 +220,10 @@ int segmi_conv3d_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float
                        float* db, int ksize, int stride, void* workspace,
                        const segmi_in_affine* in_tf, int cus, void* stream) {
   if (in_tf)
-    SEGMI_CHECK_ARG(in_tf->scale && in_tf->shift && dtype == SEGMI_BF16 && act_ok(x) && act_ok(dy) &&
+    SEGMI_CHECK_ARG(in_tf->scale && in_tf->shift && dtype_h16(dtype) && act_ok(x) && act_ok(dy) &&
                         wg_mfma_ok(dtype, x, dy, ksize),
-                    "wgrad: an input transform needs the bf16 MFMA kernel");
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "wgrad: bad dtype");
+                    "wgrad: an input transform needs the bf16 / fp16 MFMA kernel");
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "wgrad: bad dtype");
   SEGMI_CHECK_ARG(act_ok(x) && act_ok(dy) && dw && workspace, "wgrad: bad arguments");
   SEGMI_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), "wgrad: k/s");
   SEGMI_CHECK_ARG(!(ksize == 1 && stride != 1), "wgrad: k1 is stride 1 only");
@@ -247,8 +248,9 @@ int segmi_conv3d_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float
       if (in_tf) { p.in_scale = in_tf->scale; p.in_shift = in_tf->shift; p.in_alpha = in_tf->prelu_alpha; }
       const int ct = wgrad_ct_for(dtype, &xs, &ys, ksize, stride, cus);
       const bool ws = wgrad_ws_gx(dtype, &xs, &ys, ksize, stride, cus) > 0;
-      const int rc = dtype == SEGMI_F32 ? wgrad_mfma_f32(p, ksize, stride, ct, gx, st)
-                                        : wgrad_mfma_bf16(p, ksize, stride, ws ? -ct : ct, gx, st);
+      const int rc = dtype == SEGMI_F32   ? wgrad_mfma_f32(p, ksize, stride, ct, gx, st)
+                     : dtype == SEGMI_F16 ? wgrad_mfma_f16(p, ksize, stride, ws ? -ct : ct, gx, st)
+                                          : wgrad_mfma_bf16(p, ksize, stride, ws ? -ct : ct, gx, st);
       if (rc) return rc;
     }
   } else if (wg_small_ok(dtype, x, dy, ksize)) {
@@ -261,6 +263,7 @@ int segmi_conv3d_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float
     p.Cin = x->c; p.Cout = dy->c; p.ldx = x->ld; p.ldy = dy->ld; p.ks = ksize; p.stride = stride;
     p.nvox = act_voxels(dy); p.chunk = 512;
     if (dtype == SEGMI_F32) hipLaunchKernelGGL(wgrad_direct_kernel<float>, slabs, 256, 0, st, p);
+    else if (dtype == SEGMI_F16) hipLaunchKernelGGL(wgrad_direct_kernel<f16_t>, slabs, 256, 0, st, p);
     else hipLaunchKernelGGL(wgrad_direct_kernel<bf16_t>, slabs, 256, 0, st, p);
     SEGMI_LAUNCH_CHECK("conv3d_wgrad(direct)");
   }

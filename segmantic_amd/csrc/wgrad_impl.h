@@ -217,11 +217,11 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(WgradParams p) {
   auto commit = [&]() {
     if constexpr (sizeof(T) == 2) {
       if (in_act && in_alpha >= 0.f && in_alpha <= 1.f) {
-        commit_with([&](frag_t v) { return bn_prelu01_bf16x8(v, tsc, tsh, in_alpha); });
+        commit_with([&](frag_t v) { return bn_prelu01_h8<T>(v, tsc, tsh, in_alpha); });
         return;
       }
-      if (in_act) { commit_with([&](frag_t v) { return bn_prelu_bf16x8(v, tsc, tsh, in_alpha, true); }); return; }
-      if (in_tf) { commit_with([&](frag_t v) { return bn_prelu_bf16x8(v, tsc, tsh, 0.f, false); }); return; }
+      if (in_act) { commit_with([&](frag_t v) { return bn_prelu_h8<T>(v, tsc, tsh, in_alpha, true); }); return; }
+      if (in_tf) { commit_with([&](frag_t v) { return bn_prelu_h8<T>(v, tsc, tsh, 0.f, false); }); return; }
     }
     commit_with([](frag_t v) { return v; });
   };
@@ -351,7 +351,7 @@ static inline int wgrad_tiles(const segmi_act* dy, int stride, bool one_block) {
 // where X is the big tensor) 2 output tiles share one staging of X (4x1 measured slower: 360
 // VGPRs).
 static inline int wgrad_ct(int dtype, int cin, int cout) {
-  if (dtype != SEGMI_BF16) return 11;
+  if (!dtype_h16(dtype)) return 11;
   if (cin % 32 == 0 && cout % 32 == 0) return 22;
   if (cin % 32 == 0) return 11;
   if (cout % 32 == 0) return 21;
@@ -375,7 +375,7 @@ static inline bool wgrad_ws_cfg_ok(int stride, int ct) {
 int wgrad_cus(int cus);
 static inline int wgrad_ws_gx_ct(int dtype, const segmi_act* x, const segmi_act* dy, int ksize, int stride, int cus, int ct) {
   static const bool enabled = !(getenv("SEGMI_WGRAD_WS") && atoi(getenv("SEGMI_WGRAD_WS")) == 0);
-  if (!enabled || dtype != SEGMI_BF16 || ksize != 3) return 0;
+  if (!enabled || !dtype_h16(dtype) || ksize != 3) return 0;
   if (!wgrad_ws_cfg_ok(stride, ct)) return 0;
   const int cto = ct / 10, cti = ct % 10;
   const int chunks = (x->c / (16 * cti)) * (dy->c / (16 * cto));

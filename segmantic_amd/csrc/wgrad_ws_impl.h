@@ -54,9 +54,8 @@ __device__ __forceinline__ void ws_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-template <int KS, int S, int CTO, int CTI, int TD, int TH, int TW>
+template <typename T, int KS, int S, int CTO, int CTI, int TD, int TH, int TW>
 __global__ __launch_bounds__(768) void wgrad_ws_kernel(WgradParams p) {
-  using T = bf16_t;
   using G = WgradGeom<T, KS, S, CTO, CTI, TD, TH, TW>;
   constexpr int BUF = (G::LDS_BYTES + 255) / 256 * 256;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -486,9 +485,9 @@ __global__ __launch_bounds__(768) void wgrad_ws_kernel(WgradParams p) {
       if (border) commit_with(buf, ry, rx, xmask, cont, tf, Yes{});
       else commit_with(buf, ry, rx, xmask, cont, tf, No{});
     };
-    if (mode == 3) with_mask([&](frag_t v) { return bn_prelu01_bf16x8(v, tsc, tsh, in_alpha); });
-    else if (mode == 2) with_mask([&](frag_t v) { return bn_prelu_bf16x8(v, tsc, tsh, in_alpha, true); });
-    else with_mask([&](frag_t v) { return bn_prelu_bf16x8(v, tsc, tsh, 0.f, false); });
+    if (mode == 3) with_mask([&](frag_t v) { return bn_prelu01_h8<T>(v, tsc, tsh, in_alpha); });
+    else if (mode == 2) with_mask([&](frag_t v) { return bn_prelu_h8<T>(v, tsc, tsh, in_alpha, true); });
+    else with_mask([&](frag_t v) { return bn_prelu_h8<T>(v, tsc, tsh, 0.f, false); });
   };
 
   // Every producer wave takes its share of EVERY tile (an eighth of the chunks) and keeps two tiles
@@ -535,9 +534,9 @@ static constexpr int wgrad_ws_lds() {
   return 2 * ((G::LDS_BYTES + 255) / 256 * 256);
 }
 
-template <int KS, int S, int CTO, int CTI, int TD, int TH, int TW>
+template <typename T, int KS, int S, int CTO, int CTI, int TD, int TH, int TW>
 static int launch_wgrad_ws_cfg(WgradParams p, int gx, hipStream_t st) {
-  using G = WgradGeom<bf16_t, KS, S, CTO, CTI, TD, TH, TW>;
+  using G = WgradGeom<T, KS, S, CTO, CTI, TD, TH, TW>;
   constexpr int LDS = wgrad_ws_lds<KS, S, CTO, CTI, TD, TH, TW>();
   static_assert(LDS <= 160 * 1024, "two tile buffers must fit the CU's LDS");
   p.tz = cdiv(p.Dy, TD);
@@ -569,7 +568,7 @@ static int launch_wgrad_ws_cfg(WgradParams p, int gx, hipStream_t st) {
 #endif
   const int co_chunks = p.Cout / (16 * CTO);
   dim3 grid((unsigned)gx, (unsigned)(co_chunks * p.ci_chunks));
-  auto kern = wgrad_ws_kernel<KS, S, CTO, CTI, TD, TH, TW>;
+  auto kern = wgrad_ws_kernel<T, KS, S, CTO, CTI, TD, TH, TW>;
   static bool attr_done = false;
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),

@@ -220,6 +220,9 @@ int segmi_wpack(int dtype, int kind, const float* w_src, const float* scale, int
     if (dtype == SEGMI_F32)
       hipLaunchKernelGGL(wpack_convT_kernel<float>, grid, 256, 0, st, w_src, scale,
                          (float*)packed, cin_k, cout_k, g.CK, g.SPT, g.nchunks, g.ntiles);
+    else if (dtype == SEGMI_F16)
+      hipLaunchKernelGGL(wpack_convT_kernel<f16_t>, grid, 256, 0, st, w_src, scale,
+                         (f16_t*)packed, cin_k, cout_k, g.CK, g.SPT, g.nchunks, g.ntiles);
     else
       hipLaunchKernelGGL(wpack_convT_kernel<bf16_t>, grid, 256, 0, st, w_src, scale,
                          (bf16_t*)packed, cin_k, cout_k, g.CK, g.SPT, g.nchunks, g.ntiles);
@@ -231,6 +234,10 @@ int segmi_wpack(int dtype, int kind, const float* w_src, const float* scale, int
     if (dtype == SEGMI_F32)
       hipLaunchKernelGGL(wpack_conv_kernel<float>, blocks, 256, 0, st, w_src, scale,
                          (float*)packed, kind, cin_k, cout_k, g.ntaps, g.CK, g.SPT, g.nsteps,
+                         g.ntiles, total);
+    else if (dtype == SEGMI_F16)
+      hipLaunchKernelGGL(wpack_conv_kernel<f16_t>, blocks, 256, 0, st, w_src, scale,
+                         (f16_t*)packed, kind, cin_k, cout_k, g.ntaps, g.CK, g.SPT, g.nsteps,
                          g.ntiles, total);
     else
       hipLaunchKernelGGL(wpack_conv_kernel<bf16_t>, blocks, 256, 0, st, w_src, scale,
@@ -245,7 +252,7 @@ int segmi_wpack_batch(int dtype, const segmi_wpack_desc* descs_host, int ndesc,
                       segmi_wpack_desc* descs_dev, int upload, void* stream) {
   SEGMI_CHECK_ARG(descs_host && descs_dev, "wpack_batch: null descriptor table");
   SEGMI_CHECK_ARG(ndesc > 0 && ndesc <= 65535, "wpack_batch: ndesc %d out of range", ndesc);
-  SEGMI_CHECK_ARG(dtype == SEGMI_F32 || dtype == SEGMI_BF16, "wpack_batch: bad dtype %d", dtype);
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "wpack_batch: bad dtype %d", dtype);
   for (int i = 0; i < ndesc; ++i) {
     const segmi_wpack_desc& d = descs_host[i];
     SEGMI_CHECK_ARG(d.w_src && d.packed, "wpack_batch[%d]: null pointer", i);
@@ -271,6 +278,8 @@ int segmi_wpack_batch(int dtype, const segmi_wpack_desc* descs_host, int ndesc,
   dim3 grid(64, ndesc);
   if (dtype == SEGMI_F32)
     hipLaunchKernelGGL(wpack_batch_kernel<float>, grid, 256, 0, st, descs_dev);
+  else if (dtype == SEGMI_F16)
+    hipLaunchKernelGGL(wpack_batch_kernel<f16_t>, grid, 256, 0, st, descs_dev);
   else
     hipLaunchKernelGGL(wpack_batch_kernel<bf16_t>, grid, 256, 0, st, descs_dev);
   SEGMI_LAUNCH_CHECK("wpack_batch");

@@ -13,16 +13,16 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import SEGMI_BF16, SEGMI_F32, Act, BnBwdFin, BnBwdSums, BnFin, InAffine, Windows, check, lib
+from ._lib import SEGMI_BF16, SEGMI_F16, SEGMI_F32, Act, BnBwdFin, BnBwdSums, BnFin, InAffine, Windows, check, lib
 
-_DT = {torch.float32: SEGMI_F32, torch.bfloat16: SEGMI_BF16}
+_DT = {torch.float32: SEGMI_F32, torch.bfloat16: SEGMI_BF16, torch.float16: SEGMI_F16}
 
 
 def dtype_code(t: torch.Tensor) -> int:
     try:
         return _DT[t.dtype]
     except KeyError:
-        raise TypeError(f"unsupported activation dtype {t.dtype} (float32 / bfloat16 only)")
+        raise TypeError(f"unsupported activation dtype {t.dtype} (float32 / bfloat16 / float16 only)")
 
 
 def _stream() -> int:
@@ -266,11 +266,12 @@ def dectop_ok(x, y) -> bool:
     return bool(lib.segmi_dectop_ok(dtype_code(x), C.byref(ax), C.byref(ay)))
 
 
-def dectop_up_frag(w_t: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+def dectop_up_frag(w_t: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
     """A-operand fragments of the transposed conv for ``segmi_dectop_fwd``: w_t [32, 16, 3, 3, 3] f32
-    (torch ConvTranspose3d layout), scale f32[16] (folded BatchNorm) -> bf16 [27, 64, 8]."""
+    (torch ConvTranspose3d layout), scale f32[16] (folded BatchNorm) -> [27, 64, 8] of the layer's 16-bit
+    storage ``dtype`` (bfloat16 / float16)."""
     ws = (w_t * scale.view(1, -1, 1, 1, 1)).reshape(32, 16, 27)
-    return ws.permute(2, 0, 1).reshape(27, 4, 8, 16).permute(0, 1, 3, 2).contiguous().to(torch.bfloat16).reshape(27, 64, 8)
+    return ws.permute(2, 0, 1).reshape(27, 4, 8, 16).permute(0, 1, 3, 2).contiguous().to(dtype).reshape(27, 64, 8)
 
 
 def dectop_fwd(x, y, up_frag, up_bias, up_alpha, conv_packed, conv_bias, alpha_in_unit_range=False) -> None:
@@ -553,6 +554,44 @@ def adabelief_step(param, grad, exp_avg, exp_avg_var, lr, beta1, beta2, eps, wei
                                    param.numel(), lr, beta1, beta2, eps, weight_decay,
                                    int(weight_decouple), step, grad_scale, _stream()),
           "adabelief_step")
+
+
+# ------------------------------------------------------------------ dynamic loss scaling
+# amp: f32[3] device tensor {scale, found_inf, skipped steps}; tracker: int32[1]; step: int64[1] (segmi.h)
+def softmax_dice_bwd_amp(logits, labels, coef, amp, dlogits, scratch=None, bias_grad=None) -> None:
+    """softmax_dice_bwd with the loss scale read from ``amp[0]`` on the device."""
+    a, b = act(logits), act(dlogits)
+    check(lib.segmi_softmax_dice_bwd_amp(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef), _ptr(amp),
+                                         C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
+          "softmax_dice_bwd_amp")
+
+
+def amp_check_finite(grad, amp) -> None:
+    check(lib.segmi_amp_check_finite(_ptr(grad), grad.numel(), _ptr(amp), _stream()), "amp_check_finite")
+
+
+def amp_update_scale(amp, tracker, step, growth_factor, backoff_factor, growth_interval) -> None:
+    check(lib.segmi_amp_update_scale(_ptr(amp), _ptr(tracker), _ptr(step), float(growth_factor),
+                                     float(backoff_factor), int(growth_interval), _stream()), "amp_update_scale")
+
+
+def adam_step_amp(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
+                  amp, step, grad_scale=1.0) -> None:
+    check(lib.segmi_adam_step_amp(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                  _ptr(max_exp_avg_sq), param.numel(), lr, beta1, beta2, eps, weight_decay,
+                                  _ptr(amp), _ptr(step), grad_scale, _stream()), "adam_step_amp")
+
+
+def sgd_step_amp(param, grad, buf, lr, momentum, weight_decay, amp, step, grad_scale=1.0) -> None:
+    check(lib.segmi_sgd_step_amp(_ptr(param), _ptr(grad), _ptr(buf), param.numel(), lr, momentum, weight_decay,
+                                 _ptr(amp), _ptr(step), grad_scale, _stream()), "sgd_step_amp")
+
+
+def adabelief_step_amp(param, grad, exp_avg, exp_avg_var, lr, beta1, beta2, eps, weight_decay, weight_decouple,
+                       amp, step, grad_scale=1.0) -> None:
+    check(lib.segmi_adabelief_step_amp(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_var), param.numel(),
+                                       lr, beta1, beta2, eps, weight_decay, int(weight_decouple), _ptr(amp),
+                                       _ptr(step), grad_scale, _stream()), "adabelief_step_amp")
 
 
 # ------------------------------------------------------------------ sliding window

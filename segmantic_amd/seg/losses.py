@@ -56,13 +56,21 @@ def dice_forward(state: _DiceState, logits_ndhwc: torch.Tensor, labels: torch.Te
 
 def dice_backward(state: _DiceState, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
                   out: Optional[torch.Tensor] = None,
-                  bias_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  bias_grad: Optional[torch.Tensor] = None,
+                  amp: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``bias_grad`` (f32[K]): also receives sum_voxels dlogits, i.e. the bias gradient of the conv
-    that produced the logits (saves that layer a pass over the gradient tensor)."""
+    that produced the logits (saves that layer a pass over the gradient tensor).  ``amp`` (the f32[3]
+    state of a ``GradScaler``): the gradient is scaled by the loss scale held there on the device
+    (``grad_scale`` is then ignored)."""
     if out is None or out.shape != logits_ndhwc.shape or out.dtype != logits_ndhwc.dtype:
         out = torch.empty_like(logits_ndhwc)
-    ops.softmax_dice_bwd(logits_ndhwc, state.labels, state.coef, grad_scale, out,
-                         scratch=state.partials if bias_grad is not None else None, bias_grad=bias_grad)
+    scratch = state.partials if bias_grad is not None else None
+    if amp is not None:
+        ops.softmax_dice_bwd_amp(logits_ndhwc, state.labels, state.coef, amp, out, scratch=scratch,
+                                 bias_grad=bias_grad)
+    else:
+        ops.softmax_dice_bwd(logits_ndhwc, state.labels, state.coef, grad_scale, out, scratch=scratch,
+                             bias_grad=bias_grad)
     return out
 
 
@@ -97,7 +105,7 @@ class DiceLoss(torch.nn.Module):
         self._state = _DiceState()
 
     def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        """logits [N,K,D,H,W] (float32/bfloat16), labels [N,1,D,H,W] integer-valued."""
+        """logits [N,K,D,H,W] (float32/bfloat16/float16), labels [N,1,D,H,W] integer-valued."""
         if logits.requires_grad and torch.is_grad_enabled():
             return _DiceFn.apply(logits, labels, self)
         lg = as_ndhwc(logits)

@@ -5,20 +5,23 @@ this module is MONAI / Lightning: the network runs on the hand-written HIP kerne
 ``libsegmi.so`` through ``UNetEngine``; the training loop, checkpoint format, early stopping
 and top-k checkpointing of Lightning (``:503-541``) are re-stated in ~100 lines of host code.
 
-``mixed_precision=True`` selects bf16 storage with f32 accumulation (the reference's
-``precision=16`` AMP, ``:533``); ``False`` selects the exact-f32 MFMA path used for parity.
+``mixed_precision=True`` (or ``"bf16"``) selects bf16 storage with f32 accumulation; ``"fp16"`` selects
+IEEE fp16 storage with f32 accumulation, f32 master weights and dynamic loss scaling -- the reference's
+``precision=16`` AMP (``:424,533``) -- (``seg/amp.py``); ``False`` selects the exact-f32 MFMA path used for
+parity.
 """
 import json
 import os
 import re
 from collections.abc import Sequence
 from pathlib import Path
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Union
 
 import numpy as np
 import torch
 
 from .. import ops
+from .amp import GradScaler, precision_dtype, precision_mode
 from ..image.labels import load_decathlon_tissuelist, load_tissue_list
 from .distributed import (GradSync, broadcast_buffers, env_world, init_distributed,
                           rank_device_index)
@@ -104,6 +107,7 @@ class Net(torch.nn.Module):
         self._opt = None
         self._sched = None
         self._gsync: Optional[GradSync] = None
+        self._scaler: Optional[GradScaler] = None
         self.dataset = None
 
     # ------------------------------------------------------------------ properties
@@ -121,7 +125,15 @@ class Net(torch.nn.Module):
 
     @property
     def compute_dtype(self):
-        return torch.bfloat16 if self.mixed_precision else torch.float32
+        """True / "bf16" -> bfloat16, "fp16" -> float16, False -> float32"""
+        return precision_dtype(self.mixed_precision)
+
+    def grad_scaler(self) -> GradScaler:
+        """The dynamic loss scaler of fp16 training (created with the first fp16 step; tests may replace it
+        or shorten its ``growth_interval`` before that)."""
+        if self._scaler is None or self._scaler.device != self.device:
+            self._scaler = GradScaler(self.device)
+        return self._scaler
 
     # ------------------------------------------------------------------ engine
     def _engine_for(self, x: Optional[torch.Tensor] = None) -> UNetEngine:
@@ -265,16 +277,25 @@ class Net(torch.nn.Module):
             st = self.loss_function._state
             loss = dice_forward(st, logits, labels, self.loss_function.smooth_nr,
                                 self.loss_function.smooth_dr)
+            # fp16: the Dice gradient is multiplied by the loss scale (device memory), and the weight gradients
+            # are not carried over the end of the step -- the Inf / NaN check must see the whole arena before
+            # any of it is applied (all-or-nothing skip)
+            scaler = self.grad_scaler() if eng.dtype == torch.float16 else None
             dlogits = dice_backward(st, logits, 1.0, eng.dlogits_buffer(logits),
-                                    bias_grad=eng.top_bias_grad())
+                                    bias_grad=eng.top_bias_grad(), amp=scaler.amp if scaler else None)
             if self._gsync is not None:
                 self._gsync.start()
-            carried = eng.backward(dlogits, top_bias_done=True, carry=self._gsync is None)
+            carried = eng.backward(dlogits, top_bias_done=True, carry=self._gsync is None and scaler is None)
             scale = 1.0
             if self._gsync is not None:
                 self._gsync.finish()
                 scale = self._gsync.grad_scale
-            if carried:
+            if scaler is not None:
+                # after the all-reduce: every rank sees the same found_inf and takes the same decision
+                scaler.check(eng.flat_grad)
+                opt.step_amp(scaler, scale)
+                scaler.update(opt)
+            elif carried:
                 # the weight gradients of the two full-resolution decoder convolutions are still running on
                 # the weight-gradient stream (they overlap the NEXT step's forward, UNetEngine.carry_top_wgrad):
                 # update the rest of the arena here, the suffix behind them on their stream
@@ -399,7 +420,7 @@ def train(
     lr_scheduling=None,
     max_epochs: int = 600,
     early_stop_patience: int = 50,
-    mixed_precision: bool = True,
+    mixed_precision: Union[bool, str] = True,
     cache_rate: float = 1.0,
     gpu_ids: list = [0],
     tissue_list: Path = None,
@@ -500,7 +521,9 @@ def train(
     net.optimizer = optimizer
     net.lr_scheduling = lr_scheduling
     net.cache_rate = cache_rate
-    net.mixed_precision = bool(mixed_precision)
+    # True / False as before; "bf16" / "fp16" (YAML / JSON) select the 16-bit format; a bad string fails here
+    net.mixed_precision = (precision_mode(mixed_precision) if isinstance(mixed_precision, str)
+                           else bool(mixed_precision))
 
     # process group first: nothing above has made a device call (the runtime environment was set when
     # the package was imported), and init_distributed() binds the rank to its GPU before the first one

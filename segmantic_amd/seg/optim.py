@@ -21,12 +21,28 @@ class FlatOptimizer:
         self.lr = float(lr)
         self.base_lr = float(lr)
         self.steps = 0
+        self._dev_steps = None   # loss-scaled training: count of APPLIED updates, on the device
+
+    def device_steps(self) -> torch.Tensor:
+        """int64[1] device counter of applied updates (``step_amp``; advanced by ``GradScaler.update``)"""
+        if self._dev_steps is None:
+            self._dev_steps = torch.full((1,), self.steps, dtype=torch.int64, device=self.flat.device)
+        return self._dev_steps
+
+    def applied_steps(self) -> int:
+        return self.steps if self._dev_steps is None else int(self._dev_steps.item())
+
+    def step_amp(self, scaler, grad_scale: float = 1.0):
+        """One loss-scaled update of the whole arena: the gradient is unscaled by 1 / scale on the device, and
+        a step whose gradients hold Inf / NaN (``scaler.check``) leaves parameters and moments untouched and
+        does not count (bias corrections and SGD's first-step rule follow the device count)."""
+        raise NotImplementedError
 
     def zero_grad(self):  # gradients are overwritten by the engine's backward
         pass
 
     def state_dict(self):
-        return {"lr": self.lr, "steps": self.steps}
+        return {"lr": self.lr, "steps": self.applied_steps()}
 
     def step(self, grad_scale: float = 1.0, lo: int = 0, hi: Optional[int] = None, advance: bool = True):
         """One update of the arena range ``[lo, hi)`` (default: all of it).  A training step that updates
@@ -60,6 +76,11 @@ class FlatAdam(FlatOptimizer):
                           None if self.max_exp_avg_sq is None else self.max_exp_avg_sq[lo:hi], self.lr,
                           self.betas[0], self.betas[1], self.eps, self.weight_decay, self.steps, grad_scale)
 
+    def step_amp(self, scaler, grad_scale: float = 1.0):
+        ops.adam_step_amp(self.flat, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.max_exp_avg_sq, self.lr,
+                          self.betas[0], self.betas[1], self.eps, self.weight_decay, scaler.amp,
+                          self.device_steps(), grad_scale)
+
 
 class FlatSGD(FlatOptimizer):
     def __init__(self, flat, flat_grad, lr, momentum=0.0, weight_decay=0.0):
@@ -74,6 +95,10 @@ class FlatSGD(FlatOptimizer):
         if hi > lo:
             ops.sgd_step(self.flat[lo:hi], self.flat_grad[lo:hi], None if self.buf is None else self.buf[lo:hi],
                          self.lr, self.momentum, self.weight_decay, self.steps == 1, grad_scale)
+
+    def step_amp(self, scaler, grad_scale: float = 1.0):
+        ops.sgd_step_amp(self.flat, self.flat_grad, self.buf, self.lr, self.momentum, self.weight_decay, scaler.amp,
+                         self.device_steps(), grad_scale)
 
 
 class FlatAdaBelief(FlatOptimizer):
@@ -93,6 +118,11 @@ class FlatAdaBelief(FlatOptimizer):
             ops.adabelief_step(self.flat[lo:hi], self.flat_grad[lo:hi], self.exp_avg[lo:hi],
                                self.exp_avg_var[lo:hi], self.lr, self.betas[0], self.betas[1], self.eps,
                                self.weight_decay, self.weight_decouple, self.steps, grad_scale)
+
+    def step_amp(self, scaler, grad_scale: float = 1.0):
+        ops.adabelief_step_amp(self.flat, self.flat_grad, self.exp_avg, self.exp_avg_var, self.lr, self.betas[0],
+                               self.betas[1], self.eps, self.weight_decay, self.weight_decouple, scaler.amp,
+                               self.device_steps(), grad_scale)
 
 
 def make_optimizer(cfg: dict, flat, flat_grad) -> FlatOptimizer:

@@ -27,6 +27,9 @@ import torch.nn as nn
 from .. import ops
 from . import streams
 
+# the 16-bit storage formats: every fused path and kernel family treats them alike
+_HALF = (torch.bfloat16, torch.float16)
+
 
 # =============================================================================================
 # parameter container (MONAI key layout)
@@ -320,8 +323,8 @@ class UNetEngine:
     def __init__(self, params: UNetParams, device: torch.device, dtype: torch.dtype):
         if params.dimensions not in (2, 3):
             raise NotImplementedError("segmantic_amd: spatial_dims must be 2 or 3")
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise TypeError("compute dtype must be float32 or bfloat16")
+        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise TypeError("compute dtype must be float32, bfloat16 or float16")
         if any(s not in (1, 2) for s in params.strides):
             raise NotImplementedError("segmantic_amd: strides must be 1 or 2")
         self.net = params
@@ -632,7 +635,7 @@ class UNetEngine:
     def _tf_ok(self, x, y, conv: _Conv) -> bool:
         """the BatchNorm-apply + PReLU that would produce ``conv``'s input can be done by the conv
         itself while it stages x (segmi_in_affine): no normalised copy of x is ever written"""
-        return (self.fuse_bn_apply and self.dtype == torch.bfloat16 and self.dropout_p <= 0.0
+        return (self.fuse_bn_apply and self.dtype in _HALF and self.dropout_p <= 0.0
                 and not conv.transposed and conv.k == 3 and conv.stride == 1 and conv.mfma
                 and ops.conv3d_in_affine_ok(x, y, 3, 1))
 
@@ -782,7 +785,7 @@ class UNetEngine:
         # the variant that fits its registers computes the 32 outputs as two 16-channel tiles on grid.y and the
         # 160^3 / batch 4 step went 9.75 -> 10.2 ms with it (both tiles in one workgroup: 96 spilled registers,
         # 10.9 ms).  SEGMI_BSUM32=1 asks for them anyway (A/B).
-        return (bn is not None and self.fuse_bn_bwd and self.dtype == torch.bfloat16 and self.dropout_p <= 0.0
+        return (bn is not None and self.fuse_bn_bwd and self.dtype in _HALF and self.dropout_p <= 0.0
                 and not conv.transposed and conv.stride == 1 and conv.k == 3 and conv.mfma
                 and (conv.cout == 16 or self._bsum32)
                 and ops.conv3d_bn_bwd_sums_ok(dy, dx, 3, 1))
@@ -1128,7 +1131,7 @@ class UNetEngine:
             sc, sh = ubn.eval_affine()
             upru = lvl["upru"]
             conv0, bn0 = upru["units"][0]
-            if (self.fuse_eval_top and lvl["is_top"] and self.dtype == torch.bfloat16 and bn0 is None
+            if (self.fuse_eval_top and lvl["is_top"] and self.dtype in _HALF and bn0 is None
                     and upru["res"] is None and up.cin == 32 and up.cout == 16 and conv0.cin == conv0.cout == 16
                     and ops.dectop_ok(cat, out)):
                 # the full-resolution decoder as ONE launch: the 16-channel tensor between the
@@ -1137,7 +1140,7 @@ class UNetEngine:
                 if hit is None or hit[0] != self.weights_version:
                     # (one host read of the slope per weights version: the kernel's PReLU fast path)
                     a = float(ubn.alpha.reshape(-1)[0])
-                    hit = (self.weights_version, ops.dectop_up_frag(up.w, sc), torch.addcmul(sh, up.b, sc),
+                    hit = (self.weights_version, ops.dectop_up_frag(up.w, sc, self.dtype), torch.addcmul(sh, up.b, sc),
                            0.0 <= a <= 1.0)
                     lvl["_dectop"] = hit
                 self._timed(conv0.prefix + ":fwd", ops.dectop_fwd, cat, out, hit[1], hit[2], ubn.alpha,
