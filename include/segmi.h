@@ -22,6 +22,7 @@
 #ifndef SEGMI_H_
 #define SEGMI_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -511,6 +512,51 @@ int segmi_ensemble_vote(const int32_t* const* labels_host, int models, int64_t n
 int segmi_ensemble_select(const int32_t* const* labels_host, int models, const int32_t* tissue_host,
                           const int32_t* model_host, int pairs, int64_t n, int32_t* out,
                           void* stream);
+
+/* ---------------------------------------------------------------- evaluation ----------- */
+/* Segmentation evaluation (src/segmantic/seg/evaluation.py:5-125 and scripts/evaluate_segmentations.py).
+ * Label volumes are read in place as label_bytes in {1 (uint8), 2 (int16), 4 (int32)}, [d][h][w]
+ * (a 2-D input is d = 1 with spatial_dims = 2).  Boxes are half-open (z0 z1 y0 y1 x0 x1).
+ *
+ * Per-label bounding box of pred==c OR truth==c and the two voxel counts, in one pass over both
+ * volumes (k <= 1024; an absent label gets the empty box 0 0 0 0 0 0).  Replaces the full-volume
+ * SimpleITK filters of evaluation.py:18-26: every voxel outside the box is background of both
+ * masks, so distance maps over the box are exact. */
+int segmi_label_boxes(const void* pred, const void* truth, int label_bytes, int d, int h, int w, int k,
+                      int32_t* boxes /* [k][6] */, int64_t* counts /* [k][2] pred, truth */, void* stream);
+/* Workspace of segmi_edt_sq / segmi_edt_sample for a box of bd x bh x bw voxels. */
+int64_t segmi_edt_workspace_bytes(int bd, int bh, int bw);
+/* Exact squared Euclidean distance (physical, spacing per array axis z y x) from every voxel of the box
+ * to the nearest feature voxel of `label`: feature 0 = labels == label, 1 = its contour (voxels of the
+ * label with a face neighbour -- 6 in 3-D, 4 in 2-D -- that is not, outside the volume = background).
+ * dist_sq: f32 [bd][bw][bh] (x before y: the layout of the last pass); +inf when the box holds no
+ * feature.  The contour map is signed as SignedMaurerDistanceMap(insideIsPositive=False): voxels of
+ * the label carry the sign bit.  Unit spacing is bit-exact.  box and spacing_zyx are HOST arrays.
+ * Replaces sitk.BinaryContour + sitk.SignedMaurerDistanceMap, evaluation.py:18-26,61-66. */
+int segmi_edt_sq(const void* labels, int label_bytes, int d, int h, int w, int spatial_dims, int label,
+                 int feature, const int32_t* box, const float* spacing_zyx, float* dist_sq, void* workspace,
+                 size_t ws_bytes, void* stream);
+/* Distances of the query voxels (query 0 = labels == label, 1 = its contour, inside the box) on a
+ * distance map of segmi_edt_sq: a contour query takes |dist_sq|, a foreground query clamps dist_sq <= 0
+ * (inside the target) to 0.  stats f64[4] = count, sum, sum of squares, max of the distances,
+ * finalised inside the launch in a fixed order (repeated calls are bit-identical).  values (nullable):
+ * the squared distances are appended at values[*n_values ...] and *n_values (device) advanced; their
+ * order varies between runs, the caller zeroes the counter and sizes values for every query voxel.
+ * Replaces the masking and numpy statistics of evaluation.py:28-47,71-92. */
+int segmi_edt_sample(const float* dist_sq, const void* labels, int label_bytes, int d, int h, int w,
+                     int spatial_dims, int label, int query, const int32_t* box, double* stats, float* values,
+                     int64_t* n_values, void* workspace, size_t ws_bytes, void* stream);
+/* Exact order statistics of n (device) non-negative f32 values: out[i] = the value of rank ranks[i]
+ * (device i64, clamped to [0, n-1]; NaN when n == 0), 1 <= n_ranks <= 4.  Radix select over the bit
+ * patterns (11 + 11 + 10 bits); the passes keep their state on the device.
+ * Replaces np.median of evaluation.py:44,88 and MONAI's percentile Hausdorff. */
+int64_t segmi_select_workspace_bytes(int n_ranks);
+int segmi_select_f32(const float* values, const int64_t* n, const int64_t* ranks, int n_ranks, float* out,
+                     void* workspace, size_t ws_bytes, void* stream);
+/* cm i64[k][k], cm[truth][pred] voxel counts (k <= 4096; labels outside [0, k) are not counted).
+ * Replaces confusion_matrix, evaluation.py:96-125. */
+int segmi_confusion_counts(const void* pred, const void* truth, int label_bytes, int64_t n, int k,
+                           int64_t* cm, void* stream);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,36 @@ class Image:
     def numpy(self) -> np.ndarray:
         return self.data.detach().cpu().numpy()
 
+    # --- pixel access in sitk index order: x first (ints and slices)
+    def _index(self, key):
+        key = key if isinstance(key, tuple) else (key,)
+        d = self.data.dim()
+        if len(key) > d:
+            raise IndexError(f"{len(key)} indices for a {d}-D image")
+        for k in key:
+            if not isinstance(k, (int, np.integer, slice)):
+                raise TypeError(f"Image indices are ints or slices, not {type(k).__name__}")
+        return (slice(None),) * (d - len(key)) + tuple(reversed(key))
+
+    def __getitem__(self, key):
+        """``image[x, y, z]`` -> pixel value; with slices -> an ``Image`` over that region (a view;
+        the spacing of the kept axes, origin and direction carried over unchanged)."""
+        idx = self._index(key)
+        sub = self.data[idx]
+        if sub.dim() == 0:
+            return sub.item()
+        kept = [a for a, k in zip(range(self.data.dim() - 1, -1, -1), idx) if isinstance(k, slice)]
+        kept = sorted(kept)  # (x, y, z) axis numbers of the kept array axes
+        dd = self.data.dim()
+        direction = np.asarray(self.direction).reshape(dd, dd)[np.ix_(kept, kept)].reshape(-1)
+        return Image(sub, [self.spacing[a] for a in kept], [self.origin[a] for a in kept], direction)
+
+    def __setitem__(self, key, value):
+        """``image[3:6, 3:6] = 1`` in sitk index order (x first)."""
+        if isinstance(value, Image):
+            value = value.data
+        self.data[self._index(key)] = value
+
 
 def make_image(shape: Sequence[int], spacing: Optional[Sequence[float]] = None,
                value: Union[int, float] = 0, pixel_type: Any = sitkUInt8) -> Image:

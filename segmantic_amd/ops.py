@@ -818,3 +818,79 @@ def ensemble_select(labels, tissue_model: dict, out) -> None:
     check(lib.segmi_ensemble_select(tab, len(labels), ts.ctypes.data_as(C.c_void_p),
                                     ms.ctypes.data_as(C.c_void_p), len(ts), out.numel(), _ptr(out),
                                     _stream()), "ensemble_select")
+
+
+# ------------------------------------------------------------------ evaluation (distance.hip)
+def label_bytes(t: torch.Tensor) -> int:
+    """label_bytes of a label volume read in place: uint8 -> 1, int16 -> 2, int32 -> 4."""
+    try:
+        return _LABEL_BYTES[t.dtype]
+    except KeyError:
+        raise ValueError(f"label volumes are uint8, int16 or int32 (label_bytes 1, 2, 4), not {t.dtype}")
+
+
+def _labels3(t: torch.Tensor):
+    """(d, h, w) of a contiguous 2-D [h, w] or 3-D [d, h, w] label volume on the device"""
+    _require_device(t)
+    if t.dim() not in (2, 3) or not t.is_contiguous():
+        raise ValueError("label volumes are contiguous [h, w] or [d, h, w] tensors")
+    return (1,) + tuple(t.shape) if t.dim() == 2 else tuple(t.shape)
+
+
+def _host_i32(v):
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.int32))
+    return a, a.ctypes.data_as(C.c_void_p)
+
+
+def label_boxes(pred, truth, k, boxes, counts) -> None:
+    """boxes i32 [k, 6] (half-open z0 z1 y0 y1 x0 x1 of pred==c | truth==c), counts i64 [k, 2]."""
+    if pred.shape != truth.shape or pred.dtype != truth.dtype:
+        raise ValueError("label_boxes: pred and truth differ in shape or dtype")
+    d, h, w = _labels3(pred)
+    check(lib.segmi_label_boxes(_ptr(pred), _ptr(truth), label_bytes(pred), d, h, w, int(k), _ptr(boxes),
+                                _ptr(counts), _stream()), "label_boxes")
+
+
+def edt_workspace_bytes(box) -> int:
+    z0, z1, y0, y1, x0, x1 = (int(v) for v in box)
+    return int(lib.segmi_edt_workspace_bytes(z1 - z0, y1 - y0, x1 - x0))
+
+
+def edt_sq(labels, label, feature, box, spacing_zyx, dist_sq, workspace) -> None:
+    """Squared distance to label's foreground (feature 0) or signed, to its contour (feature 1), over box;
+    dist_sq f32 [bd, bw, bh]."""
+    d, h, w = _labels3(labels)
+    b, bp = _host_i32(box)
+    sp = np.ascontiguousarray(np.asarray(spacing_zyx, dtype=np.float32).reshape(3))
+    check(lib.segmi_edt_sq(_ptr(labels), label_bytes(labels), d, h, w, labels.dim(), int(label), int(feature), bp,
+                           sp.ctypes.data_as(C.c_void_p), _ptr(dist_sq), _ptr(workspace), workspace.numel(),
+                           _stream()), "edt_sq")
+
+
+def edt_sample(dist_sq, labels, label, query, box, stats, workspace, values=None, n_values=None) -> None:
+    """stats f64[4] = count, sum, sum of squares, max of the distances at labels' query voxels;
+    squared distances appended to values[n_values ...] when given."""
+    d, h, w = _labels3(labels)
+    b, bp = _host_i32(box)
+    check(lib.segmi_edt_sample(_ptr(dist_sq), _ptr(labels), label_bytes(labels), d, h, w, labels.dim(), int(label),
+                               int(query), bp, _ptr(stats), _ptr(values), _ptr(n_values), _ptr(workspace),
+                               workspace.numel(), _stream()), "edt_sample")
+
+
+def select_workspace_bytes(n_ranks: int) -> int:
+    return int(lib.segmi_select_workspace_bytes(int(n_ranks)))
+
+
+def select_f32(values, n, ranks, out, workspace) -> None:
+    """out[i] = value of rank ranks[i] among the first n[0] (device) non-negative f32 values."""
+    check(lib.segmi_select_f32(_ptr(values), _ptr(n), _ptr(ranks), ranks.numel(), _ptr(out), _ptr(workspace),
+                               workspace.numel(), _stream()), "select_f32")
+
+
+def confusion_counts(pred, truth, k, cm) -> None:
+    """cm i64 [k, k], cm[truth, pred]."""
+    if pred.shape != truth.shape or pred.dtype != truth.dtype:
+        raise ValueError("confusion_counts: pred and truth differ in shape or dtype")
+    _require_device(pred)
+    check(lib.segmi_confusion_counts(_ptr(pred), _ptr(truth), label_bytes(pred), pred.numel(), int(k), _ptr(cm),
+                                     _stream()), "confusion_counts")
