@@ -497,7 +497,7 @@ def cast_copy(src, dst) -> None:
 
 
 def nchw_to_ndhwc(src: torch.Tensor, dst: torch.Tensor) -> None:
-    """src f32 [N,C,D,H,W] contiguous -> dst NDHWC (f32 or bf16)."""
+    """src f32 [N,C,D,H,W] contiguous -> dst NDHWC (f32, bf16 or fp16)."""
     if src.dtype != torch.float32 or not src.is_contiguous():
         raise ValueError("nchw_to_ndhwc expects a contiguous float32 NCDHW tensor")
     b = act(dst)
@@ -636,7 +636,7 @@ def sw_finalize(acc, cnt, labels, write_logits=True) -> None:
 
 def sw_blend(cache, starts_zyx, win_lo, win_hi, roi, d, h, w, importance=None, out_logits=None,
              out_count=None, labels=None, normalize=True) -> None:
-    """cache [slots, rd, rh, rw, K] (NDHWC, bf16/f32); starts_zyx = three ascending origin lists."""
+    """cache [slots, rd, rh, rw, K] (NDHWC, f32, bf16 or fp16); starts_zyx = three ascending origin lists."""
     _require_device(cache)
     if cache.dim() != 5 or cache.stride(4) != 1 or not cache.is_contiguous():
         raise ValueError("sw_blend: cache must be a contiguous [slots, rd, rh, rw, K] tensor")

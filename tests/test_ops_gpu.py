@@ -1,7 +1,9 @@
 """GPU parity of every HIP op against the CPU oracle operators (torch CPU fp32 = what MONAI's
 UNet / DiceLoss reduce to, see oracle/unet_ref.py).  Tolerances are written next to each check:
 f32 kernels are exact-f32 MFMA chains (only the summation order differs from oneDNN), bf16
-kernels are compared against the oracle evaluated on bf16-rounded inputs.
+kernels are compared against the oracle evaluated on bf16-rounded inputs.  fp16 kernels are compared the same
+way at a tighter tolerance and, where a test has a float64 reference of the same op, element by element against
+the bound of tests/helpers/lowp_bounds.py (one output rounding + f32 accumulation noise).
 """
 import math
 import os
@@ -14,10 +16,16 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from segmantic_amd import ops  # noqa: E402
+from tests.helpers import lowp_bounds as lb  # noqa: E402
 
 DEV = "cuda:0"
 F32_RTOL = 2e-5      # f32 path: relative to max |ref|
 BF16_RTOL = 1.5e-2   # bf16 path: output rounding (2^-8) + accumulate-order noise
+F16_RTOL = 2e-3      # fp16 path: output rounding (2^-11) + accumulate-order noise
+F16 = torch.float16
+# the f32 / bf16 instances keep the ids pytest gave them before fp16 joined (dtype0, dtype1); fp16 is "f16"
+DTYPES = [pytest.param(torch.float32, id="dtype0"), pytest.param(torch.bfloat16, id="dtype1"),
+          pytest.param(torch.float16, id="f16")]
 
 
 def to_ndhwc(x_ncdhw, dtype):
@@ -42,7 +50,25 @@ def relerr(a, b):
 
 
 def tol(dtype):
+    if dtype == torch.float16:
+        return F16_RTOL
     return F32_RTOL if dtype == torch.float32 else BF16_RTOL
+
+
+def f16_bound(dtype, got, ref, absref, what=""):
+    """fp16 only: every element of ``got`` (NCDHW) inside the lowp_bounds bound around the float64 ``ref``"""
+    if dtype == torch.float16:
+        lb.assert_within(got, ref, absref, what=what)
+
+
+def epilogue64(ref, absref, alpha=None, res=None):
+    """PReLU and residual applied in float64 to a convolution reference and its |operand| companion"""
+    if alpha is not None:
+        ref = torch.where(ref > 0, ref, alpha * ref)
+        absref = absref * max(1.0, abs(alpha))
+    if res is not None:
+        ref, absref = ref + res.double(), absref + res.double().abs()
+    return ref, absref
 
 
 CONV_CASES = [
@@ -70,7 +96,7 @@ CONV_CASES = [
 ]
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv3d_fwd(case, dtype):
     cin, cout, k, s, sp, n = case
@@ -88,6 +114,10 @@ def test_conv3d_fwd(case, dtype):
     torch.cuda.synchronize()
     got = from_ndhwc(yd)
     assert relerr(got, ref) < tol(dtype)
+    if dtype == F16:
+        # the direct kernel reads the f32 weights as they are; the MFMA kernels (small-Cin included) round them
+        wq = w if "direct" in ops.conv3d_fwd_kernel_name(xd, yd, k, s) else q(w, dtype)
+        f16_bound(dtype, got, *lb.conv_ref(q(x, dtype), wq, b, stride=s, padding=(k - 1) // 2))
     # fused statistics: per-channel sum / sum of squares of the (pre-rounding) conv output
     ssum = stats[:, 0].double().sum(0).cpu()
     ssq = stats[:, 1].double().sum(0).cpu()
@@ -98,7 +128,7 @@ def test_conv3d_fwd(case, dtype):
     assert float(((ssq - rq).abs() / rq).max()) < (1e-4 if dtype == torch.float32 else 3e-2)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("cin,cout,stride,sp", [(1, 16, 2, (20, 34, 70)), (2, 32, 1, (5, 9, 19)),
                                                  (4, 16, 2, (9, 9, 9))])
 def test_conv3d_fwd_pair_equals_two_convs(dtype, cin, cout, stride, sp):
@@ -129,6 +159,7 @@ def test_conv3d_fwd_pair_equals_two_convs(dtype, cin, cout, stride, sp):
             assert torch.equal(st1[:real], st2[:real])
     ref = F.conv3d(q(x, dtype), q(wb, dtype), bb, stride=stride, padding=1)
     assert relerr(from_ndhwc(pb), ref) < tol(dtype)
+    f16_bound(dtype, from_ndhwc(pb), *lb.conv_ref(q(x, dtype), q(wb, dtype), bb, stride=stride, padding=1))
     # MFMA-shaped layers do not qualify
     big = torch.empty((1, 4, 4, 4, 16), dtype=dtype, device=DEV)
     assert not ops.conv3d_pair_ok(big, big.clone(), big.clone())
@@ -137,11 +168,10 @@ def test_conv3d_fwd_pair_equals_two_convs(dtype, cin, cout, stride, sp):
 @pytest.mark.parametrize("c,cout,with_alpha,mode", [(16, 16, 0.15, "identity"), (16, 16, None, "stats"),
                                                    (32, 32, 0.15, "stats"), (16, 32, 1.5, "plain"),
                                                    (16, 16, 0.0, "plain")])
-def test_conv3d_input_transform_equals_separate_bn_pass(c, cout, with_alpha, mode):
+def test_conv3d_input_transform_equals_separate_bn_pass(c, cout, with_alpha, mode, dtype=torch.bfloat16):
     """segmi_in_affine: the consumer conv (forward and weight gradient) applies the producer's
     BatchNorm-apply + PReLU while staging -- bit-identical to bn_act_fwd followed by the plain calls,
     zero padding and the identity residual included."""
-    dtype = torch.bfloat16
     n, sp = 4, (18, 60, 120)          # 256 ragged columns: the ring kernel takes the layer
     u = to_ndhwc(rnd((n, c) + sp, 401, 2.0), dtype)
     scale = (1 + 0.3 * rnd((c,), 402)).to(DEV)
@@ -182,7 +212,14 @@ def test_conv3d_input_transform_equals_separate_bn_pass(c, cout, with_alpha, mod
     assert not ops.conv3d_in_affine_ok(u, half, 3, 2)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("c,cout,with_alpha,mode", [(16, 16, 0.15, "identity"), (16, 16, None, "stats"),
+                                                   (32, 32, 0.15, "stats"), (16, 32, 1.5, "plain"),
+                                                   (16, 16, 0.0, "plain")])
+def test_conv3d_input_transform_equals_separate_bn_pass_f16(c, cout, with_alpha, mode):
+    test_conv3d_input_transform_equals_separate_bn_pass(c, cout, with_alpha, mode, dtype=F16)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_conv3d_epilogue_prelu_residual_and_views(dtype):
     """PReLU + residual epilogue, reading from / writing into channel slices (concat by offset)."""
     n, cin, cout, sp = 1, 16, 16, (6, 10, 18)
@@ -203,25 +240,27 @@ def test_conv3d_epilogue_prelu_residual_and_views(dtype):
                    prelu_alpha=ad, residual=rd)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(big_out[..., 16:32]), ref) < tol(dtype)
+    f16_bound(dtype, from_ndhwc(big_out[..., 16:32]),
+              *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), alpha, q(r, dtype)))
     assert float(big_out[..., :16].float().abs().max()) == 0.0
 
 
 @pytest.mark.parametrize("n,sp,mode", [(4, (18, 64, 120), "tf_identity"), (1, (64, 64, 128), "tf_identity"),
                                        (4, (18, 64, 120), "alpha_res_stats"), (1, (62, 60, 128), "plain"),
                                        (2, (33, 61, 125), "sums")])
-def test_conv_ring3_dma_ring_ragged_and_segmented_shapes(n, sp, mode):
+def test_conv_ring3_dma_ring_ragged_and_segmented_shapes(n, sp, mode, dtype=torch.bfloat16):
     """conv_ring3_kernel (LDS-DMA ring, round 4) away from the benchmark shape: extents that are not multiples of the
     (4, 8, 16) step / tile (the zero fill of partial planes, rows and columns comes from the buffer range check, the
     stores of lanes outside the tensor are dropped by it), z-split columns (several segments per column: the halo
     planes of a segment are real data of its neighbour), the in-place input transform on border workgroups (padding
-    chunks must stay zero), every epilogue.  Against torch on the bf16-rounded operands."""
-    dtype = torch.bfloat16
+    chunks must stay zero), every epilogue.  Against torch on the rounded operands."""
     c = 16
     x, r = rnd((n, c) + sp, 521), rnd((n, c) + sp, 522)
     w, b = rnd((c, c, 3, 3, 3), 523, 0.05), rnd((c,), 524, 0.1)
     xd, rd = to_ndhwc(x, dtype), to_ndhwc(r, dtype)
     yd = torch.full_like(xd, float("nan"))
-    assert "ring3" in ops.conv3d_fwd_kernel_name(xd, yd, 3, 1), ops.conv3d_fwd_kernel_name(xd, yd, 3, 1)
+    name = ops.conv3d_fwd_kernel_name(xd, yd, 3, 1)
+    assert "ring3" in name and ("f16" in name.replace("bf16", "")) == (dtype == F16), name
     if mode == "tf_identity":
         scale, shift = (rnd((c,), 525) * 0.3 + 1.0).to(DEV), (rnd((c,), 526) * 0.2).to(DEV)
         alpha = torch.tensor([0.2], device=DEV)
@@ -264,10 +303,21 @@ def test_conv_ring3_dma_ring_ragged_and_segmented_shapes(n, sp, mode):
     torch.cuda.synchronize()
     got = from_ndhwc(yd)
     assert bool(torch.isfinite(got).all())                          # every voxel written (the output started as NaN)
-    assert relerr(got, ref) < BF16_RTOL
+    assert relerr(got, ref) < tol(dtype)
+    if mode == "plain":
+        f16_bound(dtype, got, *lb.conv_ref(q(x, dtype), q(w, dtype)))
+    elif mode == "alpha_res_stats":
+        f16_bound(dtype, got, *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), 0.3, q(r, dtype)))
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("n,sp,mode", [(4, (18, 64, 120), "tf_identity"), (1, (64, 64, 128), "tf_identity"),
+                                       (4, (18, 64, 120), "alpha_res_stats"), (1, (62, 60, 128), "plain"),
+                                       (2, (33, 61, 125), "sums")])
+def test_conv_ring3_dma_ring_ragged_and_segmented_shapes_f16(n, sp, mode):
+    test_conv_ring3_dma_ring_ragged_and_segmented_shapes(n, sp, mode, dtype=F16)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_conv3d_ring_kernel_epilogue(dtype):
     """ring kernel (full-resolution shapes): PReLU + prefetched residual + fused statistics"""
     n, c, sp = 4, 16, (16, 64, 128)
@@ -285,12 +335,13 @@ def test_conv3d_ring_kernel_epilogue(dtype):
                    residual=rd, stats=stats)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(yd), ref) < tol(dtype)
+    f16_bound(dtype, from_ndhwc(yd), *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), 0.3, q(r, dtype)))
     ssum = stats[:, 0].double().sum(0).cpu()
     assert float((ssum - raw.double().sum((0, 2, 3, 4))).abs().max()) / (raw.numel() / c) < \
         (1e-5 if dtype == torch.float32 else 2e-2) * float(raw.abs().max())
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_conv3d_ksplit_kernel_epilogue(dtype):
     """k-split kernel (deep layers): PReLU + residual + fused statistics, channel-slice views"""
     n, cin, cout, sp = 2, 128, 64, (6, 9, 11)
@@ -310,6 +361,7 @@ def test_conv3d_ksplit_kernel_epilogue(dtype):
                    prelu_alpha=torch.tensor([0.3], device=DEV), residual=rd, stats=stats)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(yd), ref) < tol(dtype)
+    f16_bound(dtype, from_ndhwc(yd), *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), 0.3, q(r, dtype)))
     ssum = stats[:, 0].double().sum(0).cpu()
     assert float((ssum - raw.double().sum((0, 2, 3, 4))).abs().max()) / (raw.numel() / cout) < \
         (1e-5 if dtype == torch.float32 else 2e-2) * float(raw.abs().max())
@@ -318,7 +370,7 @@ def test_conv3d_ksplit_kernel_epilogue(dtype):
         (1e-5 if dtype == torch.float32 else 2e-2)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("c,sp", [(16, (16, 64, 128)), (32, (20, 30, 70))])
 def test_conv3d_ring_kernel_identity_residual(dtype, c, sp):
     """out = conv(x) + x with residual == input view: the ring kernel takes the residual rows
@@ -337,9 +389,10 @@ def test_conv3d_ring_kernel_identity_residual(dtype, c, sp):
     torch.cuda.synchronize()
     assert torch.equal(y1, y2)
     assert relerr(from_ndhwc(y1), ref) < tol(dtype)
+    f16_bound(dtype, from_ndhwc(y1), *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), None, q(x, dtype)))
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", [(16, 16, (6, 8, 20), 2), (32, 16, (4, 6, 8), 1), (4, 8, (5, 5, 5), 1)])
 def test_conv3d_dgrad_s1(case, dtype):
     """stride-1 dgrad = conv with flipped / transposed weights (pack kind 1)."""
@@ -354,6 +407,9 @@ def test_conv3d_dgrad_s1(case, dtype):
     ops.conv3d_fwd(dyd, dxd, packed, wd, 1, None, 3, 1)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(dxd), ref) < tol(dtype)
+    if dtype == F16:
+        wq = q(w, dtype) if packed is not None else w
+        f16_bound(dtype, from_ndhwc(dxd), *lb.convT_ref(q(dy, dtype), wq, stride=1, padding=1, output_padding=0))
 
 
 CONVT_CASES = [
@@ -370,7 +426,7 @@ CONVT_CASES = [
 ]
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_wpack_batch_is_bit_identical_to_single_packs(dtype):
     """One batched launch (every layer, every kind) == the per-layer packs, byte for byte."""
     g = torch.Generator(device="cpu").manual_seed(3)
@@ -395,7 +451,7 @@ def test_wpack_batch_is_bit_identical_to_single_packs(dtype):
             assert torch.equal(got, want)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", CONVT_CASES)
 def test_convT3d_fwd(case, dtype):
     cin, cout, sp, n, odd = case
@@ -413,12 +469,15 @@ def test_convT3d_fwd(case, dtype):
     ops.convT3d_fwd(xd, yd, packed, wd, bd, stats=stats)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(yd), ref) < tol(dtype)
+    if dtype == F16:
+        wq = q(w, dtype) if packed is not None else w
+        f16_bound(dtype, from_ndhwc(yd), *lb.convT_ref(q(x, dtype), wq, b, output_padding=0 if odd else 1))
     ssum = stats[:, 0].double().sum(0).cpu()
     rs = ref.double().sum((0, 2, 3, 4))
     assert float((ssum - rs).abs().max()) / (ref.numel() / cout) < (1e-5 if dtype == torch.float32 else 2e-2) * float(ref.abs().max())
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", [(32, 16, (4, 6, 20), 2), (64, 16, (3, 3, 16), 1), (128, 32, (4, 4, 8), 1),
                                   (32, 32, (3, 4, 18), 1)])
 def test_convT3d_epilogue_prelu_residual(case, dtype):
@@ -440,6 +499,7 @@ def test_convT3d_epilogue_prelu_residual(case, dtype):
     ops.convT3d_fwd(xd, yd, packed, wd, b.to(DEV), prelu_alpha=alpha.to(DEV), residual=rd)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(yd), ref) < tol(dtype)
+    f16_bound(dtype, from_ndhwc(yd), *epilogue64(*lb.convT_ref(q(x, dtype), q(w, dtype), b), 0.2, q(res, dtype)))
 
 
 WGRAD_CASES = [
@@ -462,7 +522,7 @@ WGRAD_CASES = [
 ]
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", WGRAD_CASES)
 def test_conv3d_wgrad(case, dtype):
     cin, cout, k, s, sp, n = case
@@ -485,13 +545,12 @@ def test_conv3d_wgrad(case, dtype):
 
 
 @pytest.mark.parametrize("case", [(16, 16, 3, 1, (32, 32, 32), 2), (32, 64, 3, 2, (16, 16, 16), 2)])
-def test_wgrad_grid_budget_changes_the_partition_not_the_gradient(case):
+def test_wgrad_grid_budget_changes_the_partition_not_the_gradient(case, dtype=torch.bfloat16):
     """The `cus` argument of segmi_conv3d_wgrad: the weight-gradient kernels size their grids (and their partial
     slabs) for that many compute units -- the engine gives them half the chip beside the main chain.  Any budget
     yields the gradient of the torch reference (another partition of the same f32 sums); the budget is a per-call
     argument (no process-wide state), clamped to multiples of 8 in [8, 256], <= 0 = the whole chip."""
     cin, cout, k, s, sp, n = case
-    dtype = torch.bfloat16
     x = rnd((n, cin) + sp, 131)
     osp = tuple((d + 2 * ((k - 1) // 2) - k) // s + 1 for d in sp)
     dy = rnd((n, cout) + osp, 132)
@@ -515,7 +574,12 @@ def test_wgrad_grid_budget_changes_the_partition_not_the_gradient(case):
         assert sizes[8] < sizes[0]          # fewer slabs for a smaller budget
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("case", [(16, 16, 3, 1, (32, 32, 32), 2), (32, 64, 3, 2, (16, 16, 16), 2)])
+def test_wgrad_grid_budget_changes_the_partition_not_the_gradient_f16(case):
+    test_wgrad_grid_budget_changes_the_partition_not_the_gradient(case, dtype=F16)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_convT3d_wgrad_via_conv_wgrad(dtype):
     """ConvTranspose3d weight grad == stride-2 conv wgrad with x := dy_T, dy := x_T."""
     n, cin, cout, sp = 1, 32, 16, (4, 6, 10)
@@ -532,7 +596,7 @@ def test_convT3d_wgrad_via_conv_wgrad(dtype):
     assert relerr(dw.cpu(), w0.grad) < 5e-5
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("c", [16, 32, 3])
 def test_bn_prelu_fwd_bwd(dtype, c):
     n, sp = 2, (6, 10, 14)
@@ -595,10 +659,9 @@ def _drop_mask(numel, p, seed):
 
 
 @pytest.mark.parametrize("c", [3, 16, 64])
-def test_bn_dropout_prelu_fwd_bwd(c):
+def test_bn_dropout_prelu_fwd_bwd(c, dtype=torch.float32):
     """ADN ordering "NDA" (MONAI blocks/adn.py as used by monai_unet.py:83-92): norm -> dropout -> act.
     The mask is a counter hash of the logical element index, recomputed in backward."""
-    dtype = torch.float32
     n, sp = 2, (6, 10, 14)
     pdrop, seed = 0.3, 0xC0FFEE
     x = rnd((n, c) + sp, 151, 2.0)
@@ -606,6 +669,8 @@ def test_bn_dropout_prelu_fwd_bwd(c):
     beta = 0.1 * rnd((c,), 153)
     alpha = torch.tensor([0.25])
     dy = rnd((n, c) + sp, 155)
+    if dtype != torch.float32:       # the reference on the operands the kernels read
+        x, dy = q(x, dtype), q(dy, dtype)
     count = n * sp[0] * sp[1] * sp[2]
     mask_ndhwc = torch.from_numpy(_drop_mask(count * c, pdrop, seed)).reshape((n,) + sp + (c,))
     mask = mask_ndhwc.permute(0, 4, 1, 2, 3)
@@ -629,7 +694,7 @@ def test_bn_dropout_prelu_fwd_bwd(c):
     torch.cuda.synchronize()
     got = from_ndhwc(yd)
     assert torch.equal(got == 0, (mask == 0) | (y.detach() == 0))     # the very same voxels are dropped
-    assert relerr(got, y.detach()) < 1e-5
+    assert relerr(got, y.detach()) < (1e-5 if dtype == torch.float32 else tol(dtype))
     dyd = to_ndhwc(dy, dtype)
     rrows = ops.bn_act_bwd_rows(xd)
     rp = torch.empty((rrows, 3, c), device=DEV)
@@ -643,7 +708,7 @@ def test_bn_dropout_prelu_fwd_bwd(c):
     assert relerr(dg.cpu(), g0.grad) < 1e-4
     assert relerr(dbt.cpu(), b0.grad) < 1e-4
     assert relerr(da.cpu(), a0.grad) < 1e-4
-    assert relerr(from_ndhwc(dxd), xq.grad) < 1e-4
+    assert relerr(from_ndhwc(dxd), xq.grad) < (1e-4 if dtype == torch.float32 else tol(dtype))
     # p = 0 is the identity (no mask evaluated)
     y0 = torch.empty_like(xd)
     ops.bn_act_fwd(xd, y0, scale, shift, ad, None, dropout=(0.0, seed))
@@ -652,7 +717,12 @@ def test_bn_dropout_prelu_fwd_bwd(c):
     assert torch.equal(y0, y1)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("c", [3, 16, 64])
+def test_bn_dropout_prelu_fwd_bwd_f16(c):
+    test_bn_dropout_prelu_fwd_bwd(c, dtype=F16)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("k", [2, 3, 16, 32])
 def test_softmax_dice(dtype, k):
     from oracle.unet_ref import ref_dice_loss
@@ -765,7 +835,7 @@ def test_argmax_bit_exact_with_ties():
         lg[0, K // 2, 1, 2, 3] = float("nan")                             # NaN counts as maximal
         lg[1, 1, 0, 0, 0] = float("nan"); lg[1, K - 1, 0, 0, 0] = float("nan")   # first NaN wins
         ref = torch.argmax(lg, dim=1)
-        for dt in (torch.float32, torch.bfloat16):
+        for dt in (torch.float32, torch.bfloat16, torch.float16):
             ld = to_ndhwc(lg, dt)
             for ldt in (torch.uint8, torch.int16, torch.int32):
                 lab = torch.empty((2, 5, 6, 9), dtype=ldt, device=DEV)
@@ -817,7 +887,7 @@ def test_sw_gather_more_than_16_windows_per_group():
         assert torch.equal(wd[i, ..., 0].cpu(), img[0, 0, z:z + 8, y:y + 8, x:x + 8]), i
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("K", [4, 16, 3])
 def test_sliding_window_deferred_blend_matches_oracle(K, dtype):
     """segmi_sw_blend: every window kept, one ordered blend pass == the sequential reference
@@ -852,7 +922,7 @@ def test_sliding_window_deferred_blend_matches_oracle(K, dtype):
         assert torch.equal(lab.cpu().long(), torch.argmax(ref, 1)[0])
         # labels only (no f32 logits volume)
         lab2 = torch.empty_like(lab)
-        if K % (8 if dtype == torch.bfloat16 else 4) == 0:
+        if K % (4 if dtype == torch.float32 else 8) == 0:
             ops.sw_blend(cache, per_dim, 0, len(wins), roi, 20, 27, 33, labels=lab2)
             torch.cuda.synchronize()
             assert torch.equal(lab2, lab)
@@ -1147,15 +1217,17 @@ def test_confusion_matrix_metric_and_empty_dice_aggregate_match_monai_rule():
     assert float(ref_dice_metric(pred[:1, :, :4, :4, :4], zeros, K)[1]) == 0.0
 
 
-def test_bn_bwd_sums_stay_accurate_when_the_mean_dwarfs_the_spread():
+def test_bn_bwd_sums_stay_accurate_when_the_mean_dwarfs_the_spread(dtype=torch.bfloat16):
     """the fused epilogue accumulates sum dz*(x - mean); the round-2 form sum dz*x - mean*sum dz
     cancelled when |mean| >> std.  x = 50 + N(0, 1): dgamma from the fused sums must match an f64 reference."""
+    # fp16 keeps the same magnitudes: 50 is far inside its range and resolved to 2^-5 there (bf16: 2^-2), so the
+    # spread survives the rounding of x in both formats.
     n, d, h, w, c = 2, 32, 64, 128, 16
     g = torch.Generator().manual_seed(5)
     dy = rnd((n, c, d, h, w), 411, 0.5)
     xr = torch.randn((n, c, d, h, w), generator=g) + 50.0
-    dyd, xd = to_ndhwc(dy, torch.bfloat16), to_ndhwc(xr, torch.bfloat16)
-    pk = ops.wpack(torch.bfloat16, 1, rnd((c, c, 3, 3, 3), 413, 0.08).to(DEV), c, c, 3)
+    dyd, xd = to_ndhwc(dy, dtype), to_ndhwc(xr, dtype)
+    pk = ops.wpack(dtype, 1, rnd((c, c, 3, 3, 3), 413, 0.08).to(DEV), c, c, 3)
     xq = from_ndhwc(xd).double()
     mean = xq.mean((0, 2, 3, 4))
     invstd = 1.0 / torch.sqrt(xq.var((0, 2, 3, 4), unbiased=False) + 1e-5)
@@ -1175,9 +1247,13 @@ def test_bn_bwd_sums_stay_accurate_when_the_mean_dwarfs_the_spread():
     assert float((db.cpu().double() - want_db).abs().max()) < 2e-4 * float(want_db.abs().max()) + 1e-3 * float(want_db.abs().mean())
 
 
+def test_bn_bwd_sums_stay_accurate_when_the_mean_dwarfs_the_spread_f16():
+    test_bn_bwd_sums_stay_accurate_when_the_mean_dwarfs_the_spread(dtype=F16)
+
+
 @pytest.mark.parametrize("c", [16, 32])
 @pytest.mark.parametrize("shape,residual", [((2, 32, 64, 128), "in"), ((2, 33, 60, 120), "other"), ((4, 16, 64, 128), None)])
-def test_bn_bwd_sums_in_the_input_gradient_epilogue_match_the_separate_pass(shape, residual, c):
+def test_bn_bwd_sums_in_the_input_gradient_epilogue_match_the_separate_pass(shape, residual, c, dtype=torch.bfloat16):
     """segmi_bn_bwd_sums: the ring kernel's input-gradient launch also writes the partial rows of the
     BatchNorm-backward reduction over (its own stored output, x_raw).  Same dx bits; dgamma / dbeta /
     dalpha / coef equal to the separate two-tensor pass up to f32 summation order.  c = 32: the 32 -> 32
@@ -1186,15 +1262,15 @@ def test_bn_bwd_sums_in_the_input_gradient_epilogue_match_the_separate_pass(shap
     dy = rnd((n, c, d, h, w), 401, 0.5)
     xr = rnd((n, c, d, h, w), 402, 2.0) + 0.3
     wt = rnd((c, c, 3, 3, 3), 403, 0.08)
-    dyd, xd = to_ndhwc(dy, torch.bfloat16), to_ndhwc(xr, torch.bfloat16)
-    pk = ops.wpack(torch.bfloat16, 1, wt.to(DEV), c, c, 3)
+    dyd, xd = to_ndhwc(dy, dtype), to_ndhwc(xr, dtype)
+    pk = ops.wpack(dtype, 1, wt.to(DEV), c, c, 3)
     assert ops.conv3d_bn_bwd_sums_ok(dyd, dyd, 3, 1) and ops.conv3d_in_affine_ok(dyd, dyd, 3, 1)
     mean = (rnd((c,), 404) * 0.5).to(DEV)
     invstd = (rnd((c,), 405).abs() + 0.5).to(DEV)
     gamma = (rnd((c,), 406) + 1.5).to(DEV)
     beta = (rnd((c,), 407) * 0.3).to(DEV)
     alpha = torch.full((1,), 0.25, device=DEV)
-    res = {"in": dyd, "other": to_ndhwc(rnd((n, c, d, h, w), 408), torch.bfloat16), None: None}[residual]
+    res = {"in": dyd, "other": to_ndhwc(rnd((n, c, d, h, w), 408), dtype), None: None}[residual]
     count = n * d * h * w
 
     def finalize(part, rows):
@@ -1235,13 +1311,19 @@ def test_bn_bwd_sums_in_the_input_gradient_epilogue_match_the_separate_pass(shap
     assert float((db - db2).abs().max()) < 2e-4 * float(db.abs().max()) + 1e-3 * float(db.abs().mean())
 
 
+@pytest.mark.parametrize("c", [16, 32])
+@pytest.mark.parametrize("shape,residual", [((2, 32, 64, 128), "in"), ((2, 33, 60, 120), "other"), ((4, 16, 64, 128), None)])
+def test_bn_bwd_sums_in_the_input_gradient_epilogue_match_the_separate_pass_f16(shape, residual, c):
+    test_bn_bwd_sums_in_the_input_gradient_epilogue_match_the_separate_pass(shape, residual, c, dtype=F16)
+
+
 @pytest.mark.parametrize("slope", [0.25, 1.7, -0.3])
 @pytest.mark.parametrize("shape", [(2, 8, 16, 16), (1, 16, 24, 32), (3, 6, 8, 40), (1, 2, 8, 8)])
-def test_fused_full_resolution_decoder_is_bit_identical_to_the_two_launches(shape, slope):
+def test_fused_full_resolution_decoder_is_bit_identical_to_the_two_launches(shape, slope, dtype=torch.bfloat16):
     """segmi_dectop_fwd: ConvTranspose3d(32 -> 16) + folded BN + PReLU -> conv(16 -> 16) + identity
     residual in one launch; same tap order and k-slot layout as the separate kernels => same bits."""
     n, d, h, w = shape
-    x = to_ndhwc(rnd((n, 32, d, h, w), 501), torch.bfloat16)
+    x = to_ndhwc(rnd((n, 32, d, h, w), 501), dtype)
     wt = (rnd((32, 16, 3, 3, 3), 502, 0.06)).to(DEV)          # ConvTranspose3d layout [Cin, Cout, 3,3,3]
     wc = (rnd((16, 16, 3, 3, 3), 503, 0.08)).to(DEV)
     scale = (rnd((16,), 504).abs() + 0.5).to(DEV)
@@ -1250,34 +1332,40 @@ def test_fused_full_resolution_decoder_is_bit_identical_to_the_two_launches(shap
     alpha = torch.full((1,), slope, device=DEV)
     fine = (n, 2 * d, 2 * h, 2 * w, 16)
     # two launches
-    up_pack = ops.wpack(torch.bfloat16, 2, wt, 32, 16, 3, scale=scale)
-    cv_pack = ops.wpack(torch.bfloat16, 0, wc, 16, 16, 3)
-    hmid = torch.empty(fine, dtype=torch.bfloat16, device=DEV)
+    up_pack = ops.wpack(dtype, 2, wt, 32, 16, 3, scale=scale)
+    cv_pack = ops.wpack(dtype, 0, wc, 16, 16, 3)
+    hmid = torch.empty(fine, dtype=dtype, device=DEV)
     ops.convT3d_fwd(x, hmid, up_pack, None, ub, prelu_alpha=alpha)
     ref = torch.empty_like(hmid)
     ops.conv3d_fwd(hmid, ref, cv_pack, None, 0, cb, 3, 1, residual=hmid)
     # one launch
-    out = torch.full(fine, float("nan"), dtype=torch.bfloat16, device=DEV)
+    out = torch.full(fine, float("nan"), dtype=dtype, device=DEV)
     assert ops.dectop_ok(x, out)
-    ops.dectop_fwd(x, out, ops.dectop_up_frag(wt, scale), ub, alpha, cv_pack, cb, alpha_in_unit_range=0.0 <= slope <= 1.0)
+    ops.dectop_fwd(x, out, ops.dectop_up_frag(wt, scale, dtype=dtype), ub, alpha, cv_pack, cb, alpha_in_unit_range=0.0 <= slope <= 1.0)
     torch.cuda.synchronize()
     assert bool(torch.isfinite(out.float()).all())
     assert torch.equal(out, ref), f"max diff {float((out.float() - ref.float()).abs().max())}"
     if 0.0 <= slope <= 1.0:        # the generic PReLU path gives the same bits
-        out2 = torch.full(fine, float("nan"), dtype=torch.bfloat16, device=DEV)
-        ops.dectop_fwd(x, out2, ops.dectop_up_frag(wt, scale), ub, alpha, cv_pack, cb, alpha_in_unit_range=False)
+        out2 = torch.full(fine, float("nan"), dtype=dtype, device=DEV)
+        ops.dectop_fwd(x, out2, ops.dectop_up_frag(wt, scale, dtype=dtype), ub, alpha, cv_pack, cb, alpha_in_unit_range=False)
         torch.cuda.synchronize()
         assert torch.equal(out2, ref)
-    # independent check of the pair against torch (oracle semantics), bf16 tolerance
+    # independent check of the pair against torch (oracle semantics), 16-bit tolerance
     xr = from_ndhwc(x)
-    hq = F.prelu(F.conv_transpose3d(xr, q(wt.cpu() * scale.cpu().view(1, -1, 1, 1, 1), torch.bfloat16), ub.cpu(),
+    hq = F.prelu(F.conv_transpose3d(xr, q(wt.cpu() * scale.cpu().view(1, -1, 1, 1, 1), dtype), ub.cpu(),
                                     stride=2, padding=1, output_padding=1), alpha.cpu())
-    hq = q(hq, torch.bfloat16)
-    want = F.conv3d(hq, q(wc.cpu(), torch.bfloat16), cb.cpu(), padding=1) + hq
-    assert relerr(from_ndhwc(out), want) < BF16_RTOL
+    hq = q(hq, dtype)
+    want = F.conv3d(hq, q(wc.cpu(), dtype), cb.cpu(), padding=1) + hq
+    assert relerr(from_ndhwc(out), want) < tol(dtype)
     # shapes the kernel does not take are refused by the query
-    bad = torch.empty((n, 2 * d, 2 * h + 2, 2 * w, 16), dtype=torch.bfloat16, device=DEV)
+    bad = torch.empty((n, 2 * d, 2 * h + 2, 2 * w, 16), dtype=dtype, device=DEV)
     assert not ops.dectop_ok(x, bad)
+
+
+@pytest.mark.parametrize("slope", [0.25, 1.7, -0.3])
+@pytest.mark.parametrize("shape", [(2, 8, 16, 16), (1, 16, 24, 32), (3, 6, 8, 40), (1, 2, 8, 8)])
+def test_fused_full_resolution_decoder_is_bit_identical_to_the_two_launches_f16(shape, slope):
+    test_fused_full_resolution_decoder_is_bit_identical_to_the_two_launches(shape, slope, dtype=F16)
 
 
 WS_WGRAD_CASES = [
@@ -1298,15 +1386,15 @@ WS_WGRAD_CASES = [
 
 
 @pytest.mark.parametrize("case", WS_WGRAD_CASES)
-def test_wave_specialised_wgrad_matches_torch(case):
+def test_wave_specialised_wgrad_matches_torch(case, dtype=torch.bfloat16):
     cin, cout, k, s, sp, n = case
     x = rnd((n, cin) + sp, 331)
     osp = tuple((d + 2 - k) // s + 1 for d in sp)
     dy = rnd((n, cout) + osp, 332)
     w0 = torch.zeros((cout, cin, k, k, k), requires_grad=True)
     b0 = torch.zeros((cout,), requires_grad=True)
-    F.conv3d(q(x, torch.bfloat16), w0, b0, stride=s, padding=1).backward(q(dy, torch.bfloat16))
-    xd, dyd = to_ndhwc(x, torch.bfloat16), to_ndhwc(dy, torch.bfloat16)
+    F.conv3d(q(x, dtype), w0, b0, stride=s, padding=1).backward(q(dy, dtype))
+    xd, dyd = to_ndhwc(x, dtype), to_ndhwc(dy, dtype)
     dw = torch.empty_like(w0, device=DEV)
     db = torch.empty_like(b0, device=DEV)
     ws = torch.empty(ops.conv3d_wgrad_workspace(xd, dyd, k, s), dtype=torch.uint8, device=DEV)
@@ -1315,7 +1403,7 @@ def test_wave_specialised_wgrad_matches_torch(case):
     assert relerr(dw.cpu(), w0.grad) < 5e-5
     assert relerr(db.cpu(), b0.grad) < 5e-5
     # a channel-slice view (ld > c) of a wider buffer as X: the buffer descriptor covers the view
-    wide = torch.zeros(xd.shape[:4] + (2 * cin,), dtype=torch.bfloat16, device=DEV)
+    wide = torch.zeros(xd.shape[:4] + (2 * cin,), dtype=dtype, device=DEV)
     wide[..., cin:] = xd
     ops.conv3d_wgrad(wide[..., cin:], dyd, dw, None, k, s, ws)
     torch.cuda.synchronize()
@@ -1332,6 +1420,11 @@ def test_wave_specialised_wgrad_matches_torch(case):
     ops.conv3d_wgrad(xd, dyd, dw_tf, None, k, s, ws, in_tf=(scale, shift, alpha))
     torch.cuda.synchronize()
     assert torch.equal(dw_ref, dw_tf)
+
+
+@pytest.mark.parametrize("case", WS_WGRAD_CASES)
+def test_wave_specialised_wgrad_matches_torch_f16(case):
+    test_wave_specialised_wgrad_matches_torch(case, dtype=F16)
 
 
 def test_wgrad_of_an_operand_past_the_4GiB_descriptor_is_cut_along_the_batch():
@@ -1389,7 +1482,7 @@ FIN_CONV_CASES = [
 ]
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", FIN_CONV_CASES)
 def test_bn_statistics_finalised_by_the_producing_launch(case, dtype):
     """segmi_bn_fin (csrc/fin_tail.h): the convolution that writes the statistics rows also finalises
@@ -1440,13 +1533,12 @@ def test_bn_statistics_finalised_by_the_producing_launch(case, dtype):
 
 @pytest.mark.parametrize("case", [(16, 32, (32, 34, 66), 2), (32, 64, (16, 32, 32), 2), (64, 128, (8, 16, 16), 3),
                                   (16, 16, (16, 32, 64), 1)])
-def test_training_pair_of_a_residual_units_stride2_convolutions_is_the_two_launches(case):
+def test_training_pair_of_a_residual_units_stride2_convolutions_is_the_two_launches(case, dtype=torch.bfloat16):
     """segmi_conv3d_fwd_split_act in training: the first subunit's convolution (with its BatchNorm statistics and
     their finalisation) and the residual convolution of one input as ONE launch over a pack built from the two
     parameter tensors (segmi_wpack_desc.w_src2) -- the output halves are the two launches' tensors bit for bit, the
     statistics are those of the first half alone (same rows, same finalisation)."""
     cin, c, sp, n = case
-    dtype = torch.bfloat16
     xd = to_ndhwc(rnd((n, cin) + sp, 41), dtype)
     wa = rnd((c, cin, 3, 3, 3), 42, 1.0 / math.sqrt(cin * 27)).to(DEV)
     wb = rnd((c, cin, 3, 3, 3), 43, 1.0 / math.sqrt(cin * 27)).to(DEV)
@@ -1484,7 +1576,7 @@ def test_training_pair_of_a_residual_units_stride2_convolutions_is_the_two_launc
     cat = ops.wpack(dtype, 0, torch.cat([wa, wb], 0).contiguous(), cin, 2 * c, 3)
     assert torch.equal(cat, batch.packed[0])
     # the paired INPUT gradient: one transposed convolution over [dy_a | dy_b] with the kind-2 pack of the two
-    # sources = the sum of the two input gradients (f32 accumulation over 2c channels instead of two bf16-rounded
+    # sources = the sum of the two input gradients (f32 accumulation over 2c channels instead of two rounded
     # launches: tolerance), and that pack is the pack of the concatenated weight
     bd = ops.WpackBatch(dtype, [(2, wa, None, 2 * c, cin, 3, wb, c)])
     bd.run()
@@ -1496,7 +1588,7 @@ def test_training_pair_of_a_residual_units_stride2_convolutions_is_the_two_launc
     ops.convT3d_fwd(dy[..., c:], dx_two, ops.wpack(dtype, 2, wb, c, cin, 3), None, None)
     ops.convT3d_fwd(dy[..., :c], dx_two, ops.wpack(dtype, 2, wa, c, cin, 3), None, None, residual=dx_two)
     torch.cuda.synchronize()
-    assert relerr(from_ndhwc(dx_pair), from_ndhwc(dx_two)) < BF16_RTOL
+    assert relerr(from_ndhwc(dx_pair), from_ndhwc(dx_two)) < tol(dtype)
     # a bias table for both halves in one tensor (bias_b = None) gives the same tensor
     m2 = torch.empty_like(m)
     ops.conv3d_fwd_split_act(xd, m2, cat, torch.cat([ba, bb]).contiguous(), None, c, 3, 2)
@@ -1504,9 +1596,14 @@ def test_training_pair_of_a_residual_units_stride2_convolutions_is_the_two_launc
     assert torch.equal(m2, m)
 
 
-def test_bn_statistics_finalised_by_the_pair_launch():
+@pytest.mark.parametrize("case", [(16, 32, (32, 34, 66), 2), (32, 64, (16, 32, 32), 2), (64, 128, (8, 16, 16), 3),
+                                  (16, 16, (16, 32, 64), 1)])
+def test_training_pair_of_a_residual_units_stride2_convolutions_is_the_two_launches_f16(case):
+    test_training_pair_of_a_residual_units_stride2_convolutions_is_the_two_launches(case, dtype=F16)
+
+
+def test_bn_statistics_finalised_by_the_pair_launch(dtype=torch.bfloat16):
     cin, cout, sp, n, s = 1, 16, (20, 34, 70), 2, 2
-    dtype = torch.bfloat16
     xd = to_ndhwc(rnd((n, cin) + sp, 21), dtype)
     wa, wb = rnd((cout, cin, 3, 3, 3), 22, 0.2).to(DEV), rnd((cout, cin, 3, 3, 3), 23, 0.2).to(DEV)
     ba, bb = rnd((cout,), 24, 0.1).to(DEV), rnd((cout,), 25, 0.1).to(DEV)
@@ -1535,7 +1632,11 @@ def test_bn_statistics_finalised_by_the_pair_launch():
         assert float((a - g_).abs().max()) <= 1e-6 * float(a.abs().max()) + 1e-9
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_bn_statistics_finalised_by_the_pair_launch_f16():
+    test_bn_statistics_finalised_by_the_pair_launch(dtype=F16)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("c,sp,n", [(16, (16, 64, 64), 2), (64, (9, 10, 12), 2), (256, (8, 8, 8), 1), (3, (5, 6, 7), 2)])
 def test_bn_backward_sums_finalised_by_the_reduce_launch(c, sp, n, dtype):
     x = rnd((n, c) + sp, 31, 2.0)
@@ -1566,13 +1667,13 @@ def test_bn_backward_sums_finalised_by_the_reduce_launch(c, sp, n, dtype):
         assert torch.equal(g_, g2), name
 
 
-def test_bn_backward_sums_finalised_by_the_input_gradient_launch():
+def test_bn_backward_sums_finalised_by_the_input_gradient_launch(dtype=torch.bfloat16):
     """ring kernel MODE 4 (segmi_bn_bwd_sums) with its `fin`: the launch that produces the gradient and the
     partial rows also writes dgamma / dbeta / dalpha / coef"""
     n, d, h, w, c = 2, 32, 64, 128, 16
-    dyd = to_ndhwc(rnd((n, c, d, h, w), 41, 0.5), torch.bfloat16)
-    xd = to_ndhwc(rnd((n, c, d, h, w), 42, 2.0) + 0.3, torch.bfloat16)
-    pk = ops.wpack(torch.bfloat16, 1, rnd((c, c, 3, 3, 3), 43, 0.08).to(DEV), c, c, 3)
+    dyd = to_ndhwc(rnd((n, c, d, h, w), 41, 0.5), dtype)
+    xd = to_ndhwc(rnd((n, c, d, h, w), 42, 2.0) + 0.3, dtype)
+    pk = ops.wpack(dtype, 1, rnd((c, c, 3, 3, 3), 43, 0.08).to(DEV), c, c, 3)
     mean, invstd = (rnd((c,), 44) * 0.5).to(DEV), (rnd((c,), 45).abs() + 0.5).to(DEV)
     gamma, beta = (rnd((c,), 46) + 1.5).to(DEV), (rnd((c,), 47) * 0.3).to(DEV)
     alpha = torch.full((1,), 0.25, device=DEV)
@@ -1599,6 +1700,10 @@ def test_bn_backward_sums_finalised_by_the_input_gradient_launch():
         assert float((a - g_).abs().max()) <= 1e-6 * float(a.abs().max()) + 1e-9, name
 
 
+def test_bn_backward_sums_finalised_by_the_input_gradient_launch_f16():
+    test_bn_backward_sums_finalised_by_the_input_gradient_launch(dtype=F16)
+
+
 def test_ring_kernel_predicates_refuse_samples_beyond_its_32_bit_addressing():
     """the z-marching ring kernel addresses one sample with 32-bit offsets; samples beyond
     that must be routed to the 64-bit kernels by EVERY predicate (not fail in the launcher)."""
@@ -1621,7 +1726,7 @@ def test_ring_kernel_predicates_refuse_samples_beyond_its_32_bit_addressing():
     assert relerr(from_ndhwc(y), ref) < BF16_RTOL
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("c,sp,n,with_alpha", [(32, (32, 32, 32), 8, True), (64, (16, 16, 16), 8, True),
                                                (256, (8, 8, 8), 8, True), (128, (8, 8, 8), 2, False),
                                                (48, (5, 6, 7), 2, True), (16, (9, 10, 12), 1, True)])
@@ -1680,11 +1785,11 @@ def test_bn_backward_as_one_launch_matches_the_three_calls(c, sp, n, with_alpha,
 
 
 @pytest.mark.parametrize("max_wgs", [128, 40, 1])
-def test_bn_backward_one_launch_under_a_workgroup_cap(max_wgs):
+def test_bn_backward_one_launch_under_a_workgroup_cap(max_wgs, dtype=torch.bfloat16):
     """`max_wgs` of segmi_bn_act_bwd_fused: the engine caps the launch at the CUs the weight-gradient stream leaves
     free, so that every workgroup of the grid-wide hand-off is resident.  Any cap gives the sums of the three calls
     (another partition of the rows) and a finite dx; the launch never exceeds the cap or the device's capacity."""
-    c, sp, n, dtype = 32, (32, 32, 32), 4, torch.bfloat16
+    c, sp, n = 32, (32, 32, 32), 4
     x, dy = rnd((n, c) + sp, 71, 2.0), rnd((n, c) + sp, 72)
     xd, dyd = to_ndhwc(x, dtype), to_ndhwc(dy, dtype)
     mean, invstd = (rnd((c,), 73) * 0.5).to(DEV), (rnd((c,), 74).abs() + 0.5).to(DEV)
@@ -1711,6 +1816,11 @@ def test_bn_backward_one_launch_under_a_workgroup_cap(max_wgs):
     assert bool(torch.isfinite(dx1.float()).all())
     assert float((dx0.float() - dx1.float()).abs().max()) <= 1e-2 * float(dx0.float().abs().max())
     assert ops.fused_timeouts() == 0
+
+
+@pytest.mark.parametrize("max_wgs", [128, 40, 1])
+def test_bn_backward_one_launch_under_a_workgroup_cap_f16(max_wgs):
+    test_bn_backward_one_launch_under_a_workgroup_cap(max_wgs, dtype=F16)
 
 
 def test_bn_backward_one_launch_expiry_is_counted_and_raised():
@@ -1753,13 +1863,12 @@ def test_bn_backward_one_launch_expiry_is_counted_and_raised():
                                                              (1, (18, 20, 34), 64, True, True),
                                                              (1, (31, 33, 37), 16, False, True),
                                                              (2, (16, 24, 40), 32, True, False)])
-def test_bn_backward_apply_inside_the_stride2_convolution_equals_the_two_calls(n, sp, cout, with_alpha, with_affine):
+def test_bn_backward_apply_inside_the_stride2_convolution_equals_the_two_calls(n, sp, cout, with_alpha, with_affine, dtype=torch.bfloat16):
     """segmi_bn_act_bwd_apply_conv: the BatchNorm / PReLU backward apply computed while the stride-2
     convolution (a transposed convolution's input gradient) stages its halo tile.  dx and the convolution
     result must equal segmi_bn_act_bwd_apply followed by segmi_conv3d_fwd bit for bit -- odd extents cover
     partial tiles and the ownership rule (every dx voxel written exactly once)."""
     c = 16
-    dtype = torch.bfloat16
     x = rnd((n, c) + sp, 71, 2.0)
     dy = rnd((n, c) + sp, 72)
     xd, dyd = to_ndhwc(x, dtype), to_ndhwc(dy, dtype)
@@ -1790,6 +1899,14 @@ def test_bn_backward_apply_inside_the_stride2_convolution_equals_the_two_calls(n
     assert not ops.bn_act_bwd_apply_conv_ok(dyd.float(), xd.float(), dx1.float(), out1.float())
     with pytest.raises(Exception):
         ops.bn_act_bwd_apply_conv(dyd, xd, xd, mean, invstd, gamma, beta, alpha, coef, out1, pack)
+
+
+@pytest.mark.parametrize("n,sp,cout,with_alpha,with_affine", [(2, (32, 32, 32), 32, True, True),
+                                                             (1, (18, 20, 34), 64, True, True),
+                                                             (1, (31, 33, 37), 16, False, True),
+                                                             (2, (16, 24, 40), 32, True, False)])
+def test_bn_backward_apply_inside_the_stride2_convolution_equals_the_two_calls_f16(n, sp, cout, with_alpha, with_affine):
+    test_bn_backward_apply_inside_the_stride2_convolution_equals_the_two_calls(n, sp, cout, with_alpha, with_affine, dtype=F16)
 
 
 def test_cu_masked_stream_runs_kernels():
