@@ -558,6 +558,30 @@ int segmi_select_f32(const float* values, const int64_t* n, const int64_t* ranks
 int segmi_confusion_counts(const void* pred, const void* truth, int label_bytes, int64_t n, int k,
                            int64_t* cm, void* stream);
 
+
+/* ---------------------------------------------------------------- Nyul standardisation -- */
+/* Nyul-Udupa histogram standardisation, src/segmantic/seg/nyul_normalize.py.  x: contiguous f32
+ * [segments][seg_len] (one segment per channel, or the whole tensor as one); mask = x != 0 when
+ * nonzero, else every value.  2 <= n_quantiles <= 64.
+ * Landmarks of each segment: quantiles_host (HOST f64, sorted, in [0, 1]) of the masked values by
+ * linear interpolation between exact order statistics (-0.0 == +0.0), out landmarks f32 [segments]
+ * [n_quantiles] and counts i64 [segments] (masked values, NaN included).  Ranks and lerp follow
+ * torch.quantile's f32 arithmetic for counts <= 2^24 and numpy.quantile's f64 arithmetic above; a
+ * segment holding a masked NaN, or none, gets NaN landmarks.  Segmented, masked, multi-rank radix
+ * select (11 + 11 + 10 bits) with its state in the workspace: no host round trip.
+ * Replaces torch.quantile(img[mask], quantiles) of nyul_normalize.py:66-68. */
+int64_t segmi_nyul_workspace_bytes(int segments, int n_quantiles);
+int segmi_nyul_landmarks(const float* x, int segments, int64_t seg_len, int nonzero,
+                         const double* quantiles_host, int n_quantiles, float* landmarks, int64_t* counts,
+                         void* workspace, size_t ws_bytes, void* stream);
+/* In place, every masked value of a segment whose counts entry is non-zero (counts nullable = all):
+ * y = m[i]*x + b[i], i = clip(#{landmarks < x} - 1, 0, L-2), m[i] = (s[i+1]-s[i]) / (xp[i+1]-xp[i]),
+ * b[i] = s[i] - m[i]*xp[i] in f32, each operation rounded (no FMA); standard_scale_host HOST f32 [L].
+ * Duplicate landmarks give the reference's Inf / NaN.  Replaces interp1d + img[mask] = ... of
+ * nyul_normalize.py:28-43,70. */
+int segmi_nyul_apply(float* x, int segments, int64_t seg_len, int nonzero, const float* landmarks,
+                     const int64_t* counts, const float* standard_scale_host, int n_quantiles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

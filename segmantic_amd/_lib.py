@@ -171,6 +171,9 @@ SIGNATURES = {
     "segmi_select_workspace_bytes": (_i64, [_i]),
     "segmi_select_f32": (_i, [_P, _P, _P, _i, _P, _P, C.c_size_t, _P]),
     "segmi_confusion_counts": (_i, [_P, _P, _i, _i64, _i, _P, _P]),
+    "segmi_nyul_workspace_bytes": (_i64, [_i, _i]),
+    "segmi_nyul_landmarks": (_i, [_P, _i, _i64, _i, _P, _i, _P, _P, _P, C.c_size_t, _P]),
+    "segmi_nyul_apply": (_i, [_P, _i, _i64, _i, _P, _P, _P, _i, _P]),
 }
 
 

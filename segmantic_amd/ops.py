@@ -894,3 +894,51 @@ def confusion_counts(pred, truth, k, cm) -> None:
     _require_device(pred)
     check(lib.segmi_confusion_counts(_ptr(pred), _ptr(truth), label_bytes(pred), pred.numel(), int(k), _ptr(cm),
                                      _stream()), "confusion_counts")
+
+
+# ------------------------------------------------------------------ Nyul standardisation
+NYUL_MAX_LANDMARKS = 64
+
+
+def nyul_workspace_bytes(segments: int, n_quantiles: int) -> int:
+    return int(lib.segmi_nyul_workspace_bytes(int(segments), int(n_quantiles)))
+
+
+def nyul_landmarks(x: torch.Tensor, segments: int, nonzero: bool, quantiles, landmarks=None, counts=None,
+                   workspace=None):
+    """Quantile landmarks of each of ``segments`` equal slices of a contiguous f32 device tensor ``x``
+    (mask ``x != 0`` when ``nonzero``); ``quantiles`` is a host sequence, sorted, in [0, 1].
+    Returns (landmarks f32 [segments, L], counts i64 [segments]), both on the device."""
+    _require_device(x)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("nyul_landmarks expects contiguous float32")
+    if x.numel() == 0 or x.numel() % segments:
+        raise ValueError("nyul_landmarks: the tensor does not split into that many non-empty segments")
+    q = np.ascontiguousarray(np.asarray(quantiles, dtype=np.float64))
+    nq = q.size
+    if landmarks is None:
+        landmarks = torch.empty(segments, nq, dtype=torch.float32, device=x.device)
+    if counts is None:
+        counts = torch.empty(segments, dtype=torch.int64, device=x.device)
+    if workspace is None:
+        workspace = torch.empty(nyul_workspace_bytes(segments, nq), dtype=torch.uint8, device=x.device)
+    check(lib.segmi_nyul_landmarks(_ptr(x), int(segments), x.numel() // segments, int(bool(nonzero)),
+                                   q.ctypes.data_as(C.c_void_p), nq, _ptr(landmarks), _ptr(counts),
+                                   _ptr(workspace), workspace.numel(), _stream()), "nyul_landmarks")
+    return landmarks, counts
+
+
+def nyul_apply_(x: torch.Tensor, segments: int, nonzero: bool, landmarks, counts, standard_scale) -> torch.Tensor:
+    """in place: the piecewise-linear map of each segment's landmarks onto ``standard_scale`` (host
+    sequence) for its masked values; segments whose ``counts`` entry is 0 are untouched (None: none is)."""
+    _require_device(x)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("nyul_apply_ expects contiguous float32")
+    if x.numel() == 0 or x.numel() % segments:
+        raise ValueError("nyul_apply_: the tensor does not split into that many non-empty segments")
+    s = np.ascontiguousarray(np.asarray(standard_scale, dtype=np.float32))
+    if landmarks.dtype != torch.float32 or not landmarks.is_contiguous() or landmarks.numel() != segments * s.size:
+        raise ValueError("nyul_apply_: landmarks must be contiguous float32 [segments, len(standard_scale)]")
+    check(lib.segmi_nyul_apply(_ptr(x), int(segments), x.numel() // segments, int(bool(nonzero)), _ptr(landmarks),
+                               _ptr(counts), s.ctypes.data_as(C.c_void_p), s.size, _stream()), "nyul_apply")
+    return x
