@@ -61,5 +61,5 @@ for role in roles:
         e1.record(); torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1) * 1e3)
     ts.sort()
-    print(f"ring3={os.environ.get('SEGMI_RING3', '1')} xcd={os.environ.get('SEGMI_RING3_XCD', '-')} zs={os.environ.get('SEGMI_RING_ZS', '1')} S={S} dbg={os.environ.get('SEGMI_RING3_DBG', '0'):>2} N={n} {role:10s}: "
+    print(f"ring3={os.environ.get('SEGMI_RING3', '1')} xcd={os.environ.get('SEGMI_RING3_XCD', '-')} S={S} dbg={os.environ.get('SEGMI_RING3_DBG', '0'):>2} N={n} {role:10s}: "
           f"median {ts[5]:7.1f} us  min {ts[0]:7.1f}", flush=True)

@@ -5,7 +5,7 @@
 #include "convt_ps_impl.h"
 namespace segmi {
 int conv_mfma_f32(const ConvParams& p, int ksize, int stride, hipStream_t st) {
-  if (conv_ks_ok(SEGMI_F32, p.Cin, ksize, stride)) return launch_conv_ks_t<float, 16>(p, stride, st);
+  if (conv_ks_ok(SEGMI_F32, p.Cin, ksize, stride)) return launch_conv_ks_t<float, 16>(p, st);
   return launch_conv_mfma_t<float>(p, ksize, stride, st);
 }
 int convt_mfma_f32(const ConvTParams& p, hipStream_t st) {

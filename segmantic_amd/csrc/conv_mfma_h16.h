@@ -14,7 +14,7 @@ static int conv_mfma_h16(const ConvParams& p, int ksize, int stride, hipStream_t
   constexpr int dt = DtypeOf<T>::value;
   if (conv_ring_zsplit(dt, p.Cin, ksize, stride, p.N, p.Do, p.Ho, p.Wo) > 0)
     return conv_ring3_ok(p) ? launch_conv_ring3<T>(p, st) : launch_conv_ring2<T>(p, st);
-  if (conv_ks_ok(dt, p.Cin, ksize, stride)) return launch_conv_ks_t<T, 32>(p, stride, st);
+  if (conv_ks_ok(dt, p.Cin, ksize, stride)) return launch_conv_ks_t<T, 32>(p, st);
   return launch_conv_mfma_t<T>(p, ksize, stride, st);
 }
 template <typename T>

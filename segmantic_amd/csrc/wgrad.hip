@@ -246,7 +246,7 @@ int segmi_conv3d_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float
       p.N = xs.n; p.Dx = x->d; p.Hx = x->h; p.Wx = x->w; p.Dy = dy->d; p.Hy = dy->h; p.Wy = dy->w;
       p.Cin = x->c; p.Cout = dy->c; p.ldx = x->ld; p.ldy = dy->ld;
       if (in_tf) { p.in_scale = in_tf->scale; p.in_shift = in_tf->shift; p.in_alpha = in_tf->prelu_alpha; }
-      const int ct = wgrad_ct_for(dtype, &xs, &ys, ksize, stride, cus);
+      const int ct = wgrad_ct(dtype, ys.c);
       const bool ws = wgrad_ws_gx(dtype, &xs, &ys, ksize, stride, cus) > 0;
       const int rc = dtype == SEGMI_F32   ? wgrad_mfma_f32(p, ksize, stride, ct, gx, st)
                      : dtype == SEGMI_F16 ? wgrad_mfma_f16(p, ksize, stride, ws ? -ct : ct, gx, st)
@@ -269,15 +269,9 @@ int segmi_conv3d_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float
   }
   const int rb = (int)(cdiv64(nout, 256) > 2048 ? 2048 : cdiv64(nout, 256));
   float* gsum = (float*)((char*)workspace + align256((int64_t)slabs * nout * 4));
-  static const bool two_launches = getenv("SEGMI_SLAB_REDUCE2") && atoi(getenv("SEGMI_SLAB_REDUCE2")) == 1;   // A/B
-  if (slabs > 2 * kSlabGroups && !two_launches) {
+  if (slabs > 2 * kSlabGroups) {
     const int fb = (int)(cdiv64(nout, 64) > 4096 ? 4096 : cdiv64(nout, 64));
     hipLaunchKernelGGL(slab_reduce_fused_kernel, dim3(fb), 1024, 0, st, (const float*)partials, slabs, nout, dw);
-  } else if (slabs > 2 * kSlabGroups) {
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(rb, kSlabGroups), 256, 0, st, (const float*)partials,
-                       slabs, nout, gsum);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(rb, 1), 256, 0, st, (const float*)gsum, kSlabGroups,
-                       nout, dw);
   } else {
     hipLaunchKernelGGL(slab_reduce_kernel, dim3(rb, 1), 256, 0, st, (const float*)partials, slabs,
                        nout, dw);

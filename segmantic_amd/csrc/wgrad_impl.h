@@ -347,25 +347,14 @@ static inline int wgrad_tiles(const segmi_act* dy, int stride, bool one_block) {
   return dy->n * cdiv(dy->d, td) * cdiv(dy->h, th) * cdiv(dy->w, tw);
 }
 // channel blocking of one workgroup, encoded 10*CTO + CTI (16-channel tiles of dY x of X).
-// bf16 only: 2x2 when both channel counts allow it; with 16 input channels (the wide layers,
-// where X is the big tensor) 2 output tiles share one staging of X (4x1 measured slower: 360
-// VGPRs).
-static inline int wgrad_ct(int dtype, int cin, int cout) {
-  if (!dtype_h16(dtype)) return 11;
-  if (cin % 32 == 0 && cout % 32 == 0) return 22;
-  if (cin % 32 == 0) return 11;
-  if (cout % 32 == 0) return 21;
-  return 11;
-}
-// ---- wave-specialised kernel (wgrad_ws_impl.h): bf16 k3 layers whose two tile buffers fit one CU
-// and that have enough tiles per workgroup for its pipeline to matter.  Encodes the choice made by
-// the launcher (wgrad_mfma_bf16) so that the workspace query sizes the same number of slabs.
-static inline bool wgrad_ws_cfg_ok(int stride, int ct) {
-  // 16-channel X (the wide, memory-bound layers).  2x2 channel tiles: stride 1 measured 2x slower
-  // than wgrad_mfma_kernel on 32x32 @ 32^3 (latency-bound, 16 tiles per workgroup); stride 2 does
-  // not fit (2 x 103 KB of LDS)
-  (void)stride;
-  return ct == 11 || ct == 21;
+// bf16 / fp16 only: 2 output tiles share one staging of X when the output channels allow it (4x1
+// measured slower: 360 VGPRs).  Layers with >= 32 input and output channels took the 2 x 2 tile
+// (220 VGPRs, one workgroup per CU) until round 4; with the 2 x 1 tile (the wave-specialised kernel
+// where the layer has the tiles for it, wgrad_mfma_kernel's 2 x 1 form elsewhere) the training step
+// went 4.98 -> 4.75 ms and the 160^3 / 32-label step at batch 4 11.1 -> 9.9 ms, alternating runs (the
+// operand read twice costs less than the 2 x 2 tile's occupancy).
+static inline int wgrad_ct(int dtype, int cout) {
+  return dtype_h16(dtype) && cout % 32 == 0 ? 21 : 11;
 }
 // CUs the weight-gradient kernels size their grids for (the `cus` argument of segmi_conv3d_wgrad and of its
 // workspace query; SEGMI_WGRAD_CUS overrides).  These
@@ -373,10 +362,13 @@ static inline bool wgrad_ws_cfg_ok(int stride, int ct) {
 // EVERY CU the dependent chain of the main stream gets no CU until they retire; sized for half the chip the two
 // streams really run side by side (5.55 -> 5.28 ms per training step, round 3).
 int wgrad_cus(int cus);
-static inline int wgrad_ws_gx_ct(int dtype, const segmi_act* x, const segmi_act* dy, int ksize, int stride, int cus, int ct) {
+// ---- wave-specialised kernel (wgrad_ws_impl.h): bf16 k3 layers whose two tile buffers fit one CU
+// and that have enough tiles per workgroup for its pipeline to matter.  Encodes the choice made by
+// the launcher (wgrad_mfma_bf16) so that the workspace query sizes the same number of slabs.
+static inline int wgrad_ws_gx(int dtype, const segmi_act* x, const segmi_act* dy, int ksize, int stride, int cus) {
   static const bool enabled = !(getenv("SEGMI_WGRAD_WS") && atoi(getenv("SEGMI_WGRAD_WS")) == 0);
   if (!enabled || !dtype_h16(dtype) || ksize != 3) return 0;
-  if (!wgrad_ws_cfg_ok(stride, ct)) return 0;
+  const int ct = wgrad_ct(dtype, dy->c);
   const int cto = ct / 10, cti = ct % 10;
   const int chunks = (x->c / (16 * cti)) * (dy->c / (16 * cto));
   int gx = wgrad_cus(cus) / chunks / 8 * 8;        // one 768-thread workgroup per CU, a multiple of the 8 XCDs
@@ -389,43 +381,19 @@ static inline int wgrad_ws_gx_ct(int dtype, const segmi_act* x, const segmi_act*
   const int64_t nt = (int64_t)dy->n * cdiv(dy->d, td) * cdiv(dy->h, th) * cdiv(dy->w, tw);
   // raw buffer loads: 32-bit offsets / num_records over each tensor
   if (act_voxels(x) * x->ld * 2 >= 0xfff00000ll || act_voxels(dy) * dy->ld * 2 >= 0xfff00000ll) return 0;
-  static const int min_tiles = getenv("SEGMI_WGRAD_WS_MINT") ? atoi(getenv("SEGMI_WGRAD_WS_MINT")) : 4;   // A/B
-  return nt >= min_tiles * (int64_t)gx ? gx : 0;
-}
-// Channel tile of THIS layer.  Layers with >= 32 input and output channels took the 2 x 2 tile of wgrad_mfma_kernel
-// (220 VGPRs, one workgroup per CU) until round 4; with the 2 x 1 tile (32 output x 16 input channels per workgroup:
-// the wave-specialised kernel where the layer has the tiles for it, wgrad_mfma_kernel's 2 x 1 form elsewhere) the
-// training step went 4.98 -> 4.75 ms and the 160^3 / 32-label step at batch 4 11.1 -> 9.9 ms, alternating runs
-// (the operand read twice costs less than the 2 x 2 tile's occupancy).  SEGMI_WGRAD_CT22 (A/B): 22 = the 2 x 2 tile
-// as before (4.98), 2122 = 2 x 1 only where the wave-specialised kernel then takes the layer (4.79), 11 / 1122
-// likewise with 1 x 1 (4.82 / 4.82).
-static inline int wgrad_ct_for(int dtype, const segmi_act* x, const segmi_act* dy, int ksize, int stride, int cus) {
-  const int ct = wgrad_ct(dtype, x->c, dy->c);
-  if (ct != 22) return ct;
-  static const int mode = getenv("SEGMI_WGRAD_CT22") ? atoi(getenv("SEGMI_WGRAD_CT22")) : 21;
-  if (mode == 21 || mode == 11) return mode;
-  if (mode == 2122 || mode == 1122) {
-    const int alt = mode / 100;
-    return wgrad_ws_gx_ct(dtype, x, dy, ksize, stride, cus, alt) > 0 ? alt : 22;
-  }
-  return ct;
-}
-static inline int wgrad_ws_gx(int dtype, const segmi_act* x, const segmi_act* dy, int ksize, int stride, int cus) {
-  return wgrad_ws_gx_ct(dtype, x, dy, ksize, stride, cus, wgrad_ct_for(dtype, x, dy, ksize, stride, cus));
+  return nt >= 4 * (int64_t)gx ? gx : 0;           // at least 4 tiles per workgroup
 }
 static inline int wgrad_gx(int dtype, const segmi_act* x, const segmi_act* dy, int ksize, int stride, int cus_arg) {
   const int ws = wgrad_ws_gx(dtype, x, dy, ksize, stride, cus_arg);
   if (ws > 0) return ws;
-  const int ct = wgrad_ct_for(dtype, x, dy, ksize, stride, cus_arg);
+  const int ct = wgrad_ct(dtype, dy->c);
   const int cto = ct / 10, cti = ct % 10;
   const int chunks = (x->c / (16 * cti)) * (dy->c / (16 * cto));
   // workgroups wanted = a multiple of the 256 CUs; one per CU once the kernel holds > 1 channel
   // tile (200-400 VGPRs, 55-110 KB slabs).  Measured on MI355X: 1x1 blocks
   // 704/508/540/608 us at 256/512/1024/2048 workgroups, 2x2 blocks 125/198/348 us at 256/512/1024.
-  static const int mfma_env = getenv("SEGMI_WGRAD_CUS_MFMA") ? atoi(getenv("SEGMI_WGRAD_CUS_MFMA")) / 8 * 8 : 0;   // experiments
-  const int cus = mfma_env >= 8 ? mfma_env : wgrad_cus(cus_arg);
-  static const int mul21 = getenv("SEGMI_WGRAD_MUL21") ? atoi(getenv("SEGMI_WGRAD_MUL21")) : 1;             // A/B
-  const int target = cto * cti == 1 ? 2 * cus : (cto * cti == 2 ? mul21 * cus : cus);
+  const int cus = wgrad_cus(cus_arg);
+  const int target = cto * cti == 1 ? 2 * cus : cus;
   int gx = target / chunks;
   if (gx < 1) gx = 1;
   const int nt = wgrad_tiles(dy, stride, cto * cti == 1);
@@ -447,17 +415,14 @@ static int launch_wgrad_mfma_t(const WgradParams& p, int ksize, int stride, int 
   const bool wide = p.Wy > 8;
   if (ksize == 1) {
     if constexpr (sizeof(T) == 2) {
-      if (ct == 22) WG_CFG(1, 1, 2, 2);
       if (ct == 21) WG_CFG(1, 1, 2, 1);
     }
     WG_CFG(1, 1, 1, 1);
   }
   if constexpr (sizeof(T) == 2) {
     if (stride == 1) {
-      if (ct == 22) WG_CFG(3, 1, 2, 2);
       if (ct == 21) WG_CFG(3, 1, 2, 1);
     } else {
-      if (ct == 22) WG_CFG(3, 2, 2, 2);
       if (ct == 21) WG_CFG(3, 2, 2, 1);
     }
   }

@@ -12,7 +12,7 @@ wait, so two users of one stream gain ordering between their launches, never los
 
     0  weight gradients (training)      | inference lane 0
     1  weight re-pack (training)        | inference lane 1
-    2  residual branch / batch sampler  | inference lane 2
+    2  batch sampler                    | inference lane 2
     3  gradient buckets (data-parallel) | ordered blend of the sliding-window driver
     4+ further inference lanes
 """

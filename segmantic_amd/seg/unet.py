@@ -231,22 +231,6 @@ class _Conv:
         self._packs[key] = (ver, buf)
         return buf
 
-    def pair_dgrad_pack(self):
-        """input-gradient operand of the pair: ONE transposed convolution over [dy of this conv | dy of pair_with]
-        (2 cout input channels)"""
-        key = ("pair_dgrad", self.eng.dtype)
-        ver = self.eng.weights_version
-        if self.eng._packed_version != ver:
-            self.eng._repack_all()
-        self.eng._await_packs()
-        hit = self._packs.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        cat = torch.cat([self.w, self.pair_with.w], 0).contiguous()
-        buf = ops.wpack(self.eng.dtype, 2, cat, 2 * self.cout, self.cin, 3, out=hit[1] if hit is not None else None)
-        self._packs[key] = (ver, buf)
-        return buf
-
     # eval mode: BatchNorm folded into the weights (scale) and bias
     def folded(self, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor]):
         ver = self.eng.weights_version
@@ -465,9 +449,6 @@ class UNetEngine:
                 if conv.pair_with is not None and self.pair_train and conv not in self._carry_convs:
                     entries.append((0, conv.w, None, conv.cin, 2 * conv.cout, conv.k, conv.pair_with.w, conv.cout))
                     slots.append((conv, ("pair", self.dtype)))
-                    if self.pair_bwd:
-                        entries.append((2, conv.w, None, 2 * conv.cout, conv.cin, 3, conv.pair_with.w, conv.cout))
-                        slots.append((conv, ("pair_dgrad", self.dtype)))
             self._wbatch = {c: ((ops.WpackBatch(self.dtype, e), sl) if e else (None, [])) for c, (e, sl) in groups.items()}
         for carried in (False, True):
             if carried and self._tail_packed_version == ver:
@@ -654,27 +635,6 @@ class UNetEngine:
     # one and two levels down.  The eval pairing with BatchNorm statistics on the first half (round 4) runs them as
     # one launch each.  SEGMI_PAIR_TRAIN=0: two launches (A/B).
     pair_train = os.environ.get("SEGMI_PAIR_TRAIN", "1") != "0"
-    # ... and their input gradients as ONE transposed convolution over the two output gradients, which then live in
-    # the halves of one [.., 2c] buffer: the BatchNorm backward of subunit 0 writes the first half, the producer of
-    # the unit's output gradient (the level below) the second.  SEGMI_PAIR_BWD=0: two launches.
-    pair_bwd = pair_train and os.environ.get("SEGMI_PAIR_BWD", "1") != "0"
-
-    def _pair_grad_buf(self, ru, shape):
-        """[.., 2c] gradient buffer of a unit whose forward ran paired (this step), else None"""
-        c0 = ru["units"][0][0]
-        sv = self._saved.get(ru["prefix"])
-        if not self.pair_bwd or c0.pair_with is None or sv is None or not sv.get("tpair"):
-            return None
-        return self._buf(f"{ru['prefix']}.mg", tuple(shape[:4]) + (2 * c0.cout,))
-
-    def _dout_slot(self, ru, name, shape):
-        """where the gradient of a residual unit's OUTPUT is to be written: the second half of the unit's pair
-        buffer when its two stride-2 input gradients run as one launch, else the plain buffer `name`"""
-        mg = self._pair_grad_buf(ru, shape)
-        if mg is not None and shape[4] == ru["units"][0][0].cout:
-            return mg[..., shape[4]:]
-        return self._buf(name, shape)
-
     def _train_pair(self, ru, x, oshape):
         """the [.., 2c] buffer of the merged first subunit + residual convolution (training), or None"""
         c0 = ru["units"][0][0]
@@ -746,14 +706,8 @@ class UNetEngine:
         # concurrently with the dgrad / BatchNorm-backward chain of the main stream (the
         # mid / deep levels do not fill 256 CUs with one kernel at a time).  All wgrads share the
         # side stream, hence also their scratch buffer, in issue order.
-        if self._diag_skip_wgrad:      # diagnostics only: time the main chain without its side-stream partner
-            return
         if self._carry_open and conv in self._carry_convs:
             self._carried.append((conv, x, dy, need_bias, in_tf))     # issued after the end of backward
-            return
-        if self._defer_open:
-            # issued later, when the main chain is down in the small deep levels (see defer_top_wgrad)
-            self._deferred.append((conv, x, dy, need_bias, in_tf))
             return
         main = torch.cuda.current_stream()
         side = self._side_stream() if self.overlap_wgrad else None
@@ -784,13 +738,11 @@ class UNetEngine:
         # 32 -> 32 layers (BASELINE config 4): the kernel takes the sums (tested), this engine does not ask for them --
         # the variant that fits its registers computes the 32 outputs as two 16-channel tiles on grid.y and the
         # 160^3 / batch 4 step went 9.75 -> 10.2 ms with it (both tiles in one workgroup: 96 spilled registers,
-        # 10.9 ms).  SEGMI_BSUM32=1 asks for them anyway (A/B).
+        # 10.9 ms).
         return (bn is not None and self.fuse_bn_bwd and self.dtype in _HALF and self.dropout_p <= 0.0
                 and not conv.transposed and conv.stride == 1 and conv.k == 3 and conv.mfma
-                and (conv.cout == 16 or self._bsum32)
+                and conv.cout == 16
                 and ops.conv3d_bn_bwd_sums_ok(dy, dx, 3, 1))
-
-    _bsum32 = os.environ.get("SEGMI_BSUM32", "0") == "1"
 
     def _dgrad(self, conv: _Conv, dy, dx, residual=None, bsum=None):
         """dx = dgrad(conv, dy) (+ residual).  ``bsum`` = (bn, x_raw): also the partial rows of that
@@ -869,9 +821,7 @@ class UNetEngine:
         cur = x
         nun = len(ru["units"])
         saved = {"x": x}
-        # residual branch straight into `out` (read back as the epilogue residual of the last
-        # unit); it is independent of the conv-unit chain, so it runs on a side stream
-        br = None
+        # residual branch straight into `out` (read back as the epilogue residual of the last unit)
         paired = False
         tpair = None
         if ru["res"] is not None:
@@ -880,9 +830,7 @@ class UNetEngine:
             if not paired and in_tf is None:
                 tpair = self._train_pair(ru, x, (n, d, h, w))
             if not paired and tpair is None:
-                br = self._fork_branch()
-                with torch.cuda.stream(br) if br is not None else _NullCtx():
-                    ops.conv3d_fwd(x, out, rc.fwd_pack(), rc.w, 0, rc.b, rc.k, rc.stride)
+                ops.conv3d_fwd(x, out, rc.fwd_pack(), rc.w, 0, rc.b, rc.k, rc.stride)
             resid = out
         else:
             resid = x
@@ -926,7 +874,6 @@ class UNetEngine:
                                     bn.rv, self.momentum, self.eps, bn.mean, bn.invstd, bn.scale, bn.shift)
                 saved[f"in{i}"] = cur
                 saved[f"r{i}"] = r
-                saved["tpair"] = True
                 nconv = ru["units"][i + 1][0]
                 if self._tf_ok(r, r, nconv) and nconv.cin == conv.cout and nconv.cout == conv.cout:
                     in_tf = (bn.scale, bn.shift, bn.alpha)
@@ -938,7 +885,6 @@ class UNetEngine:
                 continue
             if bn is None:
                 # conv-only last unit (top of the net): out = conv(cur) + residual
-                self._join_branch(br)
                 self._timed(conv.prefix + ":fwd", ops.conv3d_fwd, cur, out, conv.fwd_pack(), conv.w,
                             0, conv.b, conv.k, conv.stride, residual=resid, in_tf=in_tf)
                 saved[f"in{i}"] = cur
@@ -951,7 +897,6 @@ class UNetEngine:
             saved[f"tf{i}"] = in_tf
             in_tf = None
             if last:
-                self._join_branch(br)
                 ops.bn_act_fwd(r, out, bn.scale, bn.shift, bn.alpha, residual=resid, dropout=bn.drop())
             else:
                 nconv = ru["units"][i + 1][0]
@@ -976,19 +921,10 @@ class UNetEngine:
         x = sv["x"]
         nun = len(ru["units"])
         rc = ru["res"]
-        # paired input gradients: dout is the second half of the unit's [.., 2c] gradient buffer (the caller got it
-        # from _dout_slot), subunit 0's BatchNorm backward writes the first half, ONE transposed convolution over the
-        # buffer replaces the two input-gradient launches
-        mg = self._pair_grad_buf(ru, dout.shape) if (rc is not None and dx is not None) else None
-        if mg is not None and dout.data_ptr() != mg[..., dout.shape[4]:].data_ptr():
-            mg = None
-        # the residual conv's input gradient depends only on dout: side stream, joined before
-        # the first unit's dgrad accumulates on top of it
-        br = None
-        if rc is not None and dx is not None and mg is None:
-            br = self._fork_branch()
-            with torch.cuda.stream(br) if br is not None else _NullCtx():
-                self._dgrad(rc, dout, dx, residual=extra)
+        # the residual conv's input gradient depends only on dout: it goes into dx first, the first
+        # unit's dgrad accumulates on top of it
+        if rc is not None and dx is not None:
+            self._dgrad(rc, dout, dx, residual=extra)
         g = dout            # gradient flowing back through the conv branch
         g_rows = 0          # > 0: the launch that wrote g also wrote the next BatchNorm's reduction rows
         for i in range(nun - 1, -1, -1):
@@ -996,7 +932,7 @@ class UNetEngine:
             xin = sv[f"in{i}"]
             if bn is not None:
                 r = sv[f"r{i}"]
-                dr = mg[..., :r.shape[4]] if (mg is not None and i == 0) else self._buf(f"{pre}.dr{i}", r.shape)
+                dr = self._buf(f"{pre}.dr{i}", r.shape)
                 self._bn_bwd(bn, g, r, dr, sums_rows=g_rows)
             else:
                 dr = g
@@ -1020,12 +956,8 @@ class UNetEngine:
         if dx is None:
             return 0
         conv0 = ru["units"][0][0]
-        if mg is not None:
-            ops.convT3d_fwd(mg, dx, conv0.pair_dgrad_pack(), None, None, residual=extra)
-            return 0
         bsum = dx_bn if dx_bn is not None and self._bsum_ok(conv0, first_dr, dx, dx_bn[0]) else None
         if rc is not None:
-            self._join_branch(br)
             return self._dgrad(conv0, first_dr, dx, residual=dx, bsum=bsum) or 0
         # identity residual: dx = dgrad(conv0) + dout (+ extra)
         if extra is not None:
@@ -1036,7 +968,6 @@ class UNetEngine:
     def _ru_fwd_eval(self, ru, x, out):
         pre = ru["prefix"]
         n, d, h, w = self._down_shape(x.shape, ru["stride"])
-        br = None
         paired = False
         merged = None
         if ru["res"] is not None:
@@ -1046,9 +977,7 @@ class UNetEngine:
                 raise RuntimeError("window views need the first-layer pair kernel (window_views_ok said yes?)")
             merged = None if paired else self._merged_eval(ru, x, (n, d, h, w))
             if not paired and merged is None:
-                br = self._fork_branch()
-                with torch.cuda.stream(br) if br is not None else _NullCtx():
-                    ops.conv3d_fwd(x, out, rc.fwd_pack(), rc.w, 0, rc.b, rc.k, rc.stride)
+                ops.conv3d_fwd(x, out, rc.fwd_pack(), rc.w, 0, rc.b, rc.k, rc.stride)
             resid = out
         else:
             resid = x
@@ -1073,15 +1002,12 @@ class UNetEngine:
                 cur = dst
                 continue
             if bn is None:
-                self._join_branch(br)
                 self._timed(conv.prefix + ":fwd", ops.conv3d_fwd, cur, out, conv.fwd_pack(), conv.w, 0,
                             conv.b, conv.k, conv.stride, residual=resid)
                 break
             sc, sh = bn.eval_affine()
             pack, wsrc, bias = conv.folded(sc, sh)
             dst = out if last else self._buf(f"{pre}.ea{i}", (n, d, h, w, conv.cout))
-            if last:
-                self._join_branch(br)
             ops.conv3d_fwd(cur, dst, pack, wsrc, 0, bias, conv.k, conv.stride,
                            prelu_alpha=bn.alpha, residual=resid if last else None)
             cur = dst
@@ -1153,15 +1079,6 @@ class UNetEngine:
             self._ru_fwd_eval(lvl["upru"], au, out)
 
     def _level_bwd(self, lvl, dout, dx=None, extra=None):
-        if self._defer_open and self._bwd_depth >= self.defer_flush_depth:
-            self._flush_deferred()
-        self._bwd_depth += 1
-        try:
-            self._level_bwd_body(lvl, dout, dx, extra)
-        finally:
-            self._bwd_depth -= 1
-
-    def _level_bwd_body(self, lvl, dout, dx=None, extra=None):
         p = lvl["prefix"]
         sv = self._saved[p + "up"]
         cat, u = sv["cat"], sv["u"]
@@ -1177,7 +1094,7 @@ class UNetEngine:
         if not conv_done:
             self._dgrad(up, du, dcat)
         d_down, d_sub = dcat[..., :c], dcat[..., c:]
-        dsum = self._dout_slot(lvl["down"], f"{p}ddown", (cat.shape[0], cat.shape[1], cat.shape[2], cat.shape[3], c))
+        dsum = self._buf(f"{p}ddown", (cat.shape[0], cat.shape[1], cat.shape[2], cat.shape[3], c))
         if lvl["sub"] is not None:
             self._level_bwd(lvl["sub"], d_sub, dx=dsum, extra=d_down)
         else:
@@ -1319,18 +1236,11 @@ class UNetEngine:
                 full = self._bufs["dlogits"]
                 full[..., :dlogits.shape[4]].copy_(dlogits)
             dlogits = full
-        self._deferred = []
-        self._defer_open = self.defer_top_wgrad and self.grad_hook is None and self.overlap_wgrad
         self._carried = []
-        self._carry_open = (carry and self.carry_top_wgrad and self.grad_hook is None and self.overlap_wgrad
-                            and not self._diag_skip_wgrad)
-        self._bwd_depth = 0
+        self._carry_open = carry and self.carry_top_wgrad and self.grad_hook is None and self.overlap_wgrad
         try:
             self._level_bwd(self.levels, dlogits)
-            if self._defer_open:                 # a net shallower than the flush depth
-                self._flush_deferred()
         finally:
-            self._defer_open = False
             carried, self._carry_open = self._carry_open, False
         self._top_bias_conv = None
         self._join_side()
@@ -1420,21 +1330,11 @@ class UNetEngine:
     # latency-bound levels of the main chain, which need CUs, not bandwidth.
     wgrad_cus_overlap = 128
 
-    # SEGMI_SIDE_CUS=k: the weight-gradient stream may use only k CUs (k / 8 per XCD; a CU-masked HIP
-    # stream) -- set SEGMI_WGRAD_CUS to the same value so the persistent kernels size their grids for it
-    _side_cus = int(os.environ.get("SEGMI_SIDE_CUS", "0") or 0)
-
     def _side_stream(self):
         if self._side is None:
-            if self._side_cus:
-                self._side = ops.cu_masked_stream(self._side_cus, self.device)
-            else:
-                self._side = streams.shared_stream(self.device, streams.WGRAD)
+            self._side = streams.shared_stream(self.device, streams.WGRAD)
         return self._side
 
-    # residual-branch overlap on a second side stream: measured neutral on MI355X (the branch
-    # convs are short and the join sits on the critical path), so it is off by default
-    overlap_branches = os.environ.get("SEGMI_OVERLAP_BRANCHES", "0") == "1"
     # BatchNorm-apply + PReLU folded into the consumer conv's staging where the kernels allow it
     # (segmi_in_affine); SEGMI_FUSE_BN=0 keeps the separate pass for A/B measurements
     fuse_bn_apply = os.environ.get("SEGMI_FUSE_BN", "1") != "0"
@@ -1444,70 +1344,14 @@ class UNetEngine:
     # BatchNorm / PReLU backward of the small (<= 32 MB) tensors as one launch with a grid-wide hand-off
     # instead of reduce -> apply (SEGMI_FUSE_BN_BWD_SMALL=0: two launches)
     fuse_bn_bwd_small = os.environ.get("SEGMI_FUSE_BN_BWD_SMALL", "1") != "0"
-    _fused_wgs_env = int(os.environ.get("SEGMI_FUSED_BN_WGS", "-1"))      # A/B: -1 = derive from the schedule
 
     def fused_bn_max_wgs(self) -> int:
         """workgroups the one-launch BatchNorm backward may hold: the CUs the weight-gradient stream's budget
         leaves free (0 = the device's capacity when nothing CU-exclusive runs beside it)"""
-        if self._fused_wgs_env >= 0:
-            return self._fused_wgs_env
         return max(8, 256 - ops.wgrad_cus(self.wgrad_cus_overlap)) if self.overlap_wgrad else 0
     # BatchNorm-backward reduction in the epilogue of the input-gradient launch that produces its
     # operand (segmi_bn_bwd_sums); SEGMI_FUSE_BN_BWD=0 keeps the separate two-tensor pass (A/B)
     fuse_bn_bwd = os.environ.get("SEGMI_FUSE_BN_BWD", "1") != "0"
-    # Single-GPU training: the weight gradients of the decoder levels above the deepest one (among them
-    # the persistent wgrad_ws launches of the two full-resolution levels, ~0.7 ms) are ISSUED only when
-    # the main chain enters the deepest level: beside the big bandwidth-bound input-gradient /
-    # BatchNorm-backward kernels of the upper levels they only take CUs and fabric away, beside the
-    # latency-bound 16^3 / 8^3 kernels they fill an idle chip.  5.64-5.72 vs 5.69-5.77 ms per step
-    # (alternating runs, one box; flushing one level earlier: no gain, at the very end: 6.2 ms).
-    # Not with a grad_hook (data parallel): the arena suffix would become final later and every gradient
-    # bucket with it (tried with the notifications held back until the flush: 5.89-5.94 vs 5.86-5.87 ms
-    # per step with the buckets going through RCCL on one rank).  SEGMI_DEFER_DEPTH overrides the level at which
-    # the queue is flushed.
-    # OFF by default since the weight-gradient kernels are sized for half the chip (wgrad_cus_overlap): they no
-    # longer take every CU away from the main chain, and the earlier they start the more of them hides --
-    # 5.20-5.29 without against 5.32-5.40 ms with the deferral, three alternating runs on one box, 5.17-5.23
-    # against 5.23-5.30 on another (`gpurun_out/r3/sched_ab.txt`, `sched2_ab.txt`).  SEGMI_DEFER_TOP_WGRAD=1: on.
-    defer_top_wgrad = os.environ.get("SEGMI_DEFER_TOP_WGRAD", "0") != "0"
-    _diag_skip_wgrad = os.environ.get("SEGMI_DIAG_SKIP_WGRAD") == "1"      # WRONG gradients: timing probes only
-    _defer_depth_env = os.environ.get("SEGMI_DEFER_DEPTH")
-
-    @property
-    def defer_flush_depth(self) -> int:
-        if self._defer_depth_env is not None:
-            return int(self._defer_depth_env)
-        depth, lvl = 0, self.levels
-        while lvl.get("sub") is not None:
-            depth, lvl = depth + 1, lvl["sub"]
-        return depth                                  # index of the deepest level
-    _defer_open = False
-    _deferred: list = []
-    _bwd_depth = 0
-
-    def _flush_deferred(self):
-        self._defer_open = False
-        todo, self._deferred = self._deferred, []
-        for conv, x, dy, need_bias, in_tf in todo:
-            self._wgrad(conv, x, dy, need_bias=need_bias, in_tf=in_tf)
-    _side2 = None
-
-    def _fork_branch(self):
-        """second side stream, ordered after the main stream's current point (None = disabled)"""
-        if not self.overlap_branches:
-            return None
-        if self._side2 is None:
-            self._side2 = streams.shared_stream(self.device, streams.AUX)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self._side2.wait_event(ev)
-        return self._side2
-
-    @staticmethod
-    def _join_branch(s):
-        if s is not None:
-            torch.cuda.current_stream().wait_stream(s)
-
     def _join_side(self):
         """main stream waits for every weight-gradient kernel issued so far"""
         if self._side is not None:

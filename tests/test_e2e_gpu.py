@@ -872,18 +872,17 @@ def test_convergence_matches_cpu_reference(golden_dir, record_property):
 
 
 @pytest.mark.parametrize("size,batch", [(64, 2), (128, 1)])
-def test_deferred_and_fused_schedules_leave_bit_identical_gradients(size, batch):
-    """the default training path re-orders side-stream launches (weight gradients of the upper
-    decoder levels issued late, SEGMI_DEFER_TOP_WGRAD) and holds operand buffers across levels; round 3
-    carries the weight gradients of the two full-resolution decoder convolutions (and the optimiser update
-    + re-pack of those layers) over the END of the step, beside the next forward.  None of it may change a
-    single bit of the gradient arena, of the updated weights, of a checkpoint taken right after a step or
-    of an eval forward: immediate issue, every flush depth and carry on / off give the same."""
+def test_carried_and_fused_schedules_leave_bit_identical_gradients(size, batch):
+    """the default training path re-orders side-stream launches and holds operand buffers across
+    levels; round 3 carries the weight gradients of the two full-resolution decoder convolutions (and the optimiser
+    update + re-pack of those layers) over the END of the step, beside the next forward.  None of it may change a
+    single bit of the gradient arena, of the updated weights, of a checkpoint taken right after a step or of an
+    eval forward: carry on / off, every carried depth and the separate BatchNorm-backward apply give the same."""
     K = 16
     img, lab = synthetic_batch(batch, size, K, seed=5)
     batch_d = {"image": img.to(DEV), "label": lab.to(DEV)}
 
-    def run(defer, depth=None, carry=False, steps=3, apply_conv=True, carry_levels=1):
+    def run(carry=False, steps=3, apply_conv=True, carry_levels=1):
         from segmantic_amd.seg.unet import UNetEngine
         _, net = pair(K, (16, 32, 64, 128, 256), (2, 2, 2, 2))
         net.mixed_precision = True
@@ -895,11 +894,8 @@ def test_deferred_and_fused_schedules_leave_bit_identical_gradients(size, batch)
         finally:
             UNetEngine.carry_levels = keep
         assert len(eng._carry_lvls) == carry_levels
-        eng.defer_top_wgrad = defer
         eng.carry_top_wgrad = carry
         eng.fuse_apply_conv = apply_conv
-        if depth is not None:
-            eng._defer_depth_env = str(depth)
         for _ in range(steps):
             net.training_step(batch_d)
         sd = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}    # reader of the arena: syncs by itself
@@ -910,24 +906,22 @@ def test_deferred_and_fused_schedules_leave_bit_identical_gradients(size, batch)
             y = net(batch_d["image"]).float().cpu()
         return eng.flat_grad.clone(), eng.flat.clone(), sd, y
 
-    g0, w0, sd0, y0 = run(False)
-    # (defer, flush depth, weight gradients of the full-resolution decoder carried into the next step)
-    for defer, depth, carry in ((True, None, False), (True, 0, False), (True, 2, False), (True, None, True),
-                                (False, None, True)):
-        g, w, sd, y = run(defer, depth, carry)
-        assert torch.equal(g0, g), (defer, depth, carry, float((g0 - g).abs().max()))
-        assert torch.equal(w0, w), (defer, depth, carry)
-        assert all(torch.equal(sd0[k], sd[k]) for k in sd0), (defer, depth, carry)
-        assert torch.equal(y0, y), (defer, depth, carry)
+    g0, w0, sd0, y0 = run()
+    # the weight gradients of the full-resolution decoder carried into the next step
+    g, w, sd, y = run(carry=True)
+    assert torch.equal(g0, g), ("carry", float((g0 - g).abs().max()))
+    assert torch.equal(w0, w), "carry"
+    assert all(torch.equal(sd0[k], sd[k]) for k in sd0), "carry"
+    assert torch.equal(y0, y), "carry"
     # the up paths of the two / three upper levels carried over the step boundary
     for lv in (2, 3):
-        g, w, sd, y = run(False, None, True, carry_levels=lv)
+        g, w, sd, y = run(carry=True, carry_levels=lv)
         assert torch.equal(g0, g), ("carry levels", lv, float((g0 - g).abs().max()))
         assert torch.equal(w0, w) and torch.equal(y0, y), ("carry levels", lv)
         assert all(torch.equal(sd0[k], sd[k]) for k in sd0), ("carry levels", lv)
     # the up layers' BatchNorm-backward apply as its own launch instead of inside the stride-2 convolution
     # that consumes it (segmi_bn_act_bwd_apply_conv): same bits
-    g, w, sd, y = run(True, None, True, apply_conv=False)
+    g, w, sd, y = run(carry=True, apply_conv=False)
     assert torch.equal(g0, g), ("apply_conv off", float((g0 - g).abs().max()))
     assert torch.equal(w0, w) and torch.equal(y0, y)
 
