@@ -582,6 +582,39 @@ int segmi_nyul_landmarks(const float* x, int segments, int64_t seg_len, int nonz
 int segmi_nyul_apply(float* x, int segments, int64_t seg_len, int nonzero, const float* landmarks,
                      const int64_t* counts, const float* standard_scale_host, int n_quantiles, void* stream);
 
+/* ---------------------------------------------------------------- vertebra landmarks -- */
+/* Landmark transforms of src/segmantic/detect/transforms.py.  Volumes are [C][d][h][w] = [C][z][y][x];
+ * points and boxes are reported in (x, y, z) order, as the reference's MONAI arrays [C][x][y][z] give them.
+ * Per-label centroid sums of a label volume (uint8 / int16 / int32 by label_bytes) in one read:
+ * sums i64 [k + 1][4] = (count, sum x, sum y, sum z) of labels 0 .. k (k <= 255); *flag (device i32) is
+ * set when a label lies outside [0, k].  Both are zeroed by the call.  Exact integer sums.
+ * Replaces the per-label torch.where + np.average of VertHeatMap, transforms.py:264-272. */
+int segmi_label_centroids(const void* labels, int label_bytes, int d, int h, int w, int k, int64_t* sums,
+                          int32_t* flag, void* stream);
+/* The vertebra heatmap out f32 [k + 1][d][h][w], written once, in closed form from the centroid sums and
+ * flag of segmi_label_centroids (read on the device: no host round trip).  params: device i32 words
+ * [0] = k, [1] = table stride S, [2] = gamma (f32 bits), [3] = 0, [4 + L] = tail t_L of label L (256
+ * words), then f32 tables [k + 1][S] from word 260: row L holds MONAI's gaussian_1d(sigma_L, 4.0, "erf")
+ * at -t_L .. t_L.  Channel L of a present label: centre c = floor(mean index), P = k_L[z - c_z] *
+ * k_L[y - c_y] * (smooth_3d ? k_L[x - c_x] : x == c_x) on the clipped support, then (P - min P) /
+ * (max P - min P) * gamma with min / max over the channel; channel 0, absent labels, constant channels
+ * and every channel when the flag is set are 0.
+ * Replaces the one-hot + GaussianSmooth + ScaleIntensity loop of VertHeatMap, transforms.py:256-281. */
+int segmi_vert_heatmap(const int32_t* params, int k, const int64_t* sums, const int32_t* flag, int d, int h,
+                       int w, int smooth_3d, float* out, void* stream);
+/* Per channel of x f32 [c][d][h][w] (d h w < 2^32): keys u64 [c] = orderable(max) << 32 | (0xFFFFFFFF -
+ * ((x h + y) d + z)) of the first maximum in (x, y, z) lexicographic order (-0.0 == +0.0; 0 when the
+ * channel holds only NaN); nan i32 [c] = 1 when the channel holds a NaN.  Both are zeroed by the call.
+ * Replaces the numpy max + np.where(== max) of ExtractVertPosition, transforms.py:198-202. */
+int segmi_channel_argmax(const float* x, int c, int d, int h, int w, uint64_t* keys, int32_t* nan,
+                         void* stream);
+/* Half-open box of the voxels > 0 in any channel of x [c][d][h][w] (f32 when is_float, else uint8 /
+ * int16 / int32 by dtype_bytes): box i32 [6] = (x0, y0, z0, x1, y1, z1); NaN and -0.0 are not positive;
+ * no positive voxel gives six zeros.
+ * Replaces generate_spatial_bounding_box of BoundingBoxd, transforms.py:231. */
+int segmi_positive_bbox(const void* x, int dtype_bytes, int is_float, int c, int d, int h, int w, int32_t* box,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

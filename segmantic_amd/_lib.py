@@ -174,6 +174,10 @@ SIGNATURES = {
     "segmi_nyul_workspace_bytes": (_i64, [_i, _i]),
     "segmi_nyul_landmarks": (_i, [_P, _i, _i64, _i, _P, _i, _P, _P, _P, C.c_size_t, _P]),
     "segmi_nyul_apply": (_i, [_P, _i, _i64, _i, _P, _P, _P, _i, _P]),
+    "segmi_label_centroids": (_i, [_P, _i, _i, _i, _i, _i, _P, _P, _P]),
+    "segmi_vert_heatmap": (_i, [_P, _i, _P, _P, _i, _i, _i, _i, _P, _P]),
+    "segmi_channel_argmax": (_i, [_P, _i, _i, _i, _i, _P, _P, _P]),
+    "segmi_positive_bbox": (_i, [_P, _i, _i, _i, _i, _i, _i, _P, _P]),
 }
 
 

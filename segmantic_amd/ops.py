@@ -942,3 +942,89 @@ def nyul_apply_(x: torch.Tensor, segments: int, nonzero: bool, landmarks, counts
     check(lib.segmi_nyul_apply(_ptr(x), int(segments), x.numel() // segments, int(bool(nonzero)), _ptr(landmarks),
                                _ptr(counts), s.ctypes.data_as(C.c_void_p), s.size, _stream()), "nyul_apply")
     return x
+
+
+# ------------------------------------------------------------------ vertebra landmarks
+LANDMARK_MAX_LABELS = 255
+HEATMAP_TAIL_OFFSET = 4        # words of the heatmap parameter buffer: k, stride, gamma, 0, tails[256], tables
+HEATMAP_TABLE_OFFSET = 4 + 256
+
+
+def _dense3(t: torch.Tensor, what: str):
+    """(d, h, w) of a contiguous [d, h, w] or [c, d, h, w] device tensor"""
+    _require_device(t)
+    if t.dim() not in (3, 4) or not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous [d, h, w] or [c, d, h, w] tensor")
+    return tuple(int(v) for v in t.shape[-3:])
+
+
+def label_centroids(labels, k, sums=None, flag=None):
+    """sums i64 [k + 1, 4] = (count, sum x, sum y, sum z) of labels 0 .. k of a [d, h, w] label volume read in
+    place; flag i32 [1] set when a label lies outside [0, k].  Both on the device, no host synchronisation."""
+    if labels.dim() != 3:
+        raise ValueError("label_centroids: labels are a contiguous [d, h, w] volume")
+    d, h, w = _labels3(labels)
+    if sums is None:
+        sums = torch.empty(int(k) + 1, 4, dtype=torch.int64, device=labels.device)
+    if flag is None:
+        flag = torch.empty(1, dtype=torch.int32, device=labels.device)
+    check(lib.segmi_label_centroids(_ptr(labels), label_bytes(labels), d, h, w, int(k), _ptr(sums), _ptr(flag),
+                                    _stream()), "label_centroids")
+    return sums, flag
+
+
+def vert_heatmap(params, k, sums, flag, shape_zyx, smooth_3d=False, out=None):
+    """out f32 [k + 1, *shape_zyx], the closed-form heatmap of the centroid sums of label_centroids;
+    params: the device parameter buffer (i32 words, see segmi.h)."""
+    d, h, w = (int(v) for v in shape_zyx)
+    if out is None:
+        out = torch.empty(int(k) + 1, d, h, w, dtype=torch.float32, device=sums.device)
+    if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (int(k) + 1, d, h, w):
+        raise ValueError("vert_heatmap: out must be contiguous float32 [k + 1, d, h, w]")
+    check(lib.segmi_vert_heatmap(_ptr(params), int(k), _ptr(sums), _ptr(flag), d, h, w, int(bool(smooth_3d)),
+                                 _ptr(out), _stream()), "vert_heatmap")
+    return out
+
+
+def channel_argmax(x: torch.Tensor, keys=None, nan=None):
+    """Per channel of a contiguous f32 [c, d, h, w] device tensor: keys u64 (as i64) [c] of the max and its
+    first (x, y, z) in lexicographic order, nan i32 [c]; decode with decode_argmax_keys."""
+    d, h, w = _dense3(x, "channel_argmax")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("channel_argmax: expected float32 [c, d, h, w]")
+    c = int(x.shape[0])
+    if keys is None:
+        keys = torch.empty(c, dtype=torch.int64, device=x.device)
+    if nan is None:
+        nan = torch.empty(c, dtype=torch.int32, device=x.device)
+    check(lib.segmi_channel_argmax(_ptr(x), c, d, h, w, _ptr(keys), _ptr(nan), _stream()), "channel_argmax")
+    return keys, nan
+
+
+def decode_argmax_keys(keys: np.ndarray, shape_zyx):
+    """host u64 keys of channel_argmax -> (max values f32 [c], indices i64 [c, 3] in (x, y, z) order)"""
+    d, h, _ = (int(v) for v in shape_zyx)
+    k = np.asarray(keys).astype(np.uint64)
+    hi = (k >> np.uint64(32)).astype(np.uint32)
+    bits = np.where(hi & np.uint32(0x80000000), hi & np.uint32(0x7FFFFFFF), ~hi).astype(np.uint32)
+    lex = (np.uint64(0xFFFFFFFF) - (k & np.uint64(0xFFFFFFFF))).astype(np.int64)
+    xyz = np.stack([lex // (h * d), (lex // d) % h, lex % d], axis=1)
+    return bits.view(np.float32), xyz
+
+
+_BBOX_DTYPES = {torch.float32: (4, 1), torch.uint8: (1, 0), torch.int16: (2, 0), torch.int32: (4, 0)}
+
+
+def positive_bbox(x: torch.Tensor, box=None):
+    """box i32 [6] = (x0, y0, z0, x1, y1, z1), the half-open box of the voxels > 0 of any channel of a
+    contiguous [d, h, w] or [c, d, h, w] device tensor (f32, uint8, int16 or int32)."""
+    d, h, w = _dense3(x, "positive_bbox")
+    try:
+        nbytes, is_float = _BBOX_DTYPES[x.dtype]
+    except KeyError:
+        raise ValueError(f"positive_bbox: float32, uint8, int16 or int32 data, not {x.dtype}")
+    c = int(x.shape[0]) if x.dim() == 4 else 1
+    if box is None:
+        box = torch.empty(6, dtype=torch.int32, device=x.device)
+    check(lib.segmi_positive_bbox(_ptr(x), nbytes, is_float, c, d, h, w, _ptr(box), _stream()), "positive_bbox")
+    return box
