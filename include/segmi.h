@@ -490,13 +490,17 @@ int segmi_intensity_augment(float* patches, int count, int rd, int rh, int rw, i
  * RandGibbsNoised (spectrum outside radius (1-alpha)*max(shape)*sqrt(2)/2 of the centred k-space
  * zeroed) then RandKSpaceSpikeNoised (one bin at spike_loc_host int32[count][3] = (z,y,x) of the
  * centred k-space set to magnitude exp(2.5 * mean log|K| * (0.95 + 0.15 * spike_u)), phase kept).
+ * flips_host (uint8[count], bit0=z bit1=y bit2=x; nullable = none): the patch was flipped BEFORE
+ * this call while the reference flips after it (RandFlipd last): the Gibbs mask is evaluated at the
+ * mirrored bin; spike_loc_host must already be mirrored by the caller.
  * 3-D DFT of any extents <= 512 (direct per-axis transform in LDS; only selected patches are
  * transformed).  workspace >= segmi_kspace_workspace(count, rd, rh, rw) bytes. */
 int64_t segmi_kspace_workspace(int count, int rd, int rh, int rw);
 int segmi_kspace_augment(float* patches, int count, int rd, int rh, int rw, int c,
                          const uint8_t* gibbs_on_host, const float* gibbs_alpha_host,
                          const uint8_t* spike_on_host, const int32_t* spike_loc_host,
-                         const float* spike_u_host, void* workspace, void* stream);
+                         const float* spike_u_host, const uint8_t* flips_host, void* workspace,
+                         void* stream);
 
 /* ---------------------------------------------------------------- model ensembles ------ */
 /* Combination of `models` (<= 16) predictions over n elements, monai_unet.py:848-1004.

@@ -171,9 +171,10 @@ __global__ void bias_field_kernel(float* __restrict__ x, int rd, int rh, int rw,
     const int64_t v = i / C;   // NDHWC patch: the field is shared by the channels of a voxel
     const int vx = (int)(v % rw), vy = (int)((v / rw) % rh), vz = (int)(v / ((int64_t)rw * rh));
     float Lz[4], Ly[4], Lx[4];
-    legendre4(rd > 1 ? -1.f + 2.f * vz / (rd - 1) : 0.f, Lz);
-    legendre4(rh > 1 ? -1.f + 2.f * vy / (rh - 1) : 0.f, Ly);
-    legendre4(rw > 1 ? -1.f + 2.f * vx / (rw - 1) : 0.f, Lx);
+    // numpy.linspace(-1, 1, n): a single point is -1
+    legendre4(rd > 1 ? -1.f + 2.f * vz / (rd - 1) : -1.f, Lz);
+    legendre4(rh > 1 ? -1.f + 2.f * vy / (rh - 1) : -1.f, Ly);
+    legendre4(rw > 1 ? -1.f + 2.f * vx / (rw - 1) : -1.f, Lx);
     float s = 0.f;
     int ci = 0;
     // coefficient order of numpy.polynomial.legendre.leggrid3d over the upper "triangle" that
@@ -352,6 +353,7 @@ struct KspaceParams {   // indexed by SLOT: only the patches a transform fired f
   float gibbs_r[kMaxCrops];        // mask radius (1 - alpha) * max(shape) * sqrt(2) / 2
   int spike_loc[kMaxCrops][3];     // (z, y, x) in the SHIFTED k-space, as the reference draws it
   float spike_u[kMaxCrops];        // U(0,1): intensity = mean(log|K|) * 2.5 * (0.95 + 0.15 u)
+  unsigned char flip[kMaxCrops];   // axes the patch was flipped along (bit 0 = z, 1 = y, 2 = x)
 };
 
 __global__ void real_to_cplx_kernel(const float* __restrict__ x, cplx* __restrict__ k, int64_t per,
@@ -370,17 +372,26 @@ __global__ void cplx_to_real_kernel(const cplx* __restrict__ k, float* __restric
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256)
     x[(src * per + i) * C + ch] = k[(int64_t)pidx * per + i].x;
 }
-// GibbsNoise._apply_mask on the un-shifted spectrum
+// shifted-spectrum bin that a flip of an n-long axis maps bin s to (frequency k -> -k)
+__device__ __forceinline__ int mirror_bin(int s, int n) { return (n & 1) ? n - 1 - s : (n - s) % n; }
+
+// GibbsNoise._apply_mask on the un-shifted spectrum.  The reference flips after the transform; a
+// patch that was flipped before it gets the mask evaluated at the mirrored bin, which is the same
+// (the mask is centred at (n - 1) / 2: not symmetric under the mirror when n is even).
 __global__ void gibbs_mask_kernel(cplx* __restrict__ k, int rd, int rh, int rw, KspaceParams p) {
   const int pidx = blockIdx.y;
   if (!p.gibbs_on[pidx]) return;
   const int64_t per = (int64_t)rd * rh * rw;
   const float r = p.gibbs_r[pidx];
   const float cz = (rd - 1) * 0.5f, cy = (rh - 1) * 0.5f, cx = (rw - 1) * 0.5f;
+  const unsigned char f = p.flip[pidx];
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
     const int x = (int)(i % rw), y = (int)((i / rw) % rh), z = (int)(i / ((int64_t)rw * rh));
-    const float sz = (float)((z + rd / 2) % rd) - cz, sy = (float)((y + rh / 2) % rh) - cy,
-                sx = (float)((x + rw / 2) % rw) - cx;       // position in the shifted spectrum
+    int iz = (z + rd / 2) % rd, iy = (y + rh / 2) % rh, ix = (x + rw / 2) % rw;   // shifted spectrum
+    if (f & 1) iz = mirror_bin(iz, rd);
+    if (f & 2) iy = mirror_bin(iy, rh);
+    if (f & 4) ix = mirror_bin(ix, rw);
+    const float sz = (float)iz - cz, sy = (float)iy - cy, sx = (float)ix - cx;
     if (sqrtf(sz * sz + sy * sy + sx * sx) > r) k[(int64_t)pidx * per + i] = cplx{0.f, 0.f};
   }
 }
@@ -435,7 +446,9 @@ static int dft3d(cplx* buf, int count, int rd, int rh, int rw, int inverse, hipS
     const int64_t nlines = per / N * count;
     // lines of axis a inside the [count * per] buffer: for the contiguous axis a line is
     // `outer`-indexed (inner = 1); for the others consecutive lines are adjacent in memory
-    const size_t lds = (size_t)(N + 16 * (N + 1)) * sizeof(cplx);
+    const size_t lds = (size_t)(N + 16 * (N + 1)) * sizeof(cplx);   // > 64 KiB for N > 480
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dft_axis_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(dft_axis_kernel, (unsigned)cdiv64(nlines, 16), 256, lds, st, buf, N,
                        strides[a], strides[a], nlines, inverse);
   }
@@ -454,7 +467,8 @@ int64_t segmi_kspace_workspace(int count, int rd, int rh, int rw) {
 int segmi_kspace_augment(float* patches, int count, int rd, int rh, int rw, int c,
                          const uint8_t* gibbs_on_host, const float* gibbs_alpha_host,
                          const uint8_t* spike_on_host, const int32_t* spike_loc_host,
-                         const float* spike_u_host, void* workspace, void* stream) {
+                         const float* spike_u_host, const uint8_t* flips_host, void* workspace,
+                         void* stream) {
   SEGMI_CHECK_ARG(patches && workspace && count > 0 && count <= kMaxCrops && rd > 0 && rh > 0 &&
                       rw > 0 && c > 0, "kspace_augment: bad arguments (1..%d patches)", kMaxCrops);
   SEGMI_CHECK_ARG((!gibbs_on_host || gibbs_alpha_host) && (!spike_on_host || (spike_loc_host && spike_u_host)),
@@ -475,6 +489,7 @@ int segmi_kspace_augment(float* patches, int count, int rd, int rh, int rw, int 
     for (int i = 0; i < count; ++i) {
       if (pass == 0 && gibbs_on_host && gibbs_on_host[i]) {
         q.src[ns] = (unsigned char)i; q.gibbs_on[ns] = 1;
+        q.flip[ns] = flips_host ? flips_host[i] : 0;
         q.gibbs_r[ns] = (1.0f - gibbs_alpha_host[i]) * (float)mx * 1.41421356f / 2.0f;
         ++ns;
       } else if (pass == 1 && spike_on_host && spike_on_host[i]) {

@@ -703,89 +703,114 @@ def normalize_intensity_(x: torch.Tensor) -> torch.Tensor:
     return x
 
 
+AUG_MAX_PATCHES = 16    # patches per segmi_crop_patches / warp_crop / intensity / kspace call (kMaxCrops)
+
+
+def _flips_arg(flips, i, n):
+    if flips is None:
+        return None, None
+    fl = np.ascontiguousarray(np.asarray(flips, dtype=np.uint8).reshape(-1)[i:i + n])
+    return fl, fl.ctypes.data_as(C.c_void_p)
+
+
+def _rows(x, i, n):
+    return None if x is None else x[i:i + n]
+
+
 def crop_patches(image, label, starts, flips, out_image, out_label) -> None:
-    a, b = act(image), act(out_image)
-    arr, p = _starts(starts, 4)
-    fl = None
-    flp = None
-    if flips is not None:
-        fl = np.ascontiguousarray(np.asarray(flips, dtype=np.uint8))
-        flp = fl.ctypes.data_as(C.c_void_p)
-    check(lib.segmi_crop_patches(C.byref(a), _ptr(label), p, flp, arr.shape[0],
-                                 dtype_code(out_image), C.byref(b), _ptr(out_label),
-                                 _stream()), "crop_patches")
+    """``len(starts)`` crops (any number: one launch per 16) of ``image`` / ``label`` into
+    ``out_image`` / ``out_label``."""
+    a = act(image)
+    for i in range(0, len(starts), AUG_MAX_PATCHES):
+        arr, p = _starts(starts[i:i + AUG_MAX_PATCHES], 4)
+        n = arr.shape[0]
+        b = act(out_image[i:i + n])
+        _fl, flp = _flips_arg(flips, i, n)
+        check(lib.segmi_crop_patches(C.byref(a), _ptr(label), p, flp, n,
+                                     dtype_code(out_image), C.byref(b), _ptr(_rows(out_label, i, n)),
+                                     _stream()), "crop_patches")
 
 
 def warp_crop_patches(image, label, starts, flips, index_map, out_image, out_label) -> None:
     """crop_patches with a 3x4 affine (augmented index (x,y,z,1) -> source index) composed in."""
-    a, b = act(image), act(out_image)
-    arr, p = _starts(starts, 4)
-    flp = None
-    if flips is not None:
-        fl = np.ascontiguousarray(np.asarray(flips, dtype=np.uint8))
-        flp = fl.ctypes.data_as(C.c_void_p)
+    a = act(image)
     m = np.ascontiguousarray(np.asarray(index_map, dtype=np.float64).reshape(12))
-    check(lib.segmi_warp_crop_patches(C.byref(a), _ptr(label), p, flp, arr.shape[0],
-                                      m.ctypes.data_as(C.c_void_p), dtype_code(out_image),
-                                      C.byref(b), _ptr(out_label), _stream()), "warp_crop_patches")
+    for i in range(0, len(starts), AUG_MAX_PATCHES):
+        arr, p = _starts(starts[i:i + AUG_MAX_PATCHES], 4)
+        n = arr.shape[0]
+        b = act(out_image[i:i + n])
+        _fl, flp = _flips_arg(flips, i, n)
+        check(lib.segmi_warp_crop_patches(C.byref(a), _ptr(label), p, flp, n,
+                                          m.ctypes.data_as(C.c_void_p), dtype_code(out_image),
+                                          C.byref(b), _ptr(_rows(out_label, i, n)), _stream()),
+              "warp_crop_patches")
+
+
+def _host_arrays():
+    keep = []
+
+    def arr(x, dt, i, n):
+        if x is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(x, dtype=dt)[i:i + n])
+        keep.append(a)
+        return a.ctypes.data_as(C.c_void_p)
+    return arr
 
 
 def intensity_augment(patches, contrast=None, hist=None, bias=None) -> None:
     """In-place RandAdjustContrast / RandHistogramShift / RandBiasField on f32 NDHWC patches.
 
-    contrast = (on uint8[n], gamma f32[n]); hist = (on, ctrl f32[n][k]); bias = (on, coef f32[n][20])."""
+    contrast = (on uint8[n], gamma f32[n]); hist = (on, ctrl f32[n][k]); bias = (on, coef f32[n][20]).
+    Any n: one call per 16 patches (every transform is per patch)."""
     _require_device(patches)
     if patches.dtype != torch.float32 or patches.dim() != 5 or not patches.is_contiguous():
         raise ValueError("intensity_augment: dense float32 [n, d, h, w, c] patches expected")
-    n, rd, rh, rw, c = patches.shape
-    ws = torch.empty(int(lib.segmi_intensity_workspace(n)), dtype=torch.uint8, device=patches.device)
-    keep = []
-
-    def arr(x, dt):
-        if x is None:
-            return None
-        a = np.ascontiguousarray(np.asarray(x, dtype=dt))
-        keep.append(a)
-        return a.ctypes.data_as(C.c_void_p)
-
+    N, rd, rh, rw, c = patches.shape
     con, gam = (contrast if contrast is not None else (None, None))
     hon, ctl = (hist if hist is not None else (None, None))
     bon, cof = (bias if bias is not None else (None, None))
     nctrl = int(np.asarray(ctl).shape[1]) if ctl is not None else 0
-    check(lib.segmi_intensity_augment(_ptr(patches), n, rd, rh, rw, c, arr(con, np.uint8),
-                                      arr(gam, np.float32), arr(hon, np.uint8), arr(ctl, np.float32),
-                                      nctrl, arr(bon, np.uint8), arr(cof, np.float32), _ptr(ws),
-                                      _stream()), "intensity_augment")
+    ws = torch.empty(int(lib.segmi_intensity_workspace(min(N, AUG_MAX_PATCHES))), dtype=torch.uint8,
+                     device=patches.device)
+    for i in range(0, N, AUG_MAX_PATCHES):
+        n = min(AUG_MAX_PATCHES, N - i)
+        arr = _host_arrays()
+        check(lib.segmi_intensity_augment(_ptr(patches[i:i + n]), n, rd, rh, rw, c, arr(con, np.uint8, i, n),
+                                          arr(gam, np.float32, i, n), arr(hon, np.uint8, i, n),
+                                          arr(ctl, np.float32, i, n), nctrl, arr(bon, np.uint8, i, n),
+                                          arr(cof, np.float32, i, n), _ptr(ws), _stream()),
+              "intensity_augment")
 
 
-def kspace_augment(patches, gibbs=None, spike=None) -> None:
+def kspace_augment(patches, gibbs=None, spike=None, flips=None) -> None:
     """In-place RandGibbsNoise / RandKSpaceSpikeNoise on f32 NDHWC patches.
 
-    gibbs = (on uint8[n], alpha f32[n]); spike = (on uint8[n], loc int32[n][3] (z,y,x), u f32[n])."""
+    gibbs = (on uint8[n], alpha f32[n]); spike = (on uint8[n], loc int32[n][3] (z,y,x), u f32[n]).
+    ``flips`` (uint8[n], bit 0 = z, 1 = y, 2 = x): the patches were flipped before this call and the
+    reference flips after it -- the Gibbs mask is evaluated at the mirrored bin (the spike location
+    must come mirrored already: ``seg.augment.flip_params``).  Any n: one call per 16 patches."""
     _require_device(patches)
     if patches.dtype != torch.float32 or patches.dim() != 5 or not patches.is_contiguous():
         raise ValueError("kspace_augment: dense float32 [n, d, h, w, c] patches expected")
-    n, rd, rh, rw, c = patches.shape
+    N, rd, rh, rw, c = patches.shape
     gon, alpha = gibbs if gibbs is not None else (None, None)
     son, loc, u = spike if spike is not None else (None, None, None)
-    nsel = max(int(np.asarray(gon).astype(bool).sum()) if gon is not None else 0,
-               int(np.asarray(son).astype(bool).sum()) if son is not None else 0)
-    if nsel == 0:
-        return
-    ws = torch.empty(int(lib.segmi_kspace_workspace(n, rd, rh, rw)), dtype=torch.uint8,
-                     device=patches.device)
-    keep = []
-
-    def arr(x, dt):
-        if x is None:
-            return None
-        a = np.ascontiguousarray(np.asarray(x, dtype=dt))
-        keep.append(a)
-        return a.ctypes.data_as(C.c_void_p)
-
-    check(lib.segmi_kspace_augment(_ptr(patches), n, rd, rh, rw, c, arr(gon, np.uint8),
-                                   arr(alpha, np.float32), arr(son, np.uint8), arr(loc, np.int32),
-                                   arr(u, np.float32), _ptr(ws), _stream()), "kspace_augment")
+    ws = None
+    for i in range(0, N, AUG_MAX_PATCHES):
+        n = min(AUG_MAX_PATCHES, N - i)
+        nsel = max(int(np.asarray(gon)[i:i + n].astype(bool).sum()) if gon is not None else 0,
+                   int(np.asarray(son)[i:i + n].astype(bool).sum()) if son is not None else 0)
+        if nsel == 0:
+            continue
+        if ws is None:
+            ws = torch.empty(int(lib.segmi_kspace_workspace(min(N, AUG_MAX_PATCHES), rd, rh, rw)),
+                             dtype=torch.uint8, device=patches.device)
+        arr = _host_arrays()
+        check(lib.segmi_kspace_augment(_ptr(patches[i:i + n]), n, rd, rh, rw, c, arr(gon, np.uint8, i, n),
+                                       arr(alpha, np.float32, i, n), arr(son, np.uint8, i, n),
+                                       arr(loc, np.int32, i, n), arr(u, np.float32, i, n),
+                                       arr(flips, np.uint8, i, n), _ptr(ws), _stream()), "kspace_augment")
 
 
 def _ptr_table(tensors, dtype):

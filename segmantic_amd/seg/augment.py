@@ -14,6 +14,10 @@ MONAI's transforms do and composes the spatial ones into one index map:
   ``RandGibbsNoised(prob=0.2, alpha=(0, 1))``, ``RandKSpaceSpikeNoised(prob=0.2)`` per patch (the
   spike intensity's default range, 0.95..1.1 x 2.5 x mean log|K|, is evaluated on the device from a
   host-drawn U(0,1)).
+* ``RandFlipd`` runs last in the reference, after the k-space transforms.  Here the flips happen
+  in the crop gather and the intensity / k-space transforms then run with parameters mirrored by
+  the flips (``flip_params``; the Gibbs mask is mirrored inside ``ops.kspace_augment``), which
+  gives the same patch without a separate flip pass.
 
 Spatial axes: the cached volumes are [C, d0, d1, d2]; ``range_x`` rotates about d0, ``range_y``
 about d1, ``range_z`` about d2, as MONAI names the axes of a channel-first array.
@@ -102,3 +106,46 @@ def draw_intensity(rng: np.random.RandomState, n: int, roi=None):
     loc = np.stack([rng.randint(0, int(r), n) for r in roi], 1).astype(np.int32)
     u = rng.rand(n).astype(np.float32)
     return out + ((gon, alpha), (son, loc, u))
+
+
+def mirror_index(i, n: int):
+    """Index of the k-space bin that a flip of an n-long axis moves bin ``i`` of the CENTRED
+    spectrum (``fftshift(fftn(ifftshift(x)))``) to: frequency k goes to -k, i.e. ``(n - i) mod n``
+    for even n and ``n - 1 - i`` for odd n."""
+    return (n - np.asarray(i)) % n if n % 2 == 0 else n - 1 - np.asarray(i)
+
+
+def flip_params(intensity, flips, roi):
+    """The draws of ``draw_intensity`` (made for the unflipped patch) rewritten for a patch whose
+    axes were already flipped by ``flips`` (bit 0 = d0, bit 1 = d1, bit 2 = d2).
+
+    The reference flips last (``RandFlipd`` after the k-space transforms); the crop kernels flip
+    during the gather, before the intensity transforms run.  With these parameters the result is
+    the same: flip(T(x, p)) == T(flip(x), p').  Contrast and histogram shift do not depend on
+    position.  The bias field's Legendre term of degree i in an axis is odd in that axis when i is
+    odd: those coefficients are negated (axes of one voxel excepted).  The spike moves to the
+    mirrored bin (``mirror_index``).  The Gibbs mask is centred at (n - 1) / 2, which is not symmetric under the mirror for even n:
+    ``ops.kspace_augment`` takes the flips and evaluates the mask at the mirrored bin itself."""
+    con, hist, (bon, coef), *ks = intensity
+    flips = np.asarray(flips, dtype=np.int64)
+    if not flips.any():
+        return intensity
+    coef = np.array(coef, dtype=np.float32, copy=True)
+    k = 0
+    for a in range(4):                                  # leggrid3d order, as bias_field_kernel reads it
+        for b in range(4 - a):
+            for c in range(4 - a - b):
+                for d, deg in enumerate((a, b, c)):
+                    # linspace(-1, 1, 1) == [-1] is no symmetric grid; a flip of 1 voxel is no flip
+                    if deg % 2 == 1 and int(roi[d]) > 1:
+                        coef[:, k] = np.where((flips & (1 << d)) != 0, -coef[:, k], coef[:, k])
+                k += 1
+    out = (con, hist, (bon, coef))
+    if not ks:
+        return out
+    gibbs, (son, loc, u) = ks
+    loc = np.array(loc, dtype=np.int32, copy=True)
+    for d in range(3):
+        fl = (flips & (1 << d)) != 0
+        loc[:, d] = np.where(fl, mirror_index(loc[:, d], int(roi[d])), loc[:, d])
+    return out + (gibbs, (son, loc, u))

@@ -23,7 +23,7 @@ import torch
 
 from .. import ops
 from . import streams
-from .augment import draw_intensity, draw_spatial, forward_point, to_index_map_xyz
+from .augment import draw_intensity, draw_spatial, flip_params, forward_point, to_index_map_xyz
 from .distributed import broadcast_buffers, env_world, init_distributed
 from .pipeline import PredictPipeline
 
@@ -131,20 +131,39 @@ def batch_buffers(net, cache: CachedVolumes, n_volumes: int) -> Dict:
             "label": torch.empty((B, roi[0], roi[1], roi[2]), dtype=torch.float32, device=dev)}
 
 
-def make_batch(net, cache: CachedVolumes, vol_ids, rng, out: Optional[Dict] = None) -> Dict:
-    """2 volumes x num_samples crops -> {'image': [B,C,*roi] f32, 'label': [B,1,*roi] f32}.
+def draw_batch(net, cache: CachedVolumes, vol_ids, rng) -> List[Dict]:
+    """The host half of ``make_batch``: every random draw of one batch, in the order the sampler
+    has always made them (``bench.py``'s fit mode and the prefetcher's bit-identity rely on it).
 
-    ``out`` (``batch_buffers``): the crops are written straight into these buffers -- no allocation
-    and no concatenation per step; the returned tensors are views of them (the image as the
-    NCDHW-shaped view of the NDHWC buffer the crop kernels fill)."""
+    One record per volume: ``vid``, ``spatial`` (pull-back map or None), ``starts`` (crop origins),
+    ``flips`` (bit 0 = d0, bit 1 = d1, bit 2 = d2) and ``intensity`` (the five parameter tuples of
+    ``augment.draw_intensity`` as the reference draws them, i.e. for the UNflipped patch; or None)."""
     roi = list(net.spatial_size)
-    dev = net.device
-    imgs, labs = [], []
-    row = 0
+    fp = float(getattr(net, "flip_prob", 0.2))
+    records = []
     for vid in vol_ids:
         it = cache.items[vid]
         spatial = draw_spatial(rng, it["label"].shape[1:]) if net.augment_spatial else None
         starts = crop_centers(rng, it, roi, net.num_samples, net.num_classes, spatial, cache)
+        flips = [(int(rng.rand() < fp)) | (int(rng.rand() < fp) << 1) | (int(rng.rand() < fp) << 2)
+                 for _ in starts]
+        intensity = draw_intensity(rng, len(starts), roi) if net.augment_intensity else None
+        records.append({"vid": vid, "spatial": spatial, "starts": starts, "flips": flips,
+                        "intensity": intensity})
+    return records
+
+
+def apply_batch(net, cache: CachedVolumes, records: List[Dict], out: Optional[Dict] = None) -> Dict:
+    """The device half of ``make_batch``: the crops of ``draw_batch``'s records, flipped in the gather,
+    then the intensity and k-space transforms with their parameters mirrored by the flips
+    (``augment.flip_params``), which gives the reference's order crop -> intensity -> k-space -> flip."""
+    roi = list(net.spatial_size)
+    dev = net.device
+    imgs, labs = [], []
+    row = 0
+    for rec in records:
+        it = cache.items[rec["vid"]]
+        starts, flips, spatial = rec["starts"], rec["flips"], rec["spatial"]
         C = it["image"].shape[0]
         src = it["image_ndhwc"]                                              # NDHWC, n = 1
         if out is not None and out["image"].shape[0] >= row + len(starts) and out["image"].shape[4] == C:
@@ -155,24 +174,30 @@ def make_batch(net, cache: CachedVolumes, vol_ids, rng, out: Optional[Dict] = No
             out_i = torch.empty((len(starts), roi[0], roi[1], roi[2], C), dtype=torch.float32, device=dev)
             out_l = torch.empty((len(starts), roi[0], roi[1], roi[2]), dtype=torch.float32, device=dev)
         row += len(starts)
-        fp = float(getattr(net, "flip_prob", 0.2))
-        flips = [(int(rng.rand() < fp)) | (int(rng.rand() < fp) << 1) | (int(rng.rand() < fp) << 2)
-                 for _ in starts]
         if spatial is None:
             ops.crop_patches(src, it["label_dhw"], [[0] + s for s in starts], flips, out_i, out_l)
         else:
             ops.warp_crop_patches(src, it["label_dhw"], [[0] + s for s in starts], flips,
                                   to_index_map_xyz(spatial), out_i, out_l)
-        if net.augment_intensity:
-            con, hist, bias, gibbs, spike = draw_intensity(rng, len(starts), roi)
+        if rec["intensity"] is not None:
+            con, hist, bias, gibbs, spike = flip_params(rec["intensity"], flips, roi)
             ops.intensity_augment(out_i, con, hist, bias)
-            ops.kspace_augment(out_i, gibbs, spike)
+            ops.kspace_augment(out_i, gibbs, spike, flips)
         imgs.append(out_i.permute(0, 4, 1, 2, 3))
         labs.append(out_l.unsqueeze(1))
     if out is not None:
         img = out["image"][:row].permute(0, 4, 1, 2, 3)
         return {"image": img if img.is_contiguous() else img.contiguous(), "label": out["label"][:row].unsqueeze(1)}
     return {"image": torch.cat(imgs).contiguous(), "label": torch.cat(labs).contiguous()}
+
+
+def make_batch(net, cache: CachedVolumes, vol_ids, rng, out: Optional[Dict] = None) -> Dict:
+    """2 volumes x num_samples crops -> {'image': [B,C,*roi] f32, 'label': [B,1,*roi] f32}.
+
+    ``out`` (``batch_buffers``): the crops are written straight into these buffers -- no allocation
+    and no concatenation per step; the returned tensors are views of them (the image as the
+    NCDHW-shaped view of the NDHWC buffer the crop kernels fill)."""
+    return apply_batch(net, cache, draw_batch(net, cache, vol_ids, rng), out)
 
 
 class BatchPrefetcher:
