@@ -32,7 +32,8 @@ extern "C" {
 #define SEGMI_VERSION 1
 
 enum { SEGMI_F32 = 0, SEGMI_BF16 = 1, SEGMI_F16 = 2 };
-enum { SEGMI_OK = 0, SEGMI_EINVAL = -1, SEGMI_EUNSUPPORTED = -2, SEGMI_ELAUNCH = -3 };
+enum { SEGMI_OK = 0, SEGMI_EINVAL = -1, SEGMI_EUNSUPPORTED = -2, SEGMI_ELAUNCH = -3,
+       SEGMI_EDATA = -4 /* the data cannot be processed (an empty or constant N4 fit set) */ };
 
 /* NDHWC activation view */
 typedef struct segmi_act {
@@ -618,6 +619,50 @@ int segmi_channel_argmax(const float* x, int c, int d, int h, int w, uint64_t* k
  * Replaces generate_spatial_bounding_box of BoundingBoxd, transforms.py:231. */
 int segmi_positive_bbox(const void* x, int dtype_bytes, int is_float, int c, int d, int h, int w, int32_t* box,
                         void* stream);
+
+/* ---------------------------------------------------------------- MRI / CT preprocessing -- */
+/* src/segmantic/image/modality.py: N4 bias-field correction, its Otsu mask and shrink, and the CT
+ * median / clamp / scale.  Volumes are contiguous [nz][ny][nx] (2-D: nz = 1).
+ * Otsu: bins equal bins over [min, max] of the finite values of x (n values), bin = min(floor((v - min) / w),
+ * bins - 1); counts i64 [bins] (nullable) and stats f64 [4] = {min, w, threshold, finite count}, both device;
+ * threshold = min + (k + 1) w for the first k maximising the between-class variance.  2 <= bins <= 512. */
+int64_t segmi_otsu_workspace_bytes(int bins);
+int segmi_otsu(const float* x, int64_t n, int bins, int64_t* counts, double* stats, void* workspace,
+               size_t ws_bytes, void* stream);
+/* One gather: output voxel j of each axis takes input voxel j f + o, ns = max(1, n / f), o = floor(((n - 1) -
+ * (ns - 1) f) / 2 + 0.5).  Mask: mask (u8, nullable) at that voxel, else outside / inside by v > otsu_stats[2]
+ * (nullable: every voxel is 1).  Outputs (each nullable): the shrunk image, the shrunk mask, and
+ * log(v) where mask == 1, v > 0 and v finite, NaN elsewhere (the N4 fit set, f64). */
+int segmi_n4_shrink(const float* x, int nz, int ny, int nx, int fz, int fy, int fx, const uint8_t* mask,
+                    const double* otsu_stats, int inside, int outside, float* out_img, uint8_t* out_mask,
+                    double* out_log, void* stream);
+/* N4 on a grid of log values (NaN: not in the fit set): levels fitting levels of (control_points - 3) 2^l
+ * spans per axis of size > 1, iterations_host[l] iterations at most, stopping early when the CV of exp(old -
+ * new field) is <= threshold.  Writes the final lattice f64 [Lz][Ly][Lx] (L = 1 on axes of size 1, else
+ * (control_points - 3) 2^(levels-1) + 3), the field on the grid f64 (nullable), elapsed_host[levels] and
+ * cv_host (HOST).  One 8-byte device-to-host read per iteration.  SEGMI_EDATA when the fit set has fewer
+ * than 2 voxels or one log value. */
+int64_t segmi_n4_workspace_bytes(int nz, int ny, int nx, int control_points, int levels, int bins);
+int segmi_n4_fit(const double* logimg, int nz, int ny, int nx, const int* iterations_host, int levels,
+                 int control_points, int bins, double fwhm, double noise, double threshold, double* lattice,
+                 double* field, int* elapsed_host, double* cv_host, void* workspace, size_t ws_bytes, void* stream);
+/* One sharpening of the finite values of u: E f64 [bins] and each value's sharpened value (NaN elsewhere).
+ * Workspace: segmi_n4_workspace_bytes(nz, ny, nx, 4, 1, bins). */
+int segmi_n4_sharpen(const double* u, int nz, int ny, int nx, int bins, double fwhm, double noise, double* E,
+                     double* sharpened, void* workspace, size_t ws_bytes, void* stream);
+/* One B-spline BA fit of the finite values of r at `spans` spans per axis into lattice (overwritten).
+ * Workspace: segmi_n4_workspace_bytes(nz, ny, nx, spans + 3, 1, 2). */
+int segmi_n4_bspline_fit(const double* r, int nz, int ny, int nx, int spans, double* lattice, void* workspace,
+                         size_t ws_bytes, void* stream);
+/* Exact cubic subdivision of a lattice: each axis of L > 1 control points becomes 2 (L - 3) + 3. */
+int segmi_n4_refine(const double* coarse, int lz, int ly, int lx, double* fine, void* stream);
+/* The lattice's field over an nz x ny x nx index range (u = i / (N - 1) m per axis), f32: out = x / exp(field)
+ * when x is given, else the field. */
+int segmi_n4_evaluate(const double* lattice, int lz, int ly, int lx, const float* x, float* out, int nz, int ny,
+                      int nx, void* stream);
+/* scale_clamp_ct: radius-1 median with replicate borders, clamp to [-1100, 3100], (v + 1100) * fl(255 / 4200) in f32
+ * with each operation rounded.  out must not alias x. */
+int segmi_ct_scale(const float* x, int nz, int ny, int nx, float* out, void* stream);
 
 #ifdef __cplusplus
 }

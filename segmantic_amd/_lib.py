@@ -178,6 +178,16 @@ SIGNATURES = {
     "segmi_vert_heatmap": (_i, [_P, _i, _P, _P, _i, _i, _i, _i, _P, _P]),
     "segmi_channel_argmax": (_i, [_P, _i, _i, _i, _i, _P, _P, _P]),
     "segmi_positive_bbox": (_i, [_P, _i, _i, _i, _i, _i, _i, _P, _P]),
+    "segmi_otsu_workspace_bytes": (_i64, [_i]),
+    "segmi_otsu": (_i, [_P, _i64, _i, _P, _P, _P, C.c_size_t, _P]),
+    "segmi_n4_shrink": (_i, [_P, _i, _i, _i, _i, _i, _i, _P, _P, _i, _i, _P, _P, _P, _P]),
+    "segmi_n4_workspace_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
+    "segmi_n4_fit": (_i, [_P, _i, _i, _i, _P, _i, _i, _i, _d, _d, _d, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "segmi_n4_sharpen": (_i, [_P, _i, _i, _i, _i, _d, _d, _P, _P, _P, C.c_size_t, _P]),
+    "segmi_n4_bspline_fit": (_i, [_P, _i, _i, _i, _i, _P, _P, C.c_size_t, _P]),
+    "segmi_n4_refine": (_i, [_P, _i, _i, _i, _P, _P]),
+    "segmi_n4_evaluate": (_i, [_P, _i, _i, _i, _P, _P, _i, _i, _i, _P]),
+    "segmi_ct_scale": (_i, [_P, _i, _i, _i, _P, _P]),
 }
 
 

@@ -1053,3 +1053,153 @@ def positive_bbox(x: torch.Tensor, box=None):
         box = torch.empty(6, dtype=torch.int32, device=x.device)
     check(lib.segmi_positive_bbox(_ptr(x), nbytes, is_float, c, d, h, w, _ptr(box), _stream()), "positive_bbox")
     return box
+
+
+# ------------------------------------------------------------------ MRI / CT preprocessing (N4, Otsu, CT scale)
+SEGMI_EDATA = -4
+N4_MAX_BINS = 512
+
+
+def _vol3(t: torch.Tensor, dtype, what: str):
+    """(nz, ny, nx) of a contiguous 2-D / 3-D device tensor of `dtype`"""
+    _require_device(t)
+    if t.dtype != dtype or not t.is_contiguous() or t.dim() not in (2, 3):
+        raise ValueError(f"{what}: contiguous {dtype} [z, y, x] or [y, x] tensor expected")
+    return (1,) + tuple(t.shape) if t.dim() == 2 else tuple(t.shape)
+
+
+def _check_n4(rc: int, what: str) -> None:
+    if rc == SEGMI_EDATA:
+        raise ValueError(_lib.last_error())
+    check(rc, what)
+
+
+def otsu(x: torch.Tensor, bins: int = 200):
+    """Otsu statistics of the finite values of a contiguous f32 device tensor: (counts i64 [bins],
+    stats f64 [4] = (min, bin width, threshold, finite count)), both on the device; no host read."""
+    _require_device(x)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("otsu expects a non-empty contiguous float32 tensor")
+    if not 2 <= bins <= N4_MAX_BINS:
+        raise ValueError(f"otsu: 2 <= bins <= {N4_MAX_BINS}")
+    counts = torch.empty(bins, dtype=torch.int64, device=x.device)
+    stats = torch.empty(4, dtype=torch.float64, device=x.device)
+    ws = torch.empty(int(lib.segmi_otsu_workspace_bytes(bins)), dtype=torch.uint8, device=x.device)
+    check(lib.segmi_otsu(_ptr(x), x.numel(), bins, _ptr(counts), _ptr(stats), _ptr(ws), ws.numel(), _stream()),
+          "otsu")
+    return counts, stats
+
+
+def n4_shrink(x: torch.Tensor, factors, mask: Optional[torch.Tensor] = None,
+              otsu_stats: Optional[torch.Tensor] = None, inside: int = 0, outside: int = 1,
+              want_image: bool = True, want_mask: bool = True, want_log: bool = False):
+    """One gather of a f32 [z, y, x] / [y, x] volume at the shrink indices; `factors` per array axis.
+    Mask: `mask` (uint8, same shape), else the Otsu threshold in `otsu_stats`, else all ones.
+    Returns (image f32, mask uint8, log f64 with NaN off the fit set), each None when not wanted."""
+    dims = _vol3(x, torch.float32, "n4_shrink")
+    f = [1] * (3 - x.dim()) + [int(v) for v in factors]
+    if len(f) != 3 or min(f) < 1:
+        raise ValueError("n4_shrink: one factor >= 1 per axis")
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(x.shape)
+                             or not mask.is_contiguous()):
+        raise ValueError("n4_shrink: the mask must be a contiguous uint8 tensor of the image's shape")
+    ns = [max(1, n // fa) for n, fa in zip(dims, f)]
+    shape = tuple(ns[3 - x.dim():])
+    img = torch.empty(shape, dtype=torch.float32, device=x.device) if want_image else None
+    msk = torch.empty(shape, dtype=torch.uint8, device=x.device) if want_mask else None
+    lg = torch.empty(shape, dtype=torch.float64, device=x.device) if want_log else None
+    if otsu_stats is not None and (otsu_stats.dtype != torch.float64 or otsu_stats.numel() < 3):
+        raise ValueError("n4_shrink: otsu_stats is the f64 [4] tensor of ops.otsu")
+    check(lib.segmi_n4_shrink(_ptr(x), *dims, *f, _ptr(mask), _ptr(otsu_stats), int(inside), int(outside),
+                              _ptr(img), _ptr(msk), _ptr(lg), _stream()), "n4_shrink")
+    return img, msk, lg
+
+
+def n4_lattice_shape(dims3, spans: int):
+    return tuple(1 if n == 1 else spans + 3 for n in dims3)
+
+
+def n4_fit(logimg: torch.Tensor, iterations, control_points: int = 4, bins: int = 200, fwhm: float = 0.15,
+           noise: float = 0.01, threshold: float = 0.001, want_field: bool = False):
+    """N4 on a f64 [z, y, x] / [y, x] grid of log values (NaN off the fit set).  Returns (lattice f64
+    [Lz, Ly, Lx] on the device, field f64 on the grid or None, elapsed iterations per level, final CV).
+    ValueError when the fit set is empty or constant."""
+    dims = _vol3(logimg, torch.float64, "n4_fit")
+    it = np.ascontiguousarray(np.asarray([int(v) for v in iterations], dtype=np.int32))
+    levels = it.size
+    if levels < 1 or (it < 0).any():
+        raise ValueError("n4_fit: one non-negative iteration count per level")
+    nbytes = int(lib.segmi_n4_workspace_bytes(*dims, int(control_points), levels, int(bins)))
+    if nbytes <= 0:
+        raise ValueError("n4_fit: unsupported size, number of levels, control points or bins")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=logimg.device)
+    lat = torch.empty(n4_lattice_shape(dims, (int(control_points) - 3) << (levels - 1)), dtype=torch.float64,
+                      device=logimg.device)
+    field = torch.empty_like(logimg) if want_field else None
+    elapsed = np.zeros(levels, np.int32)
+    cv = C.c_double(0.0)
+    _check_n4(lib.segmi_n4_fit(_ptr(logimg), *dims, it.ctypes.data_as(C.c_void_p), levels, int(control_points),
+                               int(bins), float(fwhm), float(noise), float(threshold), _ptr(lat), _ptr(field),
+                               elapsed.ctypes.data_as(C.c_void_p), C.byref(cv), _ptr(ws), ws.numel(), _stream()),
+              "n4_fit")
+    return lat, field, [int(v) for v in elapsed], float(cv.value)
+
+
+def n4_sharpen(u: torch.Tensor, bins: int = 200, fwhm: float = 0.15, noise: float = 0.01):
+    """One sharpening of the finite values of a f64 grid: (E f64 [bins], sharpened f64, NaN elsewhere)."""
+    dims = _vol3(u, torch.float64, "n4_sharpen")
+    nbytes = int(lib.segmi_n4_workspace_bytes(*dims, 4, 1, int(bins)))
+    if nbytes <= 0:
+        raise ValueError("n4_sharpen: unsupported size or bins")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=u.device)
+    E = torch.empty(bins, dtype=torch.float64, device=u.device)
+    out = torch.empty_like(u)
+    check(lib.segmi_n4_sharpen(_ptr(u), *dims, int(bins), float(fwhm), float(noise), _ptr(E), _ptr(out), _ptr(ws),
+                               ws.numel(), _stream()), "n4_sharpen")
+    return E, out
+
+
+def n4_bspline_fit(r: torch.Tensor, spans: int) -> torch.Tensor:
+    """One BA fit of the finite values of a f64 grid at `spans` spans per axis: the lattice (f64)."""
+    dims = _vol3(r, torch.float64, "n4_bspline_fit")
+    nbytes = int(lib.segmi_n4_workspace_bytes(*dims, int(spans) + 3, 1, 2))
+    if nbytes <= 0:
+        raise ValueError("n4_bspline_fit: unsupported size or spans")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=r.device)
+    lat = torch.empty(n4_lattice_shape(dims, int(spans)), dtype=torch.float64, device=r.device)
+    check(lib.segmi_n4_bspline_fit(_ptr(r), *dims, int(spans), _ptr(lat), _ptr(ws), ws.numel(), _stream()),
+          "n4_bspline_fit")
+    return lat
+
+
+def n4_refine(lat: torch.Tensor) -> torch.Tensor:
+    """Exact cubic subdivision of a contiguous f64 [Lz, Ly, Lx] lattice."""
+    dims = _vol3(lat, torch.float64, "n4_refine")
+    if lat.dim() != 3:
+        raise ValueError("n4_refine: [Lz, Ly, Lx] lattice expected")
+    out = torch.empty(tuple(1 if n == 1 else 2 * (n - 3) + 3 for n in dims), dtype=torch.float64, device=lat.device)
+    check(lib.segmi_n4_refine(_ptr(lat), *dims, _ptr(out), _stream()), "n4_refine")
+    return out
+
+
+def n4_evaluate(lat: torch.Tensor, shape, x: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The field of a f64 [Lz, Ly, Lx] lattice over an index range `shape` ([z, y, x] or [y, x]) as f32, or
+    x / exp(field) when the f32 volume x of that shape is given."""
+    if lat.dtype != torch.float64 or not lat.is_contiguous() or lat.dim() != 3:
+        raise ValueError("n4_evaluate: contiguous f64 [Lz, Ly, Lx] lattice expected")
+    _require_device(lat)
+    shape = tuple(int(v) for v in shape)
+    dims = (1,) + shape if len(shape) == 2 else shape
+    if x is not None and (_vol3(x, torch.float32, "n4_evaluate") != dims):
+        raise ValueError("n4_evaluate: x does not have the evaluation shape")
+    out = torch.empty(shape, dtype=torch.float32, device=lat.device)
+    check(lib.segmi_n4_evaluate(_ptr(lat), *lat.shape, _ptr(x), _ptr(out), *dims, _stream()), "n4_evaluate")
+    return out
+
+
+def ct_scale(x: torch.Tensor) -> torch.Tensor:
+    """radius-1 median (replicate borders), clamp to [-1100, 3100], (v + 1100) * 255 / 4200 of a f32 volume"""
+    dims = _vol3(x, torch.float32, "ct_scale")
+    out = torch.empty_like(x)
+    check(lib.segmi_ct_scale(_ptr(x), *dims, _ptr(out), _stream()), "ct_scale")
+    return out
