@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Time the full-resolution 16 -> 16 ring conv alone (cold caches) in its three training roles; with
-SEGMI_RING3_DBG bits the time splits (conv_ring3_impl.h).  usage: ring3_diag.py [N] [role ...]"""
+"""Time the full-resolution 16 -> 16 ring conv alone (cold caches) in its three training roles
+(conv_ring3_impl.h).  usage: ring3_diag.py [N] [role ...]; DIAG_SIZE sets the edge (default 128)."""
 import os, sys, torch
 sys.path.insert(0, ".")
 from segmantic_amd import ops
@@ -61,5 +61,5 @@ for role in roles:
         e1.record(); torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1) * 1e3)
     ts.sort()
-    print(f"ring3={os.environ.get('SEGMI_RING3', '1')} xcd={os.environ.get('SEGMI_RING3_XCD', '-')} S={S} dbg={os.environ.get('SEGMI_RING3_DBG', '0'):>2} N={n} {role:10s}: "
+    print(f"S={S} N={n} {role:10s}: "
           f"median {ts[5]:7.1f} us  min {ts[0]:7.1f}", flush=True)

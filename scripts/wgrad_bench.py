@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cold-cache timings of the weight-gradient launches of the benchmark step (bf16, B=8, 128^3 net):
-   python scripts/wgrad_bench.py            (SEGMI_WGRAD_WS=0 for the previous kernel)"""
-import os, sys, torch
+   python scripts/wgrad_bench.py [B]"""
+import sys, torch
 sys.path.insert(0, ".")
 from segmantic_amd import ops
 DEV = "cuda:0"
@@ -31,7 +31,6 @@ def run(name, xs, dys, k, s, tf=False, reps=6):
     print(f"{name:34s} {us:8.1f} us  {nbytes / us / 1e6:6.2f} TB/s algorithmic (incl. slab reduce)")
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-print("SEGMI_WGRAD_WS =", os.environ.get("SEGMI_WGRAD_WS", "1"))
 run("top 16x16 s1 @128^3", (B, 128, 128, 128, 16), (B, 128, 128, 128, 16), 3, 1)
 run("top 16x16 s1 @128^3 + in_tf", (B, 128, 128, 128, 16), (B, 128, 128, 128, 16), 3, 1, tf=True)
 run("upconvT top: x16@128^3 dy32@64^3 s2", (B, 128, 128, 128, 16), (B, 64, 64, 64, 32), 3, 2)

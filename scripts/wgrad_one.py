@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""One configuration of the weight gradient, N launches (for rocprofv3 / diag timing).
+"""One configuration of the weight gradient, N launches (cold caches; also for rocprofv3).
 usage: wgrad_one.py [top|toptf|upT] [reps]"""
-import os, sys, torch
+import sys, torch
 sys.path.insert(0, ".")
 from segmantic_amd import ops
 DEV = "cuda:0"
@@ -28,4 +28,4 @@ for i in range(reps + 1):
     ops.conv3d_wgrad(x, dy, dw, None, k, s, ws, in_tf=in_tf)
     e1.record(); torch.cuda.synchronize()
     if i: tot += e0.elapsed_time(e1)
-print(f"{which} dbg={os.environ.get('SEGMI_WGRAD_DBG', '0')} ws={os.environ.get('SEGMI_WGRAD_WS', '1')}: {tot / reps * 1e3:7.1f} us (incl. slab reduce)")
+print(f"{which}: {tot / reps * 1e3:7.1f} us (incl. slab reduce)")

@@ -55,7 +55,6 @@ struct ConvParams {
   BnFin bfin;
   BnBwdFin bbfin;
   int xcd;   // ring2: 1 = XCD-aware blockIdx -> column map (grid.x % 8 == 0)
-  int dbg;   // diagnostics only (SEGMI_RING2_DBG): 1 = no staging loads, 2 = no stores, 4 = no MFMA loop
 };
 
 template <typename T, int CK, int KS, int S, int TD, int TH, int TW>

@@ -263,17 +263,15 @@ static inline int conv_ks_rows(const segmi_act* out) {
   const int td = wide ? 2 : 4, th = 4, tw = wide ? 16 : 8;
   return out->n * cdiv(out->d, td) * cdiv(out->h, th) * cdiv(out->w, tw);
 }
-// Layers the k-split kernel takes: k3 s1 with at least two channel chunks of one-k-step-per-tap
-// width.  Measured with cold caches (scripts/conv_microbench.py, batch 8): 128->128 @16^3
-// 99 -> 56 us, 256->256 @8^3 60 -> 36 us, 256->128 @16^3 181 -> 98 us, 64->64 @32^3 119 -> 114 us;
+// Layers the k-split kernel takes: k3 s1 with at least one channel chunk (single-chunk layers
+// included) of one-k-step-per-tap width.  Measured with cold caches (scripts/conv_microbench.py,
+// batch 8): 128->128 @16^3 99 -> 56 us, 256->256 @8^3 60 -> 36 us, 256->128 @16^3 181 -> 98 us, 64->64 @32^3 119 -> 114 us;
 // stride 2 does not gain (86 -> 97 us) and stays on conv_fwd_impl.h.
 static inline bool conv_ks_ok(int dtype, int cin, int ksize, int stride) {
-  static const bool off = getenv("SEGMI_CONV_KS") && atoi(getenv("SEGMI_CONV_KS")) == 0;
-  static const bool one = !(getenv("SEGMI_CONV_KS_1CH") && atoi(getenv("SEGMI_CONV_KS_1CH")) == 0);
-  if (off || ksize != 3 || stride != 1) return false;
+  if (ksize != 3 || stride != 1) return false;
   const int ck = pick_ck(dtype, cin);
   const int spt = ck / (dtype == SEGMI_F32 ? 4 : 8);
-  return spt == 4 && cin / ck >= (one ? 1 : 2);
+  return spt == 4 && cin >= ck;
 }
 
 template <typename T, int CK>

@@ -21,16 +21,6 @@
 #pragma once
 #include "conv_ring_impl.h"
 
-// Time-split diagnostic (build with -DSEGMI_RING2_DIAG, run with SEGMI_RING2_DBG=bits: 1 = no staging
-// loads, 2 = no stores, 4 = no MFMA loop, 8 = no commit, 16 = no epilogue, 32 = no end-of-step barrier
-// (only meaningful together with 4 + 8); scripts/ring2_diag.py).  Compiled out of the product build:
-// the extra live flag costs the 32 -> 64 variant its last free registers.
-#ifdef SEGMI_RING2_DIAG
-#define RING2_DBG(p, bit) (((p).dbg & (bit)) != 0)
-#else
-#define RING2_DBG(p, bit) false
-#endif
-
 namespace segmi {
 
 // MODE 4 = PLAIN + the BatchNorm-backward sums of the layer the output gradient flows into
@@ -56,7 +46,7 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
   // in raster order, so that x/y-neighbours share one L2 and their halos are fetched once.  L2 fetch
   // of the 8 x 128^3 x 16 launch: 1.41x -> 1.02x of the input bytes.  Alone the launch is 1-2 % slower
   // (361 -> 369 us: the re-fetches were MALL hits), inside the training step, where the weight-gradient
-  // stream competes for the fabric, it is 3 % faster (step 5.83 -> 5.78 ms).  SEGMI_RING2_XCD=0: off.
+  // stream competes for the fabric, it is 3 % faster (step 5.83 -> 5.78 ms).
   int t = blockIdx.x;
   if (p.xcd) t = (t & 7) * (gridDim.x >> 3) + (t >> 3);
   const int seg = t % p.tz; t /= p.tz;
@@ -245,8 +235,8 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
   // Staging loads: the 4 new planes step k + 1 computes from (z = z0 + 4k + 5 .. + 8) are committed to the
   // ring at the end of step k and issued at its start.  PF2 = issue them a whole step earlier into a second
   // set of 32 staging registers (the step body then exists twice, for static register indexing): tried in
-  // round 3 for the 16 -> 16 forward variants (MODE 0 / 1: 252 / 256 VGPRs, no spill) because time splits of
-  // the diagnostic build show the launch ADDING its memory time to its compute time (compute only 209 us,
+  // round 3 for the 16 -> 16 forward variants (MODE 0 / 1: 252 / 256 VGPRs, no spill) because time splits
+  // (measured with a timing probe since removed) show the launch ADDING its memory time to its compute time (compute only 209 us,
   // + loads 104, + stores 66 of 361) -- and measured SLOWER: 382-389 vs 361 us alone, 0.338 vs 0.317 ms inside
   // the training step.  The loads are not late; left in the source, off.
   constexpr bool PF2 = false;
@@ -257,7 +247,7 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
     for (int pl = 0; pl < G::TD; ++pl) {
       const int z = z0 + zbk + 5 + pl;
       const unsigned poff = (unsigned)z * plane_b32;
-      const bool zok = morek && z < p.Di && !RING2_DBG(p, 1);
+      const bool zok = morek && z < p.Di;
 #pragma unroll
       for (int q = 0; q < NLP; ++q)
         dst[pl][q] = __builtin_amdgcn_raw_buffer_load_b128(
@@ -320,7 +310,6 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
     };
 #pragma unroll
     for (int q = 0; q < PD; ++q) issue(q, a[q]);
-    if (!RING2_DBG(p, 4))
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       if (it + PD < NIT) issue(it + PD, a[(it + PD) % (PD + 1)]);
@@ -342,7 +331,7 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
       __builtin_amdgcn_sched_barrier(0);
     }
     // ---- write the prefetched planes into the free ring slots (zb+6 .. zb+9 mod R)
-    if (more && !RING2_DBG(p, 8)) {
+    if (more) {
       // three copies of the commit loop behind wave-uniform branches (none / affine / affine +
       // PReLU) instead of per-element selects on the two runtime flags
       auto commit = [&](auto tf) {
@@ -431,12 +420,11 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
       }
     }
     // ---- epilogue of this step
-    if (!RING2_DBG(p, 16))
 #pragma unroll
     for (int zi = 0; zi < 4; ++zi) {
       const int oz = z0 + zb + zi;
       const unsigned opoff = (unsigned)oz * oplane_b;        // wave-uniform plane offset
-      const bool zin_out = oz < p.Do && !RING2_DBG(p, 2);
+      const bool zin_out = oz < p.Do;
       const int rz = PRE_RES ? zi : 0;
       if constexpr (!PRE_RES) {
         if (res_in) {
@@ -497,7 +485,7 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
         }
     }
     slot0 = slot0 + G::TD >= G::R ? slot0 + G::TD - G::R : slot0 + G::TD;
-    if (!RING2_DBG(p, 32)) __syncthreads();
+    __syncthreads();
   };
   if constexpr (PF2) {
     // two staging sets, alternating roles (static register indexing: the step body exists twice)
@@ -570,9 +558,6 @@ static int launch_conv_ring2_k(ConvParams p, hipStream_t st) {
   using G = RingGeom<T, CK>;
   constexpr int dt = DtypeOf<T>::value;
   p.tz = conv_ring_zsplit(dt, p.Cin, 3, 1, p.N, p.Do, p.Ho, p.Wo);
-  static const int dbg = getenv("SEGMI_RING2_DBG") ? atoi(getenv("SEGMI_RING2_DBG")) : 0;
-  p.dbg = dbg;
-  static const int xcd = getenv("SEGMI_RING2_XCD") ? atoi(getenv("SEGMI_RING2_XCD")) : 1;
   p.ty = cdiv(p.Ho, G::TH);
   p.tx = cdiv(p.Wo, G::TW);
   // 32-bit byte offsets inside one input / output plane
@@ -587,7 +572,7 @@ static int launch_conv_ring2_k(ConvParams p, hipStream_t st) {
                       (int64_t)(p.Do + 4) * p.Ho * p.Wo * (p.ldbx > 0 ? p.ldbx : 1) < (1ll << 31),
                   "conv3d: sample too large for the ring kernel's 32-bit plane offsets");
   dim3 grid((unsigned)(p.N * p.ty * p.tx * p.tz), (unsigned)(p.Cout / (16 * NT)));
-  p.xcd = xcd != 0 && grid.x % 8 == 0;
+  p.xcd = grid.x % 8 == 0;
   constexpr bool kStats = (MODE & 2) != 0, kBsum = MODE == 4;
   p.fin_on = p.fin_on && (kStats || kBsum);
   (void)fin_tail_arm(p, grid, 256, (kBsum ? 3 : 2) * p.Cout, G::LDS_BYTES + 6 * CK * 4 + 4096);   // LDS: the ring is larger

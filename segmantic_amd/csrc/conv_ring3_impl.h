@@ -24,7 +24,7 @@
 //    transforms and writes them back; padding chunks are redirected to a dump slot (border workgroups only).
 //  * Stores address with a per-lane offset computed once + the plane offset as the instruction's scalar soffset.
 //
-// What it is bound by (round 4, scripts/ring3_diag.py with SEGMI_RING3_DBG; 8 x 128^3 x 16, cold, alone): full 303 us;
+// What it is bound by (round 4, time splits with timing probes since removed; 8 x 128^3 x 16, cold, alone): full 303 us;
 // MFMA loop off 288; staging DMA alone 176 (3.1 TB/s of input), stores alone 125 (4.3 TB/s), both 289: the memory
 // phases ADD and the MFMA loop (183 us alone) hides under them -- the launch is bound by what each CU pulls through its
 // vector-memory pipe (~17-20 GB/s per CU here, 23 in an element-wise kernel), L2-side bytes, the 1.41x halo of the
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void conv_ring3_kernel(ConvParams p) {
     const int zb = step * G::TD;
     const bool more = step + 1 < nsteps_z;
     // ---- the next group: planes z0 + zb + 5 .. + 8, straight into the ring
-    if (more && !(p.dbg & 2)) dma_group(g_next, z0 + zb + 5);
+    if (more) dma_group(g_next, z0 + zb + 5);
     // residual rows of this step's outputs (external residual: the gradient sums of the backward chain)
     typedef typename Raw4<T>::type raw4_t;
     raw4_t resv[4][2];
@@ -369,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void conv_ring3_kernel(ConvParams p) {
       __builtin_amdgcn_sched_barrier(0);
     }
     // ---- the landed group's input transform, in place (each thread its own chunks: its own vmcnt orders it)
-    if (in_tf && more && !(p.dbg & 16)) {
+    if (in_tf && more) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       transform_group(g_next, p.Di - (z0 + zb + 5));
     }
@@ -430,7 +430,7 @@ __global__ __launch_bounds__(256, 2) void conv_ring3_kernel(ConvParams p) {
         u32x2 o;
         o[0] = H16<T>::pack2(v[0], v[1]);
         o[1] = H16<T>::pack2(v[2], v[3]);
-        __builtin_amdgcn_raw_buffer_store_b64(o, rs_out, (p.dbg & 4) ? kOob : o_off[ro], opoff, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(o, rs_out, o_off[ro], opoff, 0);
         if constexpr (BSUM) {
           // the sums are taken of the STORED gradient (bf16-rounded), as the separate pass reads it
           f32x4 d = Raw4<T>::cvt(o);
@@ -510,22 +510,16 @@ template <typename T, int MODE>
 static int launch_conv_ring3_k(ConvParams p, hipStream_t st) {
   using G = Ring3Geom;
   p.tz = conv_ring_zsplit(DtypeOf<T>::value, p.Cin, 3, 1, p.N, p.Do, p.Ho, p.Wo);
-  // diagnostics (timing probes, WRONG results): SEGMI_RING3_DBG bits: 2 = no staging DMA in the step loop, 4 = stores
-  // dropped, 8 = no MFMA loop, 16 = no input transform
-  static const int dbg3 = getenv("SEGMI_RING3_DBG") ? atoi(getenv("SEGMI_RING3_DBG")) : 0;
-  p.dbg = dbg3;
   // ring2's XCD-aware column map (XCD k walks the k-th eighth of the columns: neighbours' halos meet in one L2) is used
   // for launches of at most one round of workgroups (<= 512: the 64^3 layers -- inference 41.4 vs 42.3 ms per volume
   // with / without) and NOT for larger ones: on the full-resolution 8 x 128^3 launch (1024 workgroups, two rounds) it
   // costs 10 % (0.300 -> 0.270 ms inside the training step, step 5.11 -> 5.02 ms, alternating runs; memory-only
-  // diagnostic 289 -> 228 us).  The halo re-reads it saves there were Infinity-Cache hits, and a CU's vector-memory
-  // pipe -- the bound of this kernel -- does not care where a line comes from.  SEGMI_RING3_XCD = 0 / 1 forces it.
-  static const int xcd_env = getenv("SEGMI_RING3_XCD") ? atoi(getenv("SEGMI_RING3_XCD")) : -1;
+  // probe 289 -> 228 us).  The halo re-reads it saves there were Infinity-Cache hits, and a CU's vector-memory
+  // pipe -- the bound of this kernel -- does not care where a line comes from.
   p.ty = cdiv(p.Ho, G::TH);
   p.tx = cdiv(p.Wo, G::TW);
   dim3 grid((unsigned)(p.N * p.ty * p.tx * p.tz), (unsigned)(p.Cout / 16));
-  const int xcd = xcd_env >= 0 ? xcd_env : (grid.x <= 512 ? 1 : 0);
-  p.xcd = xcd != 0 && grid.x % 8 == 0;
+  p.xcd = grid.x <= 512 && grid.x % 8 == 0;
   constexpr bool kStats = (MODE & 2) != 0, kBsum = MODE == 4;
   p.fin_on = p.fin_on && (kStats || kBsum);
   (void)fin_tail_arm(p, grid, 256, (kBsum ? 3 : 2) * p.Cout, G::LDS_BYTES);   // LDS: the ring is larger than the tail's need

@@ -45,7 +45,6 @@ struct DecTopParams {
   const float* cv_bias;
   int N, Dc, Hc, Wc, Do, Ho, Wo, ldi, ldo;
   int ty, tx, tz;
-  int dbg;   // SEGMI_DECTOP_DBG, timing probes: 1 = producers idle, 2 = consumers idle (wrong output)
   int alpha01;   // the caller asserts 0 <= *up_alpha <= 1: PReLU as max(v, slope v)
 };
 
@@ -238,7 +237,7 @@ __global__ __launch_bounds__(512, 1) void dectop_kernel(DecTopParams p) {
       const int cb0 = cz0 - 1 + 2 * rr;
       if (work) cat_commit(cb0 + 1, 2);
       ws_barrier();                                  // X: the coarse planes are in LDS
-      if (work && !(p.dbg & 1)) {
+      if (work) {
         if (rr + 1 <= nsteps_z) cat_fetch(cb0 + 3, 2);
         int cslot[3], pl[4];
         bool zin[4];
@@ -301,7 +300,6 @@ __global__ __launch_bounds__(512, 1) void dectop_kernel(DecTopParams p) {
   for (int step = 0; step < nsteps_z; ++step) {
     const int zb = step * TD;
     ws_barrier();                                      // X (the producers' hand-off among themselves)
-    if (p.dbg & 2) { ws_barrier(); continue; }         // timing probes only
     // ---- conv: input plane c (z = z0 + zb - 1 + c) lives in ring slot (zb + c + 1) % R
     f32x4 acc[4][NRO];
     int pofs[6];
@@ -404,8 +402,6 @@ int segmi_dectop_fwd(int dtype, const segmi_act* in, const segmi_act* out, const
   p.ldi = in->ld; p.ldo = out->ld;
   p.ty = out->h / dectop::TH; p.tx = out->w / dectop::TW;
   p.tz = dectop_tz(in->n, out->d, out->h, out->w);
-  static const int dbg = getenv("SEGMI_DECTOP_DBG") ? atoi(getenv("SEGMI_DECTOP_DBG")) : 0;
-  p.dbg = dbg;
   p.alpha01 = up_alpha_in_unit_range ? 1 : 0;
   const unsigned grid = (unsigned)(p.N * p.ty * p.tx * p.tz);
   if (dtype == SEGMI_F16) return launch_dectop<f16_t>(p, grid, (hipStream_t)stream);

@@ -15,19 +15,13 @@
 // their 7*CT*CT accumulators in registers across all tiles of the range (persistent loop).
 // Per-workgroup partial slabs are reduced in fixed order by wgrad_reduce_kernel: bitwise
 // reproducible, no atomics.
-#pragma once
-#include "common.h"
-
-// Time-split diagnostic (build with -DSEGMI_WGRAD_DIAG, run with SEGMI_WGRAD_DBG=bits: 1 = no global
-// loads, 4 = no LDS-read / MFMA loop; scripts/wgrad_diag.py).  Measured on the 128^3 x 8, 16 x 16 layer
-// (cold caches, us): all 444, no loads 316, no MFMA loop 254, neither 137 -- the three phases of a
+//
+// Time split, measured with timing probes since removed, on the 128^3 x 8, 16 x 16 layer (cold caches,
+// us): all 444, no global loads 316, no LDS-read / MFMA loop 254, neither 137 -- the three phases of a
 // tile barely overlap at 2 workgroups per CU; the MFMA-loop phase sits at the LDS instruction
 // rate (2 ds_read_b64_tr_b16 per operand, ~2.4 clk each, 2.3 per MFMA).
-#ifdef SEGMI_WGRAD_DIAG
-#define WGRAD_DBG(p, bit) (((p).dbg & (bit)) != 0)
-#else
-#define WGRAD_DBG(p, bit) false
-#endif
+#pragma once
+#include "common.h"
 
 namespace segmi {
 
@@ -40,10 +34,7 @@ struct WgradParams {
   int ntiles;
   int zs, zper;   // wave-specialised kernel: z-segments per column, z-tiles per segment
   unsigned x_bytes, y_bytes;   // ... and the byte extents of the two tensors (buffer num_records)
-  unsigned long long* stamps;  // diag build: s_memtime stamps of workgroup 0, [iter][12 waves][4]
   int ci_chunks;
-  int dbg;
-  int zmarch;     // wave-specialised kernel: shared input planes of consecutive z-tiles are copied LDS -> LDS (1 = on)
   // optional input transform of X (segmi_in_affine): the BatchNorm-apply + PReLU that produced the
   // forward input is applied while the X tile is committed to LDS (bf16 only)
   const float* in_scale;
@@ -181,14 +172,14 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(WgradParams p) {
     for (int k = 0; k < NLY; ++k) {        // dY tile [NV][16*CTO]
       const unsigned pk = y_pk[k];
       ry[k] = frag_t{0u, 0u, 0u, 0u};
-      if ((pk & 255u) < lz && ((pk >> 8) & 255u) < ly && (pk >> 16) < lx && !WGRAD_DBG(p, 1))
+      if ((pk & 255u) < lz && ((pk >> 8) & 255u) < ly && (pk >> 16) < lx)
         ry[k] = *reinterpret_cast<const frag_t*>(ybase + (unsigned)y_goff[k]);
     }
 #pragma unroll
     for (int k = 0; k < NLX; ++k) {        // X halo tile [HD*HH*HW][16*CTI]
       const unsigned pk = x_pk[k];
       rx[k] = frag_t{0u, 0u, 0u, 0u};
-      const bool inside = pk != 0xffffffffu && !WGRAD_DBG(p, 1) && (unsigned)((int)(pk & 255u) + iz0) < (unsigned)p.Dx &&
+      const bool inside = pk != 0xffffffffu && (unsigned)((int)(pk & 255u) + iz0) < (unsigned)p.Dx &&
           (unsigned)((int)((pk >> 8) & 255u) + iy0) < (unsigned)p.Hx &&
           (unsigned)((int)(pk >> 16) + ix0) < (unsigned)p.Wx;
       if (inside) rx[k] = *reinterpret_cast<const frag_t*>(xbase + (unsigned)x_goff[k]);
@@ -232,7 +223,6 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(WgradParams p) {
     __syncthreads();
     if (tile + (int)gridDim.x < p.ntiles) fetch(tile + gridDim.x);
 
-    if (!WGRAD_DBG(p, 4))
 #pragma unroll
     for (int lg = 0; lg < G::NL / G::LPG; ++lg) {
       frag_t af[CTO];
@@ -322,8 +312,6 @@ static int launch_wgrad_cfg(WgradParams p, int gx_hint, hipStream_t st) {
                       (int64_t)TD * p.Hy * p.Wy * p.ldy * (int64_t)sizeof(T) < (1ll << 31),
                   "conv3d_wgrad: plane too large for the MFMA kernel's 32-bit tile offsets");
   p.ci_chunks = p.Cin / (16 * CTI);
-  static const int dbg = getenv("SEGMI_WGRAD_DBG") ? atoi(getenv("SEGMI_WGRAD_DBG")) : 0;
-  p.dbg = dbg;
   const int co_chunks = p.Cout / (16 * CTO);
   dim3 grid((unsigned)gx_hint, (unsigned)(co_chunks * p.ci_chunks));
   auto kern = wgrad_mfma_kernel<T, KS, S, CTO, CTI, TD, TH, TW>;
@@ -366,8 +354,7 @@ int wgrad_cus(int cus);
 // and that have enough tiles per workgroup for its pipeline to matter.  Encodes the choice made by
 // the launcher (wgrad_mfma_bf16) so that the workspace query sizes the same number of slabs.
 static inline int wgrad_ws_gx(int dtype, const segmi_act* x, const segmi_act* dy, int ksize, int stride, int cus) {
-  static const bool enabled = !(getenv("SEGMI_WGRAD_WS") && atoi(getenv("SEGMI_WGRAD_WS")) == 0);
-  if (!enabled || !dtype_h16(dtype) || ksize != 3) return 0;
+  if (!dtype_h16(dtype) || ksize != 3) return 0;
   const int ct = wgrad_ct(dtype, dy->c);
   const int cto = ct / 10, cti = ct % 10;
   const int chunks = (x->c / (16 * cti)) * (dy->c / (16 * cto));

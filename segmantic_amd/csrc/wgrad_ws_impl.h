@@ -32,20 +32,11 @@
 // The halo planes a tile shares with its z-predecessor were fetched one iteration earlier by the
 // same CU, and the y / x halos belong to units that neighbouring workgroups of the same XCD walk at
 // the same time: both come from that XCD's L2 instead of HBM (measured with FETCH_SIZE: 1.10 GB
-// per launch for 1.07 GB of tensors; the 4x8x16 tile's halo is 2.1x of X).
+// per launch for 1.07 GB of tensors; the 4x8x16 tile's halo is 2.1x of X; A/B against the plain
+// unit order: 4.99 vs 5.02 ms per training step).
 #pragma once
 #include <type_traits>
 #include "wgrad_impl.h"
-
-#ifdef SEGMI_WGRAD_DIAG
-#define WS_STAMP(it, slot)                                                                      \
-  do {                                                                                          \
-    if (p.stamps && blockIdx.x == 0 && blockIdx.y == 0 && (threadIdx.x & 63) == 0 && (it) < 128) \
-      p.stamps[(((it) * 12) + (threadIdx.x >> 6)) * 4 + (slot)] = __builtin_amdgcn_s_memtime();    \
-  } while (0)
-#else
-#define WS_STAMP(it, slot) do {} while (0)
-#endif
 
 namespace segmi {
 
@@ -71,7 +62,7 @@ __global__ __launch_bounds__(768) void wgrad_ws_kernel(WgradParams p) {
   const int cols = p.ty * p.tx;
   const int nunits = p.N * p.zs * cols;
   int u_begin, u_end, u_stride;
-  if ((nx & 7) == 0 && !(p.dbg & 64)) {        // SEGMI_WGRAD_DBG bit 64: the plain unit order (A/B of the XCD grouping)
+  if ((nx & 7) == 0) {
     const int xcd = bid & 7, slot = bid >> 3;
     u_begin = (int)((int64_t)nunits * xcd / 8) + slot;
     u_end = (int)((int64_t)nunits * (xcd + 1) / 8);
@@ -130,48 +121,43 @@ __global__ __launch_bounds__(768) void wgrad_ws_kernel(WgradParams p) {
       ws_barrier();                                   // tile 0 is in buffer 0
       for (int it = 0; it < niter; ++it) {
         const char* buf = smem + (it & 1) * BUF;
-        WS_STAMP(it, 0);
-        if (!WGRAD_DBG(p, 4)) {
-          frag_t af[TD];
+        frag_t af[TD];
 #pragma unroll
-          for (int z = 0; z < TD; ++z) {
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (lds_s16x4*)(buf + ybase + ((z * TH) * TW) * G::YROWB));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (lds_s16x4*)(buf + ybase + ((z * TH + 1) * TW) * G::YROWB));
-            const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-            af[z] = frag_t{l2[0], l2[1], h2[0], h2[1]};
-          }
-          u32x8 strip[PD + 1];
+        for (int z = 0; z < TD; ++z) {
+          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (lds_s16x4*)(buf + ybase + ((z * TH) * TW) * G::YROWB));
+          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (lds_s16x4*)(buf + ybase + ((z * TH + 1) * TW) * G::YROWB));
+          const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
+          af[z] = frag_t{l2[0], l2[1], h2[0], h2[1]};
+        }
+        u32x8 strip[PD + 1];
 #pragma unroll
-          for (int s0 = 0; s0 < PD; ++s0) strip[s0] = read_strip(buf, s0);
+        for (int s0 = 0; s0 < PD; ++s0) strip[s0] = read_strip(buf, s0);
 #pragma unroll
-          for (int sidx = 0; sidx < NSTRIP; ++sidx) {
-            if (sidx + PD < NSTRIP) strip[(sidx + PD) % (PD + 1)] = read_strip(buf, sidx + PD);
-            __builtin_amdgcn_sched_barrier(0);
-            const int c = sidx / 3, dx = sidx % 3;
-            const u32x8 st = strip[sidx % (PD + 1)];
-            const frag_t bfs[3] = {__builtin_shufflevector(st, st, 0, 1, 2, 3),
-                                   __builtin_shufflevector(st, st, 2, 3, 4, 5),
-                                   __builtin_shufflevector(st, st, 4, 5, 6, 7)};
+        for (int sidx = 0; sidx < NSTRIP; ++sidx) {
+          if (sidx + PD < NSTRIP) strip[(sidx + PD) % (PD + 1)] = read_strip(buf, sidx + PD);
+          __builtin_amdgcn_sched_barrier(0);
+          const int c = sidx / 3, dx = sidx % 3;
+          const u32x8 st = strip[sidx % (PD + 1)];
+          const frag_t bfs[3] = {__builtin_shufflevector(st, st, 0, 1, 2, 3),
+                                 __builtin_shufflevector(st, st, 2, 3, 4, 5),
+                                 __builtin_shufflevector(st, st, 4, 5, 6, 7)};
 #pragma unroll
-            for (int kh = 0; kh < 3; ++kh) {
-              const frag_t bf = bfs[kh];
+          for (int kh = 0; kh < 3; ++kh) {
+            const frag_t bf = bfs[kh];
 #pragma unroll
-              for (int kd = 0; kd < 3; ++kd) {
-                const int z = c - kd;
-                if (z >= 0 && z < TD) {
-                  const int t = (kd * 3 + kh) * 3 + dx;
-                  acc[t] = mma16<T>(af[z], bf, acc[t]);
-                }
+            for (int kd = 0; kd < 3; ++kd) {
+              const int z = c - kd;
+              if (z >= 0 && z < TD) {
+                const int t = (kd * 3 + kh) * 3 + dx;
+                acc[t] = mma16<T>(af[z], bf, acc[t]);
               }
             }
-            __builtin_amdgcn_sched_barrier(0);
           }
+          __builtin_amdgcn_sched_barrier(0);
         }
-        WS_STAMP(it, 1);
         ws_barrier();                                 // done with buffer it & 1; tile it + 1 is ready
-        WS_STAMP(it, 2);
       }
       // ---- sum the four waves' accumulators through LDS: (w0 + w2) + (w1 + w3), fixed order
       f32x4* red = reinterpret_cast<f32x4*>(smem);    // [2][27][64] f32x4 = 55 KB (buffers are free now)
@@ -266,21 +252,19 @@ __global__ __launch_bounds__(768) void wgrad_ws_kernel(WgradParams p) {
     for (int it = 0; it < niter; ++it) {
       char* ysm = smem + (it & 1) * BUF;
       char* xsm = ysm + G::YBYTES;
-      if (!WGRAD_DBG(p, 4)) {
-        read_group(ysm, xsm, 0, af[0], bf[0]);
+      read_group(ysm, xsm, 0, af[0], bf[0]);
 #pragma unroll
-        for (int lg = 0; lg < NKG; ++lg) {
-          if (lg + 1 < NKG) read_group(ysm, xsm, lg + 1, af[(lg + 1) & 1], bf[(lg + 1) & 1]);
-          __builtin_amdgcn_sched_barrier(0);
+      for (int lg = 0; lg < NKG; ++lg) {
+        if (lg + 1 < NKG) read_group(ysm, xsm, lg + 1, af[(lg + 1) & 1], bf[(lg + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int ti = 0; ti < G::NTW; ++ti)
+        for (int ti = 0; ti < G::NTW; ++ti)
 #pragma unroll
-            for (int ct = 0; ct < CTO; ++ct)
+          for (int ct = 0; ct < CTO; ++ct)
 #pragma unroll
-              for (int c = 0; c < CTI; ++c)
-                acc[ti][ct][c] = mma16<T>(af[lg & 1][ct], bf[lg & 1][ti][c], acc[ti][ct][c]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
+            for (int c = 0; c < CTI; ++c)
+              acc[ti][ct][c] = mma16<T>(af[lg & 1][ct], bf[lg & 1][ti][c], acc[ti][ct][c]);
+        __builtin_amdgcn_sched_barrier(0);
       }
       ws_barrier();                                 // done with buffer it & 1; tile it + 1 is ready
     }
@@ -404,15 +388,15 @@ __global__ __launch_bounds__(768) void wgrad_ws_kernel(WgradParams p) {
   // `cont` (out): the tile continues its unit -- its first OV input planes are not fetched (commit copies them)
   auto fetch = [&](frag_t (&ry)[NLY], frag_t (&rx)[NLX], unsigned& xmask, bool& cont) {
     const int oz0 = cur_z * TD, iz0 = oz0 * S - G::PAD;
-    const bool border = (xy_border || iz0 < 0 || iz0 + G::HD > p.Dx || oz0 + TD > p.Dy) && !WGRAD_DBG(p, 64);
-    cont = OV > 0 && p.zmarch && cur_z != cur_zbeg;
+    const bool border = xy_border || iz0 < 0 || iz0 + G::HD > p.Dx || oz0 + TD > p.Dy;
+    cont = OV > 0 && cur_z != cur_zbeg;
     const unsigned skip = cont ? x_ov : 0u;
-    if (!border && !WGRAD_DBG(p, 1)) {
+    if (!border) {
 #pragma unroll
-      for (int k = 0; k < NLY; ++k) ry[k] = __builtin_amdgcn_raw_buffer_load_b128(yrs, WGRAD_DBG(p, 32) ? OOB : y_goff[k], ybase, 0);
+      for (int k = 0; k < NLY; ++k) ry[k] = __builtin_amdgcn_raw_buffer_load_b128(yrs, y_goff[k], ybase, 0);
       if (!cont) {
 #pragma unroll
-        for (int k = 0; k < NLX; ++k) rx[k] = __builtin_amdgcn_raw_buffer_load_b128(xrs, WGRAD_DBG(p, 16) ? OOB : x_goff[k], xbase, 0);
+        for (int k = 0; k < NLX; ++k) rx[k] = __builtin_amdgcn_raw_buffer_load_b128(xrs, x_goff[k], xbase, 0);
       } else {
         // (per-lane out-of-range marker in the vector offset, no scalar offset: marker + base must not wrap; a slot
         // whose 512 chunks ALL lie in the shared planes issues no load at all)
@@ -428,17 +412,16 @@ __global__ __launch_bounds__(768) void wgrad_ws_kernel(WgradParams p) {
       const unsigned ylim = clamp7(p.Dy - oz0 - 1) | ylim_xy;
       const unsigned xlo = clamp7(-iz0) | xlo_xy;
       const unsigned xhi = clamp7(p.Dx - iz0 - 1) | xhi_xy;
-      const bool dead = WGRAD_DBG(p, 1);
 #pragma unroll
       for (int k = 0; k < NLY; ++k) {
-        const bool ok = ((((ylim | 0x808080u) - y_pk[k]) & 0x808080u) == 0x808080u) && !dead;
+        const bool ok = (((ylim | 0x808080u) - y_pk[k]) & 0x808080u) == 0x808080u;
         ry[k] = __builtin_amdgcn_raw_buffer_load_b128(yrs, ok ? ybase + y_goff[k] : OOB, 0, 0);
       }
       unsigned xm = 0u;
 #pragma unroll
       for (int k = 0; k < NLX; ++k) {
         const unsigned t1 = (x_pk[k] | 0x808080u) - xlo, t2 = (xhi | 0x808080u) - x_pk[k];
-        const bool ok = ((t1 & t2 & 0x808080u) == 0x808080u) && !dead;
+        const bool ok = (t1 & t2 & 0x808080u) == 0x808080u;
         rx[k] = __builtin_amdgcn_raw_buffer_load_b128(xrs, ok && !((skip >> k) & 1u) ? xbase + x_goff[k] : OOB, 0, 0);
         xm |= ok ? (1u << k) : 0u;
       }
@@ -456,13 +439,13 @@ __global__ __launch_bounds__(768) void wgrad_ws_kernel(WgradParams p) {
 #pragma unroll
     for (int k = 0; k < NLY; ++k) {
       const int i = ptid + PT * k;
-      if (i < G::NV * G::YCPR && !(WGRAD_DBG(p, 8) && ry[k][0] != 0x12345u))
+      if (i < G::NV * G::YCPR)
         *reinterpret_cast<frag_t*>(ysm + (i / G::YCPR) * G::YROWB + (i % G::YCPR) * 16) = ry[k];
     }
 #pragma unroll
     for (int k = 0; k < NLX; ++k) {
       const int i = ptid + PT * k;
-      if (i < G::XROWS * G::XCPR && !(WGRAD_DBG(p, 8) && rx[k][0] != 0x12345u)) {
+      if (i < G::XROWS * G::XCPR) {
         const int lo = (i / G::XCPR) * G::XROWB + (i % G::XCPR) * 16;
         frag_t val = rx[k];
         if ((skip >> k) & 1u) {
@@ -508,21 +491,13 @@ __global__ __launch_bounds__(768) void wgrad_ws_kernel(WgradParams p) {
   }
   ws_barrier();
   for (int it = 0; it < niter; it += 2) {
-    WS_STAMP(it, 0);
     if (it + 1 < niter) commit(1, ryB, rxB, xmB, bdB, ctB);   // tile it + 1 (copies from buffer 0 = tile it)
-    WS_STAMP(it, 1);
     if (it + 3 < niter) bdB = fetch(ryB, rxB, xmB, ctB);      // tile it + 3
-    WS_STAMP(it, 2);
     ws_barrier();
-    WS_STAMP(it, 3);
     if (it + 1 >= niter) break;
-    WS_STAMP(it + 1, 0);
     if (it + 2 < niter) commit(0, ryA, rxA, xmA, bdA, ctA);   // tile it + 2 (copies from buffer 1 = tile it + 1)
-    WS_STAMP(it + 1, 1);
     if (it + 4 < niter) bdA = fetch(ryA, rxA, xmA, ctA);      // tile it + 4
-    WS_STAMP(it + 1, 2);
     ws_barrier();
-    WS_STAMP(it + 1, 3);
   }
   if constexpr (ROWS) { ws_barrier(); ws_barrier(); ws_barrier(); }   // the consumers' final reduction
 }
@@ -557,15 +532,6 @@ static int launch_wgrad_ws_cfg(WgradParams p, int gx, hipStream_t st) {
   SEGMI_CHECK_ARG(xb < 0xfff00000ll && yb < 0xfff00000ll, "conv3d_wgrad(ws): tensor beyond the 4 GB buffer range");
   p.x_bytes = (unsigned)xb; p.y_bytes = (unsigned)yb;
   p.ci_chunks = p.Cin / (16 * CTI);
-  static const int dbg = getenv("SEGMI_WGRAD_DBG") ? atoi(getenv("SEGMI_WGRAD_DBG")) : 0;
-  p.dbg = dbg;
-  static const bool zmarch = !(getenv("SEGMI_WGRAD_ZMARCH") && atoi(getenv("SEGMI_WGRAD_ZMARCH")) == 0);   // A/B
-  p.zmarch = zmarch ? 1 : 0;
-#ifdef SEGMI_WGRAD_DIAG
-  // diag build: SEGMI_WGRAD_STAMPS = device address (decimal) of a 128 * 12 * 4 u64 buffer
-  static const char* stamps_env = getenv("SEGMI_WGRAD_STAMPS");
-  p.stamps = stamps_env ? (unsigned long long*)strtoull(stamps_env, nullptr, 10) : nullptr;
-#endif
   const int co_chunks = p.Cout / (16 * CTO);
   dim3 grid((unsigned)gx, (unsigned)(co_chunks * p.ci_chunks));
   auto kern = wgrad_ws_kernel<T, KS, S, CTO, CTI, TD, TH, TW>;

@@ -446,7 +446,7 @@ class UNetEngine:
                     kind, cin_k, cout_k, k = geom
                     entries.append((kind, conv.w, None, cin_k, cout_k, k))
                     slots.append((conv, (tag, self.dtype)))
-                if conv.pair_with is not None and self.pair_train and conv not in self._carry_convs:
+                if conv.pair_with is not None and conv not in self._carry_convs:
                     entries.append((0, conv.w, None, conv.cin, 2 * conv.cout, conv.k, conv.pair_with.w, conv.cout))
                     slots.append((conv, ("pair", self.dtype)))
             self._wbatch = {c: ((ops.WpackBatch(self.dtype, e), sl) if e else (None, [])) for c, (e, sl) in groups.items()}
@@ -633,12 +633,11 @@ class UNetEngine:
     # Training: the stride-2 first subunit and the residual convolution of an encoder unit read the same input; as
     # two launches of the tile-at-a-time kernel they cost 54 + 54 us (16 -> 32 at 64^3, batch 8), 44 + 44 and 14 + 24
     # one and two levels down.  The eval pairing with BatchNorm statistics on the first half (round 4) runs them as
-    # one launch each.  SEGMI_PAIR_TRAIN=0: two launches (A/B).
-    pair_train = os.environ.get("SEGMI_PAIR_TRAIN", "1") != "0"
+    # one launch each (4.64 vs 4.72 ms per step as two launches).
     def _train_pair(self, ru, x, oshape):
         """the [.., 2c] buffer of the merged first subunit + residual convolution (training), or None"""
         c0 = ru["units"][0][0]
-        if not self.pair_train or c0.pair_with is None or c0 in self._carry_convs:
+        if c0.pair_with is None or c0 in self._carry_convs:
             return None
         m = self._buf(f"{ru['prefix']}.tm", oshape + (2 * c0.cout,))
         return m if ops.conv3d_split_act_ok(x, m, 3, c0.stride) else None
@@ -677,18 +676,14 @@ class UNetEngine:
                     else ops.conv3d_stats_rows(x, y, conv.k, conv.stride))
             stats = self._fstat(rows, conv.cout)
         # the launch that writes the statistics rows finalises them itself (segmi_bn_fin): no
-        # bn_finalize launch on the dependent chain (SEGMI_FUSE_FIN=0: separate launch, for A/B)
-        fin = self._stats_fin(bn, y) if bn is not None and self.fuse_fin else None
+        # bn_finalize launch on the dependent chain (neutral in time, 34 fewer dispatches per step)
+        fin = self._stats_fin(bn, y) if bn is not None else None
         if conv.transposed:
             self._timed(conv.prefix + ":fwd", ops.convT3d_fwd, x, y, conv.fwd_pack(), conv.w,
                         conv.b, stats=stats, stats_fin=fin)
         else:
             self._timed(conv.prefix + ":fwd", ops.conv3d_fwd, x, y, conv.fwd_pack(), conv.w, 0,
                         conv.b, conv.k, conv.stride, stats=stats, in_tf=in_tf, stats_fin=fin)
-        if bn is not None and fin is None:
-            count = y.shape[0] * y.shape[1] * y.shape[2] * y.shape[3]
-            ops.bn_finalize(stats, rows, conv.cout, count, bn.gamma, bn.beta, bn.rm, bn.rv,
-                            self.momentum, self.eps, bn.mean, bn.invstd, bn.scale, bn.shift)
 
     def _stats_fin(self, bn: "_BN", y) -> tuple:
         count = y.shape[0] * y.shape[1] * y.shape[2] * y.shape[3]
@@ -754,7 +749,7 @@ class UNetEngine:
             self._timed(conv.prefix + ":dgrad", ops.conv3d_fwd, dy, dx, conv.dgrad_pack(), conv.w, 1,
                         None, conv.k, 1, residual=residual,
                         bn_bwd=(x_raw, bn.mean, bn.invstd, bn.gamma, bn.beta, bn.alpha, part),
-                        bn_bwd_fin=self._bwd_fin(bn, x_raw) if self.fuse_fin else None)
+                        bn_bwd_fin=self._bwd_fin(bn, x_raw))
             return rows
         if conv.transposed:
             ops.conv3d_fwd(dy, dx, conv.dgrad_pack(), conv.w, 0, None, 3, 2, residual=residual)
@@ -775,12 +770,11 @@ class UNetEngine:
     fuse_apply_conv = os.environ.get("SEGMI_FUSE_APPLY_CONV", "1") != "0"
 
     def _bn_bwd(self, bn: _BN, dy, x_raw, dx, sums_rows: int = 0, then_conv=None) -> bool:
-        """``sums_rows`` > 0: the reduction's partial rows were written by the launch that produced dy
-        (``_dgrad(..., bsum=)``); only finalisation and apply remain.  ``then_conv`` = (conv, out): the
+        """``sums_rows`` > 0: the reduction's partial rows were written and finalised by the launch that
+        produced dy (``_dgrad(..., bsum=)``); only the apply remains.  ``then_conv`` = (conv, out): the
         caller's next launch is ``out = dgrad(conv, dx)`` of a transposed convolution; returns True when
         that convolution was done here, in the launch that computed dx."""
-        count = x_raw.shape[0] * x_raw.shape[1] * x_raw.shape[2] * x_raw.shape[3]
-        if (not sums_rows and self.fuse_bn_bwd_small and self.fuse_fin and self.dropout_p <= 0.0
+        if (not sums_rows and self.fuse_bn_bwd_small and self.dropout_p <= 0.0
                 and ops.bn_act_bwd_fused_ok(dy, x_raw, dx)):
             # deep levels: reduce + finalise + apply as ONE launch (csrc/norm_act.hip, bn_act_bwd_fused_kernel)
             # its workgroups hold a CU each and wait on it for the launch's last one: beside the CU-exclusive
@@ -790,17 +784,10 @@ class UNetEngine:
             ops.bn_act_bwd_fused(dy, x_raw, dx, bn.mean, bn.invstd, bn.gamma, bn.beta, bn.alpha,
                                  self._fstat(rows, bn.c), self._bwd_fin(bn, x_raw), max_wgs=self.fused_bn_max_wgs())
             return False
-        if sums_rows:
-            rows = sums_rows
-            part = self._fstat(rows, bn.c)
-        else:
-            rows = ops.bn_act_bwd_rows(x_raw)
-            part = self._fstat(rows, bn.c)
+        if not sums_rows:             # reduce + finalise as one launch
+            part = self._fstat(ops.bn_act_bwd_rows(x_raw), bn.c)
             ops.bn_act_bwd_reduce(dy, x_raw, bn.mean, bn.invstd, bn.gamma, bn.beta, bn.alpha, part,
-                                  dropout=bn.drop(), fin=self._bwd_fin(bn, x_raw) if self.fuse_fin else None)
-        if not self.fuse_fin:         # else: finalised by the launch that wrote the rows
-            ops.bn_act_bwd_finalize(part, rows, bn.c, count, bn.gamma, bn.invstd, bn.g_gamma,
-                                    bn.g_beta, bn.g_alpha, bn.coef)
+                                  dropout=bn.drop(), fin=self._bwd_fin(bn, x_raw))
         if (then_conv is not None and self.fuse_apply_conv and self.dropout_p <= 0.0 and then_conv[0].transposed
                 and ops.bn_act_bwd_apply_conv_ok(dy, x_raw, dx, then_conv[1])):
             ops.bn_act_bwd_apply_conv(dy, x_raw, dx, bn.mean, bn.invstd, bn.gamma, bn.beta, bn.alpha, bn.coef,
@@ -843,12 +830,9 @@ class UNetEngine:
                 r, resid = m[..., :conv.cout], m[..., conv.cout:]
                 rows = ops.conv3d_stats_rows(x, m, conv.k, conv.stride)
                 stats = self._fstat(rows, conv.cout)
-                fin = self._stats_fin(bn, r) if self.fuse_fin else None
                 self._timed(conv.prefix + ":fwd", ops.conv3d_fwd_split_act, x, m, conv.pair_pack(), conv.b, None,
-                            conv.cout, conv.k, conv.stride, bias_b=ru["res"].b, stats=stats, stats_fin=fin)
-                if fin is None:
-                    ops.bn_finalize(stats, rows, conv.cout, n * d * h * w, bn.gamma, bn.beta, bn.rm,
-                                    bn.rv, self.momentum, self.eps, bn.mean, bn.invstd, bn.scale, bn.shift)
+                            conv.cout, conv.k, conv.stride, bias_b=ru["res"].b, stats=stats,
+                            stats_fin=self._stats_fin(bn, r))
                 saved[f"in{i}"] = cur
                 saved[f"r{i}"] = r
                 nconv = ru["units"][i + 1][0]
@@ -866,12 +850,8 @@ class UNetEngine:
                 rows = ops.conv3d_stats_rows(x, r, conv.k, conv.stride)
                 stats = self._fstat(rows, conv.cout)
                 rc = ru["res"]
-                fin = self._stats_fin(bn, r) if self.fuse_fin else None
                 self._timed(conv.prefix + ":fwd", ops.conv3d_fwd_pair, x, r, conv.w, conv.b, out,
-                            rc.w, rc.b, conv.stride, stats_a=stats, stats_fin_a=fin)
-                if fin is None:
-                    ops.bn_finalize(stats, rows, conv.cout, n * d * h * w, bn.gamma, bn.beta, bn.rm,
-                                    bn.rv, self.momentum, self.eps, bn.mean, bn.invstd, bn.scale, bn.shift)
+                            rc.w, rc.b, conv.stride, stats_a=stats, stats_fin_a=self._stats_fin(bn, r))
                 saved[f"in{i}"] = cur
                 saved[f"r{i}"] = r
                 nconv = ru["units"][i + 1][0]
@@ -1338,9 +1318,6 @@ class UNetEngine:
     # BatchNorm-apply + PReLU folded into the consumer conv's staging where the kernels allow it
     # (segmi_in_affine); SEGMI_FUSE_BN=0 keeps the separate pass for A/B measurements
     fuse_bn_apply = os.environ.get("SEGMI_FUSE_BN", "1") != "0"
-    # Finalisation of every BatchNorm reduction (forward statistics, backward sums) by the launch that
-    # writes the partial rows (csrc/fin_tail.h); SEGMI_FUSE_FIN=0 keeps the separate one-workgroup launches
-    fuse_fin = os.environ.get("SEGMI_FUSE_FIN", "1") != "0"
     # BatchNorm / PReLU backward of the small (<= 32 MB) tensors as one launch with a grid-wide hand-off
     # instead of reduce -> apply (SEGMI_FUSE_BN_BWD_SMALL=0: two launches)
     fuse_bn_bwd_small = os.environ.get("SEGMI_FUSE_BN_BWD_SMALL", "1") != "0"
