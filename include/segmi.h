@@ -564,6 +564,54 @@ int segmi_confusion_counts(const void* pred, const void* truth, int label_bytes,
                            int64_t* cm, void* stream);
 
 
+/* ---------------------------------------------------------------- label clean-up ------- */
+/* Connected components of a label map and the clean-up transforms built on them (MONAI's
+ * KeepLargestConnectedComponent / RemoveSmallObjects / FillHoles, which are CPU loops over classes), plus
+ * MapLabels of src/segmantic/seg/transforms.py:91-127.  Label volumes are read in place as label_bytes in
+ * {1 (uint8), 2 (int16), 4 (int32)}, [d][h][w] (a 2-D input is d = 1 with spatial_dims = 2); n = d*h*w
+ * must be < 2^31.  connectivity c in 1 .. spatial_dims: neighbours differ by at most 1 along every axis
+ * and along at most c axes (scipy.ndimage.generate_binary_structure).  A component is a maximal set of
+ * voxels of ONE value linked by neighbour steps; with_background = 0 leaves the voxels equal to 0 outside
+ * every component, 1 labels the 0-regions too.  No function synchronises with the host.
+ *
+ * One workspace serves every function below. */
+int64_t segmi_cc_workspace_bytes(int d, int h, int w);
+/* root[v] = linear index of the first voxel (raster order z, y, x) of v's component, -1 for voxels outside
+ * every component.  Union-find that links towards the smaller index, in three launches (tile-local in
+ * LDS, tile seams, flatten); parent[v] <= v always holds and atomics only lower parents, so every loop
+ * terminates without waiting for another workgroup and the result does not depend on scheduling. */
+int segmi_cc_label(const void* labels, int label_bytes, int d, int h, int w, int spatial_dims, int connectivity,
+                   int with_background, int32_t* root /* [n] */, void* workspace, size_t ws_bytes, void* stream);
+/* size[r] = voxel count of the component rooted at r, 0 at every other index. */
+int segmi_cc_sizes(const int32_t* root, int64_t n, int32_t* size /* [n] */, void* stream);
+/* comp[v] = canonical number 1 .. n_comp of v's component (numbered in raster order of the first voxels),
+ * 0 outside; *n_comp (device) = the count.  Count / scan of partials / number / gather launches. */
+int segmi_cc_compact(const int32_t* root, int64_t n, int32_t* comp /* [n] */, int32_t* n_comp, void* workspace,
+                     size_t ws_bytes, void* stream);
+/* Keep, per class, the num_components (1 .. 8) largest components, ordered by (size descending, first voxel
+ * ascending); the other voxels of the class become 0.  applied_host: HOST list of the classes treated
+ * (n_applied = 0: all), other classes are copied.  independent = 0: root / size come from the union mask of
+ * the applied classes (root = -1 elsewhere) and the kept components keep their per-voxel class.  Classes
+ * index a table of 256 (uint8) or 65536 entries; values outside it are copied.  out: dtype of labels. */
+int segmi_cc_keep_largest(const void* labels, int label_bytes, int64_t n, const int32_t* root, const int32_t* size,
+                          const int32_t* applied_host, int n_applied, int independent, int num_components,
+                          void* out, void* workspace, size_t ws_bytes, void* stream);
+/* Voxels of components with size < min_size become 0. */
+int segmi_cc_remove_small(const void* labels, int label_bytes, int64_t n, const int32_t* root, const int32_t* size,
+                          int min_size, void* out, void* stream);
+/* root: labelled with with_background = 1 under the same connectivity.  A 0-component with no voxel on the
+ * array border whose neighbouring non-zero voxels all carry one value L is filled with L when L is applied
+ * (n_applied = 0: every label).  Label values must lie in 0 .. 65535. */
+int segmi_cc_fill_holes(const void* labels, int label_bytes, int d, int h, int w, int spatial_dims, int connectivity,
+                        const int32_t* root, const int32_t* applied_host, int n_applied, void* out, void* workspace,
+                        size_t ws_bytes, void* stream);
+/* out[i] = lut[in[i]] (lut: device i64 [lut_len]); in_bytes / out_bytes in {1 (uint8), 2 (int16), 4 (int32),
+ * 8 (int64)}.  The caller guarantees 0 <= in[i] < lut_len; an index outside the table writes 0 and reads
+ * nothing.  Replaces lookup[img] of transforms.py:104-107. */
+int segmi_map_labels(const void* in, int in_bytes, int64_t n, const int64_t* lut, int lut_len, void* out,
+                     int out_bytes, void* stream);
+
+
 /* ---------------------------------------------------------------- Nyul standardisation -- */
 /* Nyul-Udupa histogram standardisation, src/segmantic/seg/nyul_normalize.py.  x: contiguous f32
  * [segments][seg_len] (one segment per channel, or the whole tensor as one); mask = x != 0 when

@@ -171,6 +171,14 @@ SIGNATURES = {
     "segmi_select_workspace_bytes": (_i64, [_i]),
     "segmi_select_f32": (_i, [_P, _P, _P, _i, _P, _P, C.c_size_t, _P]),
     "segmi_confusion_counts": (_i, [_P, _P, _i, _i64, _i, _P, _P]),
+    "segmi_cc_workspace_bytes": (_i64, [_i, _i, _i]),
+    "segmi_cc_label": (_i, [_P, _i, _i, _i, _i, _i, _i, _i, _P, _P, C.c_size_t, _P]),
+    "segmi_cc_sizes": (_i, [_P, _i64, _P, _P]),
+    "segmi_cc_compact": (_i, [_P, _i64, _P, _P, _P, C.c_size_t, _P]),
+    "segmi_cc_keep_largest": (_i, [_P, _i, _i64, _P, _P, _P, _i, _i, _i, _P, _P, C.c_size_t, _P]),
+    "segmi_cc_remove_small": (_i, [_P, _i, _i64, _P, _P, _i, _P, _P]),
+    "segmi_cc_fill_holes": (_i, [_P, _i, _i, _i, _i, _i, _i, _P, _P, _i, _P, _P, C.c_size_t, _P]),
+    "segmi_map_labels": (_i, [_P, _i, _i64, _P, _i, _P, _i, _P]),
     "segmi_nyul_workspace_bytes": (_i64, [_i, _i]),
     "segmi_nyul_landmarks": (_i, [_P, _i, _i64, _i, _P, _i, _P, _P, _P, C.c_size_t, _P]),
     "segmi_nyul_apply": (_i, [_P, _i, _i64, _i, _P, _P, _P, _i, _P]),

@@ -1,7 +1,25 @@
-"""Tissue-list IO used to derive ``num_classes`` (reference ``src/segmantic/image/labels.py:89-117``)."""
+"""Tissue-list IO used to derive ``num_classes`` (reference ``src/segmantic/image/labels.py:89-117``) and the
+name-to-name tissue mapping of ``scripts/map_labels.py`` (reference ``:13-37``)."""
 import json
 from pathlib import Path
-from typing import Dict
+from typing import Callable, Dict, Tuple
+
+import numpy as np
+
+
+def build_tissue_mapping(input_label_map: Dict[str, int],
+                         mapper: Callable[[str], str]) -> Tuple[Dict[str, int], np.ndarray]:
+    """Rename tissues with ``mapper`` and renumber them: -> (output name -> id with "Background" = 0 and the
+    other output names numbered alphabetically from 1, uint16 table input id -> output id)."""
+    mapped = {name: mapper(name) for name in input_label_map}
+    others = sorted(set(mapped.values()) - {"Background"})
+    if "Background" not in mapped.values():
+        raise ValueError("no input tissue maps to 'Background'")
+    output_label_map = {name: i for i, name in enumerate(["Background"] + others)}
+    input2output = np.zeros(len(input_label_map), dtype=np.uint16)
+    for name, index in input_label_map.items():
+        input2output[index] = output_label_map[mapped[name]]
+    return output_label_map, input2output
 
 
 def load_tissue_list(file_name: Path) -> Dict[str, int]:

@@ -921,6 +921,184 @@ def confusion_counts(pred, truth, k, cm) -> None:
                                      _stream()), "confusion_counts")
 
 
+# ------------------------------------------------------------------ label clean-up (components.hip)
+CC_MAX_VOXELS = 2 ** 31       # label volumes hold fewer voxels than this (linear indices are int32)
+CC_MAX_KEEP = 8               # largest num_components of cc_keep_largest
+CC_CLASS_TABLE = 65536        # label values of the clean-up transforms lie in 0 .. CC_CLASS_TABLE - 1
+_MAP_BYTES = {torch.uint8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
+
+
+def _cc_dims(labels: torch.Tensor):
+    """(d, h, w, ndim) of a label volume of the connected-component kernels"""
+    d, h, w = _labels3(labels)
+    label_bytes(labels)
+    if labels.numel() == 0 or labels.numel() >= CC_MAX_VOXELS:
+        raise ValueError(f"label volumes hold 1 .. 2^31 - 1 voxels, got shape {tuple(labels.shape)}")
+    return d, h, w, labels.dim()
+
+
+def _cc_connectivity(connectivity, ndim: int) -> int:
+    c = ndim if connectivity is None else int(connectivity)
+    if not 1 <= c <= ndim:
+        raise ValueError(f"connectivity must be 1 .. {ndim} for a {ndim}-D volume, got {connectivity}")
+    return c
+
+
+def _cc_i32(t: torch.Tensor, like: torch.Tensor, what: str) -> None:
+    _require_device(t)
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != like.numel():
+        raise ValueError(f"{what} must be a contiguous int32 tensor with one entry per voxel")
+
+
+def _cc_applied(applied):
+    """host int32 array of the applied labels (empty = all) and its ctypes pointer"""
+    a = np.ascontiguousarray(np.asarray([] if applied is None else list(applied), dtype=np.int32).reshape(-1))
+    return a, (a.ctypes.data_as(C.c_void_p) if a.size else None)
+
+
+def _cc_workspace(labels: torch.Tensor, workspace, per_root_words: bool = False):
+    if workspace is None:
+        need = cc_workspace_bytes(labels.shape)
+        if not per_root_words:
+            # only cc_fill_holes uses the two int32 words per voxel that end the workspace
+            need -= 2 * ((4 * labels.numel() + 255) // 256 * 256)
+        return torch.empty(need, dtype=torch.uint8, device=labels.device)
+    _require_device(workspace)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("the workspace is a contiguous uint8 tensor")
+    return workspace
+
+
+def cc_workspace_bytes(shape) -> int:
+    """bytes of the workspace shared by the cc_* calls for a [d, h, w] or [h, w] volume"""
+    dims = tuple(int(v) for v in shape)
+    if len(dims) not in (2, 3) or any(v <= 0 for v in dims) or int(np.prod(dims, dtype=np.int64)) >= CC_MAX_VOXELS:
+        raise ValueError(f"label volumes are 2-D or 3-D with 1 .. 2^31 - 1 voxels, got shape {dims}")
+    d, h, w = (1,) + dims if len(dims) == 2 else dims
+    return int(lib.segmi_cc_workspace_bytes(d, h, w))
+
+
+def cc_label(labels, connectivity=None, with_background=False, root=None, workspace=None) -> torch.Tensor:
+    """root int32 (shape of labels): linear index of the first voxel of each voxel's component, -1 for voxels
+    outside every component (the zeros, unless ``with_background``)."""
+    d, h, w, ndim = _cc_dims(labels)
+    c = _cc_connectivity(connectivity, ndim)
+    if root is None:
+        root = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
+    _cc_i32(root, labels, "root")
+    ws = _cc_workspace(labels, workspace)
+    check(lib.segmi_cc_label(_ptr(labels), label_bytes(labels), d, h, w, ndim, c, int(bool(with_background)),
+                             _ptr(root), _ptr(ws), ws.numel(), _stream()), "cc_label")
+    return root
+
+
+def cc_sizes(root, size=None) -> torch.Tensor:
+    """size int32 (shape of root): the voxel count of each component at its root, 0 elsewhere."""
+    _cc_i32(root, root, "root")
+    if root.numel() == 0 or root.numel() >= CC_MAX_VOXELS:
+        raise ValueError("root holds 1 .. 2^31 - 1 voxels")
+    if size is None:
+        size = torch.empty_like(root)
+    _cc_i32(size, root, "size")
+    check(lib.segmi_cc_sizes(_ptr(root), root.numel(), _ptr(size), _stream()), "cc_sizes")
+    return size
+
+
+def cc_compact(root, comp=None, n_comp=None, workspace=None):
+    """(comp int32: canonical component number 1 .. n of every voxel, 0 outside; n_comp int32 [1] on the device)."""
+    _cc_i32(root, root, "root")
+    if root.dim() not in (2, 3):
+        raise ValueError("root has the shape of its 2-D or 3-D label volume")
+    if comp is None:
+        comp = torch.empty_like(root)
+    _cc_i32(comp, root, "comp")
+    if n_comp is None:
+        n_comp = torch.empty(1, dtype=torch.int32, device=root.device)
+    if n_comp.dtype != torch.int32 or n_comp.numel() != 1:
+        raise ValueError("n_comp is one int32")
+    ws = _cc_workspace(root, workspace)
+    check(lib.segmi_cc_compact(_ptr(root), root.numel(), _ptr(comp), _ptr(n_comp), _ptr(ws), ws.numel(), _stream()),
+          "cc_compact")
+    return comp, n_comp
+
+
+def cc_keep_largest(labels, root, size, applied=None, independent=True, num_components=1, out=None,
+                    workspace=None) -> torch.Tensor:
+    """Keep the ``num_components`` largest components per applied class (ties: the earlier first voxel); with
+    ``independent=False`` root / size describe the union mask of the applied classes."""
+    _cc_dims(labels)
+    _cc_i32(root, labels, "root")
+    _cc_i32(size, labels, "size")
+    if not 1 <= int(num_components) <= CC_MAX_KEEP:
+        raise ValueError(f"num_components must be 1 .. {CC_MAX_KEEP}, got {num_components}")
+    if out is None:
+        out = torch.empty_like(labels)
+    if out.dtype != labels.dtype or out.shape != labels.shape or not out.is_contiguous():
+        raise ValueError("out must match labels in dtype and shape")
+    a, ap = _cc_applied(applied)
+    ws = _cc_workspace(labels, workspace)
+    check(lib.segmi_cc_keep_largest(_ptr(labels), label_bytes(labels), labels.numel(), _ptr(root), _ptr(size), ap,
+                                    a.size, int(bool(independent)), int(num_components), _ptr(out), _ptr(ws),
+                                    ws.numel(), _stream()), "cc_keep_largest")
+    return out
+
+
+def cc_remove_small(labels, root, size, min_size, out=None) -> torch.Tensor:
+    """Voxels of components smaller than ``min_size`` become 0."""
+    _cc_dims(labels)
+    _cc_i32(root, labels, "root")
+    _cc_i32(size, labels, "size")
+    if int(min_size) < 0:
+        raise ValueError(f"min_size must be >= 0, got {min_size}")
+    if out is None:
+        out = torch.empty_like(labels)
+    if out.dtype != labels.dtype or out.shape != labels.shape or not out.is_contiguous():
+        raise ValueError("out must match labels in dtype and shape")
+    check(lib.segmi_cc_remove_small(_ptr(labels), label_bytes(labels), labels.numel(), _ptr(root), _ptr(size),
+                                    int(min(int(min_size), 2 ** 31 - 1)), _ptr(out), _stream()), "cc_remove_small")
+    return out
+
+
+def cc_fill_holes(labels, root, applied=None, connectivity=None, out=None, workspace=None) -> torch.Tensor:
+    """Fill the enclosed 0-regions bordered by one single label; ``root`` = cc_label(labels, connectivity,
+    with_background=True)."""
+    d, h, w, ndim = _cc_dims(labels)
+    c = _cc_connectivity(connectivity, ndim)
+    _cc_i32(root, labels, "root")
+    if out is None:
+        out = torch.empty_like(labels)
+    if out.dtype != labels.dtype or out.shape != labels.shape or not out.is_contiguous():
+        raise ValueError("out must match labels in dtype and shape")
+    a, ap = _cc_applied(applied)
+    ws = _cc_workspace(labels, workspace, per_root_words=True)
+    check(lib.segmi_cc_fill_holes(_ptr(labels), label_bytes(labels), d, h, w, ndim, c, _ptr(root), ap, a.size,
+                                  _ptr(out), _ptr(ws), ws.numel(), _stream()), "cc_fill_holes")
+    return out
+
+
+def map_labels(x, lut, out=None, out_dtype=torch.int64) -> torch.Tensor:
+    """out = lut[x] for an integer tensor x (uint8 / int16 / int32 / int64) and a device int64 table.  The
+    caller has checked 0 <= x < len(lut)."""
+    if x.dtype not in _MAP_BYTES:
+        raise TypeError(f"map_labels reads uint8, int16, int32 or int64, not {x.dtype}")
+    _require_device(x)
+    _require_device(lut)
+    if lut.dtype != torch.int64 or lut.dim() != 1 or lut.numel() == 0 or not lut.is_contiguous():
+        raise ValueError("map_labels: the table is a non-empty contiguous 1-D int64 tensor")
+    if not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("map_labels: the input must be contiguous and non-empty")
+    if out is None:
+        if out_dtype not in _MAP_BYTES:
+            raise TypeError(f"map_labels writes uint8, int16, int32 or int64, not {out_dtype}")
+        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    if out.dtype not in _MAP_BYTES or out.shape != x.shape or not out.is_contiguous():
+        raise ValueError("map_labels: out must be a contiguous integer tensor of the input's shape")
+    _require_device(out)
+    check(lib.segmi_map_labels(_ptr(x), _MAP_BYTES[x.dtype], x.numel(), _ptr(lut), lut.numel(), _ptr(out),
+                               _MAP_BYTES[out.dtype], _stream()), "map_labels")
+    return out
+
+
 # ------------------------------------------------------------------ Nyul standardisation
 NYUL_MAX_LANDMARKS = 64
 
