@@ -611,6 +611,47 @@ int segmi_cc_fill_holes(const void* labels, int label_bytes, int d, int h, int w
 int segmi_map_labels(const void* in, int in_bytes, int64_t n, const int64_t* lut, int lut_len, void* out,
                      int out_bytes, void* stream);
 
+/* ---------------------------------------------------------------- label surfaces -------- */
+/* Discrete surface nets of the selected labels of a label volume (scripts/visualize_label_surfaces.py of the
+ * reference, which uses VTK's discrete flying edges; DESIGN.md section 14 defines the output).  Label volumes
+ * are read in place as label_bytes in {1, 2, 4}, [d][h][w], with (d+1)(h+1)(w+1) < 2^31.  selected: 1 .. 65535
+ * label values in 1 .. 65535, strictly ascending.  Work is confined to every label's bounding box: the boxes
+ * are computed on the device, read back by the caller (host synchronisation 1) and handed, as HOST arrays, to
+ * workspace_bytes / count / emit, which must all see the same selected / boxes.  No function synchronises.
+ *
+ * boxes i32 [n_sel][6] (device): half-open z0 z1 y0 y1 x0 x1 of labels == selected[l]; absent: 0 0 0 0 0 0. */
+int segmi_surface_boxes(const void* labels, int label_bytes, int d, int h, int w, const int32_t* selected /* device */,
+                        int n_sel, int32_t* boxes, void* stream);
+/* 0 when the arguments are invalid or the boxes hold 2^31 chunks (64 cells along x) or more */
+int64_t segmi_surface_workspace_bytes(int d, int h, int w, const int32_t* selected_host, const int32_t* boxes_host,
+                                      int n_sel);
+/* Classify the cells of every label box and scan the per-chunk vertex / face counts into the workspace.
+ * starts i32 [n_sel + 2][2] (device): (first vertex, first face) of every label in the concatenated outputs,
+ * then the totals (V, F), then (overflow flag, 0): the flag is 1, and the totals 0, when V or F passed
+ * 2^31 - 1.  Reading starts is host synchronisation 2; it sizes the outputs of emit. */
+int segmi_surface_count(const void* labels, int label_bytes, int d, int h, int w, const int32_t* selected_host,
+                        const int32_t* boxes_host, int n_sel, int32_t* starts, void* workspace, size_t ws_bytes,
+                        void* stream);
+/* After count, on the same workspace.  offsets f32 [V][3]: cell-local vertex offsets (x, y, z) in [0, 1];
+ * cells i32 [V][3]: the vertex's cell (x, y, z), index coordinate = (cell - 1) + offset; neighbours i32 [V][6]
+ * (nullable): numbers, in the concatenated output, of the -x +x -y +y -z +z neighbours, -1 = none;
+ * faces i32 [F][3], numbered within their label. */
+int segmi_surface_emit(const void* labels, int label_bytes, int d, int h, int w, const int32_t* selected_host,
+                       const int32_t* boxes_host, int n_sel, int64_t n_vertices, int64_t n_faces, float* offsets,
+                       int32_t* cells, int32_t* neighbours, int32_t* faces, void* workspace, size_t ws_bytes,
+                       void* stream);
+/* `iterations` Jacobi sweeps o' = clamp(o + relaxation (m - o), 0, 1) over the offsets (ping-pong with scratch
+ * f32 [V][3]; offsets is clobbered), then vertices f32 [V][3] (x, y, z) = origin + Direction (spacing o index),
+ * evaluated in f64 and rounded once.  geometry_host: HOST f64 [15] = origin xyz, direction row-major, spacing xyz. */
+int segmi_surface_relax(float* offsets, float* scratch, const int32_t* cells, const int32_t* neighbours,
+                        int64_t n_vertices, int iterations, float relaxation, const double* geometry_host,
+                        float* vertices, void* stream);
+/* measures f64 [n_sel][2] (device) = (area, signed volume 1/6 sum p0 . (p1 x p2)) of every label's mesh, from the
+ * vertices and faces as emitted; f64 sums in a fixed order (bit-identical on repeated calls).
+ * workspace: n_sel * 32 * 2 doubles, rounded up to 256 bytes. */
+int segmi_surface_measure(const float* vertices, const int32_t* faces, const int32_t* starts, int n_sel,
+                          double* measures, void* workspace, size_t ws_bytes, void* stream);
+
 
 /* ---------------------------------------------------------------- Nyul standardisation -- */
 /* Nyul-Udupa histogram standardisation, src/segmantic/seg/nyul_normalize.py.  x: contiguous f32

@@ -179,6 +179,12 @@ SIGNATURES = {
     "segmi_cc_remove_small": (_i, [_P, _i, _i64, _P, _P, _i, _P, _P]),
     "segmi_cc_fill_holes": (_i, [_P, _i, _i, _i, _i, _i, _i, _P, _P, _i, _P, _P, C.c_size_t, _P]),
     "segmi_map_labels": (_i, [_P, _i, _i64, _P, _i, _P, _i, _P]),
+    "segmi_surface_boxes": (_i, [_P, _i, _i, _i, _i, _P, _i, _P, _P]),
+    "segmi_surface_workspace_bytes": (_i64, [_i, _i, _i, _P, _P, _i]),
+    "segmi_surface_count": (_i, [_P, _i, _i, _i, _i, _P, _P, _i, _P, _P, C.c_size_t, _P]),
+    "segmi_surface_emit": (_i, [_P, _i, _i, _i, _i, _P, _P, _i, _i64, _i64, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "segmi_surface_relax": (_i, [_P, _P, _P, _P, _i64, _i, _f, _P, _P, _P]),
+    "segmi_surface_measure": (_i, [_P, _P, _P, _i, _P, _P, C.c_size_t, _P]),
     "segmi_nyul_workspace_bytes": (_i64, [_i, _i]),
     "segmi_nyul_landmarks": (_i, [_P, _i, _i64, _i, _P, _i, _P, _P, _P, C.c_size_t, _P]),
     "segmi_nyul_apply": (_i, [_P, _i, _i64, _i, _P, _P, _P, _i, _P]),

@@ -1,0 +1,1 @@
+from . import surfaces  # noqa: F401

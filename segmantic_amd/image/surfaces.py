@@ -1,0 +1,273 @@
+"""Label surfaces on the MI355X: one closed triangle mesh per tissue of a label volume, written as binary PLY
+(the reference's ``scripts/visualize_label_surfaces.py``, which hands the work to VTK's
+``vtkDiscreteFlyingEdges3D``).  The meshes are computed by the HIP kernels of ``csrc/surfaces.hip``; there is no
+CPU fallback: with no GPU :func:`extract_surfaces` raises ``RuntimeError`` (after validating its input).
+
+Contract: discrete surface nets
+-------------------------------
+VTK is not part of this project and its flying-edges case table cannot be checked here, so the words below are
+the specification; ``tests/helpers/surface_ref.py`` restates them in numpy and the tests compare bit for bit.
+
+* **Input**: a 3-D label volume ``L[z, y, x]`` (``uint8`` / ``int16`` / ``int32`` are read in place, ``bool`` is
+  read as ``uint8`` and other integer types as ``int32``), never modified.  2-D or non-integer input raises
+  ``ValueError``; label values must lie in ``0..65535`` (``ValueError`` otherwise, one range check as in
+  ``seg/transforms.py``).
+* **Padded lattice**: for one label ``c``, ``P`` is ``L == c`` padded by one layer of ``False`` on every side, so
+  an object that touches the border gets a closed surface.  Lattice point ``(k, j, i)`` is voxel
+  ``(k-1, j-1, i-1)``.
+* **Cells**: one per 2x2x2 block of lattice points, cell ``(k, j, i)`` with ``0 <= k <= d`` etc. and corners
+  ``P[k..k+1, j..j+1, i..i+1]``.  ``(d+1)(h+1)(w+1)`` must stay below ``2^31`` (``ValueError``).  A cell is
+  *active* when its corners are neither all set nor all clear.
+* **Vertices**: one per active cell, numbered ``0..V-1`` in raster order (z, y, x) of the cells.  The position is
+  the mean of the midpoints of the cell's *crossing* edges (cell edges whose ends differ), held as a cell-local
+  offset ``o = float32(s) / float32(2 n)`` in ``[0, 1]^3`` (``s``: integer sum of the doubled midpoints, ``n``:
+  number of crossing edges; one IEEE division per component).  Index coordinate (voxel centres at integers)
+  ``= float32(cell - 1) + o``.
+* **Faces**: one quad per crossing lattice edge, joining the four cells around the edge, split into two
+  triangles.  For an x-edge whose lower end is set the cycle is the cells at ``(y-,z-), (y+,z-), (y+,z+),
+  (y-,z+)``; y-edge: ``(z-,x-), (z+,x-), (z+,x+), (z-,x+)``; z-edge: ``(x-,y-), (x+,y-), (x+,y+), (x-,y+)``;
+  when the upper end is the set one the cycle is read backwards (``q3, q2, q1, q0``).  The normal therefore
+  points from ``c`` to not-``c``.  Split: ``(q0, q1, q2), (q0, q2, q3)``.  Order: by the raster index of the cell
+  whose lowest corner is the edge's lower end, then x-, y-, z-edge.  ``faces`` is ``int32 [F, 3]`` with
+  ``F = 2 x`` the number of crossing edges.
+* **Relaxation** (``smooth_iterations = T >= 0``, ``relaxation = lambda in [0, 1]``): Jacobi sweeps on the local
+  offsets.  A vertex's neighbours are the face-adjacent active cells whose shared cell face is mixed (3 to 6 of
+  them); ``m`` is the mean of ``o_u + e_uv`` (``e_uv``: the unit step to the neighbour) summed in the order -x,
+  +x, -y, +y, -z, +z, and ``o_v' = clamp(o_v + lambda (m - o_v), 0, 1)``.  The clamp keeps every vertex inside its
+  cell, so the surface never leaves the band of mixed cells and the surfaces of different labels cannot cross.
+* **Physical coordinates**: ``p_xyz = origin + Direction (spacing o index_xyz)``, evaluated in float64 from the
+  float32 index coordinate and rounded once to float32.  ``vertices`` is ``float32 [V, 3]`` in ``(x, y, z)``.
+* **Measures**: surface area and enclosed volume ``1/6 sum p0 . (p1 x p2)`` of the emitted mesh in physical units,
+  float64 sums in a fixed order (repeated calls are bit-identical).
+
+Consequences: every directed mesh edge ``a->b`` occurs exactly as often as ``b->a`` (closed, consistently
+oriented) on any input; at ambiguous configurations (two voxels that touch along an edge or at a corner) an edge is
+used twice in each direction: surface nets are non-manifold there by construction, and this is not "fixed".
+``V - E + F`` is 2 for a ball or a full volume and 0 for a torus; the signed volume is positive and differs from
+the voxel count times the voxel volume by at most ``V`` voxel volumes.
+
+Deviations from the reference script: surface nets instead of flying edges (a vertex per mixed cell, not per
+crossing edge); no ``vtkDecimatePro`` (meshes have roughly 5x the reference's triangles); the default selection is
+every label present in ``1..max`` (the reference's ``range(1, max_label)`` drops the largest); a selected label
+that is absent yields an empty mesh and no file.
+
+Arrays come back where the input lived: numpy in -> numpy out, tensors in -> tensors on the input's device.
+Host synchronisations per volume: the range check, the label boxes and the vertex / face totals, whatever the
+number of labels.
+"""
+from __future__ import annotations
+
+import re
+from dataclasses import dataclass
+from pathlib import Path
+from typing import Dict, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from .processing import Image
+
+ArrayLike = Union[Image, np.ndarray, torch.Tensor]
+
+MAX_LABEL = 65535
+MAX_CELLS = 2 ** 31
+_NEEDS_GPU = "segmantic_amd.image.surfaces needs an MI355X; no GPU is visible and there is no CPU path"
+_IN_PLACE = (torch.uint8, torch.int16, torch.int32)
+
+
+@dataclass
+class Surface:
+    """``vertices`` float32 [V, 3] (x, y, z), ``faces`` int32 [F, 3], ``area`` and ``volume`` in physical units."""
+
+    vertices: Union[np.ndarray, torch.Tensor]
+    faces: Union[np.ndarray, torch.Tensor]
+    area: float = 0.0
+    volume: float = 0.0
+
+    def __eq__(self, other) -> bool:
+        if not isinstance(other, Surface):
+            return NotImplemented
+        return (np.array_equal(_host(self.vertices), _host(other.vertices))
+                and np.array_equal(_host(self.faces), _host(other.faces))
+                and self.area == other.area and self.volume == other.volume)
+
+
+def _host(a) -> np.ndarray:
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def surface_file_name(label: int, tissues: Optional[Dict[int, str]] = None) -> str:
+    """``<tissue name>.ply`` when the tissue list names the label, otherwise ``label_{label:03d}.ply``"""
+    name = tissues[label] if tissues and label in tissues else f"label_{label:03d}"
+    return f"{name}.ply"
+
+
+# ------------------------------------------------------------------ validation
+def _check_volume(labels: ArrayLike):
+    """checks that need neither a copy nor the device -> the raw array"""
+    a = labels.data if isinstance(labels, Image) else labels
+    if not isinstance(a, (np.ndarray, torch.Tensor)):
+        raise TypeError(f"expected an Image, a numpy array or a torch tensor, not {type(labels).__name__}")
+    shape = tuple(int(s) for s in a.shape)
+    if len(shape) != 3:
+        raise ValueError(f"label surfaces need a 3-D [z, y, x] label volume, got shape {shape}")
+    integer = not (a.is_floating_point() or a.is_complex()) if isinstance(a, torch.Tensor) else a.dtype.kind in "biu"
+    if not integer:
+        raise ValueError(f"label volumes must hold integers, got {a.dtype}")
+    if min(shape) == 0:
+        raise ValueError(f"empty label volume of shape {shape}")
+    if (shape[0] + 1) * (shape[1] + 1) * (shape[2] + 1) >= MAX_CELLS:
+        raise ValueError(f"(d+1)(h+1)(w+1) must stay below 2^31, got shape {shape}")
+    return a
+
+
+def _value_range(a):
+    """(min, max) of the volume where it lives: the one range check"""
+    if isinstance(a, np.ndarray):
+        return int(a.min()), int(a.max())
+    if a.dtype not in _IN_PLACE and a.dtype != torch.int64:
+        a = a.to(torch.int64)          # bool, int8 and the unsigned wide types, which aminmax does not take
+    lo, hi = torch.stack(torch.aminmax(a)).tolist()
+    return int(lo), int(hi)
+
+
+def _check_selected(selected) -> Optional[list]:
+    if selected is None:
+        return None
+    if isinstance(selected, (int, np.integer)):
+        selected = [selected]
+    out = sorted({int(v) for v in selected})
+    if not out:
+        return None
+    if out[0] < 1 or out[-1] > MAX_LABEL:
+        raise ValueError(f"selected labels must lie in 1 .. {MAX_LABEL}, got {out}")
+    return out
+
+
+def _geometry(labels: ArrayLike, spacing, origin, direction):
+    if isinstance(labels, Image):
+        spacing = labels.spacing if spacing is None else spacing
+        origin = labels.origin if origin is None else origin
+        direction = labels.direction if direction is None else direction
+    sp = np.asarray([1.0] * 3 if spacing is None else spacing, np.float64).reshape(-1)
+    og = np.asarray([0.0] * 3 if origin is None else origin, np.float64).reshape(-1)
+    dr = np.asarray(np.eye(3) if direction is None else direction, np.float64).reshape(-1)
+    if sp.size != 3 or og.size != 3 or dr.size != 9:
+        raise ValueError("spacing and origin are (x, y, z) triples and direction a row-major 3 x 3 matrix")
+    return sp, og, dr
+
+
+# ------------------------------------------------------------------ extraction
+def extract_surfaces(labels: ArrayLike, selected: Optional[Sequence[int]] = None, spacing=None, origin=None,
+                     direction=None, smooth_iterations: int = 0, relaxation: float = 0.5) -> Dict[int, Surface]:
+    """One discrete-surface-nets mesh per label (see the module docstring).  ``selected`` defaults to every label
+    present in ``1..max``; a selected label that is absent maps to an empty :class:`Surface`."""
+    a = _check_volume(labels)
+    sel = _check_selected(selected)
+    sp, og, dr = _geometry(labels, spacing, origin, direction)
+    if isinstance(smooth_iterations, bool) or int(smooth_iterations) != smooth_iterations or int(smooth_iterations) < 0:
+        raise ValueError(f"smooth_iterations must be an integer >= 0, got {smooth_iterations!r}")
+    if not 0.0 <= float(relaxation) <= 1.0:
+        raise ValueError(f"relaxation must lie in [0, 1], got {relaxation!r}")
+    lo, hi = _value_range(a)
+    if lo < 0 or hi > MAX_LABEL:
+        raise ValueError(f"label values must lie in 0 .. {MAX_LABEL}, the volume holds {lo} .. {hi}")
+    if not torch.cuda.is_available():
+        raise RuntimeError(_NEEDS_GPU)
+    from .. import ops
+
+    dev = a.device if isinstance(a, torch.Tensor) and a.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+    if t.dtype == torch.bool:
+        t = t.to(torch.uint8)
+    t = t.to(dev)
+    if t.dtype not in _IN_PLACE:
+        t = t.to(torch.int32)
+    t = t.contiguous()
+    on_host = isinstance(a, np.ndarray)
+    back = (lambda x: x.cpu().numpy()) if on_host else (lambda x: x.to(a.device))
+
+    def empty() -> Surface:
+        return Surface(back(torch.empty((0, 3), dtype=torch.float32, device=dev)),
+                       back(torch.empty((0, 3), dtype=torch.int32, device=dev)), 0.0, 0.0)
+
+    todo = list(range(1, hi + 1)) if sel is None else sel
+    if not todo:
+        return {}
+    boxes = ops.surface_boxes(t, todo).cpu().numpy()                       # host synchronisation: boxes
+    present = boxes[:, 1] > boxes[:, 0]
+    if sel is None:
+        todo = [c for c, p in zip(todo, present) if p]
+        boxes = np.ascontiguousarray(boxes[present])
+    if not todo:
+        return {}
+    ws = torch.empty(ops.surface_workspace_bytes(t.shape, todo, boxes), dtype=torch.uint8, device=dev)
+    starts_dev = ops.surface_count(t, todo, boxes, ws)
+    starts = starts_dev.cpu().numpy()                                      # host synchronisation: totals
+    if starts[-1, 0]:
+        raise ValueError("the selected labels' meshes hold 2^31 vertices or faces or more")
+    nv, nf = int(starts[-2, 0]), int(starts[-2, 1])
+    T = int(smooth_iterations)
+    offs, cells, nbr, faces = ops.surface_emit(t, todo, boxes, ws, nv, nf, with_neighbours=T > 0)
+    verts = ops.surface_relax(offs, cells, nbr, T, float(relaxation), og, dr, sp)
+    measures = ops.surface_measure(verts, faces, starts_dev).cpu().numpy()
+    verts, faces = back(verts), back(faces)
+    out: Dict[int, Surface] = {}
+    for l, c in enumerate(todo):
+        v0, f0, v1, f1 = (int(x) for x in (starts[l, 0], starts[l, 1], starts[l + 1, 0], starts[l + 1, 1]))
+        if v1 == v0:
+            out[c] = empty()
+        else:
+            out[c] = Surface(verts[v0:v1], faces[f0:f1], float(measures[l, 0]), float(measures[l, 1]))
+    return out
+
+
+# ------------------------------------------------------------------ PLY
+_PLY_HEAD = ("ply\nformat binary_little_endian 1.0\ncomment segmantic_amd label surface\n"
+             "comment area {area!r}\ncomment volume {volume!r}\n"
+             "element vertex {nv}\nproperty float x\nproperty float y\nproperty float z\n"
+             "element face {nf}\nproperty list uchar int vertex_indices\nend_header\n")
+_FACE_DT = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def ply_header(surface: Surface) -> bytes:
+    return _PLY_HEAD.format(area=float(surface.area), volume=float(surface.volume), nv=int(surface.vertices.shape[0]),
+                            nf=int(surface.faces.shape[0])).encode("ascii")
+
+
+def write_ply(path, surface: Surface) -> None:
+    """Binary little-endian PLY with float x / y / z vertices and ``uchar int`` face lists, the layout
+    ``vtkPLYWriter`` produces in binary mode; area and volume travel as comments."""
+    v = np.ascontiguousarray(_host(surface.vertices), dtype="<f4").reshape(-1, 3)
+    f = _host(surface.faces).reshape(-1, 3)
+    rec = np.empty(f.shape[0], dtype=_FACE_DT)
+    rec["n"] = 3
+    rec["v"] = f
+    with open(path, "wb") as fh:
+        fh.write(ply_header(surface))
+        fh.write(v.tobytes())
+        fh.write(rec.tobytes())
+
+
+def read_ply(path) -> Surface:
+    """Read a PLY written by :func:`write_ply` (numpy arrays)."""
+    raw = Path(path).read_bytes()
+    end = raw.find(b"end_header\n")
+    if not raw.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    head = raw[:end].decode("ascii")
+    if "format binary_little_endian 1.0" not in head or "property list uchar int vertex_indices" not in head:
+        raise ValueError(f"{path}: only the binary little-endian triangle PLY of write_ply is supported")
+    nv = int(re.search(r"^element vertex (\d+)$", head, re.M).group(1))
+    nf = int(re.search(r"^element face (\d+)$", head, re.M).group(1))
+    pos = end + len(b"end_header\n")
+    if len(raw) != pos + 12 * nv + 13 * nf:
+        raise ValueError(f"{path}: payload of {len(raw) - pos} bytes, {12 * nv + 13 * nf} expected")
+    v = np.frombuffer(raw, dtype="<f4", count=3 * nv, offset=pos).reshape(nv, 3).astype(np.float32)
+    rec = np.frombuffer(raw, dtype=_FACE_DT, count=nf, offset=pos + 12 * nv)
+    if nf and (rec["n"] != 3).any():
+        raise ValueError(f"{path}: only triangles are supported")
+    f = np.ascontiguousarray(rec["v"]).astype(np.int32).reshape(nf, 3)
+    area = re.search(r"^comment area (\S+)$", head, re.M)
+    volume = re.search(r"^comment volume (\S+)$", head, re.M)
+    return Surface(v, f, float(area.group(1)) if area else 0.0, float(volume.group(1)) if volume else 0.0)

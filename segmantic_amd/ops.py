@@ -1099,6 +1099,110 @@ def map_labels(x, lut, out=None, out_dtype=torch.int64) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------ label surfaces (surfaces.hip)
+SURFACE_MAX_CELLS = 2 ** 31     # (d+1)(h+1)(w+1) stays below this
+SURFACE_MAX_LABEL = 65535
+
+
+def _surface_dims(labels: torch.Tensor):
+    _require_device(labels)
+    if labels.dim() != 3 or not labels.is_contiguous() or labels.numel() == 0:
+        raise ValueError("label surfaces are extracted from non-empty contiguous [d, h, w] tensors")
+    label_bytes(labels)
+    d, h, w = (int(s) for s in labels.shape)
+    if (d + 1) * (h + 1) * (w + 1) >= SURFACE_MAX_CELLS:
+        raise ValueError(f"(d+1)(h+1)(w+1) must stay below 2^31, got shape {(d, h, w)}")
+    return d, h, w
+
+
+def _surface_selected(selected):
+    s = np.ascontiguousarray(np.asarray(list(selected), dtype=np.int64).reshape(-1))
+    if s.size == 0 or s.size > SURFACE_MAX_LABEL or s.min() < 1 or s.max() > SURFACE_MAX_LABEL or \
+            (np.diff(s) <= 0).any():
+        raise ValueError(f"selected labels are 1 .. {SURFACE_MAX_LABEL} strictly ascending values in "
+                         f"1 .. {SURFACE_MAX_LABEL}")
+    s = s.astype(np.int32)
+    return s, s.ctypes.data_as(C.c_void_p)
+
+
+def surface_boxes(labels: torch.Tensor, selected) -> torch.Tensor:
+    """boxes int32 [n, 6] on the device: half-open z0 z1 y0 y1 x0 x1 of ``labels == selected[l]``."""
+    d, h, w = _surface_dims(labels)
+    s, _ = _surface_selected(selected)
+    sel = torch.from_numpy(s).to(labels.device)
+    boxes = torch.empty((s.size, 6), dtype=torch.int32, device=labels.device)
+    check(lib.segmi_surface_boxes(_ptr(labels), label_bytes(labels), d, h, w, _ptr(sel), s.size, _ptr(boxes),
+                                  _stream()), "surface_boxes")
+    return boxes
+
+
+def surface_workspace_bytes(shape, selected, boxes_host) -> int:
+    d, h, w = (int(v) for v in shape)
+    s, sp = _surface_selected(selected)
+    b, bp = _host_i32(boxes_host)
+    if b.shape != (s.size, 6):
+        raise ValueError("boxes_host is [n_selected, 6]")
+    n = int(lib.segmi_surface_workspace_bytes(d, h, w, sp, bp, s.size))
+    if n <= 0:
+        raise ValueError("label surfaces: invalid boxes, or the label boxes hold 2^31 chunks of 64 cells or more")
+    return n
+
+
+def surface_count(labels: torch.Tensor, selected, boxes_host, workspace: torch.Tensor) -> torch.Tensor:
+    """starts int32 [n + 2, 2] on the device: (first vertex, first face) per label, the totals, (overflow, 0)."""
+    d, h, w = _surface_dims(labels)
+    s, sp = _surface_selected(selected)
+    b, bp = _host_i32(boxes_host)
+    starts = torch.empty((s.size + 2, 2), dtype=torch.int32, device=labels.device)
+    check(lib.segmi_surface_count(_ptr(labels), label_bytes(labels), d, h, w, sp, bp, s.size, _ptr(starts),
+                                  _ptr(workspace), workspace.numel(), _stream()), "surface_count")
+    return starts
+
+
+def surface_emit(labels: torch.Tensor, selected, boxes_host, workspace: torch.Tensor, n_vertices: int, n_faces: int,
+                 with_neighbours: bool = False):
+    """-> (offsets f32 [V, 3], cells i32 [V, 3], neighbours i32 [V, 6] or None, faces i32 [F, 3])."""
+    d, h, w = _surface_dims(labels)
+    s, sp = _surface_selected(selected)
+    b, bp = _host_i32(boxes_host)
+    dev = labels.device
+    offs = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+    cells = torch.empty((n_vertices, 3), dtype=torch.int32, device=dev)
+    nbr = torch.empty((n_vertices, 6), dtype=torch.int32, device=dev) if with_neighbours else None
+    faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+    check(lib.segmi_surface_emit(_ptr(labels), label_bytes(labels), d, h, w, sp, bp, s.size, int(n_vertices),
+                                 int(n_faces), _ptr(offs), _ptr(cells), _ptr(nbr), _ptr(faces), _ptr(workspace),
+                                 workspace.numel(), _stream()), "surface_emit")
+    return offs, cells, nbr, faces
+
+
+def surface_relax(offsets, cells, neighbours, iterations: int, relaxation: float, origin, direction,
+                  spacing) -> torch.Tensor:
+    """``iterations`` relaxation sweeps (offsets is clobbered), then the physical vertices f32 [V, 3] (x, y, z)."""
+    _require_device(offsets)
+    nv = offsets.shape[0]
+    g = np.ascontiguousarray(np.concatenate([np.asarray(origin, np.float64).reshape(3),
+                                             np.asarray(direction, np.float64).reshape(9),
+                                             np.asarray(spacing, np.float64).reshape(3)]))
+    verts = torch.empty((nv, 3), dtype=torch.float32, device=offsets.device)
+    scratch = torch.empty_like(offsets) if iterations > 0 else None
+    check(lib.segmi_surface_relax(_ptr(offsets), _ptr(scratch), _ptr(cells), _ptr(neighbours), nv, int(iterations),
+                                  float(relaxation), g.ctypes.data_as(C.c_void_p), _ptr(verts), _stream()),
+          "surface_relax")
+    return verts
+
+
+def surface_measure(vertices, faces, starts) -> torch.Tensor:
+    """measures f64 [n, 2] on the device: (area, signed volume) of every label's mesh."""
+    _require_device(starts)
+    n = starts.shape[0] - 2
+    out = torch.empty((n, 2), dtype=torch.float64, device=starts.device)
+    ws = torch.empty((n * 32 * 2 * 8 + 255) // 256 * 256, dtype=torch.uint8, device=starts.device)
+    check(lib.segmi_surface_measure(_ptr(vertices), _ptr(faces), _ptr(starts), n, _ptr(out), _ptr(ws), ws.numel(),
+                                    _stream()), "surface_measure")
+    return out
+
+
 # ------------------------------------------------------------------ Nyul standardisation
 NYUL_MAX_LANDMARKS = 64
 
