@@ -652,6 +652,32 @@ int segmi_surface_relax(float* offsets, float* scratch, const int32_t* cells, co
 int segmi_surface_measure(const float* vertices, const int32_t* faces, const int32_t* starts, int n_sel,
                           double* measures, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- mesh decimation -------- */
+/* Round-based edge collapse over independent sets (DESIGN.md section 14 defines the output; the reference runs
+ * vtkDecimatePro, whose output is not defined).  A batch of n_meshes meshes is concatenated: vertices f32 [V][3],
+ * faces i32 [F][3] numbered within their mesh, starts i32 [n_meshes + 2][2] (device) in the layout of
+ * segmi_surface_count.  1 <= V < 2^31, 1 <= 3 F < 2^31, every face index must lie inside its mesh (the caller
+ * checks), and a mesh holds fewer than 2^23 vertices (the claim key keeps 23 bits for the vertex).  Inputs are
+ * never written.  No function synchronises.  0 when the arguments are invalid. */
+int64_t segmi_decimate_workspace_bytes(int64_t n_vertices, int64_t n_faces, int n_meshes);
+/* Working copy of the faces, mesh of every vertex, live i32 [n_meshes] (device) = faces per mesh. */
+int segmi_decimate_init(const int32_t* faces, const int32_t* starts, int n_meshes, int64_t n_vertices, int64_t n_faces,
+                        int32_t* live, void* workspace, size_t ws_bytes, void* stream);
+/* Round `round` (0, 1, ...; the quadrics are built in round 0) for every mesh with live > targets (device i32
+ * [n_meshes]); live is updated.  Reading live is the caller's one device-to-host copy per round: it stops when
+ * every mesh is at its target or did not change. */
+int segmi_decimate_round(const float* vertices, const int32_t* starts, const int32_t* targets, int n_meshes,
+                         int64_t n_vertices, int64_t n_faces, int round, int32_t* live, void* workspace, size_t ws_bytes,
+                         void* stream);
+/* out_starts i32 [n_meshes + 2][2] (device): starts of the live vertices / faces, the totals, (0, 0). */
+int segmi_decimate_compact_count(const int32_t* starts, int n_meshes, int64_t n_vertices, int64_t n_faces,
+                                 int32_t* out_starts, void* workspace, size_t ws_bytes, void* stream);
+/* After compact_count: live vertices (bit copies) and faces in their original relative order, renumbered within
+ * their mesh; out_kept i32 [V']: the input number, within its mesh, of every output vertex. */
+int segmi_decimate_compact_emit(const float* vertices, const int32_t* starts, int n_meshes, int64_t n_vertices,
+                                int64_t n_faces, float* out_vertices, int32_t* out_faces, int32_t* out_kept,
+                                void* workspace, size_t ws_bytes, void* stream);
+
 
 /* ---------------------------------------------------------------- Nyul standardisation -- */
 /* Nyul-Udupa histogram standardisation, src/segmantic/seg/nyul_normalize.py.  x: contiguous f32

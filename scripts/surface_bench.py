@@ -7,7 +7,13 @@ emit, relax = --smooth sweeps + the physical transform, measure) timed with devi
 model below, the end-to-end time of extract_surfaces (host clock around a device synchronise) with the number of
 device-to-host copies it made for 1 and for all labels, and, as context only, the numpy oracle on one label's box.
 
+With --decimate R the all-label meshes are also decimated (segmantic_amd.ops.decimate_meshes): rounds, the
+device-event span of the whole decimation (it holds one live-count copy per round, so it includes the host's wait
+between rounds), that span per round, its device-to-host copies, the byte model per round and the end-to-end
+time of extract_surfaces with decimation.
+
     python scripts/surface_bench.py [--size 512] [--labels 16] [--repeats 5] [--smooth 5] [--no-oracle]
+                                    [--decimate R]
 """
 from __future__ import annotations
 
@@ -108,6 +114,29 @@ def kernel_times(vol, selected, reps: int, smooth: int):
     return res
 
 
+def decimate_times(vol, selected, reps: int, smooth: int, reduction: float):
+    """decimation of the all-label meshes.  Byte model of one round over V vertices and F faces (stars hold 3 F
+    entries): count 12 F, scan 16 V, fill 12 F + 12 F, classify 3 F * (4 + 12) + 4 * 3 F + 17 V, candidate
+    3 F * 4 + 80 V + 6 * (3 F / V) rings and faces gathered per vertex (not charged), claim 8 V + 3 F * 4,
+    apply 8 V + 3 F * 4: about 140 F + 130 V bytes charged, a lower bound as the gathers are left out"""
+    boxes = ops.surface_boxes(vol, selected).cpu().numpy()
+    ws = torch.empty(ops.surface_workspace_bytes(vol.shape, selected, boxes), dtype=torch.uint8, device=vol.device)
+    starts_dev = ops.surface_count(vol, selected, boxes, ws)
+    starts = starts_dev.cpu().numpy()
+    nv, nf = int(starts[-2, 0]), int(starts[-2, 1])
+    offs, cell_xyz, nbr, faces = ops.surface_emit(vol, selected, boxes, ws, nv, nf, with_neighbours=True)
+    verts = ops.surface_relax(offs, cell_xyz, nbr, smooth, 0.5, np.zeros(3), np.eye(3), np.ones(3))
+    stats = {}
+    out = ops.decimate_meshes(verts, faces, starts_dev, starts, reduction, 128, stats)
+    res = {"reduction": reduction, "vertices_in": nv, "faces_in": nf, "vertices_out": int(out[0].shape[0]),
+           "faces_out": int(out[1].shape[0]), "rounds": stats["rounds"], "d2h_copies": stats["d2h_copies"],
+           "model_bytes_per_round_first": 140 * nf + 130 * nv}
+    res["total"] = time_events(lambda: ops.decimate_meshes(verts, faces, starts_dev, starts, reduction, 128), reps)
+    res["per_round"] = {k: v / max(1, stats["rounds"]) for k, v in res["total"].items()}
+    res["gb_per_s_first_round_model"] = res["model_bytes_per_round_first"] / (res["per_round"]["median_ms"] * 1e-3) / 1e9
+    return res
+
+
 def count_copies(fn) -> int:
     """device-to-host copies (Tensor.cpu / Tensor.tolist of a device tensor) made by fn: each one synchronises"""
     calls = [0]
@@ -137,6 +166,7 @@ def main() -> None:
     ap.add_argument("--smooth", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-oracle", action="store_true")
+    ap.add_argument("--decimate", type=float, default=0.0, help="also decimate the all-label meshes by this share")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("surface_bench needs an MI355X; a CPU run measures nothing")
@@ -162,6 +192,12 @@ def main() -> None:
         "one_label": count_copies(lambda: surfaces.extract_surfaces(vol, [present[0]])),
         "all_labels": count_copies(lambda: surfaces.extract_surfaces(vol)),
     }
+    if args.decimate > 0.0:
+        result["decimate"] = decimate_times(vol, present, args.repeats, args.smooth, args.decimate)
+        result["decimate"]["end_to_end_all_labels"] = time_host(
+            lambda: surfaces.extract_surfaces(vol, smooth_iterations=args.smooth, decimate=args.decimate), args.repeats)
+        result["decimate"]["end_to_end_d2h_copies"] = count_copies(
+            lambda: surfaces.extract_surfaces(vol, smooth_iterations=args.smooth, decimate=args.decimate))
     if not args.no_oracle:
         from tests.helpers import surface_ref
 

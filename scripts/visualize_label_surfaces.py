@@ -1,12 +1,13 @@
 """Extract one surface per tissue of a label volume on the MI355X and write each as a binary PLY.
 
     python scripts/visualize_label_surfaces.py FILE OUTPUT_DIR TISSUELIST [--selected-tissues 1 --selected-tissues 4]
-                                               [--smooth N] [--relaxation F]
+                                               [--smooth N] [--relaxation F] [--decimate R]
 
 The reference's script of the same name and argument order.  FILE is read through data/imageio.py (NIfTI,
 MetaImage, NRRD); TISSUELIST is an iSEG tissue list (it may be missing: files are then called label_NNN.ply).
-Meshes are discrete surface nets (segmantic_amd.image.surfaces), in the RAS millimetre frame of the file's affine,
-not decimated.  The default selection is every label present; a selected label that is absent writes no file.
+Meshes are discrete surface nets (segmantic_amd.image.surfaces), in the RAS millimetre frame of the file's affine.
+--decimate R in (0, 1) decimates every mesh towards (1 - R) of its triangles by topology-preserving edge collapses;
+the default 0 leaves them as extracted, 0.8 is the reference's vtkDecimatePro setting.  The default selection is every label present; a selected label that is absent writes no file.
 """
 from __future__ import annotations
 
@@ -41,6 +42,8 @@ def extract_surfaces(
     selected_tissues: Optional[List[int]] = typer.Option(None, "--selected-tissues", help="labels to extract (default: all present)"),
     smooth: int = typer.Option(0, "--smooth", help="relaxation sweeps"),
     relaxation: float = typer.Option(0.5, "--relaxation", help="relaxation factor in [0, 1]"),
+    decimate: float = typer.Option(0.0, "--decimate", help="share of the triangles to remove, in [0, 1); 0 = off, "
+                                                           "--decimate 0.8 is the reference's setting"),
 ) -> None:
     arr, affine = read_image(file_path)
     tissues: Dict[int, str] = {}
@@ -48,7 +51,7 @@ def extract_surfaces(
         tissues = {i: name for name, i in load_tissue_list(tissuelist_path).items()}
     spacing, origin, direction = affine_geometry(affine)
     surfaces = _extract(np.ascontiguousarray(arr), selected_tissues or None, spacing, origin, direction, smooth,
-                        relaxation)
+                        relaxation, decimate)
     output_dir.mkdir(parents=True, exist_ok=True)
     for label, surf in surfaces.items():
         name = surface_file_name(label, tissues)

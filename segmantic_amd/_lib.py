@@ -185,6 +185,11 @@ SIGNATURES = {
     "segmi_surface_emit": (_i, [_P, _i, _i, _i, _i, _P, _P, _i, _i64, _i64, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "segmi_surface_relax": (_i, [_P, _P, _P, _P, _i64, _i, _f, _P, _P, _P]),
     "segmi_surface_measure": (_i, [_P, _P, _P, _i, _P, _P, C.c_size_t, _P]),
+    "segmi_decimate_workspace_bytes": (_i64, [_i64, _i64, _i]),
+    "segmi_decimate_init": (_i, [_P, _P, _i, _i64, _i64, _P, _P, C.c_size_t, _P]),
+    "segmi_decimate_round": (_i, [_P, _P, _P, _i, _i64, _i64, _i, _P, _P, C.c_size_t, _P]),
+    "segmi_decimate_compact_count": (_i, [_P, _i, _i64, _i64, _P, _P, C.c_size_t, _P]),
+    "segmi_decimate_compact_emit": (_i, [_P, _P, _i, _i64, _i64, _P, _P, _P, _P, C.c_size_t, _P]),
     "segmi_nyul_workspace_bytes": (_i64, [_i, _i]),
     "segmi_nyul_landmarks": (_i, [_P, _i, _i64, _i, _P, _i, _P, _P, _P, C.c_size_t, _P]),
     "segmi_nyul_apply": (_i, [_P, _i, _i64, _i, _P, _P, _P, _i, _P]),

@@ -1,0 +1,536 @@
+// decimate.hip -- round-based edge-collapse decimation of triangle meshes (the vtkDecimatePro step of the
+// reference's scripts/visualize_label_surfaces.py, replaced by an algorithm with a defined output).  DESIGN.md
+// section 14 holds the definition; segmantic_amd/image/surfaces.py repeats it and tests/helpers/decimate_ref.py
+// restates it in float64 Python.  In short, per round t:
+//   stars     : every live vertex's live incident faces (CSR: count, scan, fill; sorted ascending in round 0).
+//   quadrics  : round 0 only, Q_u = sum over u's faces in ascending face number of p p^T, p = (n, -n.a),
+//               n = (b - a) x (c - a); a collapse u -> v adds Q_u to Q_v.
+//   classify  : u is REGULAR when its star is one closed fan of 3 .. 32 faces; everything else is pinned.
+//   candidate : for a regular u the admissible neighbour v (regular, valences summing to >= 7, link condition,
+//               shared vertices of valence >= 4, no flipped or degenerate face) with the smallest (float32(cost) >> 23, v);
+//               key = bucket << 55 | mix32(u, t) << 23 | u.
+//   claim     : 64-bit atomicMin of the key into the slots of u and N(u).
+//   apply     : u collapses when all those slots hold its key: winners have disjoint closed 1-rings, so no
+//               winner reads what another writes.
+// Several meshes form one batch (vertex numbers offset by the mesh's first vertex; the key uses the number within
+// the mesh), every launch serves all of them, and a mesh at or under its target yields no candidate.  Phases are
+// separate launches: no grid-wide wait, no spin loop.  The candidate pass is one thread per vertex: a star has
+// 4 .. 32 faces (6 on average), so a wave per vertex would idle 58 lanes of 64 on the typical vertex, while
+// the thread-per-vertex divergence is bounded by the valence cap.  The file is compiled with -ffp-contract=off:
+// quadrics, costs and the flip test are specified operation by operation.
+#include "common.h"
+
+namespace segmi {
+
+constexpr int kDecScan = 2048;         // elements per workgroup of the scan passes (256 threads x 8)
+constexpr int kDecMaxValence = 32;
+constexpr int kDecMaxMeshes = 65535;
+constexpr unsigned long long kDecNoKey = ~0ull;
+
+static inline size_t dec_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct DecLayout { size_t wf, off, deg, adj, ring, quad, key, slot, choice, vmesh, vstate, partials, total; };
+
+static void dec_layout(int64_t nv, int64_t nf, DecLayout* L) {
+  const int64_t n = nv > nf ? nv : nf;
+  size_t o = 0;
+  L->wf = o;       o += dec_align((size_t)nf * 3 * 4);
+  L->off = o;      o += dec_align((size_t)(n + 1) * 4);
+  L->deg = o;      o += dec_align((size_t)(n + 1) * 4);
+  L->adj = o;      o += dec_align((size_t)(nf * 3 + 1) * 4);
+  L->ring = o;     o += dec_align((size_t)(nf * 3 + 1) * 4);
+  L->quad = o;     o += dec_align((size_t)nv * 10 * 8);
+  L->key = o;      o += dec_align((size_t)nv * 8);
+  L->slot = o;     o += dec_align((size_t)nv * 8);
+  L->choice = o;   o += dec_align((size_t)nv * 4);
+  L->vmesh = o;    o += dec_align((size_t)nv * 4);
+  L->vstate = o;   o += dec_align((size_t)nv);
+  L->partials = o; o += dec_align((size_t)(cdiv64(n + 1, kDecScan) + 1) * 4);
+  L->total = o;
+}
+
+struct DecWs {
+  int32_t *wf, *off, *deg, *adj, *ring, *choice, *vmesh, *partials;
+  double* quad;
+  unsigned long long *key, *slot;
+  uint8_t* vstate;                     // bit 0: live, bit 1: regular
+};
+
+static DecWs dec_ws(void* ws, const DecLayout& L) {
+  char* b = (char*)ws;
+  DecWs w;
+  w.wf = (int32_t*)(b + L.wf); w.off = (int32_t*)(b + L.off); w.deg = (int32_t*)(b + L.deg);
+  w.adj = (int32_t*)(b + L.adj); w.ring = (int32_t*)(b + L.ring); w.quad = (double*)(b + L.quad);
+  w.key = (unsigned long long*)(b + L.key); w.slot = (unsigned long long*)(b + L.slot);
+  w.choice = (int32_t*)(b + L.choice); w.vmesh = (int32_t*)(b + L.vmesh); w.vstate = (uint8_t*)(b + L.vstate);
+  w.partials = (int32_t*)(b + L.partials);
+  return w;
+}
+
+// ---- exclusive scan of int32 in[0 .. n) into out[0 .. n], out[n] = total (in == out is allowed)
+__global__ __launch_bounds__(256) void dec_scan_reduce_kernel(const int32_t* __restrict__ in, int64_t n, int32_t* partials) {
+  __shared__ int s[256];
+  const int64_t base = (int64_t)blockIdx.x * kDecScan + threadIdx.x * 8;
+  int t = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    if (base + i < n) t += in[base + i];
+  s[threadIdx.x] = t;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = s[0];
+}
+
+__global__ __launch_bounds__(1024) void dec_scan_partials_kernel(int32_t* partials, int64_t nb) {
+  __shared__ int s[1024];
+  __shared__ int carry;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (int64_t c = 0; c < nb; c += 1024) {
+    const int64_t i = c + threadIdx.x;
+    const int v = i < nb ? partials[i] : 0;
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+      const int add = (int)threadIdx.x >= o ? s[threadIdx.x - o] : 0;
+      __syncthreads();
+      s[threadIdx.x] += add;
+      __syncthreads();
+    }
+    if (i < nb) partials[i] = carry + s[threadIdx.x] - v;
+    __syncthreads();
+    if (threadIdx.x == 1023) carry += s[1023];
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void dec_scan_apply_kernel(const int32_t* in, int64_t n, const int32_t* __restrict__ partials,
+                                                             int32_t* out) {
+  __shared__ int s[256];
+  const int64_t base = (int64_t)blockIdx.x * kDecScan + threadIdx.x * 8;
+  int v[8], t = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    v[i] = base + i < n ? in[base + i] : 0;
+    t += v[i];
+  }
+  s[threadIdx.x] = t;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const int add = (int)threadIdx.x >= o ? s[threadIdx.x - o] : 0;
+    __syncthreads();
+    s[threadIdx.x] += add;
+    __syncthreads();
+  }
+  int run = partials[blockIdx.x] + s[threadIdx.x] - t;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    if (base + i <= n) out[base + i] = run;      // the element at n receives the total
+    run += v[i];
+  }
+}
+
+static void dec_scan(const int32_t* in, int64_t n, int32_t* partials, int32_t* out, hipStream_t st) {
+  const int64_t nb = cdiv64(n + 1, kDecScan);
+  hipLaunchKernelGGL(dec_scan_reduce_kernel, (unsigned)nb, 256, 0, st, in, n, partials);
+  hipLaunchKernelGGL(dec_scan_partials_kernel, 1, 1024, 0, st, partials, nb);
+  hipLaunchKernelGGL(dec_scan_apply_kernel, (unsigned)nb, 256, 0, st, in, n, (const int32_t*)partials, out);
+}
+
+// ---- init: starts i32 [n_mesh + 2][2] = (first vertex, first face) per mesh, then the totals
+__device__ __forceinline__ int dec_find_mesh(const int32_t* __restrict__ starts, int n_mesh, int64_t i, int col) {
+  int lo = 0, hi = n_mesh - 1;         // the last mesh whose start is <= i
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (starts[2 * mid + col] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void dec_init_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ starts,
+                                                       int n_mesh, int64_t nv, int64_t nf, DecWs w, int32_t* live) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < nv) {
+    w.vmesh[i] = dec_find_mesh(starts, n_mesh, i, 0);
+    w.vstate[i] = 1;
+    w.deg[i] = 0;
+  }
+  if (i < nf) {
+    const int m = dec_find_mesh(starts, n_mesh, i, 1);
+    const int v0 = starts[2 * m];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) w.wf[i * 3 + a] = faces[i * 3 + a] + v0;
+  }
+  if (i < n_mesh) live[i] = starts[2 * i + 3] - starts[2 * i + 1];
+}
+
+// ---- stars
+__global__ __launch_bounds__(256) void dec_count_kernel(DecWs w, int64_t nf) {
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (f >= nf) return;
+  const int a = w.wf[f * 3];
+  if (a < 0) return;
+  atomicAdd(&w.deg[a], 1);
+  atomicAdd(&w.deg[w.wf[f * 3 + 1]], 1);
+  atomicAdd(&w.deg[w.wf[f * 3 + 2]], 1);
+}
+
+// the counts are used up as cursors, so deg is all zero again for the next round
+__global__ __launch_bounds__(256) void dec_fill_kernel(DecWs w, int64_t nf) {
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (f >= nf) return;
+  if (w.wf[f * 3] < 0) return;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int v = w.wf[f * 3 + a];
+    w.adj[w.off[v] + atomicSub(&w.deg[v], 1) - 1] = (int)f;
+  }
+}
+
+__device__ __forceinline__ void dec_sift(int32_t* h, int n, int i) {
+  for (;;) {
+    int c = 2 * i + 1;
+    if (c >= n) return;
+    if (c + 1 < n && h[c + 1] > h[c]) ++c;
+    if (h[i] >= h[c]) return;
+    const int t = h[i]; h[i] = h[c]; h[c] = t;
+    i = c;
+  }
+}
+
+struct DecQuadric { double q[10]; };
+
+// p p^T of face (a, b, c), p = (n, -n.a), n = (b - a) x (c - a): xx xy xz xw yy yz yw zz zw ww
+__device__ __forceinline__ void dec_face_quadric(const float* __restrict__ verts, int a, int b, int c, double* k) {
+  const double ax = verts[(int64_t)a * 3], ay = verts[(int64_t)a * 3 + 1], az = verts[(int64_t)a * 3 + 2];
+  const double ux = (double)verts[(int64_t)b * 3] - ax, uy = (double)verts[(int64_t)b * 3 + 1] - ay,
+               uz = (double)verts[(int64_t)b * 3 + 2] - az;
+  const double wx = (double)verts[(int64_t)c * 3] - ax, wy = (double)verts[(int64_t)c * 3 + 1] - ay,
+               wz = (double)verts[(int64_t)c * 3 + 2] - az;
+  const double nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;
+  const double pw = -((nx * ax + ny * ay) + nz * az);
+  k[0] = nx * nx; k[1] = nx * ny; k[2] = nx * nz; k[3] = nx * pw;
+  k[4] = ny * ny; k[5] = ny * nz; k[6] = ny * pw;
+  k[7] = nz * nz; k[8] = nz * pw;
+  k[9] = pw * pw;
+}
+
+// round 0: order every star by face number, then sum the face quadrics in that order
+__global__ __launch_bounds__(256) void dec_quadric_kernel(const float* __restrict__ verts, DecWs w, int64_t nv) {
+  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (u >= nv) return;
+  const int o = w.off[u], d = w.off[u + 1] - o;
+  int32_t* h = w.adj + o;
+  if (d <= kDecMaxValence) {
+    for (int i = 1; i < d; ++i) {
+      const int x = h[i];
+      int j = i - 1;
+      for (; j >= 0 && h[j] > x; --j) h[j + 1] = h[j];
+      h[j + 1] = x;
+    }
+  } else {
+    for (int i = d / 2 - 1; i >= 0; --i) dec_sift(h, d, i);
+    for (int n = d - 1; n > 0; --n) {
+      const int t = h[0]; h[0] = h[n]; h[n] = t;
+      dec_sift(h, n, 0);
+    }
+  }
+  double q[10], k[10];
+#pragma unroll
+  for (int i = 0; i < 10; ++i) q[i] = 0.0;
+  for (int i = 0; i < d; ++i) {
+    const int64_t f = h[i];
+    dec_face_quadric(verts, w.wf[f * 3], w.wf[f * 3 + 1], w.wf[f * 3 + 2], k);
+#pragma unroll
+    for (int j = 0; j < 10; ++j) q[j] += k[j];
+  }
+#pragma unroll
+  for (int i = 0; i < 10; ++i) w.quad[u * 10 + i] = q[i];
+}
+
+// ---- classify: ring[off[u] + i] = successor of u in its i-th star face; regular when the star is one closed fan
+__global__ __launch_bounds__(256) void dec_classify_kernel(DecWs w, int64_t nv) {
+  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (u >= nv) return;
+  w.key[u] = kDecNoKey;
+  w.slot[u] = kDecNoKey;
+  const uint8_t livebit = w.vstate[u] & 1;
+  const int o = w.off[u], d = w.off[u + 1] - o;
+  bool regular = livebit && d >= 3 && d <= kDecMaxValence;
+  if (regular) {
+    int s[kDecMaxValence], p[kDecMaxValence];
+    for (int i = 0; i < d; ++i) {
+      const int64_t f = w.adj[o + i];
+      const int a = w.wf[f * 3], b = w.wf[f * 3 + 1], c = w.wf[f * 3 + 2];
+      const int si = a == u ? b : (b == u ? c : a);
+      const int pi = a == u ? c : (b == u ? a : b);
+      s[i] = si; p[i] = pi;
+      if (si == u || pi == u || si == pi) regular = false;
+    }
+    unsigned visited = 0;
+    int i = 0;
+    for (int step = 0; regular && step < d; ++step) {
+      if ((visited >> i) & 1u) { regular = false; break; }
+      visited |= 1u << i;
+      int cnt = 0, nj = 0;
+      for (int j = 0; j < d; ++j)
+        if (p[j] == s[i]) { ++cnt; nj = j; }
+      if (cnt != 1) { regular = false; break; }
+      i = nj;
+    }
+    if (regular && i != 0) regular = false;
+    if (regular)
+      for (int j = 0; j < d; ++j) w.ring[o + j] = s[j];
+  }
+  w.vstate[u] = (uint8_t)(livebit | (regular ? 2 : 0));
+}
+
+__device__ __forceinline__ uint32_t dec_mix32(uint32_t u, uint32_t t) {
+  uint32_t x = u * 0x9E3779B1u + t * 0x85EBCA77u + 0x165667B1u;
+  x ^= x >> 15; x *= 0x2C1B3C6Du;
+  x ^= x >> 12; x *= 0x297A2D39u;
+  x ^= x >> 15;
+  return x;
+}
+
+// (b - a) x (c - a) in f64 from f32 positions
+__device__ __forceinline__ void dec_normal(const float* __restrict__ verts, int a, int b, int c, double* n) {
+  const double ax = verts[(int64_t)a * 3], ay = verts[(int64_t)a * 3 + 1], az = verts[(int64_t)a * 3 + 2];
+  const double ux = (double)verts[(int64_t)b * 3] - ax, uy = (double)verts[(int64_t)b * 3 + 1] - ay,
+               uz = (double)verts[(int64_t)b * 3 + 2] - az;
+  const double wx = (double)verts[(int64_t)c * 3] - ax, wy = (double)verts[(int64_t)c * 3 + 1] - ay,
+               wz = (double)verts[(int64_t)c * 3 + 2] - az;
+  n[0] = uy * wz - uz * wy; n[1] = uz * wx - ux * wz; n[2] = ux * wy - uy * wx;
+}
+
+__global__ __launch_bounds__(256) void dec_candidate_kernel(const float* __restrict__ verts, const int32_t* __restrict__ starts,
+                                                            DecWs w, int64_t nv, const int32_t* __restrict__ live,
+                                                            const int32_t* __restrict__ targets, uint32_t round) {
+  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (u >= nv) return;
+  if (!(w.vstate[u] & 2)) return;
+  const int m = w.vmesh[u];
+  if (live[m] <= targets[m]) return;
+  const int o = w.off[u], d = w.off[u + 1] - o;
+  int ru[kDecMaxValence];
+  for (int i = 0; i < d; ++i) ru[i] = w.ring[o + i];
+  double qu[10];
+#pragma unroll
+  for (int i = 0; i < 10; ++i) qu[i] = w.quad[u * 10 + i];
+  uint32_t best_bucket = 0xFFFFFFFFu;
+  int best_v = -1;
+  for (int i = 0; i < d; ++i) {
+    const int v = ru[i];
+    if (!(w.vstate[v] & 2)) continue;
+    // link condition: N(u) and N(v) share exactly two vertices, each of valence >= 4
+    const int ov = w.off[v], dv = w.off[v + 1] - ov;
+    if (d + dv < 7) continue;          // v keeps d + dv - 4 >= 3 faces: no two-triangle pillow
+    int shared = 0;
+    bool ok = true;
+    for (int j = 0; j < dv; ++j) {
+      const int x = w.ring[ov + j];
+      for (int k = 0; k < d; ++k)
+        if (ru[k] == x) {
+          ++shared;
+          if (w.off[x + 1] - w.off[x] < 4) ok = false;
+        }
+    }
+    if (shared != 2 || !ok) continue;
+    // u's faces without v: the normal with v in u's place keeps a strictly positive dot product with the old one
+    for (int j = 0; ok && j < d; ++j) {
+      const int64_t f = w.adj[o + j];
+      const int a = w.wf[f * 3], b = w.wf[f * 3 + 1], c = w.wf[f * 3 + 2];
+      if (a == v || b == v || c == v) continue;
+      double n0[3], n1[3];
+      dec_normal(verts, a, b, c, n0);
+      dec_normal(verts, a == u ? v : a, b == u ? v : b, c == u ? v : c, n1);
+      const double dot = (n0[0] * n1[0] + n0[1] * n1[1]) + n0[2] * n1[2];
+      if (!(dot > 0.0)) ok = false;
+    }
+    if (!ok) continue;
+    double q[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) q[k] = qu[k] + w.quad[(int64_t)v * 10 + k];
+    const double x = verts[(int64_t)v * 3], y = verts[(int64_t)v * 3 + 1], z = verts[(int64_t)v * 3 + 2];
+    const double r0 = ((q[0] * x + q[1] * y) + q[2] * z) + q[3];
+    const double r1 = ((q[1] * x + q[4] * y) + q[5] * z) + q[6];
+    const double r2 = ((q[2] * x + q[5] * y) + q[7] * z) + q[8];
+    const double r3 = ((q[3] * x + q[6] * y) + q[8] * z) + q[9];
+    double cost = ((x * r0 + y * r1) + z * r2) + r3;
+    cost = cost > 0.0 ? cost : 0.0;
+    const uint32_t bucket = __float_as_uint((float)cost) >> 23;
+    if (bucket < best_bucket || (bucket == best_bucket && v < best_v)) { best_bucket = bucket; best_v = v; }
+  }
+  if (best_v < 0) return;
+  const uint32_t ul = (uint32_t)(u - starts[2 * m]);
+  w.key[u] = ((unsigned long long)best_bucket << 55) | ((unsigned long long)dec_mix32(ul, round) << 23) | ul;
+  w.choice[u] = best_v;
+}
+
+__global__ __launch_bounds__(256) void dec_claim_kernel(DecWs w, int64_t nv) {
+  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (u >= nv) return;
+  const unsigned long long key = w.key[u];
+  if (key == kDecNoKey) return;
+  atomicMin(&w.slot[u], key);
+  const int o = w.off[u], d = w.off[u + 1] - o;
+  for (int i = 0; i < d; ++i) atomicMin(&w.slot[w.ring[o + i]], key);
+}
+
+__global__ __launch_bounds__(256) void dec_apply_kernel(DecWs w, int64_t nv, int32_t* live) {
+  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (u >= nv) return;
+  const unsigned long long key = w.key[u];
+  if (key == kDecNoKey) return;
+  if (w.slot[u] != key) return;
+  const int o = w.off[u], d = w.off[u + 1] - o;
+  for (int i = 0; i < d; ++i)
+    if (w.slot[w.ring[o + i]] != key) return;
+  const int v = w.choice[u];
+  int dead = 0;
+  for (int i = 0; i < d; ++i) {
+    const int64_t f = w.adj[o + i];
+    const int a = w.wf[f * 3], b = w.wf[f * 3 + 1], c = w.wf[f * 3 + 2];
+    if (a == v || b == v || c == v) {
+      w.wf[f * 3] = -1; w.wf[f * 3 + 1] = -1; w.wf[f * 3 + 2] = -1;
+      ++dead;
+    } else {
+      w.wf[f * 3 + (a == u ? 0 : (b == u ? 1 : 2))] = v;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 10; ++k) w.quad[(int64_t)v * 10 + k] += w.quad[u * 10 + k];
+  w.vstate[u] = 0;
+  atomicSub(&live[w.vmesh[u]], dead);
+}
+
+// ---- compaction
+__global__ __launch_bounds__(256) void dec_flags_kernel(DecWs w, int64_t nv, int64_t nf) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < nv) w.deg[i] = w.vstate[i] & 1;
+  if (i < nf) w.ring[i] = w.wf[i * 3] >= 0;
+}
+
+// voff = off, foff = adj
+__global__ __launch_bounds__(256) void dec_out_starts_kernel(DecWs w, const int32_t* __restrict__ starts, int n_mesh,
+                                                             int32_t* out) {
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  if (m > n_mesh + 1) return;
+  if (m == n_mesh + 1) { out[2 * m] = 0; out[2 * m + 1] = 0; return; }
+  out[2 * m] = w.off[starts[2 * m]];
+  out[2 * m + 1] = w.adj[starts[2 * m + 1]];
+}
+
+__global__ __launch_bounds__(256) void dec_emit_kernel(const float* __restrict__ verts, const int32_t* __restrict__ starts,
+                                                       DecWs w, int64_t nv, int64_t nf, float* out_verts,
+                                                       int32_t* out_faces, int32_t* out_keep) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < nv && (w.vstate[i] & 1)) {
+    const int64_t j = w.off[i];
+    out_verts[j * 3] = verts[i * 3]; out_verts[j * 3 + 1] = verts[i * 3 + 1]; out_verts[j * 3 + 2] = verts[i * 3 + 2];
+    out_keep[j] = (int)(i - starts[2 * w.vmesh[i]]);
+  }
+  if (i < nf && w.wf[i * 3] >= 0) {
+    const int64_t j = w.adj[i];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int g = w.wf[i * 3 + a];
+      out_faces[j * 3 + a] = w.off[g] - w.off[starts[2 * w.vmesh[g]]];
+    }
+  }
+}
+
+static int dec_args(const char* what, int n_mesh, int64_t nv, int64_t nf, const void* ws, size_t ws_bytes, DecWs* w) {
+  SEGMI_CHECK_ARG(n_mesh >= 1 && n_mesh <= kDecMaxMeshes, "%s: 1 .. %d meshes", what, kDecMaxMeshes);
+  SEGMI_CHECK_ARG(nv >= 1 && nf >= 1 && nv < (1ll << 31) && nf * 3 < (1ll << 31),
+                  "%s: 1 <= n_vertices < 2^31 and 1 <= 3 n_faces < 2^31", what);
+  SEGMI_CHECK_ARG(ws, "%s: null workspace", what);
+  DecLayout L;
+  dec_layout(nv, nf, &L);
+  SEGMI_CHECK_ARG(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", what, ws_bytes, L.total);
+  *w = dec_ws((void*)ws, L);
+  return SEGMI_OK;
+}
+
+}  // namespace segmi
+
+using namespace segmi;
+
+extern "C" {
+
+int64_t segmi_decimate_workspace_bytes(int64_t n_vertices, int64_t n_faces, int n_meshes) {
+  if (n_meshes < 1 || n_meshes > kDecMaxMeshes || n_vertices < 1 || n_faces < 1 || n_vertices >= (1ll << 31) ||
+      n_faces * 3 >= (1ll << 31))
+    return 0;
+  DecLayout L;
+  dec_layout(n_vertices, n_faces, &L);
+  return (int64_t)L.total;
+}
+
+int segmi_decimate_init(const int32_t* faces, const int32_t* starts, int n_meshes, int64_t n_vertices, int64_t n_faces,
+                        int32_t* live, void* ws, size_t ws_bytes, void* stream) {
+  DecWs w;
+  if (int rc = dec_args("decimate_init", n_meshes, n_vertices, n_faces, ws, ws_bytes, &w)) return rc;
+  SEGMI_CHECK_ARG(faces && starts && live, "decimate_init: null pointer");
+  const int64_t n = std::max<int64_t>(std::max(n_vertices, n_faces), n_meshes);
+  hipLaunchKernelGGL(dec_init_kernel, (unsigned)cdiv64(n, 256), 256, 0, (hipStream_t)stream, faces, starts, n_meshes,
+                     n_vertices, n_faces, w, live);
+  SEGMI_LAUNCH_CHECK("decimate_init");
+  return SEGMI_OK;
+}
+
+int segmi_decimate_round(const float* vertices, const int32_t* starts, const int32_t* targets, int n_meshes,
+                         int64_t n_vertices, int64_t n_faces, int round, int32_t* live, void* ws, size_t ws_bytes,
+                         void* stream) {
+  DecWs w;
+  if (int rc = dec_args("decimate_round", n_meshes, n_vertices, n_faces, ws, ws_bytes, &w)) return rc;
+  SEGMI_CHECK_ARG(vertices && starts && targets && live, "decimate_round: null pointer");
+  SEGMI_CHECK_ARG(round >= 0, "decimate_round: round must be >= 0");
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned gv = (unsigned)cdiv64(n_vertices, 256), gf = (unsigned)cdiv64(n_faces, 256);
+  hipLaunchKernelGGL(dec_count_kernel, gf, 256, 0, st, w, n_faces);
+  dec_scan(w.deg, n_vertices, w.partials, w.off, st);
+  hipLaunchKernelGGL(dec_fill_kernel, gf, 256, 0, st, w, n_faces);
+  if (round == 0) hipLaunchKernelGGL(dec_quadric_kernel, gv, 256, 0, st, vertices, w, n_vertices);
+  hipLaunchKernelGGL(dec_classify_kernel, gv, 256, 0, st, w, n_vertices);
+  hipLaunchKernelGGL(dec_candidate_kernel, gv, 256, 0, st, vertices, starts, w, n_vertices, (const int32_t*)live, targets,
+                     (uint32_t)round);
+  hipLaunchKernelGGL(dec_claim_kernel, gv, 256, 0, st, w, n_vertices);
+  hipLaunchKernelGGL(dec_apply_kernel, gv, 256, 0, st, w, n_vertices, live);
+  SEGMI_LAUNCH_CHECK("decimate_round");
+  return SEGMI_OK;
+}
+
+int segmi_decimate_compact_count(const int32_t* starts, int n_meshes, int64_t n_vertices, int64_t n_faces,
+                                 int32_t* out_starts, void* ws, size_t ws_bytes, void* stream) {
+  DecWs w;
+  if (int rc = dec_args("decimate_compact_count", n_meshes, n_vertices, n_faces, ws, ws_bytes, &w)) return rc;
+  SEGMI_CHECK_ARG(starts && out_starts, "decimate_compact_count: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = std::max(n_vertices, n_faces);
+  hipLaunchKernelGGL(dec_flags_kernel, (unsigned)cdiv64(n, 256), 256, 0, st, w, n_vertices, n_faces);
+  dec_scan(w.deg, n_vertices, w.partials, w.off, st);
+  dec_scan(w.ring, n_faces, w.partials, w.adj, st);
+  hipLaunchKernelGGL(dec_out_starts_kernel, (unsigned)cdiv64(n_meshes + 2, 256), 256, 0, st, w, starts, n_meshes,
+                     out_starts);
+  SEGMI_LAUNCH_CHECK("decimate_compact_count");
+  return SEGMI_OK;
+}
+
+int segmi_decimate_compact_emit(const float* vertices, const int32_t* starts, int n_meshes, int64_t n_vertices,
+                                int64_t n_faces, float* out_vertices, int32_t* out_faces, int32_t* out_kept, void* ws,
+                                size_t ws_bytes, void* stream) {
+  DecWs w;
+  if (int rc = dec_args("decimate_compact_emit", n_meshes, n_vertices, n_faces, ws, ws_bytes, &w)) return rc;
+  SEGMI_CHECK_ARG(vertices && starts && out_vertices && out_faces && out_kept, "decimate_compact_emit: null pointer");
+  const int64_t n = std::max(n_vertices, n_faces);
+  hipLaunchKernelGGL(dec_emit_kernel, (unsigned)cdiv64(n, 256), 256, 0, (hipStream_t)stream, vertices, starts, w,
+                     n_vertices, n_faces, out_vertices, out_faces, out_kept);
+  SEGMI_LAUNCH_CHECK("decimate_compact_emit");
+  return SEGMI_OK;
+}
+
+}  // extern "C"

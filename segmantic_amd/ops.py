@@ -7,6 +7,7 @@ pointers + extents to a HIP kernel and returns.  Activations are ``[N, D, H, W, 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional, Sequence
 
 import numpy as np
@@ -1201,6 +1202,77 @@ def surface_measure(vertices, faces, starts) -> torch.Tensor:
     check(lib.segmi_surface_measure(_ptr(vertices), _ptr(faces), _ptr(starts), n, _ptr(out), _ptr(ws), ws.numel(),
                                     _stream()), "surface_measure")
     return out
+
+
+# ------------------------------------------------------------------ mesh decimation (decimate.hip)
+DECIMATE_MAX_MESH_VERTICES = 2 ** 23    # the claim key keeps 23 bits for the vertex number within its mesh
+
+
+def decimate_targets(starts_host, reduction: float) -> np.ndarray:
+    """``ceil((1 - reduction) F)`` per mesh, in float64"""
+    s = np.asarray(starts_host, np.int64)
+    return np.asarray([math.ceil((1.0 - float(reduction)) * int(f)) for f in s[1:-1, 1] - s[:-2, 1]], np.int32)
+
+
+def decimate_meshes(vertices: torch.Tensor, faces: torch.Tensor, starts: torch.Tensor, starts_host, reduction: float,
+                    max_rounds: int = 128, stats: Optional[dict] = None):
+    """Decimate a batch of meshes (``starts`` i32 [n + 2, 2] as ``surface_count`` returns it, ``starts_host`` its host
+    copy; faces are numbered within their mesh and must be in range).  -> (vertices f32 [V', 3], faces i32 [F', 3],
+    kept i32 [V'], starts i32 [n + 2, 2] on the device, its host copy).  One device-to-host copy per round (the
+    live-face counts) and one for the output totals; ``stats`` receives ``rounds`` and ``d2h_copies``."""
+    _require_device(vertices)
+    _require_device(faces)
+    _require_device(starts)
+    sh = np.asarray(starts_host, np.int64)
+    n = sh.shape[0] - 2
+    nv, nf = int(sh[n, 0]), int(sh[n, 1])
+    if vertices.dtype != torch.float32 or faces.dtype != torch.int32 or starts.dtype != torch.int32 or \
+            tuple(vertices.shape) != (nv, 3) or tuple(faces.shape) != (nf, 3) or tuple(starts.shape) != (n + 2, 2) or \
+            not (vertices.is_contiguous() and faces.is_contiguous() and starts.is_contiguous()):
+        raise ValueError("decimate_meshes: contiguous vertices f32 [V, 3], faces i32 [F, 3] and starts i32 [n + 2, 2] "
+                         "whose totals match")
+    if int(max_rounds) < 1:
+        raise ValueError(f"max_rounds must be >= 1, got {max_rounds!r}")
+    if n < 1 or nv < 1 or nf < 1:
+        raise ValueError("decimate_meshes: at least one mesh, one vertex and one face")
+    if int((sh[1:n + 1, 0] - sh[:n, 0]).max()) >= DECIMATE_MAX_MESH_VERTICES:
+        raise ValueError(f"decimation takes meshes of fewer than 2^23 vertices, got "
+                         f"{int((sh[1:n + 1, 0] - sh[:n, 0]).max())}")
+    dev = vertices.device
+    size = int(lib.segmi_decimate_workspace_bytes(nv, nf, n))
+    if size <= 0:
+        raise ValueError("decimate_meshes: 1 .. 65535 meshes, V < 2^31 and 3 F < 2^31")
+    ws = torch.empty(size, dtype=torch.uint8, device=dev)
+    targets_host = decimate_targets(sh, reduction)
+    targets = torch.from_numpy(targets_host).to(dev)
+    live = torch.empty(n, dtype=torch.int32, device=dev)
+    check(lib.segmi_decimate_init(_ptr(faces), _ptr(starts), n, nv, nf, _ptr(live), _ptr(ws), ws.numel(), _stream()),
+          "decimate_init")
+    count = (sh[1:n + 1, 1] - sh[:n, 1]).astype(np.int64)
+    rounds = copies = 0
+    active = count > targets_host
+    while active.any() and rounds < int(max_rounds):
+        check(lib.segmi_decimate_round(_ptr(vertices), _ptr(starts), _ptr(targets), n, nv, nf, rounds, _ptr(live),
+                                       _ptr(ws), ws.numel(), _stream()), "decimate_round")
+        rounds += 1
+        now = live.cpu().numpy().astype(np.int64)            # host synchronisation: live faces per mesh
+        copies += 1
+        active = (now > targets_host) & (now < count)
+        count = now
+    out_starts = torch.empty((n + 2, 2), dtype=torch.int32, device=dev)
+    check(lib.segmi_decimate_compact_count(_ptr(starts), n, nv, nf, _ptr(out_starts), _ptr(ws), ws.numel(), _stream()),
+          "decimate_compact_count")
+    out_host = out_starts.cpu().numpy()                      # host synchronisation: output totals
+    copies += 1
+    ov, of = int(out_host[n, 0]), int(out_host[n, 1])
+    out_v = torch.empty((ov, 3), dtype=torch.float32, device=dev)
+    out_f = torch.empty((of, 3), dtype=torch.int32, device=dev)
+    kept = torch.empty(ov, dtype=torch.int32, device=dev)
+    check(lib.segmi_decimate_compact_emit(_ptr(vertices), _ptr(starts), n, nv, nf, _ptr(out_v), _ptr(out_f), _ptr(kept),
+                                          _ptr(ws), ws.numel(), _stream()), "decimate_compact_emit")
+    if stats is not None:
+        stats.update(rounds=rounds, d2h_copies=copies)
+    return out_v, out_f, kept, out_starts, out_host
 
 
 # ------------------------------------------------------------------ Nyul standardisation
