@@ -611,6 +611,47 @@ int segmi_cc_fill_holes(const void* labels, int label_bytes, int d, int h, int w
 int segmi_map_labels(const void* in, int in_bytes, int64_t n, const int64_t* lut, int lut_len, void* out,
                      int out_bytes, void* stream);
 
+/* ---------------------------------------------------------------- label morphology ------ */
+/* Exact Euclidean feature transform and label morphology by a physical radius.
+ * Label volumes are read in place as label_bytes in {1 (uint8), 2 (int16), 4 (int32)}, [d][h][w] with
+ * d * h * w < 2^31 (a 2-D input is d = 1 with spatial_dims = 2).  spacing_zyx: HOST f64[3], per array axis.
+ * Squared distances are f64: with one spacing s for every axis (the z entry is ignored for a 2-D input)
+ * double(dz^2 + dy^2 + dx^2) * (s * s), the sum in i64 (bit-exact); otherwise
+ * ((sz dz)^2 + (sy dy)^2) + (sx dx)^2 formed product by product in this order, so mirrored offsets give
+ * bit-identical values.
+ *
+ * Workspace of the feature transform for a box of bd x bh x bw voxels. */
+int64_t segmi_feature_transform_workspace_bytes(int bd, int bh, int bw);
+/* index[bd][bh][bw] (plain z y x layout over the box) = linear index (z * h + y) * w + x, in the full
+ * volume, of the feature voxel of the box nearest to each voxel of the box; -1 when the box holds no feature.
+ * Among equally near features the smallest linear index wins (z, then y, then x).  Feature predicate by
+ * mode: 0 value != 0, 1 value == 0, 2 value == label, 3 value != label, 4 table[value] != 0 (table: DEVICE
+ * bytes [65536]; values outside 0 .. 65535 are no features).  box: HOST half-open (z0 z1 y0 y1 x0 x1), NULL =
+ * the whole volume; extents up to 2^20.  dist (nullable) f32 [bd][bh][bw]: the squared distance to that
+ * feature rounded to f32, or with dist_sqrt != 0 the f32 rounding of its f64 square root; +inf when there is
+ * no feature.  Three launches (x, y, z), no host synchronisation. */
+int segmi_feature_transform(const void* labels, int label_bytes, int d, int h, int w, int spatial_dims, int mode,
+                            int label, const uint8_t* table, const int32_t* box, const double* spacing_zyx,
+                            int32_t* index, float* dist, int dist_sqrt, void* workspace, size_t ws_bytes,
+                            void* stream);
+/* out[v] = labels[index[v]] where labels[v] == 0, index[v] >= 0 and the squared distance between v and
+ * index[v] is <= double(radius) * double(radius) (radius = +inf: no limit); labels[v] elsewhere.  index:
+ * whole-volume result of the feature transform.  out: dtype of labels, must not alias labels. */
+int segmi_morph_gather(const void* labels, int label_bytes, int d, int h, int w, int spatial_dims,
+                       const int32_t* index, const double* spacing_zyx, double radius, void* out, void* stream);
+/* Erosion select: out[v] = 0 for every voxel v of the box with labels[v] == label whose nearest feature
+ * index[v - box] (box-shaped result of the feature transform over the same box, mode 3) lies within the
+ * radius (squared distance <= radius * radius); other voxels of out are not written: the caller fills out
+ * with a copy of labels first.  keep (nullable, dtype of labels): voxels with keep[v] != 0 are never
+ * zeroed (closing keeps what was labelled before the dilation).  box: HOST, NULL = the whole volume. */
+int segmi_morph_erode_select(const void* labels, int label_bytes, int d, int h, int w, int spatial_dims, int label,
+                             const int32_t* box, const int32_t* index, const double* spacing_zyx, double radius,
+                             const void* keep, void* out, void* stream);
+/* planes[a][v] = coordinate a of the voxel index[v] (a = z, y, x; y, x with spatial_dims = 2): the layout
+ * of scipy's return_indices.  -1 in every plane where index[v] is -1.  planes: i32 [spatial_dims][d*h*w]. */
+int segmi_morph_index_planes(const int32_t* index, int d, int h, int w, int spatial_dims, int32_t* planes,
+                             void* stream);
+
 /* ---------------------------------------------------------------- label surfaces -------- */
 /* Discrete surface nets of the selected labels of a label volume (scripts/visualize_label_surfaces.py of the
  * reference, which uses VTK's discrete flying edges; DESIGN.md section 14 defines the output).  Label volumes

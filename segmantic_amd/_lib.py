@@ -179,6 +179,11 @@ SIGNATURES = {
     "segmi_cc_remove_small": (_i, [_P, _i, _i64, _P, _P, _i, _P, _P]),
     "segmi_cc_fill_holes": (_i, [_P, _i, _i, _i, _i, _i, _i, _P, _P, _i, _P, _P, C.c_size_t, _P]),
     "segmi_map_labels": (_i, [_P, _i, _i64, _P, _i, _P, _i, _P]),
+    "segmi_feature_transform_workspace_bytes": (_i64, [_i, _i, _i]),
+    "segmi_feature_transform": (_i, [_P, _i, _i, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _i, _P, C.c_size_t, _P]),
+    "segmi_morph_gather": (_i, [_P, _i, _i, _i, _i, _i, _P, _P, _d, _P, _P]),
+    "segmi_morph_erode_select": (_i, [_P, _i, _i, _i, _i, _i, _i, _P, _P, _P, _d, _P, _P, _P]),
+    "segmi_morph_index_planes": (_i, [_P, _i, _i, _i, _i, _P, _P]),
     "segmi_surface_boxes": (_i, [_P, _i, _i, _i, _i, _P, _i, _P, _P]),
     "segmi_surface_workspace_bytes": (_i64, [_i, _i, _i, _P, _P, _i]),
     "segmi_surface_count": (_i, [_P, _i, _i, _i, _i, _P, _P, _i, _P, _P, C.c_size_t, _P]),

@@ -1100,6 +1100,107 @@ def map_labels(x, lut, out=None, out_dtype=torch.int64) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------ label morphology (morphology.hip)
+FT_NONZERO, FT_ZERO, FT_EQUAL, FT_NOT_EQUAL, FT_TABLE = 0, 1, 2, 3, 4
+FT_TABLE_SIZE = 65536         # entries of the feature table of mode FT_TABLE (device uint8)
+
+
+def _host_f64x3(spacing_zyx):
+    a = np.ascontiguousarray(np.asarray(spacing_zyx, dtype=np.float64).reshape(3))
+    return a, a.ctypes.data_as(C.c_void_p)
+
+
+def _box_shape(labels: torch.Tensor, box):
+    if box is None:
+        return tuple(labels.shape)
+    z0, z1, y0, y1, x0, x1 = (int(v) for v in box)
+    return (z1 - z0, y1 - y0, x1 - x0) if labels.dim() == 3 else (y1 - y0, x1 - x0)
+
+
+def feature_transform_workspace_bytes(shape) -> int:
+    dims = tuple(int(v) for v in shape)
+    d, h, w = (1,) + dims if len(dims) == 2 else dims
+    return int(lib.segmi_feature_transform_workspace_bytes(d, h, w))
+
+
+def feature_transform(labels, mode, spacing_zyx, label=0, table=None, box=None, index=None, dist=None,
+                      dist_sqrt=False, with_dist=False, workspace=None):
+    """-> (index int32, dist float32 or None) over ``box`` (host z0 z1 y0 y1 x0 x1; None: the whole volume):
+    the linear index in the full volume of the nearest feature voxel (-1: none), ties to the smallest index,
+    and its squared distance (``dist_sqrt``: its distance)."""
+    d, h, w, ndim = _cc_dims(labels)
+    shape = _box_shape(labels, box)
+    if index is None:
+        index = torch.empty(shape, dtype=torch.int32, device=labels.device)
+    if index.dtype != torch.int32 or tuple(index.shape) != tuple(shape) or not index.is_contiguous():
+        raise ValueError("index must be a contiguous int32 tensor of the box's shape")
+    if dist is None and with_dist:
+        dist = torch.empty(shape, dtype=torch.float32, device=labels.device)
+    if dist is not None and (dist.dtype != torch.float32 or tuple(dist.shape) != tuple(shape)
+                             or not dist.is_contiguous()):
+        raise ValueError("dist must be a contiguous float32 tensor of the box's shape")
+    if int(mode) == FT_TABLE:
+        if table is None or table.dtype != torch.uint8 or table.numel() != FT_TABLE_SIZE or not table.is_contiguous():
+            raise ValueError(f"mode FT_TABLE needs a contiguous uint8 table of {FT_TABLE_SIZE} entries")
+    if workspace is None:
+        workspace = torch.empty(feature_transform_workspace_bytes(shape), dtype=torch.uint8, device=labels.device)
+    _require_device(workspace)
+    bp = None if box is None else _host_i32(box)
+    sp, spp = _host_f64x3(spacing_zyx)
+    check(lib.segmi_feature_transform(_ptr(labels), label_bytes(labels), d, h, w, ndim, int(mode), int(label),
+                                      _ptr(table), None if bp is None else bp[1], spp, _ptr(index), _ptr(dist),
+                                      int(bool(dist_sqrt)), _ptr(workspace), workspace.numel(), _stream()),
+          "feature_transform")
+    return index, dist
+
+
+def morph_gather(labels, index, spacing_zyx, radius, out=None) -> torch.Tensor:
+    """Zero voxels whose nearest feature ``index`` lies within ``radius`` take that voxel's label."""
+    d, h, w, ndim = _cc_dims(labels)
+    _cc_i32(index, labels, "index")
+    if out is None:
+        out = torch.empty_like(labels)
+    if out.dtype != labels.dtype or out.shape != labels.shape or not out.is_contiguous() or \
+            out.data_ptr() == labels.data_ptr():
+        raise ValueError("out must match labels in dtype and shape and be another tensor")
+    sp, spp = _host_f64x3(spacing_zyx)
+    check(lib.segmi_morph_gather(_ptr(labels), label_bytes(labels), d, h, w, ndim, _ptr(index), spp, float(radius),
+                                 _ptr(out), _stream()), "morph_gather")
+    return out
+
+
+def morph_erode_select(labels, label, box, index, spacing_zyx, radius, out, keep=None) -> torch.Tensor:
+    """out[v] = 0 for the voxels of ``label`` in ``box`` whose nearest feature (``index``, box-shaped) lies
+    within ``radius``; ``out`` starts as a copy of ``labels``.  Voxels with ``keep != 0`` are left alone."""
+    d, h, w, ndim = _cc_dims(labels)
+    shape = _box_shape(labels, box)
+    _require_device(index)
+    if index.dtype != torch.int32 or tuple(index.shape) != tuple(shape) or not index.is_contiguous():
+        raise ValueError("index must be a contiguous int32 tensor of the box's shape")
+    if out.dtype != labels.dtype or out.shape != labels.shape or not out.is_contiguous():
+        raise ValueError("out must match labels in dtype and shape")
+    if keep is not None and (keep.dtype != labels.dtype or keep.shape != labels.shape or not keep.is_contiguous()):
+        raise ValueError("keep must match labels in dtype and shape")
+    bp = None if box is None else _host_i32(box)
+    sp, spp = _host_f64x3(spacing_zyx)
+    check(lib.segmi_morph_erode_select(_ptr(labels), label_bytes(labels), d, h, w, ndim, int(label),
+                                       None if bp is None else bp[1], _ptr(index), spp, float(radius), _ptr(keep),
+                                       _ptr(out), _stream()), "morph_erode_select")
+    return out
+
+
+def morph_index_planes(index: torch.Tensor) -> torch.Tensor:
+    """-> int32 [ndim, ...]: the coordinates of the voxels ``index`` names, scipy's ``return_indices`` layout."""
+    _cc_i32(index, index, "index")
+    if index.dim() not in (2, 3) or index.numel() == 0 or index.numel() >= CC_MAX_VOXELS:
+        raise ValueError("index has the shape of its 2-D or 3-D volume")
+    d, h, w = _labels3(index)
+    planes = torch.empty((index.dim(),) + tuple(index.shape), dtype=torch.int32, device=index.device)
+    check(lib.segmi_morph_index_planes(_ptr(index), d, h, w, index.dim(), _ptr(planes), _stream()),
+          "morph_index_planes")
+    return planes
+
+
 # ------------------------------------------------------------------ label surfaces (surfaces.hip)
 SURFACE_MAX_CELLS = 2 ** 31     # (d+1)(h+1)(w+1) stays below this
 SURFACE_MAX_LABEL = 65535
