@@ -25,7 +25,7 @@
 //   diagonal pair (v, n = v + (dz, dy, +-1)): skipped when v ~ v + (dz, dy, 0) (that straight pair and
 //   n's x-run do it) or when v's x-neighbour on n's side has v's value (its straight pair does it).
 // The straight pair has fewer non-zero offsets than the diagonal one, so connectivity always admits it.
-#include "common.h"
+#include "labelvol.h"
 
 namespace segmi {
 
@@ -35,19 +35,19 @@ constexpr int kClassTable = 65536;     // classes of the keep-largest table (256
 constexpr int kMaxKeep = 8;
 constexpr int kAppliedChunk = 64;
 
-static inline size_t cc_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
+// compact needs the regions before `keys`, keep-largest those before `lo`, fill-holes all of them.  lo and hi
+// are the int32 words per voxel that ops.CC_FILL_WORDS counts: keep the two in step
 struct CcLayout { size_t partials, keys, winners, applied, lo, hi, total; };
 static CcLayout cc_layout(int64_t n) {
+  LvCarver c;
   CcLayout l{};
-  size_t off = 0;
-  l.partials = off; off += cc_align((size_t)(cdiv64(n, kScanItems) + 1) * sizeof(int32_t));
-  l.keys = off;     off += cc_align((size_t)kClassTable * sizeof(unsigned long long));
-  l.winners = off;  off += cc_align((size_t)kMaxKeep * kClassTable * sizeof(int32_t));
-  l.applied = off;  off += cc_align((size_t)kClassTable / 8);
-  l.lo = off;       off += cc_align((size_t)n * sizeof(int32_t));
-  l.hi = off;       off += cc_align((size_t)n * sizeof(int32_t));
-  l.total = off;
+  l.partials = c.take((size_t)(cdiv64(n, kScanItems) + 1) * sizeof(int32_t));
+  l.keys = c.take((size_t)kClassTable * sizeof(unsigned long long));
+  l.winners = c.take((size_t)kMaxKeep * kClassTable * sizeof(int32_t));
+  l.applied = c.take((size_t)kClassTable / 8);
+  l.lo = c.take((size_t)n * sizeof(int32_t));
+  l.hi = c.take((size_t)n * sizeof(int32_t));
+  l.total = c.off;
   return l;
 }
 
@@ -237,24 +237,6 @@ __global__ __launch_bounds__(256) void cc_count_kernel(const int32_t* __restrict
   __syncthreads();
   if (threadIdx.x == 0) partials[blockIdx.x] = tot[0] + tot[1] + tot[2] + tot[3];
 }
-// exclusive scan of nb partials in place by one workgroup; partials[nb] and *n_comp get the total
-__global__ __launch_bounds__(1024) void cc_scan_kernel(int32_t* partials, int64_t nb, int32_t* n_comp) {
-  __shared__ int sums[1024];
-  const int64_t per = (nb + 1023) / 1024, b0 = threadIdx.x * per, b1 = b0 + per < nb ? b0 + per : nb;
-  int s = 0;
-  for (int64_t b = b0; b < b1; ++b) s += partials[b];
-  sums[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int t = threadIdx.x >= off ? sums[threadIdx.x - off] : 0;
-    __syncthreads();
-    sums[threadIdx.x] += t;
-    __syncthreads();
-  }
-  int run = sums[threadIdx.x] - s;
-  for (int64_t b = b0; b < b1; ++b) { const int c = partials[b]; partials[b] = run; run += c; }
-  if (threadIdx.x == 1023) { partials[nb] = sums[1023]; *n_comp = sums[1023]; }
-}
 __global__ __launch_bounds__(256) void cc_number_kernel(const int32_t* __restrict__ root, int64_t n,
                                                         const int32_t* __restrict__ partials,
                                                         int32_t* __restrict__ comp) {
@@ -287,11 +269,12 @@ __global__ __launch_bounds__(256) void cc_gather_kernel(const int32_t* __restric
 }
 
 // ---- the set of applied labels as a bit table
-struct AppliedChunk { int n; int32_t v[kAppliedChunk]; };
-__global__ void cc_applied_kernel(unsigned* bits, AppliedChunk c) {
-  const int i = threadIdx.x;
-  if (i < c.n && c.v[i] >= 0 && c.v[i] < kClassTable) atomicOr(bits + (c.v[i] >> 5), 1u << (c.v[i] & 31));
-}
+struct CcAppliedBits {
+  unsigned* bits;
+  __device__ void operator()(int, int32_t v) const {
+    if (v >= 0 && v < kClassTable) atomicOr(bits + (v >> 5), 1u << (v & 31));
+  }
+};
 __device__ __forceinline__ bool cc_applied(const unsigned* bits, int c) {
   return c >= 0 && c < kClassTable && ((bits[c >> 5] >> (c & 31)) & 1u);
 }
@@ -434,34 +417,18 @@ __global__ __launch_bounds__(256) void map_labels_kernel(const TI* __restrict__ 
 
 static int cc_set_applied(unsigned* bits, const int32_t* applied_host, int n_applied, hipStream_t st) {
   if (hipMemsetAsync(bits, n_applied ? 0 : 0xff, kClassTable / 8, st) != hipSuccess) return 1;
-  for (int i = 0; i < n_applied; i += kAppliedChunk) {
-    AppliedChunk c{};
-    c.n = n_applied - i < kAppliedChunk ? n_applied - i : kAppliedChunk;
-    for (int j = 0; j < c.n; ++j) c.v[j] = applied_host[i + j];
-    hipLaunchKernelGGL(cc_applied_kernel, 1, kAppliedChunk, 0, st, bits, c);
-  }
+  lv_upload_table<kAppliedChunk>(applied_host, n_applied, CcAppliedBits{bits}, st);
   return 0;
-}
-
-static inline bool cc_dims_ok(int d, int h, int w) {
-  return d > 0 && h > 0 && w > 0 && (int64_t)d * h * w < (1ll << 31);
 }
 
 }  // namespace segmi
 
 using namespace segmi;
 
-#define SEGMI_BY_LABEL(lb, F, ...)                         \
-  do {                                                     \
-    if ((lb) == 1) F(uint8_t, __VA_ARGS__);                \
-    else if ((lb) == 2) F(int16_t, __VA_ARGS__);           \
-    else F(int32_t, __VA_ARGS__);                          \
-  } while (0)
-
 extern "C" {
 
 int64_t segmi_cc_workspace_bytes(int d, int h, int w) {
-  if (!cc_dims_ok(d, h, w)) return 0;
+  if (!lv_voxels_ok(d, h, w)) return 0;
   return (int64_t)cc_layout((int64_t)d * h * w).total;
 }
 
@@ -469,9 +436,9 @@ int segmi_cc_label(const void* labels, int label_bytes, int d, int h, int w, int
                    int with_background, int32_t* root, void* ws, size_t ws_bytes, void* stream) {
   (void)ws; (void)ws_bytes;   // the parent array is `root` itself; labelling needs no scratch
   SEGMI_CHECK_ARG(labels && root, "cc_label: null pointer");
-  SEGMI_CHECK_ARG(label_bytes == 1 || label_bytes == 2 || label_bytes == 4, "cc_label: label_bytes must be 1, 2 or 4");
-  SEGMI_CHECK_ARG(spatial_dims == 3 || (spatial_dims == 2 && d == 1), "cc_label: spatial_dims must be 3, or 2 with d == 1");
-  SEGMI_CHECK_ARG(cc_dims_ok(d, h, w), "cc_label: extents must be positive with d*h*w < 2^31");
+  LV_CHECK_LABEL_BYTES("cc_label", label_bytes);
+  LV_CHECK_SPATIAL_DIMS("cc_label", spatial_dims, d);
+  LV_CHECK_VOXELS("cc_label", d, h, w);
   SEGMI_CHECK_ARG(connectivity >= 1 && connectivity <= spatial_dims, "cc_label: connectivity must be 1 .. %d", spatial_dims);
   hipStream_t st = (hipStream_t)stream;
   CcParams p{labels, d, h, w, connectivity, with_background ? 1 : 0, root};
@@ -480,11 +447,11 @@ int segmi_cc_label(const void* labels, int label_bytes, int d, int h, int w, int
   const int64_t tiles = (int64_t)tx * ty * tz;
   const int64_t waves = (int64_t)d * h * tx;
   SEGMI_CHECK_ARG(tiles < (1ll << 31) && cdiv64(waves, 4) < (1ll << 31), "cc_label: too many rows for one launch");
-#define TILE(T, _) hipLaunchKernelGGL(cc_tile_kernel<T>, (unsigned)tiles, 256, 0, st, p, tx, ty)
-  SEGMI_BY_LABEL(label_bytes, TILE, 0);
+#define TILE(T) hipLaunchKernelGGL(cc_tile_kernel<T>, (unsigned)tiles, 256, 0, st, p, tx, ty)
+  LV_BY_LABEL(label_bytes, TILE);
 #undef TILE
-#define SEAM(T, _) hipLaunchKernelGGL(cc_seam_kernel<T>, (unsigned)cdiv64(waves, 4), 256, 0, st, p, tx, waves)
-  SEGMI_BY_LABEL(label_bytes, SEAM, 0);
+#define SEAM(T) hipLaunchKernelGGL(cc_seam_kernel<T>, (unsigned)cdiv64(waves, 4), 256, 0, st, p, tx, waves)
+  LV_BY_LABEL(label_bytes, SEAM);
 #undef SEAM
   hipLaunchKernelGGL(cc_flatten_kernel, (unsigned)cdiv64(n, 256), 256, 0, st, root, n);
   SEGMI_LAUNCH_CHECK("cc_label");
@@ -514,7 +481,7 @@ int segmi_cc_compact(const int32_t* root, int64_t n, int32_t* comp, int32_t* n_c
   int32_t* partials = (int32_t*)((char*)ws + l.partials);
   const int64_t nb = cdiv64(n, kScanItems);
   hipLaunchKernelGGL(cc_count_kernel, (unsigned)nb, 256, 0, st, root, n, partials);
-  hipLaunchKernelGGL(cc_scan_kernel, 1, 1024, 0, st, partials, nb, n_comp);
+  hipLaunchKernelGGL(lv_scan_partials_kernel<1>, 1, 1024, 0, st, (uint32_t*)partials, nb, (uint32_t*)n_comp, (uint32_t*)nullptr);
   hipLaunchKernelGGL(cc_number_kernel, (unsigned)nb, 256, 0, st, root, n, (const int32_t*)partials, comp);
   hipLaunchKernelGGL(cc_gather_kernel, (unsigned)cdiv64(n, 256), 256, 0, st, root, n, comp);
   SEGMI_LAUNCH_CHECK("cc_compact");
@@ -525,7 +492,7 @@ int segmi_cc_keep_largest(const void* labels, int label_bytes, int64_t n, const 
                           const int32_t* applied_host, int n_applied, int independent, int num_components,
                           void* out, void* ws, size_t ws_bytes, void* stream) {
   SEGMI_CHECK_ARG(labels && root && size && out && ws, "cc_keep_largest: null pointer");
-  SEGMI_CHECK_ARG(label_bytes == 1 || label_bytes == 2 || label_bytes == 4, "cc_keep_largest: label_bytes must be 1, 2 or 4");
+  LV_CHECK_LABEL_BYTES("cc_keep_largest", label_bytes);
   SEGMI_CHECK_ARG(n > 0 && n < (1ll << 31), "cc_keep_largest: 0 < n < 2^31");
   SEGMI_CHECK_ARG(n_applied >= 0 && (n_applied == 0 || applied_host), "cc_keep_largest: bad applied labels");
   SEGMI_CHECK_ARG(num_components >= 1 && num_components <= kMaxKeep, "cc_keep_largest: num_components must be 1 .. %d", kMaxKeep);
@@ -548,13 +515,13 @@ int segmi_cc_keep_largest(const void* labels, int label_bytes, int64_t n, const 
   }
   const unsigned grid = (unsigned)cdiv64(n, 256);
   for (int r = 0; r < num_components; ++r) {
-#define ROUND(T, _) hipLaunchKernelGGL(cc_keep_round_kernel<T>, grid, 256, 0, st, p, r)
-    SEGMI_BY_LABEL(label_bytes, ROUND, 0);
+#define ROUND(T) hipLaunchKernelGGL(cc_keep_round_kernel<T>, grid, 256, 0, st, p, r)
+    LV_BY_LABEL(label_bytes, ROUND);
 #undef ROUND
     hipLaunchKernelGGL(cc_keep_pick_kernel, cdiv(p.classes, 256), 256, 0, st, p, r);
   }
-#define APPLY(T, _) hipLaunchKernelGGL(cc_keep_apply_kernel<T>, grid, 256, 0, st, p)
-  SEGMI_BY_LABEL(label_bytes, APPLY, 0);
+#define APPLY(T) hipLaunchKernelGGL(cc_keep_apply_kernel<T>, grid, 256, 0, st, p)
+  LV_BY_LABEL(label_bytes, APPLY);
 #undef APPLY
   SEGMI_LAUNCH_CHECK("cc_keep_largest");
   return SEGMI_OK;
@@ -563,12 +530,12 @@ int segmi_cc_keep_largest(const void* labels, int label_bytes, int64_t n, const 
 int segmi_cc_remove_small(const void* labels, int label_bytes, int64_t n, const int32_t* root, const int32_t* size,
                           int min_size, void* out, void* stream) {
   SEGMI_CHECK_ARG(labels && root && size && out, "cc_remove_small: null pointer");
-  SEGMI_CHECK_ARG(label_bytes == 1 || label_bytes == 2 || label_bytes == 4, "cc_remove_small: label_bytes must be 1, 2 or 4");
+  LV_CHECK_LABEL_BYTES("cc_remove_small", label_bytes);
   SEGMI_CHECK_ARG(n > 0 && n < (1ll << 31), "cc_remove_small: 0 < n < 2^31");
   SEGMI_CHECK_ARG(min_size >= 0, "cc_remove_small: min_size must be >= 0");
   hipStream_t st = (hipStream_t)stream;
-#define SMALL(T, _) hipLaunchKernelGGL(cc_remove_small_kernel<T>, (unsigned)cdiv64(n, 256), 256, 0, st, (const T*)labels, root, size, n, min_size, (T*)out)
-  SEGMI_BY_LABEL(label_bytes, SMALL, 0);
+#define SMALL(T) hipLaunchKernelGGL(cc_remove_small_kernel<T>, (unsigned)cdiv64(n, 256), 256, 0, st, (const T*)labels, root, size, n, min_size, (T*)out)
+  LV_BY_LABEL(label_bytes, SMALL);
 #undef SMALL
   SEGMI_LAUNCH_CHECK("cc_remove_small");
   return SEGMI_OK;
@@ -578,9 +545,9 @@ int segmi_cc_fill_holes(const void* labels, int label_bytes, int d, int h, int w
                         const int32_t* root, const int32_t* applied_host, int n_applied, void* out, void* ws,
                         size_t ws_bytes, void* stream) {
   SEGMI_CHECK_ARG(labels && root && out && ws, "cc_fill_holes: null pointer");
-  SEGMI_CHECK_ARG(label_bytes == 1 || label_bytes == 2 || label_bytes == 4, "cc_fill_holes: label_bytes must be 1, 2 or 4");
-  SEGMI_CHECK_ARG(spatial_dims == 3 || (spatial_dims == 2 && d == 1), "cc_fill_holes: spatial_dims must be 3, or 2 with d == 1");
-  SEGMI_CHECK_ARG(cc_dims_ok(d, h, w), "cc_fill_holes: extents must be positive with d*h*w < 2^31");
+  LV_CHECK_LABEL_BYTES("cc_fill_holes", label_bytes);
+  LV_CHECK_SPATIAL_DIMS("cc_fill_holes", spatial_dims, d);
+  LV_CHECK_VOXELS("cc_fill_holes", d, h, w);
   SEGMI_CHECK_ARG(connectivity >= 1 && connectivity <= spatial_dims, "cc_fill_holes: connectivity must be 1 .. %d", spatial_dims);
   SEGMI_CHECK_ARG(n_applied >= 0 && (n_applied == 0 || applied_host), "cc_fill_holes: bad applied labels");
   const int64_t n = (int64_t)d * h * w;
@@ -598,13 +565,13 @@ int segmi_cc_fill_holes(const void* labels, int label_bytes, int d, int h, int w
     return SEGMI_ELAUNCH;
   }
   const unsigned grid = (unsigned)cdiv64(n, 256);
-#define FILL(T, _)                                                            \
+#define FILL(T)                                                            \
   do {                                                                        \
     hipLaunchKernelGGL(cc_fill_init_kernel<T>, grid, 256, 0, st, p, n);       \
     hipLaunchKernelGGL(cc_fill_scan_kernel<T>, grid, 256, 0, st, p, n);       \
     hipLaunchKernelGGL(cc_fill_apply_kernel<T>, grid, 256, 0, st, p, n);      \
   } while (0)
-  SEGMI_BY_LABEL(label_bytes, FILL, 0);
+  LV_BY_LABEL(label_bytes, FILL);
 #undef FILL
   SEGMI_LAUNCH_CHECK("cc_fill_holes");
   return SEGMI_OK;
@@ -617,8 +584,7 @@ int segmi_map_labels(const void* in, int in_bytes, int64_t n, const int64_t* lut
   SEGMI_CHECK_ARG(out_bytes == 1 || out_bytes == 2 || out_bytes == 4 || out_bytes == 8, "map_labels: out_bytes must be 1, 2, 4 or 8");
   SEGMI_CHECK_ARG(n > 0 && lut_len > 0, "map_labels: empty input or table");
   hipStream_t st = (hipStream_t)stream;
-  const int64_t blocks = cdiv64(n, 256);
-  const unsigned grid = (unsigned)(blocks > 65536 ? 65536 : blocks);
+  const unsigned grid = (unsigned)lv_grid(n, 256, 65536);
 #define MAP(TI, TO) hipLaunchKernelGGL((map_labels_kernel<TI, TO>), grid, 256, 0, st, (const TI*)in, n, lut, lut_len, (TO*)out)
 #define MAP_OUT(TI)                                \
   do {                                             \

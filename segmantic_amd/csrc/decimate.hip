@@ -18,7 +18,7 @@
 // 4 .. 32 faces (6 on average), so a wave per vertex would idle 58 lanes of 64 on the typical vertex, while
 // the thread-per-vertex divergence is bounded by the valence cap.  The file is compiled with -ffp-contract=off:
 // quadrics, costs and the flip test are specified operation by operation.
-#include "common.h"
+#include "labelvol.h"
 
 namespace segmi {
 
@@ -27,26 +27,24 @@ constexpr int kDecMaxValence = 32;
 constexpr int kDecMaxMeshes = 65535;
 constexpr unsigned long long kDecNoKey = ~0ull;
 
-static inline size_t dec_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct DecLayout { size_t wf, off, deg, adj, ring, quad, key, slot, choice, vmesh, vstate, partials, total; };
 
 static void dec_layout(int64_t nv, int64_t nf, DecLayout* L) {
   const int64_t n = nv > nf ? nv : nf;
-  size_t o = 0;
-  L->wf = o;       o += dec_align((size_t)nf * 3 * 4);
-  L->off = o;      o += dec_align((size_t)(n + 1) * 4);
-  L->deg = o;      o += dec_align((size_t)(n + 1) * 4);
-  L->adj = o;      o += dec_align((size_t)(nf * 3 + 1) * 4);
-  L->ring = o;     o += dec_align((size_t)(nf * 3 + 1) * 4);
-  L->quad = o;     o += dec_align((size_t)nv * 10 * 8);
-  L->key = o;      o += dec_align((size_t)nv * 8);
-  L->slot = o;     o += dec_align((size_t)nv * 8);
-  L->choice = o;   o += dec_align((size_t)nv * 4);
-  L->vmesh = o;    o += dec_align((size_t)nv * 4);
-  L->vstate = o;   o += dec_align((size_t)nv);
-  L->partials = o; o += dec_align((size_t)(cdiv64(n + 1, kDecScan) + 1) * 4);
-  L->total = o;
+  LvCarver c;
+  L->wf = c.take((size_t)nf * 3 * 4);
+  L->off = c.take((size_t)(n + 1) * 4);
+  L->deg = c.take((size_t)(n + 1) * 4);
+  L->adj = c.take((size_t)(nf * 3 + 1) * 4);
+  L->ring = c.take((size_t)(nf * 3 + 1) * 4);
+  L->quad = c.take((size_t)nv * 10 * 8);
+  L->key = c.take((size_t)nv * 8);
+  L->slot = c.take((size_t)nv * 8);
+  L->choice = c.take((size_t)nv * 4);
+  L->vmesh = c.take((size_t)nv * 4);
+  L->vstate = c.take((size_t)nv);
+  L->partials = c.take((size_t)(cdiv64(n + 1, kDecScan) + 1) * 4);
+  L->total = c.off;
 }
 
 struct DecWs {
@@ -75,36 +73,8 @@ __global__ __launch_bounds__(256) void dec_scan_reduce_kernel(const int32_t* __r
 #pragma unroll
   for (int i = 0; i < 8; ++i)
     if (base + i < n) t += in[base + i];
-  s[threadIdx.x] = t;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partials[blockIdx.x] = s[0];
-}
-
-__global__ __launch_bounds__(1024) void dec_scan_partials_kernel(int32_t* partials, int64_t nb) {
-  __shared__ int s[1024];
-  __shared__ int carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t c = 0; c < nb; c += 1024) {
-    const int64_t i = c + threadIdx.x;
-    const int v = i < nb ? partials[i] : 0;
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const int add = (int)threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-      __syncthreads();
-      s[threadIdx.x] += add;
-      __syncthreads();
-    }
-    if (i < nb) partials[i] = carry + s[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += s[1023];
-    __syncthreads();
-  }
+  lv_block_scan<256>(t, s);
+  if (threadIdx.x == 255) partials[blockIdx.x] = s[255];
 }
 
 __global__ __launch_bounds__(256) void dec_scan_apply_kernel(const int32_t* in, int64_t n, const int32_t* __restrict__ partials,
@@ -117,15 +87,7 @@ __global__ __launch_bounds__(256) void dec_scan_apply_kernel(const int32_t* in, 
     v[i] = base + i < n ? in[base + i] : 0;
     t += v[i];
   }
-  s[threadIdx.x] = t;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const int add = (int)threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-    __syncthreads();
-    s[threadIdx.x] += add;
-    __syncthreads();
-  }
-  int run = partials[blockIdx.x] + s[threadIdx.x] - t;
+  int run = partials[blockIdx.x] + lv_block_scan<256>(t, s);
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     if (base + i <= n) out[base + i] = run;      // the element at n receives the total
@@ -136,7 +98,7 @@ __global__ __launch_bounds__(256) void dec_scan_apply_kernel(const int32_t* in, 
 static void dec_scan(const int32_t* in, int64_t n, int32_t* partials, int32_t* out, hipStream_t st) {
   const int64_t nb = cdiv64(n + 1, kDecScan);
   hipLaunchKernelGGL(dec_scan_reduce_kernel, (unsigned)nb, 256, 0, st, in, n, partials);
-  hipLaunchKernelGGL(dec_scan_partials_kernel, 1, 1024, 0, st, partials, nb);
+  hipLaunchKernelGGL(lv_scan_partials_kernel<1>, 1, 1024, 0, st, (uint32_t*)partials, nb, (uint32_t*)nullptr, (uint32_t*)nullptr);
   hipLaunchKernelGGL(dec_scan_apply_kernel, (unsigned)nb, 256, 0, st, in, n, (const int32_t*)partials, out);
 }
 

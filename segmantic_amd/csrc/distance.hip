@@ -20,7 +20,7 @@
 // clamping d <= 0 to 0 gives the distance to the label (point-wise distances).
 // With unit spacing the envelope arithmetic is exact integer arithmetic (i64 products), so the result
 // is bit-exact against brute force while squared distances stay below 2^24.
-#include "common.h"
+#include "labelvol.h"
 #include "reduce_fin.h"
 
 namespace segmi {
@@ -32,7 +32,6 @@ constexpr int kSelectWgs = 512;
 constexpr int kSelectBins = 2048;     // 11-bit digits: passes over bits 31..21, 20..10, 9..0
 constexpr int kSelectMaxRanks = 4;
 
-static inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 template <typename T>
 __device__ __forceinline__ int lab_at(const T* lab, int64_t o) { return (int)lab[o]; }
@@ -439,15 +438,7 @@ __global__ __launch_bounds__(256) void select_scan_kernel(SelectParams p) {
   int64_t loc[8], tot = 0;
 #pragma unroll
   for (int j = 0; j < 8; ++j) { loc[j] = h[tid * 8 + j]; tot += loc[j]; }
-  s_scan[tid] = tot;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {     // inclusive Hillis-Steele scan
-    const int64_t v = tid >= o ? s_scan[tid - o] : 0;
-    __syncthreads();
-    s_scan[tid] += v;
-    __syncthreads();
-  }
-  const int64_t before = s_scan[tid] - tot;
+  const int64_t before = lv_block_scan<256>(tot, s_scan);
 #pragma unroll
   for (int j = 0; j < 8; ++j) h[tid * 8 + j] = 0;      // ready for the next pass
   if (rem >= 0 && rem >= before && rem < before + tot) {
@@ -496,48 +487,37 @@ struct EdtLayout {
   size_t f1, sv, sg, partials, total;
 };
 static inline EdtLayout edt_layout(int bd, int bh, int bw) {
+  LvCarver c;
   EdtLayout l;
   l.nvox = (int64_t)bd * bh * bw;
-  l.f1 = 0;
-  l.sv = l.f1 + align256((size_t)l.nvox * 4);
-  l.sg = l.sv + align256((size_t)l.nvox * 4);
-  l.partials = l.sg + align256((size_t)l.nvox * 4);
-  l.total = l.partials + align256((size_t)kSampleWgs * 4 * sizeof(double));
+  l.f1 = c.take((size_t)l.nvox * 4);
+  l.sv = c.take((size_t)l.nvox * 4);
+  l.sg = c.take((size_t)l.nvox * 4);
+  l.partials = c.take((size_t)kSampleWgs * 4 * sizeof(double));
+  l.total = c.off;
   return l;
-}
-
-static inline bool box_ok(const int32_t* b, int d, int h, int w) {
-  return b[0] >= 0 && b[0] < b[1] && b[1] <= d && b[2] >= 0 && b[2] < b[3] && b[3] <= h && b[4] >= 0 &&
-         b[4] < b[5] && b[5] <= w;
 }
 
 }  // namespace segmi
 
 using namespace segmi;
 
-#define SEGMI_BY_LABEL(lb, F, ...)                         \
-  do {                                                     \
-    if ((lb) == 1) F(uint8_t, __VA_ARGS__);                \
-    else if ((lb) == 2) F(int16_t, __VA_ARGS__);           \
-    else F(int32_t, __VA_ARGS__);                          \
-  } while (0)
-
 extern "C" {
 
 int segmi_label_boxes(const void* pred, const void* truth, int label_bytes, int d, int h, int w, int k,
                       int32_t* boxes, int64_t* counts, void* stream) {
   SEGMI_CHECK_ARG(pred && truth && boxes && counts, "label_boxes: null pointer");
-  SEGMI_CHECK_ARG(label_bytes == 1 || label_bytes == 2 || label_bytes == 4, "label_boxes: label_bytes must be 1, 2 or 4");
+  LV_CHECK_LABEL_BYTES("label_boxes", label_bytes);
   SEGMI_CHECK_ARG(d > 0 && h > 0 && w > 0 && (int64_t)d * h < (1ll << 31), "label_boxes: bad extents");
   SEGMI_CHECK_ARG(k > 0 && k <= kBoxMaxLabels, "label_boxes: 1 <= k <= %d", kBoxMaxLabels);
   hipStream_t st = (hipStream_t)stream;
   unsigned long long* cnt = (unsigned long long*)counts;
   hipLaunchKernelGGL(boxes_init_kernel, cdiv(k, 256), 256, 0, st, boxes, cnt, k);
   const int rows = d * h;
-  const int grid = cdiv(rows, 4) > 1024 ? 1024 : cdiv(rows, 4);
+  const int grid = lv_grid(rows, 4, 1024);
   const size_t lds = (size_t)k * 8 * sizeof(int);
-#define BOXES(T, _) hipLaunchKernelGGL(boxes_kernel<T>, grid, 256, lds, st, (const T*)pred, (const T*)truth, d, h, w, k, boxes, cnt)
-  SEGMI_BY_LABEL(label_bytes, BOXES, 0);
+#define BOXES(T) hipLaunchKernelGGL(boxes_kernel<T>, grid, 256, lds, st, (const T*)pred, (const T*)truth, d, h, w, k, boxes, cnt)
+  LV_BY_LABEL(label_bytes, BOXES);
 #undef BOXES
   hipLaunchKernelGGL(boxes_fin_kernel, cdiv(k, 256), 256, 0, st, boxes, (const unsigned long long*)cnt, k);
   SEGMI_LAUNCH_CHECK("label_boxes");
@@ -553,12 +533,11 @@ int segmi_edt_sq(const void* labels, int label_bytes, int d, int h, int w, int s
                  int feature, const int32_t* box, const float* spacing_zyx, float* dist_sq, void* workspace,
                  size_t ws_bytes, void* stream) {
   SEGMI_CHECK_ARG(labels && box && spacing_zyx && dist_sq && workspace, "edt_sq: null pointer");
-  SEGMI_CHECK_ARG(label_bytes == 1 || label_bytes == 2 || label_bytes == 4, "edt_sq: label_bytes must be 1, 2 or 4");
-  SEGMI_CHECK_ARG(spatial_dims == 3 || (spatial_dims == 2 && d == 1), "edt_sq: spatial_dims must be 3, or 2 with d == 1");
+  LV_CHECK_LABEL_BYTES("edt_sq", label_bytes);
+  LV_CHECK_SPATIAL_DIMS("edt_sq", spatial_dims, d);
   SEGMI_CHECK_ARG(feature == 0 || feature == 1, "edt_sq: feature must be 0 (foreground) or 1 (contour)");
-  SEGMI_CHECK_ARG(d > 0 && h > 0 && w > 0 && box_ok(box, d, h, w), "edt_sq: box outside the volume or empty");
-  for (int a = 0; a < 3; ++a)
-    SEGMI_CHECK_ARG(spacing_zyx[a] > 0.f && spacing_zyx[a] < kInf, "edt_sq: spacing must be positive and finite");
+  LV_CHECK_BOX("edt_sq", box, d, h, w);
+  LV_CHECK_SPACING("edt_sq", spacing_zyx);
   EdtParams p{};
   p.lab = labels; p.d = d; p.h = h; p.w = w; p.sd = spatial_dims; p.label = label;
   p.z0 = box[0]; p.y0 = box[2]; p.x0 = box[4];
@@ -575,8 +554,8 @@ int segmi_edt_sq(const void* labels, int label_bytes, int d, int h, int w, int s
   hipStream_t st = (hipStream_t)stream;
   const int g1 = (int)cdiv64((int64_t)p.bh * p.bw, 256);
 #define P1(T, CT) hipLaunchKernelGGL((edt_p1_kernel<T, CT>), g1, 256, 0, st, p)
-  if (feature) SEGMI_BY_LABEL(label_bytes, P1, true);
-  else SEGMI_BY_LABEL(label_bytes, P1, false);
+  if (feature) LV_BY_LABEL(label_bytes, P1, true);
+  else LV_BY_LABEL(label_bytes, P1, false);
 #undef P1
   const int g2 = (int)cdiv64((int64_t)p.bd * p.bw, 256), g3 = (int)cdiv64((int64_t)p.bd * p.bh, 256);
 #define P23(E, S)                                                  \
@@ -596,10 +575,10 @@ int segmi_edt_sample(const float* dist_sq, const void* labels, int label_bytes, 
                      int64_t* n_values, void* workspace, size_t ws_bytes, void* stream) {
   SEGMI_CHECK_ARG(dist_sq && labels && box && stats && workspace, "edt_sample: null pointer");
   SEGMI_CHECK_ARG(!values || n_values, "edt_sample: values need the n_values counter");
-  SEGMI_CHECK_ARG(label_bytes == 1 || label_bytes == 2 || label_bytes == 4, "edt_sample: label_bytes must be 1, 2 or 4");
-  SEGMI_CHECK_ARG(spatial_dims == 3 || (spatial_dims == 2 && d == 1), "edt_sample: spatial_dims must be 3, or 2 with d == 1");
+  LV_CHECK_LABEL_BYTES("edt_sample", label_bytes);
+  LV_CHECK_SPATIAL_DIMS("edt_sample", spatial_dims, d);
   SEGMI_CHECK_ARG(query == 0 || query == 1, "edt_sample: query must be 0 (foreground) or 1 (contour)");
-  SEGMI_CHECK_ARG(d > 0 && h > 0 && w > 0 && box_ok(box, d, h, w), "edt_sample: box outside the volume or empty");
+  LV_CHECK_BOX("edt_sample", box, d, h, w);
   SampleParams p{};
   p.dist = dist_sq; p.lab = labels; p.d = d; p.h = h; p.w = w; p.sd = spatial_dims; p.label = label;
   p.z0 = box[0]; p.y0 = box[2]; p.x0 = box[4];
@@ -611,11 +590,11 @@ int segmi_edt_sample(const float* dist_sq, const void* labels, int label_bytes, 
   p.partials = (double*)((char*)workspace + l.partials);
   p.ticket = g_fin_next.fetch_add(1) % kFinTickets;
   const int rows = p.bd * p.bh;
-  const int grid = cdiv(rows, 4) > kSampleWgs ? kSampleWgs : cdiv(rows, 4);
+  const int grid = lv_grid(rows, 4, kSampleWgs);
   hipStream_t st = (hipStream_t)stream;
 #define SAMPLE(T, CT) hipLaunchKernelGGL((sample_kernel<T, CT>), grid, 256, 0, st, p)
-  if (query) SEGMI_BY_LABEL(label_bytes, SAMPLE, true);
-  else SEGMI_BY_LABEL(label_bytes, SAMPLE, false);
+  if (query) LV_BY_LABEL(label_bytes, SAMPLE, true);
+  else LV_BY_LABEL(label_bytes, SAMPLE, false);
 #undef SAMPLE
   SEGMI_LAUNCH_CHECK("edt_sample");
   return SEGMI_OK;
@@ -650,21 +629,21 @@ int segmi_select_f32(const float* values, const int64_t* n, const int64_t* ranks
 int segmi_confusion_counts(const void* pred, const void* truth, int label_bytes, int64_t n, int k, int64_t* cm,
                            void* stream) {
   SEGMI_CHECK_ARG(pred && truth && cm && n > 0, "confusion_counts: bad arguments");
-  SEGMI_CHECK_ARG(label_bytes == 1 || label_bytes == 2 || label_bytes == 4, "confusion_counts: label_bytes must be 1, 2 or 4");
+  LV_CHECK_LABEL_BYTES("confusion_counts", label_bytes);
   SEGMI_CHECK_ARG(k > 0 && k <= 4096, "confusion_counts: 1 <= k <= 4096");
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(cm, 0, (size_t)k * k * 8, st) != hipSuccess) {
     set_error("confusion_counts: memset failed");
     return SEGMI_ELAUNCH;
   }
-  const int grid = cdiv64(n, 256) > 1024 ? 1024 : (int)cdiv64(n, 256);
+  const int grid = lv_grid(n, 256, 1024);
   unsigned long long* c = (unsigned long long*)cm;
-#define CM(T, _)                                                                                            \
+#define CM(T)                                                                                            \
   do {                                                                                                      \
     if (k <= 64) hipLaunchKernelGGL(confusion_lds_kernel<T>, grid, 256, 0, st, (const T*)pred, (const T*)truth, n, k, c); \
     else hipLaunchKernelGGL(confusion_global_kernel<T>, grid, 256, 0, st, (const T*)pred, (const T*)truth, n, k, c);      \
   } while (0)
-  SEGMI_BY_LABEL(label_bytes, CM, 0);
+  LV_BY_LABEL(label_bytes, CM);
 #undef CM
   SEGMI_LAUNCH_CHECK("confusion_counts");
   return SEGMI_OK;

@@ -7,7 +7,7 @@
 // Arrays are [C][D][H][W] = [C][z][y][x]; every kernel is a row walker: one wave per row (c, z, y), lanes
 // along x, so z and y are known per row and no kernel divides per voxel.  All four passes are bound by
 // HBM bandwidth; none of the entry points synchronises with the host.
-#include "common.h"
+#include "labelvol.h"
 
 namespace segmi {
 
@@ -347,20 +347,12 @@ static inline int lm_grid(int rows, int channels) {
 
 using namespace segmi;
 
-#define SEGMI_LM_BY_LABEL(lb, F, ...)                    \
-  do {                                                   \
-    if ((lb) == 1) F(uint8_t, __VA_ARGS__);              \
-    else if ((lb) == 2) F(int16_t, __VA_ARGS__);         \
-    else F(int32_t, __VA_ARGS__);                        \
-  } while (0)
-
 extern "C" {
 
 int segmi_label_centroids(const void* labels, int label_bytes, int d, int h, int w, int k, int64_t* sums,
                           int32_t* flag, void* stream) {
   SEGMI_CHECK_ARG(labels && sums && flag, "label_centroids: null pointer");
-  SEGMI_CHECK_ARG(label_bytes == 1 || label_bytes == 2 || label_bytes == 4,
-                  "label_centroids: label_bytes must be 1, 2 or 4");
+  LV_CHECK_LABEL_BYTES("label_centroids", label_bytes);
   SEGMI_CHECK_ARG(d > 0 && h > 0 && w > 0 && (int64_t)d * h < (1ll << 31), "label_centroids: bad extents");
   SEGMI_CHECK_ARG(k >= 0 && k <= kLmMaxLabels, "label_centroids: 0 <= k <= %d", kLmMaxLabels);
   hipStream_t st = (hipStream_t)stream;
@@ -369,12 +361,12 @@ int segmi_label_centroids(const void* labels, int label_bytes, int d, int h, int
   const int grid = lm_grid(d * h, 1);
   unsigned long long* s = (unsigned long long*)sums;
   const bool v4 = w % 4 == 0 && ((uintptr_t)labels % (4 * label_bytes)) == 0;
-#define CENT(T, _)                                                                                       \
+#define CENT(T)                                                                                          \
   do {                                                                                                   \
     if (v4) hipLaunchKernelGGL((centroid_kernel<T, 4>), grid, 256, 0, st, (const T*)labels, d, h, w, k, s, flag); \
     else hipLaunchKernelGGL((centroid_kernel<T, 1>), grid, 256, 0, st, (const T*)labels, d, h, w, k, s, flag); \
   } while (0)
-  SEGMI_LM_BY_LABEL(label_bytes, CENT, 0);
+  LV_BY_LABEL(label_bytes, CENT);
 #undef CENT
   SEGMI_LAUNCH_CHECK("label_centroids");
   return SEGMI_OK;
@@ -425,13 +417,13 @@ int segmi_positive_bbox(const void* x, int dtype_bytes, int is_float, int c, int
   const int grid = lm_grid(rows, 1);
   hipLaunchKernelGGL(pbox_init_kernel, 1, 64, 0, st, box);
   const bool v4 = w % 4 == 0 && ((uintptr_t)x % (4 * dtype_bytes)) == 0;
-#define PBOX(T, _)                                                                                       \
+#define PBOX(T)                                                                                          \
   do {                                                                                                   \
     if (v4) hipLaunchKernelGGL((pbox_kernel<T, 4>), grid, 256, 0, st, (const T*)x, rows, d, h, w, box);  \
     else hipLaunchKernelGGL((pbox_kernel<T, 1>), grid, 256, 0, st, (const T*)x, rows, d, h, w, box);     \
   } while (0)
-  if (is_float) PBOX(float, 0);
-  else SEGMI_LM_BY_LABEL(dtype_bytes, PBOX, 0);
+  if (is_float) PBOX(float);
+  else LV_BY_LABEL(dtype_bytes, PBOX);
 #undef PBOX
   hipLaunchKernelGGL(pbox_fin_kernel, 1, 64, 0, st, box);
   SEGMI_LAUNCH_CHECK("positive_bbox");

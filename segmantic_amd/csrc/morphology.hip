@@ -17,14 +17,12 @@
 // Arithmetic: with one spacing for all axes every comparison is i64 arithmetic on voxel counts (exact);
 // otherwise candidates are compared as the f64 value ((sz dz)^2 + (sy dy)^2) + (sx dx)^2, formed in that
 // order with no contraction, so candidates at mirrored offsets compare bit-equal.
-#include "common.h"
+#include "labelvol.h"
 
 namespace segmi {
 
 constexpr int kFtMaxExtent = 1 << 20;   // keeps the i64 products of the exact envelope test below 2^63
 constexpr float kMorphInf = __builtin_inff();
-
-static inline size_t ft_align256(size_t b) { return (b + 255) / 256 * 256; }
 
 enum { kFtNonZero = 0, kFtZero = 1, kFtEqual = 2, kFtNotEqual = 3, kFtTable = 4 };
 
@@ -324,46 +322,34 @@ __global__ __launch_bounds__(256) void morph_planes_kernel(MorphParams p) {
 }
 
 // ------------------------------------------------------------------ host helpers
-static inline bool morph_box_ok(const int32_t* b, int d, int h, int w) {
-  return b[0] >= 0 && b[0] < b[1] && b[1] <= d && b[2] >= 0 && b[2] < b[3] && b[3] <= h && b[4] >= 0 &&
-         b[4] < b[5] && b[5] <= w;
-}
-
-static inline bool morph_spacing_ok(const double* s) {
-  for (int a = 0; a < 3; ++a)
-    if (!(s[a] > 0.0) || !(s[a] < (double)kMorphInf)) return false;
-  return true;
+// the two halves of the feature-transform workspace: the value and the payload of the running envelope
+struct FtLayout { size_t sv, sp, total; };
+static inline FtLayout ft_layout(int bd, int bh, int bw) {
+  LvCarver c;
+  FtLayout l;
+  l.sv = c.take((size_t)bd * bh * bw * 4);
+  l.sp = c.take((size_t)bd * bh * bw * 4);
+  l.total = c.off;
+  return l;
 }
 
 // exact = one spacing for every axis the input has
 static inline int morph_exact(const double* s, int sd) { return s[1] == s[2] && (sd == 2 || s[0] == s[1]); }
 
-static inline int morph_grid(int64_t n) {
-  const int64_t g = cdiv64(n, 256);
-  return g > (1 << 20) ? (1 << 20) : (int)g;
-}
-
 }  // namespace segmi
 
 using namespace segmi;
 
-#define MORPH_BY_LABEL(lb, F)              \
-  do {                                     \
-    if ((lb) == 1) F(uint8_t);             \
-    else if ((lb) == 2) F(int16_t);        \
-    else F(int32_t);                       \
-  } while (0)
-
-#define MORPH_CHECK_VOLUME(what, lb, d, h, w, sd)                                                                   \
-  SEGMI_CHECK_ARG((lb) == 1 || (lb) == 2 || (lb) == 4, what ": label_bytes must be 1, 2 or 4");                     \
-  SEGMI_CHECK_ARG((sd) == 3 || ((sd) == 2 && (d) == 1), what ": spatial_dims must be 3, or 2 with d == 1");         \
-  SEGMI_CHECK_ARG((d) > 0 && (h) > 0 && (w) > 0 && (int64_t)(d) * (h) * (w) < (1ll << 31), what ": bad extents")
+#define MORPH_CHECK_VOLUME(what, lb, d, h, w, sd) \
+  LV_CHECK_LABEL_BYTES(what, lb);                   \
+  LV_CHECK_SPATIAL_DIMS(what, sd, d);               \
+  LV_CHECK_VOXELS(what, d, h, w)
 
 extern "C" {
 
 int64_t segmi_feature_transform_workspace_bytes(int bd, int bh, int bw) {
   if (bd <= 0 || bh <= 0 || bw <= 0) return 0;
-  return (int64_t)(2 * ft_align256((size_t)bd * bh * bw * 4));
+  return (int64_t)ft_layout(bd, bh, bw).total;
 }
 
 int segmi_feature_transform(const void* labels, int label_bytes, int d, int h, int w, int spatial_dims, int mode,
@@ -374,29 +360,29 @@ int segmi_feature_transform(const void* labels, int label_bytes, int d, int h, i
   MORPH_CHECK_VOLUME("feature_transform", label_bytes, d, h, w, spatial_dims);
   SEGMI_CHECK_ARG(mode >= kFtNonZero && mode <= kFtTable, "feature_transform: mode must be 0 .. 4");
   SEGMI_CHECK_ARG(mode != kFtTable || table, "feature_transform: mode 4 needs the table");
-  SEGMI_CHECK_ARG(morph_spacing_ok(spacing_zyx), "feature_transform: spacing must be positive and finite");
+  LV_CHECK_SPACING("feature_transform", spacing_zyx);
   const int32_t whole[6] = {0, d, 0, h, 0, w};
   const int32_t* b = box ? box : whole;
-  SEGMI_CHECK_ARG(morph_box_ok(b, d, h, w), "feature_transform: box outside the volume or empty");
+  LV_CHECK_BOX("feature_transform", b, d, h, w);
   FtParams p{};
   p.lab = labels; p.table = table; p.d = d; p.h = h; p.w = w; p.mode = mode; p.label = label;
   p.z0 = b[0]; p.y0 = b[2]; p.x0 = b[4];
   p.bd = b[1] - b[0]; p.bh = b[3] - b[2]; p.bw = b[5] - b[4];
   SEGMI_CHECK_ARG(p.bd <= kFtMaxExtent && p.bh <= kFtMaxExtent && p.bw <= kFtMaxExtent,
                   "feature_transform: an extent above %d", kFtMaxExtent);
-  const size_t half = ft_align256((size_t)p.bd * p.bh * p.bw * 4);
-  SEGMI_CHECK_ARG(ws_bytes >= 2 * half, "feature_transform: workspace of %zu bytes, %zu needed", ws_bytes, 2 * half);
+  const FtLayout l = ft_layout(p.bd, p.bh, p.bw);
+  SEGMI_CHECK_ARG(ws_bytes >= l.total, "feature_transform: workspace of %zu bytes, %zu needed", ws_bytes, l.total);
   p.sz = spacing_zyx[0]; p.sy = spacing_zyx[1]; p.sx = spacing_zyx[2];
   p.exact = morph_exact(spacing_zyx, spatial_dims);
   p.s2 = p.sx * p.sx;
   p.index = index; p.dist = dist; p.dist_sqrt = dist_sqrt;
-  p.sv = (int32_t*)workspace;
-  p.sp = (int32_t*)((char*)workspace + half);
+  p.sv = (int32_t*)((char*)workspace + l.sv);
+  p.sp = (int32_t*)((char*)workspace + l.sp);
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = (int64_t)p.bd * p.bh;
-  const int g1 = cdiv64(rows, 4) > (1 << 20) ? (1 << 20) : (int)cdiv64(rows, 4);
+  const int g1 = lv_grid(rows, 4, 1 << 20);
 #define P1(T) hipLaunchKernelGGL(ft_p1_kernel<T>, g1, 256, 0, st, p)
-  MORPH_BY_LABEL(label_bytes, P1);
+  LV_BY_LABEL(label_bytes, P1);
 #undef P1
   const int g2 = (int)cdiv64((int64_t)p.bd * p.bw, 256), g3 = (int)cdiv64((int64_t)p.bh * p.bw, 256);
   if (p.exact) {
@@ -412,10 +398,7 @@ int segmi_feature_transform(const void* labels, int label_bytes, int d, int h, i
 
 static int morph_params(MorphParams& p, const char* what, const void* labels, int d, int h, int w, int spatial_dims,
                         const int32_t* index, const double* spacing_zyx, double radius) {
-  if (!morph_spacing_ok(spacing_zyx)) {
-    set_error("%s: spacing must be positive and finite", what);
-    return SEGMI_EINVAL;
-  }
+  SEGMI_CHECK_ARG(lv_spacing_ok(spacing_zyx), "%s: spacing must be positive and finite", what);
   if (!(radius >= 0.0)) {
     set_error("%s: the radius must be >= 0 (infinity: no limit)", what);
     return SEGMI_EINVAL;
@@ -437,9 +420,9 @@ int segmi_morph_gather(const void* labels, int label_bytes, int d, int h, int w,
   if (rc != SEGMI_OK) return rc;
   p.out = out;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = morph_grid((int64_t)d * h * w);
+  const int grid = lv_grid((int64_t)d * h * w, 256, 1 << 20);
 #define GATHER(T) hipLaunchKernelGGL(morph_gather_kernel<T>, grid, 256, 0, st, p)
-  MORPH_BY_LABEL(label_bytes, GATHER);
+  LV_BY_LABEL(label_bytes, GATHER);
 #undef GATHER
   SEGMI_LAUNCH_CHECK("morph_gather");
   return SEGMI_OK;
@@ -452,7 +435,7 @@ int segmi_morph_erode_select(const void* labels, int label_bytes, int d, int h, 
   MORPH_CHECK_VOLUME("morph_erode_select", label_bytes, d, h, w, spatial_dims);
   const int32_t whole[6] = {0, d, 0, h, 0, w};
   const int32_t* b = box ? box : whole;
-  SEGMI_CHECK_ARG(morph_box_ok(b, d, h, w), "morph_erode_select: box outside the volume or empty");
+  LV_CHECK_BOX("morph_erode_select", b, d, h, w);
   MorphParams p{};
   const int rc = morph_params(p, "morph_erode_select", labels, d, h, w, spatial_dims, index, spacing_zyx, radius);
   if (rc != SEGMI_OK) return rc;
@@ -460,9 +443,9 @@ int segmi_morph_erode_select(const void* labels, int label_bytes, int d, int h, 
   p.z0 = b[0]; p.y0 = b[2]; p.x0 = b[4];
   p.bd = b[1] - b[0]; p.bh = b[3] - b[2]; p.bw = b[5] - b[4];
   hipStream_t st = (hipStream_t)stream;
-  const int grid = morph_grid((int64_t)p.bd * p.bh * p.bw);
+  const int grid = lv_grid((int64_t)p.bd * p.bh * p.bw, 256, 1 << 20);
 #define ERODE(T) hipLaunchKernelGGL(morph_erode_kernel<T>, grid, 256, 0, st, p)
-  MORPH_BY_LABEL(label_bytes, ERODE);
+  LV_BY_LABEL(label_bytes, ERODE);
 #undef ERODE
   SEGMI_LAUNCH_CHECK("morph_erode_select");
   return SEGMI_OK;
@@ -474,7 +457,7 @@ int segmi_morph_index_planes(const int32_t* index, int d, int h, int w, int spat
   MORPH_CHECK_VOLUME("morph_index_planes", 4, d, h, w, spatial_dims);
   MorphParams p{};
   p.index = index; p.d = d; p.h = h; p.w = w; p.planes = planes; p.ndim = spatial_dims;
-  hipLaunchKernelGGL(morph_planes_kernel, morph_grid((int64_t)d * h * w), 256, 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(morph_planes_kernel, lv_grid((int64_t)d * h * w, 256, 1 << 20), 256, 0, (hipStream_t)stream, p);
   SEGMI_LAUNCH_CHECK("morph_index_planes");
   return SEGMI_OK;
 }

@@ -8,7 +8,7 @@
 //   full-resolution     : B-spline evaluation fused with the division, separable per row;
 //   scale_clamp_ct      : 27-voxel median (forgetful selection), clamp and scale.
 // Every sum is exact (integer) or runs in a fixed order, so repeated calls are bit-identical.
-#include "common.h"
+#include "labelvol.h"
 
 // the clamp / scale expression and the Otsu / sharpening arithmetic are rounded operation by operation
 // (the Makefile also gives this file -ffp-contract=off)
@@ -24,7 +24,6 @@ constexpr int kBaMaxT = 16;              // tile points per axis
 constexpr size_t kBaLdsBudget = 48 * 1024;
 constexpr double kHistFix = 4294967296.0;  // 2^32: histogram weights as exact u64 fixed point
 
-static inline size_t n4_align(size_t b) { return (b + 255) / 256 * 256; }
 
 // ------------------------------------------------------------------ per-axis B-spline geometry
 // lat == 1: an axis without spline dimension (weight 1); else m = lat - 3 spans, u = i / (n - 1) * m.
@@ -850,14 +849,14 @@ static N4Layout n4_layout(int nz, int ny, int nx, int control_points, int levels
     maxlat = std::max(maxlat, (size_t)g.lat[0] * g.lat[1] * g.lat[2]);
   }
   l.state = 0;
-  l.hist = n4_align(sizeof(N4State));
-  l.E = l.hist + n4_align((size_t)bins * 8);
-  l.parts = l.E + n4_align((size_t)bins * 8);
-  l.field = l.parts + n4_align((size_t)kN4RedBlocks * sizeof(N4Part));
-  l.lat0 = l.field + n4_align((size_t)n * 8);
-  l.lat1 = l.lat0 + n4_align(maxlat * 8);
-  l.part = l.lat1 + n4_align(maxlat * 8);
-  l.total = l.part + n4_align(maxpart * 8);
+  l.hist = lv_align256(sizeof(N4State));
+  l.E = l.hist + lv_align256((size_t)bins * 8);
+  l.parts = l.E + lv_align256((size_t)bins * 8);
+  l.field = l.parts + lv_align256((size_t)kN4RedBlocks * sizeof(N4Part));
+  l.lat0 = l.field + lv_align256((size_t)n * 8);
+  l.lat1 = l.lat0 + lv_align256(maxlat * 8);
+  l.part = l.lat1 + lv_align256(maxlat * 8);
+  l.total = l.part + lv_align256(maxpart * 8);
   return l;
 }
 
@@ -897,7 +896,7 @@ extern "C" {
 
 int64_t segmi_otsu_workspace_bytes(int bins) {
   if (bins < 2 || bins > kN4MaxBins) return 0;
-  return (int64_t)(256 + n4_align((size_t)bins * 8));
+  return (int64_t)(256 + lv_align256((size_t)bins * 8));
 }
 
 int segmi_otsu(const float* x, int64_t n, int bins, int64_t* counts, double* stats, void* ws, size_t ws_bytes,

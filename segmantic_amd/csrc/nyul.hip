@@ -15,7 +15,7 @@
 //   finalise: lerp of the two order statistics per landmark.
 // All state lives in the workspace; no host round trip between passes.  Same-bin runs (a constant
 // background) are aggregated per wave before the LDS atomic.
-#include "common.h"
+#include "labelvol.h"
 
 // Built with -ffp-contract=off (Makefile): the HIP headers' __fmul_rn & co. are plain operators that
 // would otherwise be fused with their neighbours; the two fused lerps are explicit __fmaf_rn calls.
@@ -30,7 +30,6 @@ constexpr int kSlotsLds = 16;             // 16 slots x 2048 u32 = 128 KiB of LD
 constexpr int kHistThreads = 1024;
 constexpr int kExactRankLimit = 1 << 24;  // torch.quantile's largest input
 
-static inline size_t nyul_align(size_t b) { return (b + 255) / 256 * 256; }
 
 // per-segment workspace record (then the histograms)
 struct NyulSeg {
@@ -51,10 +50,10 @@ struct NyulLayout {
 static NyulLayout nyul_layout(int segments, int n_ranks) {
   NyulLayout l{};
   l.seg = 0;
-  l.hist0 = nyul_align((size_t)segments * sizeof(NyulSeg));
-  l.hist1 = l.hist0 + nyul_align((size_t)segments * kNyulBins * 8);
-  l.hist2 = l.hist1 + nyul_align((size_t)segments * n_ranks * kNyulBins * 8);
-  l.total = l.hist2 + nyul_align((size_t)segments * n_ranks * (kNyulBins / 2) * 8);
+  l.hist0 = lv_align256((size_t)segments * sizeof(NyulSeg));
+  l.hist1 = l.hist0 + lv_align256((size_t)segments * kNyulBins * 8);
+  l.hist2 = l.hist1 + lv_align256((size_t)segments * n_ranks * kNyulBins * 8);
+  l.total = l.hist2 + lv_align256((size_t)segments * n_ranks * (kNyulBins / 2) * 8);
   return l;
 }
 

@@ -24,6 +24,7 @@
 //             tree, and the workgroup that draws the last ticket folds the table (fin_tail.h protocol).
 // Phases are separate launches: no grid-wide wait, no spin loop, no cooperative launch.  The file is compiled
 // with -ffp-contract=off: positions are specified operation by operation.
+#include "labelvol.h"
 #include "reduce_fin.h"
 
 namespace segmi {
@@ -35,8 +36,6 @@ constexpr int kSurfMaxLabels = 65535;
 
 // cells z0 .. z0+nz-1, y0 .. y0+ny-1, chunk columns cx0 .. cx0+ncx-1 (cells 64*cx .. 64*cx+63)
 struct SurfLabel { int c, z0, y0, cx0, nz, ny, ncx, base; };
-
-static inline size_t surf_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct SurfLayout { size_t table, mask, vpre, fpre, partials, total; int64_t chunks; };
 
@@ -62,15 +61,15 @@ static int surf_layout(const int32_t* sel, const int32_t* boxes, int n_sel, int 
   }
   if (chunks >= (1ll << 31)) return 2;
   SurfLayout y{};
-  size_t off = 0;
+  LvCarver c;
   y.chunks = chunks;
-  y.table = off;    off += surf_align((size_t)(n_sel + 1) * sizeof(SurfLabel));
-  y.mask = off;     off += surf_align((size_t)(chunks + 1) * sizeof(unsigned long long));
-  y.vpre = off;     off += surf_align((size_t)(chunks + 1) * sizeof(uint32_t));
-  y.fpre = off;     off += surf_align((size_t)(chunks + 1) * sizeof(uint32_t));
+  y.table = c.take((size_t)(n_sel + 1) * sizeof(SurfLabel));
+  y.mask = c.take((size_t)(chunks + 1) * sizeof(unsigned long long));
+  y.vpre = c.take((size_t)(chunks + 1) * sizeof(uint32_t));
+  y.fpre = c.take((size_t)(chunks + 1) * sizeof(uint32_t));
   // the block sums of the scan, then the three words of its totals
-  y.partials = off; off += surf_align((size_t)(cdiv64(chunks, kSurfScan) + 2) * 2 * sizeof(uint32_t));
-  y.total = off;
+  y.partials = c.take((size_t)(cdiv64(chunks, kSurfScan) + 2) * 2 * sizeof(uint32_t));
+  y.total = c.off;
   *out = y;
   return 0;
 }
@@ -163,71 +162,32 @@ __global__ __launch_bounds__(256) void surf_count_kernel(SurfParams p) {
 }
 
 // ---- scan over the chunk counts (vertices and faces together)
+// partials[b] = (vertices, faces) of block b; the totals of the partials scan: totals[0..1] = the sums,
+// totals[2] = 1 when a sum passed 2^31 - 1 (the host then refuses the volume)
 __global__ __launch_bounds__(256) void surf_sum_kernel(const uint32_t* __restrict__ v, const uint32_t* __restrict__ f,
                                                        int64_t n, uint32_t* __restrict__ partials) {
-  __shared__ uint32_t sv[256], sf[256];
-  uint32_t a = 0, b = 0;
+  __shared__ u32x2 s[256];
+  u32x2 t{};
   for (int u = 0; u < 4; ++u) {
     const int64_t i = (int64_t)blockIdx.x * kSurfScan + threadIdx.x * 4 + u;
-    if (i < n) { a += v[i]; b += f[i]; }
+    if (i < n) { t[0] += v[i]; t[1] += f[i]; }
   }
-  sv[threadIdx.x] = a; sf[threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { sv[threadIdx.x] += sv[threadIdx.x + o]; sf[threadIdx.x] += sf[threadIdx.x + o]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { partials[2 * blockIdx.x] = sv[0]; partials[2 * blockIdx.x + 1] = sf[0]; }
-}
-// exclusive scan of nb pairs in place by one workgroup; totals[0..1] = the sums, totals[2] = 1 when a sum
-// passed 2^31 - 1 (the host then refuses the volume)
-__global__ __launch_bounds__(1024) void surf_scan_partials_kernel(uint32_t* partials, int64_t nb, uint32_t* totals) {
-  __shared__ unsigned long long sums[2][1024];
-  const int64_t per = (nb + 1023) / 1024, b0 = threadIdx.x * per, b1 = b0 + per < nb ? b0 + per : nb;
-  unsigned long long s[2] = {0ull, 0ull};
-  for (int64_t b = b0; b < b1; ++b) { s[0] += partials[2 * b]; s[1] += partials[2 * b + 1]; }
-  sums[0][threadIdx.x] = s[0]; sums[1][threadIdx.x] = s[1];
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    unsigned long long t0 = 0, t1 = 0;
-    if ((int)threadIdx.x >= off) { t0 = sums[0][threadIdx.x - off]; t1 = sums[1][threadIdx.x - off]; }
-    __syncthreads();
-    sums[0][threadIdx.x] += t0; sums[1][threadIdx.x] += t1;
-    __syncthreads();
-  }
-  unsigned long long run0 = sums[0][threadIdx.x] - s[0], run1 = sums[1][threadIdx.x] - s[1];
-  for (int64_t b = b0; b < b1; ++b) {
-    const uint32_t c0 = partials[2 * b], c1 = partials[2 * b + 1];
-    partials[2 * b] = (uint32_t)run0; partials[2 * b + 1] = (uint32_t)run1;
-    run0 += c0; run1 += c1;
-  }
-  if (threadIdx.x == 1023) {
-    const bool over = sums[0][1023] > 0x7fffffffull || sums[1][1023] > 0x7fffffffull;
-    totals[0] = over ? 0u : (uint32_t)sums[0][1023];
-    totals[1] = over ? 0u : (uint32_t)sums[1][1023];
-    totals[2] = over ? 1u : 0u;
-  }
+  lv_block_scan<256>(t, s);
+  if (threadIdx.x == 255) { partials[2 * blockIdx.x] = s[255][0]; partials[2 * blockIdx.x + 1] = s[255][1]; }
 }
 __global__ __launch_bounds__(256) void surf_scan_apply_kernel(uint32_t* v, uint32_t* f, int64_t n,
                                                               const uint32_t* __restrict__ partials,
                                                               const uint32_t* __restrict__ totals) {
-  __shared__ uint32_t sv[256], sf[256];
-  uint32_t cv[4], cf[4], a = 0, b = 0;
+  __shared__ u32x2 s[256];
+  uint32_t cv[4], cf[4];
+  u32x2 t{};
   for (int u = 0; u < 4; ++u) {
     const int64_t i = (int64_t)blockIdx.x * kSurfScan + threadIdx.x * 4 + u;
     cv[u] = i < n ? v[i] : 0u; cf[u] = i < n ? f[i] : 0u;
-    a += cv[u]; b += cf[u];
+    t[0] += cv[u]; t[1] += cf[u];
   }
-  sv[threadIdx.x] = a; sf[threadIdx.x] = b;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {
-    uint32_t t0 = 0, t1 = 0;
-    if ((int)threadIdx.x >= off) { t0 = sv[threadIdx.x - off]; t1 = sf[threadIdx.x - off]; }
-    __syncthreads();
-    sv[threadIdx.x] += t0; sf[threadIdx.x] += t1;
-    __syncthreads();
-  }
-  uint32_t rv = partials[2 * blockIdx.x] + sv[threadIdx.x] - a, rf = partials[2 * blockIdx.x + 1] + sf[threadIdx.x] - b;
+  const u32x2 before = lv_block_scan<256>(t, s);
+  uint32_t rv = partials[2 * blockIdx.x] + before[0], rf = partials[2 * blockIdx.x + 1] + before[1];
   for (int u = 0; u < 4; ++u) {
     const int64_t i = (int64_t)blockIdx.x * kSurfScan + threadIdx.x * 4 + u;
     if (i < n) { v[i] = rv; f[i] = rf; }
@@ -244,11 +204,6 @@ __global__ void surf_starts_kernel(SurfParams p, const uint32_t* __restrict__ to
   starts[2 * l] = (int32_t)p.vpre[ch];
   starts[2 * l + 1] = (int32_t)p.fpre[ch];
   if (l == p.n_sel) { starts[2 * l + 2] = (int32_t)totals[2]; starts[2 * l + 3] = 0; }
-}
-
-struct SurfTableChunk { int first, n; SurfLabel e[kSurfTableChunk]; };
-__global__ void surf_table_kernel(SurfLabel* table, SurfTableChunk c) {
-  if ((int)threadIdx.x < c.n) table[c.first + threadIdx.x] = c.e[threadIdx.x];
 }
 
 // ---- emit
@@ -503,24 +458,13 @@ __global__ void surf_boxes_fin_kernel(int32_t* boxes, int n_sel) {
   }
 }
 
-static inline bool surf_dims_ok(int d, int h, int w) {
-  return d > 0 && h > 0 && w > 0 && ((int64_t)d + 1) * ((int64_t)h + 1) * ((int64_t)w + 1) < (1ll << 31);
-}
-
 }  // namespace segmi
 
 using namespace segmi;
 
-#define SURF_BY_LABEL(lb, F)                     \
-  do {                                           \
-    if ((lb) == 1) F(uint8_t);                   \
-    else if ((lb) == 2) F(int16_t);              \
-    else F(int32_t);                             \
-  } while (0)
-
 #define SURF_COMMON_ARGS(what)                                                                                   \
-  SEGMI_CHECK_ARG(label_bytes == 1 || label_bytes == 2 || label_bytes == 4, what ": label_bytes must be 1, 2 or 4"); \
-  SEGMI_CHECK_ARG(surf_dims_ok(d, h, w), what ": extents must be positive with (d+1)(h+1)(w+1) < 2^31");           \
+  LV_CHECK_LABEL_BYTES(what, label_bytes);                                                                       \
+  LV_CHECK_CELLS(what, d, h, w);                                                                                 \
   SEGMI_CHECK_ARG(n_sel >= 1 && n_sel <= kSurfMaxLabels, what ": 1 .. %d selected labels", kSurfMaxLabels)
 
 extern "C" {
@@ -532,9 +476,9 @@ int segmi_surface_boxes(const void* labels, int label_bytes, int d, int h, int w
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(surf_boxes_init_kernel, cdiv(n_sel, 256), 256, 0, st, boxes, n_sel);
   const int64_t rows = (int64_t)d * h;
-  const int grid = (int)(cdiv64(rows, 4) > 4096 ? 4096 : cdiv64(rows, 4));
+  const int grid = lv_grid(rows, 4, 4096);
 #define BOXES(T) hipLaunchKernelGGL(surf_boxes_kernel<T>, grid, 256, 0, st, (const T*)labels, d, h, w, selected, n_sel, boxes)
-  SURF_BY_LABEL(label_bytes, BOXES);
+  LV_BY_LABEL(label_bytes, BOXES);
 #undef BOXES
   hipLaunchKernelGGL(surf_boxes_fin_kernel, cdiv(n_sel, 256), 256, 0, st, boxes, n_sel);
   SEGMI_LAUNCH_CHECK("surface_boxes");
@@ -543,7 +487,7 @@ int segmi_surface_boxes(const void* labels, int label_bytes, int d, int h, int w
 
 int64_t segmi_surface_workspace_bytes(int d, int h, int w, const int32_t* selected_host, const int32_t* boxes_host,
                                       int n_sel) {
-  if (!surf_dims_ok(d, h, w) || !selected_host || !boxes_host || n_sel < 1 || n_sel > kSurfMaxLabels) return 0;
+  if (!lv_cells_ok(d, h, w) || !selected_host || !boxes_host || n_sel < 1 || n_sel > kSurfMaxLabels) return 0;
   SurfLayout y;
   if (surf_layout(selected_host, boxes_host, n_sel, d, h, w, nullptr, &y)) return 0;
   return (int64_t)y.total;
@@ -577,24 +521,18 @@ int segmi_surface_count(const void* labels, int label_bytes, int d, int h, int w
   if (rc != SEGMI_OK) { delete[] table; return rc; }
   hipStream_t st = (hipStream_t)stream;
   char* w8 = (char*)ws;
-  for (int i = 0; i < n_sel; i += kSurfTableChunk) {
-    SurfTableChunk c{};
-    c.first = i;
-    c.n = n_sel - i < kSurfTableChunk ? n_sel - i : kSurfTableChunk;
-    for (int j = 0; j < c.n; ++j) c.e[j] = table[i + j];
-    hipLaunchKernelGGL(surf_table_kernel, 1, kSurfTableChunk, 0, st, (SurfLabel*)(w8 + y.table), c);
-  }
+  lv_upload_table<kSurfTableChunk>((const SurfLabel*)table, n_sel, LvStore<SurfLabel>{(SurfLabel*)(w8 + y.table)}, st);
   delete[] table;
   uint32_t* partials = (uint32_t*)(w8 + y.partials);
   const int64_t nb = cdiv64(y.chunks, kSurfScan);
   uint32_t* totals = partials + 2 * nb;
   if (y.chunks > 0) {
 #define COUNT(T) hipLaunchKernelGGL(surf_count_kernel<T>, (unsigned)cdiv64(y.chunks, 4), 256, 0, st, p)
-    SURF_BY_LABEL(label_bytes, COUNT);
+    LV_BY_LABEL(label_bytes, COUNT);
 #undef COUNT
     hipLaunchKernelGGL(surf_sum_kernel, (unsigned)nb, 256, 0, st, (const uint32_t*)p.vpre, (const uint32_t*)p.fpre, y.chunks, partials);
   }
-  hipLaunchKernelGGL(surf_scan_partials_kernel, 1, 1024, 0, st, partials, nb, totals);
+  hipLaunchKernelGGL(lv_scan_partials_kernel<2>, 1, 1024, 0, st, partials, nb, (uint32_t*)nullptr, totals + 2);
   // with no chunk at all the apply kernel still writes the (zero) totals behind the empty arrays
   hipLaunchKernelGGL(surf_scan_apply_kernel, (unsigned)(nb > 0 ? nb : 1), 256, 0, st, p.vpre, p.fpre, y.chunks,
                      (const uint32_t*)partials, (const uint32_t*)totals);
@@ -619,7 +557,7 @@ int segmi_surface_emit(const void* labels, int label_bytes, int d, int h, int w,
   p.offs = offsets; p.cells = cells; p.nbr = neighbours; p.faces = faces; p.nv = n_vertices; p.nf = n_faces;
   hipStream_t st = (hipStream_t)stream;
 #define EMIT(T) hipLaunchKernelGGL(surf_emit_kernel<T>, (unsigned)cdiv64(y.chunks, 4), 256, 0, st, p)
-  SURF_BY_LABEL(label_bytes, EMIT);
+  LV_BY_LABEL(label_bytes, EMIT);
 #undef EMIT
   SEGMI_LAUNCH_CHECK("surface_emit");
   return SEGMI_OK;
@@ -654,7 +592,7 @@ int segmi_surface_measure(const float* vertices, const int32_t* faces, const int
                           double* measures, void* ws, size_t ws_bytes, void* stream) {
   SEGMI_CHECK_ARG(starts && measures && ws, "surface_measure: null pointer");
   SEGMI_CHECK_ARG(n_sel >= 1 && n_sel <= kSurfMaxLabels, "surface_measure: 1 .. %d selected labels", kSurfMaxLabels);
-  const size_t need = surf_align((size_t)n_sel * kSurfMeasureWgs * 2 * sizeof(double));
+  const size_t need = lv_align256((size_t)n_sel * kSurfMeasureWgs * 2 * sizeof(double));
   SEGMI_CHECK_ARG(ws_bytes >= need, "surface_measure: workspace of %zu bytes, %zu needed", ws_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   const unsigned ticket = g_fin_next.fetch_add(1) % kFinTickets;

@@ -108,14 +108,13 @@ from typing import Dict, Optional, Sequence, Union
 import numpy as np
 import torch
 
+# the module, not its names: image/__init__.py imports this file, possibly while _arrays is still importing Image
+from .. import _arrays
 from .processing import Image
-
-ArrayLike = Union[Image, np.ndarray, torch.Tensor]
 
 MAX_LABEL = 65535
 MAX_CELLS = 2 ** 31
-_NEEDS_GPU = "segmantic_amd.image.surfaces needs an MI355X; no GPU is visible and there is no CPU path"
-_IN_PLACE = (torch.uint8, torch.int16, torch.int32)
+_NEEDS_GPU = "segmantic_amd.image.surfaces needs an MI355X"
 
 
 @dataclass
@@ -146,16 +145,13 @@ def surface_file_name(label: int, tissues: Optional[Dict[int, str]] = None) -> s
 
 
 # ------------------------------------------------------------------ validation
-def _check_volume(labels: ArrayLike):
+def _check_volume(labels: _arrays.ArrayLike):
     """checks that need neither a copy nor the device -> the raw array"""
-    a = labels.data if isinstance(labels, Image) else labels
-    if not isinstance(a, (np.ndarray, torch.Tensor)):
-        raise TypeError(f"expected an Image, a numpy array or a torch tensor, not {type(labels).__name__}")
+    a = _arrays._raw(labels)
     shape = tuple(int(s) for s in a.shape)
     if len(shape) != 3:
         raise ValueError(f"label surfaces need a 3-D [z, y, x] label volume, got shape {shape}")
-    integer = not (a.is_floating_point() or a.is_complex()) if isinstance(a, torch.Tensor) else a.dtype.kind in "biu"
-    if not integer:
+    if not _arrays._is_integer(a):
         raise ValueError(f"label volumes must hold integers, got {a.dtype}")
     if min(shape) == 0:
         raise ValueError(f"empty label volume of shape {shape}")
@@ -168,7 +164,7 @@ def _value_range(a):
     """(min, max) of the volume where it lives: the one range check"""
     if isinstance(a, np.ndarray):
         return int(a.min()), int(a.max())
-    if a.dtype not in _IN_PLACE and a.dtype != torch.int64:
+    if a.dtype not in _arrays._IN_PLACE and a.dtype != torch.int64:
         a = a.to(torch.int64)          # bool, int8 and the unsigned wide types, which aminmax does not take
     lo, hi = torch.stack(torch.aminmax(a)).tolist()
     return int(lo), int(hi)
@@ -187,7 +183,7 @@ def _check_selected(selected) -> Optional[list]:
     return out
 
 
-def _geometry(labels: ArrayLike, spacing, origin, direction):
+def _geometry(labels: _arrays.ArrayLike, spacing, origin, direction):
     if isinstance(labels, Image):
         spacing = labels.spacing if spacing is None else spacing
         origin = labels.origin if origin is None else origin
@@ -212,7 +208,7 @@ def _check_decimate(reduction, max_rounds) -> float:
     return r
 
 
-def extract_surfaces(labels: ArrayLike, selected: Optional[Sequence[int]] = None, spacing=None, origin=None,
+def extract_surfaces(labels: _arrays.ArrayLike, selected: Optional[Sequence[int]] = None, spacing=None, origin=None,
                      direction=None, smooth_iterations: int = 0, relaxation: float = 0.5, decimate: float = 0.0,
                      decimate_max_rounds: int = 128) -> Dict[int, Surface]:
     """One discrete-surface-nets mesh per label (see the module docstring).  ``selected`` defaults to every label
@@ -230,24 +226,14 @@ def extract_surfaces(labels: ArrayLike, selected: Optional[Sequence[int]] = None
     lo, hi = _value_range(a)
     if lo < 0 or hi > MAX_LABEL:
         raise ValueError(f"label values must lie in 0 .. {MAX_LABEL}, the volume holds {lo} .. {hi}")
-    if not torch.cuda.is_available():
-        raise RuntimeError(_NEEDS_GPU)
+    dev = _arrays._require_gpu(_NEEDS_GPU, near=a)
     from .. import ops
 
-    dev = a.device if isinstance(a, torch.Tensor) and a.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
-    if t.dtype == torch.bool:
-        t = t.to(torch.uint8)
-    t = t.to(dev)
-    if t.dtype not in _IN_PLACE:
-        t = t.to(torch.int32)
-    t = t.contiguous()
-    on_host = isinstance(a, np.ndarray)
-    back = (lambda x: x.cpu().numpy()) if on_host else (lambda x: x.to(a.device))
+    t = _arrays._to_device(a, dev)
 
     def empty() -> Surface:
-        return Surface(back(torch.empty((0, 3), dtype=torch.float32, device=dev)),
-                       back(torch.empty((0, 3), dtype=torch.int32, device=dev)), 0.0, 0.0)
+        return Surface(_arrays._wrap(a, torch.empty((0, 3), dtype=torch.float32, device=dev)),
+                       _arrays._wrap(a, torch.empty((0, 3), dtype=torch.int32, device=dev)), 0.0, 0.0)
 
     todo = list(range(1, hi + 1)) if sel is None else sel
     if not todo:
@@ -272,7 +258,7 @@ def extract_surfaces(labels: ArrayLike, selected: Optional[Sequence[int]] = None
         verts, faces, _, starts_dev, starts = ops.decimate_meshes(verts, faces, starts_dev, starts, reduction,
                                                                   int(decimate_max_rounds))
     measures = ops.surface_measure(verts, faces, starts_dev).cpu().numpy()
-    verts, faces = back(verts), back(faces)
+    verts, faces = _arrays._wrap(a, verts), _arrays._wrap(a, faces)
     out: Dict[int, Surface] = {}
     for l, c in enumerate(todo):
         v0, f0, v1, f1 = (int(x) for x in (starts[l, 0], starts[l, 1], starts[l + 1, 0], starts[l + 1, 1]))
@@ -306,23 +292,15 @@ def decimate_surface(surface: Surface, reduction: float, max_rounds: int = 128) 
         raise ValueError(f"decimation takes meshes of fewer than 2^23 vertices, got {nv}")
     if r == 0.0 or nf == 0:
         return surface
-    if not torch.cuda.is_available():
-        raise RuntimeError(_NEEDS_GPU)
+    dev = _arrays._require_gpu(_NEEDS_GPU, near=v if isinstance(v, torch.Tensor) else f)
     from .. import ops
 
-    src = v if isinstance(v, torch.Tensor) else f
-    dev = src.device if isinstance(src, torch.Tensor) and src.is_cuda else \
-        torch.device("cuda", torch.cuda.current_device())
-    as_tensor = lambda x: torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x  # noqa: E731
-    vt = as_tensor(v).to(dev, torch.float32).contiguous()
-    ft = as_tensor(f).to(dev, torch.int32).contiguous()
+    vt = _arrays._tensor(v).to(dev, torch.float32).contiguous()
+    ft = _arrays._tensor(f).to(dev, torch.int32).contiguous()
     starts = np.asarray([[0, 0], [nv, nf], [0, 0]], np.int32)
     ov, of, _, out_starts, _ = ops.decimate_meshes(vt, ft, torch.from_numpy(starts).to(dev), starts, r, int(max_rounds))
     m = ops.surface_measure(ov, of, out_starts).cpu().numpy()
-
-    def back(x, like):
-        return x.cpu().numpy() if isinstance(like, np.ndarray) else x.to(like.device)
-    return Surface(back(ov, v), back(of, f), float(m[0, 0]), float(m[0, 1]))
+    return Surface(_arrays._wrap(v, ov), _arrays._wrap(f, of), float(m[0, 0]), float(m[0, 1]))
 
 
 # ------------------------------------------------------------------ PLY

@@ -855,24 +855,65 @@ def label_bytes(t: torch.Tensor) -> int:
         raise ValueError(f"label volumes are uint8, int16 or int32 (label_bytes 1, 2, 4), not {t.dtype}")
 
 
-def _labels3(t: torch.Tensor):
-    """(d, h, w) of a contiguous 2-D [h, w] or 3-D [d, h, w] label volume on the device"""
+def _label_dims(t: torch.Tensor, ranks=(2, 3), limit: Optional[str] = None):
+    """(d, h, w) of a contiguous label volume on the device whose rank is one of ``ranks`` ([h, w]: d = 1).
+    ``limit`` "voxels" / "cells" also asks for a label dtype and 1 .. 2^31 - 1 voxels / cells (d+1)(h+1)(w+1)."""
     _require_device(t)
-    if t.dim() not in (2, 3) or not t.is_contiguous():
-        raise ValueError("label volumes are contiguous [h, w] or [d, h, w] tensors")
-    return (1,) + tuple(t.shape) if t.dim() == 2 else tuple(t.shape)
+    if t.dim() not in ranks or not t.is_contiguous():
+        raise ValueError(f"label volumes are contiguous {' or '.join(f'{r}-D' for r in ranks)} tensors, "
+                         f"got shape {tuple(t.shape)}")
+    d, h, w = (1,) * (3 - t.dim()) + tuple(int(v) for v in t.shape)
+    if limit is not None:
+        label_bytes(t)
+        count = (d + 1) * (h + 1) * (w + 1) if limit == "cells" else d * h * w
+        if t.numel() == 0 or count >= CC_MAX_VOXELS:
+            raise ValueError(f"label volumes hold 1 .. 2^31 - 1 {limit}, got shape {tuple(t.shape)}")
+    return d, h, w
 
 
-def _host_i32(v):
-    a = np.ascontiguousarray(np.asarray(v, dtype=np.int32))
-    return a, a.ctypes.data_as(C.c_void_p)
+def _like_labels(labels: torch.Tensor, t, what: str = "out", distinct: bool = False) -> torch.Tensor:
+    """``t`` (None: a fresh tensor) checked to match ``labels`` in dtype and shape; ``distinct``: not labels itself"""
+    if t is None:
+        t = torch.empty_like(labels)
+    if t.dtype != labels.dtype or t.shape != labels.shape or not t.is_contiguous() or \
+            (distinct and t.data_ptr() == labels.data_ptr()):
+        raise ValueError(f"{what} must match labels in dtype and shape" + (" and be another tensor" if distinct else ""))
+    return t
+
+
+def _i32_of(t: torch.Tensor, shape, what: str) -> None:
+    _require_device(t)
+    if t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous int32 tensor of shape {tuple(shape)}")
+
+
+def _host(v, dtype, shape=None):
+    """contiguous host array of ``dtype`` (reshaped to ``shape`` when given) and its ctypes pointer, None when empty"""
+    a = np.ascontiguousarray(np.asarray(v, dtype=dtype))
+    if shape is not None:
+        a = np.ascontiguousarray(a.reshape(shape))
+    return a, (a.ctypes.data_as(C.c_void_p) if a.size else None)
+
+
+def _align256(nbytes: int) -> int:
+    return (int(nbytes) + 255) // 256 * 256
+
+
+def _workspace(workspace, need: int, device) -> torch.Tensor:
+    """``workspace`` checked, or a fresh one of ``need`` bytes"""
+    if workspace is None:
+        return torch.empty(int(need), dtype=torch.uint8, device=device)
+    _require_device(workspace)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("the workspace is a contiguous uint8 tensor")
+    return workspace
 
 
 def label_boxes(pred, truth, k, boxes, counts) -> None:
     """boxes i32 [k, 6] (half-open z0 z1 y0 y1 x0 x1 of pred==c | truth==c), counts i64 [k, 2]."""
     if pred.shape != truth.shape or pred.dtype != truth.dtype:
         raise ValueError("label_boxes: pred and truth differ in shape or dtype")
-    d, h, w = _labels3(pred)
+    d, h, w = _label_dims(pred)
     check(lib.segmi_label_boxes(_ptr(pred), _ptr(truth), label_bytes(pred), d, h, w, int(k), _ptr(boxes),
                                 _ptr(counts), _stream()), "label_boxes")
 
@@ -885,19 +926,19 @@ def edt_workspace_bytes(box) -> int:
 def edt_sq(labels, label, feature, box, spacing_zyx, dist_sq, workspace) -> None:
     """Squared distance to label's foreground (feature 0) or signed, to its contour (feature 1), over box;
     dist_sq f32 [bd, bw, bh]."""
-    d, h, w = _labels3(labels)
-    b, bp = _host_i32(box)
-    sp = np.ascontiguousarray(np.asarray(spacing_zyx, dtype=np.float32).reshape(3))
+    d, h, w = _label_dims(labels)
+    b, bp = _host(box, np.int32)
+    sp, spp = _host(spacing_zyx, np.float32, 3)
     check(lib.segmi_edt_sq(_ptr(labels), label_bytes(labels), d, h, w, labels.dim(), int(label), int(feature), bp,
-                           sp.ctypes.data_as(C.c_void_p), _ptr(dist_sq), _ptr(workspace), workspace.numel(),
+                           spp, _ptr(dist_sq), _ptr(workspace), workspace.numel(),
                            _stream()), "edt_sq")
 
 
 def edt_sample(dist_sq, labels, label, query, box, stats, workspace, values=None, n_values=None) -> None:
     """stats f64[4] = count, sum, sum of squares, max of the distances at labels' query voxels;
     squared distances appended to values[n_values ...] when given."""
-    d, h, w = _labels3(labels)
-    b, bp = _host_i32(box)
+    d, h, w = _label_dims(labels)
+    b, bp = _host(box, np.int32)
     check(lib.segmi_edt_sample(_ptr(dist_sq), _ptr(labels), label_bytes(labels), d, h, w, labels.dim(), int(label),
                                int(query), bp, _ptr(stats), _ptr(values), _ptr(n_values), _ptr(workspace),
                                workspace.numel(), _stream()), "edt_sample")
@@ -929,15 +970,6 @@ CC_CLASS_TABLE = 65536        # label values of the clean-up transforms lie in 0
 _MAP_BYTES = {torch.uint8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
 
 
-def _cc_dims(labels: torch.Tensor):
-    """(d, h, w, ndim) of a label volume of the connected-component kernels"""
-    d, h, w = _labels3(labels)
-    label_bytes(labels)
-    if labels.numel() == 0 or labels.numel() >= CC_MAX_VOXELS:
-        raise ValueError(f"label volumes hold 1 .. 2^31 - 1 voxels, got shape {tuple(labels.shape)}")
-    return d, h, w, labels.dim()
-
-
 def _cc_connectivity(connectivity, ndim: int) -> int:
     c = ndim if connectivity is None else int(connectivity)
     if not 1 <= c <= ndim:
@@ -945,29 +977,18 @@ def _cc_connectivity(connectivity, ndim: int) -> int:
     return c
 
 
-def _cc_i32(t: torch.Tensor, like: torch.Tensor, what: str) -> None:
-    _require_device(t)
-    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != like.numel():
-        raise ValueError(f"{what} must be a contiguous int32 tensor with one entry per voxel")
-
-
-def _cc_applied(applied):
+def _applied(applied):
     """host int32 array of the applied labels (empty = all) and its ctypes pointer"""
-    a = np.ascontiguousarray(np.asarray([] if applied is None else list(applied), dtype=np.int32).reshape(-1))
-    return a, (a.ctypes.data_as(C.c_void_p) if a.size else None)
+    return _host([] if applied is None else list(applied), np.int32, -1)
 
 
-def _cc_workspace(labels: torch.Tensor, workspace, per_root_words: bool = False):
-    if workspace is None:
-        need = cc_workspace_bytes(labels.shape)
-        if not per_root_words:
-            # only cc_fill_holes uses the two int32 words per voxel that end the workspace
-            need -= 2 * ((4 * labels.numel() + 255) // 256 * 256)
-        return torch.empty(need, dtype=torch.uint8, device=labels.device)
-    _require_device(workspace)
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise ValueError("the workspace is a contiguous uint8 tensor")
-    return workspace
+CC_FILL_WORDS = 2             # the int32 words per voxel (lo, hi) that end cc_layout in components.hip, each
+                              # region rounded up to 256 bytes; only cc_fill_holes uses them
+
+
+def _cc_workspace(t: torch.Tensor, workspace, fill_holes: bool = False) -> torch.Tensor:
+    need = cc_workspace_bytes(t.shape) - (0 if fill_holes else CC_FILL_WORDS * _align256(4 * t.numel()))
+    return _workspace(workspace, need, t.device)
 
 
 def cc_workspace_bytes(shape) -> int:
@@ -982,11 +1003,12 @@ def cc_workspace_bytes(shape) -> int:
 def cc_label(labels, connectivity=None, with_background=False, root=None, workspace=None) -> torch.Tensor:
     """root int32 (shape of labels): linear index of the first voxel of each voxel's component, -1 for voxels
     outside every component (the zeros, unless ``with_background``)."""
-    d, h, w, ndim = _cc_dims(labels)
+    d, h, w = _label_dims(labels, limit="voxels")
+    ndim = labels.dim()
     c = _cc_connectivity(connectivity, ndim)
     if root is None:
         root = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
-    _cc_i32(root, labels, "root")
+    _i32_of(root, labels.shape, "root")
     ws = _cc_workspace(labels, workspace)
     check(lib.segmi_cc_label(_ptr(labels), label_bytes(labels), d, h, w, ndim, c, int(bool(with_background)),
                              _ptr(root), _ptr(ws), ws.numel(), _stream()), "cc_label")
@@ -995,24 +1017,24 @@ def cc_label(labels, connectivity=None, with_background=False, root=None, worksp
 
 def cc_sizes(root, size=None) -> torch.Tensor:
     """size int32 (shape of root): the voxel count of each component at its root, 0 elsewhere."""
-    _cc_i32(root, root, "root")
+    _i32_of(root, root.shape, "root")
     if root.numel() == 0 or root.numel() >= CC_MAX_VOXELS:
         raise ValueError("root holds 1 .. 2^31 - 1 voxels")
     if size is None:
         size = torch.empty_like(root)
-    _cc_i32(size, root, "size")
+    _i32_of(size, root.shape, "size")
     check(lib.segmi_cc_sizes(_ptr(root), root.numel(), _ptr(size), _stream()), "cc_sizes")
     return size
 
 
 def cc_compact(root, comp=None, n_comp=None, workspace=None):
     """(comp int32: canonical component number 1 .. n of every voxel, 0 outside; n_comp int32 [1] on the device)."""
-    _cc_i32(root, root, "root")
+    _i32_of(root, root.shape, "root")
     if root.dim() not in (2, 3):
         raise ValueError("root has the shape of its 2-D or 3-D label volume")
     if comp is None:
         comp = torch.empty_like(root)
-    _cc_i32(comp, root, "comp")
+    _i32_of(comp, root.shape, "comp")
     if n_comp is None:
         n_comp = torch.empty(1, dtype=torch.int32, device=root.device)
     if n_comp.dtype != torch.int32 or n_comp.numel() != 1:
@@ -1027,16 +1049,13 @@ def cc_keep_largest(labels, root, size, applied=None, independent=True, num_comp
                     workspace=None) -> torch.Tensor:
     """Keep the ``num_components`` largest components per applied class (ties: the earlier first voxel); with
     ``independent=False`` root / size describe the union mask of the applied classes."""
-    _cc_dims(labels)
-    _cc_i32(root, labels, "root")
-    _cc_i32(size, labels, "size")
+    _label_dims(labels, limit="voxels")
+    _i32_of(root, labels.shape, "root")
+    _i32_of(size, labels.shape, "size")
     if not 1 <= int(num_components) <= CC_MAX_KEEP:
         raise ValueError(f"num_components must be 1 .. {CC_MAX_KEEP}, got {num_components}")
-    if out is None:
-        out = torch.empty_like(labels)
-    if out.dtype != labels.dtype or out.shape != labels.shape or not out.is_contiguous():
-        raise ValueError("out must match labels in dtype and shape")
-    a, ap = _cc_applied(applied)
+    out = _like_labels(labels, out)
+    a, ap = _applied(applied)
     ws = _cc_workspace(labels, workspace)
     check(lib.segmi_cc_keep_largest(_ptr(labels), label_bytes(labels), labels.numel(), _ptr(root), _ptr(size), ap,
                                     a.size, int(bool(independent)), int(num_components), _ptr(out), _ptr(ws),
@@ -1046,15 +1065,12 @@ def cc_keep_largest(labels, root, size, applied=None, independent=True, num_comp
 
 def cc_remove_small(labels, root, size, min_size, out=None) -> torch.Tensor:
     """Voxels of components smaller than ``min_size`` become 0."""
-    _cc_dims(labels)
-    _cc_i32(root, labels, "root")
-    _cc_i32(size, labels, "size")
+    _label_dims(labels, limit="voxels")
+    _i32_of(root, labels.shape, "root")
+    _i32_of(size, labels.shape, "size")
     if int(min_size) < 0:
         raise ValueError(f"min_size must be >= 0, got {min_size}")
-    if out is None:
-        out = torch.empty_like(labels)
-    if out.dtype != labels.dtype or out.shape != labels.shape or not out.is_contiguous():
-        raise ValueError("out must match labels in dtype and shape")
+    out = _like_labels(labels, out)
     check(lib.segmi_cc_remove_small(_ptr(labels), label_bytes(labels), labels.numel(), _ptr(root), _ptr(size),
                                     int(min(int(min_size), 2 ** 31 - 1)), _ptr(out), _stream()), "cc_remove_small")
     return out
@@ -1063,15 +1079,13 @@ def cc_remove_small(labels, root, size, min_size, out=None) -> torch.Tensor:
 def cc_fill_holes(labels, root, applied=None, connectivity=None, out=None, workspace=None) -> torch.Tensor:
     """Fill the enclosed 0-regions bordered by one single label; ``root`` = cc_label(labels, connectivity,
     with_background=True)."""
-    d, h, w, ndim = _cc_dims(labels)
+    d, h, w = _label_dims(labels, limit="voxels")
+    ndim = labels.dim()
     c = _cc_connectivity(connectivity, ndim)
-    _cc_i32(root, labels, "root")
-    if out is None:
-        out = torch.empty_like(labels)
-    if out.dtype != labels.dtype or out.shape != labels.shape or not out.is_contiguous():
-        raise ValueError("out must match labels in dtype and shape")
-    a, ap = _cc_applied(applied)
-    ws = _cc_workspace(labels, workspace, per_root_words=True)
+    _i32_of(root, labels.shape, "root")
+    out = _like_labels(labels, out)
+    a, ap = _applied(applied)
+    ws = _cc_workspace(labels, workspace, fill_holes=True)
     check(lib.segmi_cc_fill_holes(_ptr(labels), label_bytes(labels), d, h, w, ndim, c, _ptr(root), ap, a.size,
                                   _ptr(out), _ptr(ws), ws.numel(), _stream()), "cc_fill_holes")
     return out
@@ -1105,11 +1119,6 @@ FT_NONZERO, FT_ZERO, FT_EQUAL, FT_NOT_EQUAL, FT_TABLE = 0, 1, 2, 3, 4
 FT_TABLE_SIZE = 65536         # entries of the feature table of mode FT_TABLE (device uint8)
 
 
-def _host_f64x3(spacing_zyx):
-    a = np.ascontiguousarray(np.asarray(spacing_zyx, dtype=np.float64).reshape(3))
-    return a, a.ctypes.data_as(C.c_void_p)
-
-
 def _box_shape(labels: torch.Tensor, box):
     if box is None:
         return tuple(labels.shape)
@@ -1128,12 +1137,12 @@ def feature_transform(labels, mode, spacing_zyx, label=0, table=None, box=None, 
     """-> (index int32, dist float32 or None) over ``box`` (host z0 z1 y0 y1 x0 x1; None: the whole volume):
     the linear index in the full volume of the nearest feature voxel (-1: none), ties to the smallest index,
     and its squared distance (``dist_sqrt``: its distance)."""
-    d, h, w, ndim = _cc_dims(labels)
+    d, h, w = _label_dims(labels, limit="voxels")
+    ndim = labels.dim()
     shape = _box_shape(labels, box)
     if index is None:
         index = torch.empty(shape, dtype=torch.int32, device=labels.device)
-    if index.dtype != torch.int32 or tuple(index.shape) != tuple(shape) or not index.is_contiguous():
-        raise ValueError("index must be a contiguous int32 tensor of the box's shape")
+    _i32_of(index, shape, "index")
     if dist is None and with_dist:
         dist = torch.empty(shape, dtype=torch.float32, device=labels.device)
     if dist is not None and (dist.dtype != torch.float32 or tuple(dist.shape) != tuple(shape)
@@ -1142,11 +1151,9 @@ def feature_transform(labels, mode, spacing_zyx, label=0, table=None, box=None, 
     if int(mode) == FT_TABLE:
         if table is None or table.dtype != torch.uint8 or table.numel() != FT_TABLE_SIZE or not table.is_contiguous():
             raise ValueError(f"mode FT_TABLE needs a contiguous uint8 table of {FT_TABLE_SIZE} entries")
-    if workspace is None:
-        workspace = torch.empty(feature_transform_workspace_bytes(shape), dtype=torch.uint8, device=labels.device)
-    _require_device(workspace)
-    bp = None if box is None else _host_i32(box)
-    sp, spp = _host_f64x3(spacing_zyx)
+    workspace = _workspace(workspace, feature_transform_workspace_bytes(shape), labels.device)
+    bp = None if box is None else _host(box, np.int32)
+    sp, spp = _host(spacing_zyx, np.float64, 3)
     check(lib.segmi_feature_transform(_ptr(labels), label_bytes(labels), d, h, w, ndim, int(mode), int(label),
                                       _ptr(table), None if bp is None else bp[1], spp, _ptr(index), _ptr(dist),
                                       int(bool(dist_sqrt)), _ptr(workspace), workspace.numel(), _stream()),
@@ -1156,14 +1163,11 @@ def feature_transform(labels, mode, spacing_zyx, label=0, table=None, box=None, 
 
 def morph_gather(labels, index, spacing_zyx, radius, out=None) -> torch.Tensor:
     """Zero voxels whose nearest feature ``index`` lies within ``radius`` take that voxel's label."""
-    d, h, w, ndim = _cc_dims(labels)
-    _cc_i32(index, labels, "index")
-    if out is None:
-        out = torch.empty_like(labels)
-    if out.dtype != labels.dtype or out.shape != labels.shape or not out.is_contiguous() or \
-            out.data_ptr() == labels.data_ptr():
-        raise ValueError("out must match labels in dtype and shape and be another tensor")
-    sp, spp = _host_f64x3(spacing_zyx)
+    d, h, w = _label_dims(labels, limit="voxels")
+    ndim = labels.dim()
+    _i32_of(index, labels.shape, "index")
+    out = _like_labels(labels, out, distinct=True)
+    sp, spp = _host(spacing_zyx, np.float64, 3)
     check(lib.segmi_morph_gather(_ptr(labels), label_bytes(labels), d, h, w, ndim, _ptr(index), spp, float(radius),
                                  _ptr(out), _stream()), "morph_gather")
     return out
@@ -1172,17 +1176,15 @@ def morph_gather(labels, index, spacing_zyx, radius, out=None) -> torch.Tensor:
 def morph_erode_select(labels, label, box, index, spacing_zyx, radius, out, keep=None) -> torch.Tensor:
     """out[v] = 0 for the voxels of ``label`` in ``box`` whose nearest feature (``index``, box-shaped) lies
     within ``radius``; ``out`` starts as a copy of ``labels``.  Voxels with ``keep != 0`` are left alone."""
-    d, h, w, ndim = _cc_dims(labels)
+    d, h, w = _label_dims(labels, limit="voxels")
+    ndim = labels.dim()
     shape = _box_shape(labels, box)
-    _require_device(index)
-    if index.dtype != torch.int32 or tuple(index.shape) != tuple(shape) or not index.is_contiguous():
-        raise ValueError("index must be a contiguous int32 tensor of the box's shape")
-    if out.dtype != labels.dtype or out.shape != labels.shape or not out.is_contiguous():
-        raise ValueError("out must match labels in dtype and shape")
-    if keep is not None and (keep.dtype != labels.dtype or keep.shape != labels.shape or not keep.is_contiguous()):
-        raise ValueError("keep must match labels in dtype and shape")
-    bp = None if box is None else _host_i32(box)
-    sp, spp = _host_f64x3(spacing_zyx)
+    _i32_of(index, shape, "index")
+    _like_labels(labels, out)
+    if keep is not None:
+        _like_labels(labels, keep, "keep")
+    bp = None if box is None else _host(box, np.int32)
+    sp, spp = _host(spacing_zyx, np.float64, 3)
     check(lib.segmi_morph_erode_select(_ptr(labels), label_bytes(labels), d, h, w, ndim, int(label),
                                        None if bp is None else bp[1], _ptr(index), spp, float(radius), _ptr(keep),
                                        _ptr(out), _stream()), "morph_erode_select")
@@ -1191,10 +1193,8 @@ def morph_erode_select(labels, label, box, index, spacing_zyx, radius, out, keep
 
 def morph_index_planes(index: torch.Tensor) -> torch.Tensor:
     """-> int32 [ndim, ...]: the coordinates of the voxels ``index`` names, scipy's ``return_indices`` layout."""
-    _cc_i32(index, index, "index")
-    if index.dim() not in (2, 3) or index.numel() == 0 or index.numel() >= CC_MAX_VOXELS:
-        raise ValueError("index has the shape of its 2-D or 3-D volume")
-    d, h, w = _labels3(index)
+    _i32_of(index, index.shape, "index")
+    d, h, w = _label_dims(index, limit="voxels")
     planes = torch.empty((index.dim(),) + tuple(index.shape), dtype=torch.int32, device=index.device)
     check(lib.segmi_morph_index_planes(_ptr(index), d, h, w, index.dim(), _ptr(planes), _stream()),
           "morph_index_planes")
@@ -1206,30 +1206,18 @@ SURFACE_MAX_CELLS = 2 ** 31     # (d+1)(h+1)(w+1) stays below this
 SURFACE_MAX_LABEL = 65535
 
 
-def _surface_dims(labels: torch.Tensor):
-    _require_device(labels)
-    if labels.dim() != 3 or not labels.is_contiguous() or labels.numel() == 0:
-        raise ValueError("label surfaces are extracted from non-empty contiguous [d, h, w] tensors")
-    label_bytes(labels)
-    d, h, w = (int(s) for s in labels.shape)
-    if (d + 1) * (h + 1) * (w + 1) >= SURFACE_MAX_CELLS:
-        raise ValueError(f"(d+1)(h+1)(w+1) must stay below 2^31, got shape {(d, h, w)}")
-    return d, h, w
-
-
 def _surface_selected(selected):
     s = np.ascontiguousarray(np.asarray(list(selected), dtype=np.int64).reshape(-1))
     if s.size == 0 or s.size > SURFACE_MAX_LABEL or s.min() < 1 or s.max() > SURFACE_MAX_LABEL or \
             (np.diff(s) <= 0).any():
         raise ValueError(f"selected labels are 1 .. {SURFACE_MAX_LABEL} strictly ascending values in "
                          f"1 .. {SURFACE_MAX_LABEL}")
-    s = s.astype(np.int32)
-    return s, s.ctypes.data_as(C.c_void_p)
+    return _host(s, np.int32)
 
 
 def surface_boxes(labels: torch.Tensor, selected) -> torch.Tensor:
     """boxes int32 [n, 6] on the device: half-open z0 z1 y0 y1 x0 x1 of ``labels == selected[l]``."""
-    d, h, w = _surface_dims(labels)
+    d, h, w = _label_dims(labels, (3,), "cells")
     s, _ = _surface_selected(selected)
     sel = torch.from_numpy(s).to(labels.device)
     boxes = torch.empty((s.size, 6), dtype=torch.int32, device=labels.device)
@@ -1241,7 +1229,7 @@ def surface_boxes(labels: torch.Tensor, selected) -> torch.Tensor:
 def surface_workspace_bytes(shape, selected, boxes_host) -> int:
     d, h, w = (int(v) for v in shape)
     s, sp = _surface_selected(selected)
-    b, bp = _host_i32(boxes_host)
+    b, bp = _host(boxes_host, np.int32)
     if b.shape != (s.size, 6):
         raise ValueError("boxes_host is [n_selected, 6]")
     n = int(lib.segmi_surface_workspace_bytes(d, h, w, sp, bp, s.size))
@@ -1252,9 +1240,9 @@ def surface_workspace_bytes(shape, selected, boxes_host) -> int:
 
 def surface_count(labels: torch.Tensor, selected, boxes_host, workspace: torch.Tensor) -> torch.Tensor:
     """starts int32 [n + 2, 2] on the device: (first vertex, first face) per label, the totals, (overflow, 0)."""
-    d, h, w = _surface_dims(labels)
+    d, h, w = _label_dims(labels, (3,), "cells")
     s, sp = _surface_selected(selected)
-    b, bp = _host_i32(boxes_host)
+    b, bp = _host(boxes_host, np.int32)
     starts = torch.empty((s.size + 2, 2), dtype=torch.int32, device=labels.device)
     check(lib.segmi_surface_count(_ptr(labels), label_bytes(labels), d, h, w, sp, bp, s.size, _ptr(starts),
                                   _ptr(workspace), workspace.numel(), _stream()), "surface_count")
@@ -1264,9 +1252,9 @@ def surface_count(labels: torch.Tensor, selected, boxes_host, workspace: torch.T
 def surface_emit(labels: torch.Tensor, selected, boxes_host, workspace: torch.Tensor, n_vertices: int, n_faces: int,
                  with_neighbours: bool = False):
     """-> (offsets f32 [V, 3], cells i32 [V, 3], neighbours i32 [V, 6] or None, faces i32 [F, 3])."""
-    d, h, w = _surface_dims(labels)
+    d, h, w = _label_dims(labels, (3,), "cells")
     s, sp = _surface_selected(selected)
-    b, bp = _host_i32(boxes_host)
+    b, bp = _host(boxes_host, np.int32)
     dev = labels.device
     offs = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
     cells = torch.empty((n_vertices, 3), dtype=torch.int32, device=dev)
@@ -1299,7 +1287,7 @@ def surface_measure(vertices, faces, starts) -> torch.Tensor:
     _require_device(starts)
     n = starts.shape[0] - 2
     out = torch.empty((n, 2), dtype=torch.float64, device=starts.device)
-    ws = torch.empty((n * 32 * 2 * 8 + 255) // 256 * 256, dtype=torch.uint8, device=starts.device)
+    ws = _workspace(None, _align256(n * 32 * 2 * 8), starts.device)
     check(lib.segmi_surface_measure(_ptr(vertices), _ptr(faces), _ptr(starts), n, _ptr(out), _ptr(ws), ws.numel(),
                                     _stream()), "surface_measure")
     return out
@@ -1443,7 +1431,7 @@ def label_centroids(labels, k, sums=None, flag=None):
     place; flag i32 [1] set when a label lies outside [0, k].  Both on the device, no host synchronisation."""
     if labels.dim() != 3:
         raise ValueError("label_centroids: labels are a contiguous [d, h, w] volume")
-    d, h, w = _labels3(labels)
+    d, h, w = _label_dims(labels)
     if sums is None:
         sums = torch.empty(int(k) + 1, 4, dtype=torch.int64, device=labels.device)
     if flag is None:

@@ -35,63 +35,41 @@ neither bug is reproduced here.
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Sequence, Union
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
 
-from ..image.processing import Image
-
-ArrayLike = Union[Image, np.ndarray, torch.Tensor]
+from .._arrays import ArrayLike, Image, _is_integer, _raw, _require_gpu, _tensor, _to_device
 
 SURFACE_KEYS = ("mean", "median", "std", "max")
-_NEEDS_GPU = "segmantic_amd.seg.evaluation runs on an MI355X only; no GPU is visible and there is no CPU path"
+_NEEDS_GPU = "segmantic_amd.seg.evaluation runs on an MI355X only"
 
 
-def _require_gpu() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError(_NEEDS_GPU)
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _split(x: ArrayLike, spacing: Optional[Sequence[float]]):
-    """-> (torch tensor [z, y, x] / [y, x], spacing per array axis or None)"""
-    if isinstance(x, Image):
-        return x.data, tuple(reversed(x.spacing)) if spacing is None else spacing
-    if isinstance(x, np.ndarray):
-        return torch.from_numpy(np.ascontiguousarray(x)), spacing
-    if isinstance(x, torch.Tensor):
-        return x, spacing
-    raise TypeError(f"expected an Image, a numpy array or a torch tensor, not {type(x).__name__}")
+def _axis_spacing(x: ArrayLike, spacing: Optional[Sequence[float]]):
+    """spacing per array axis: the argument, else an Image's own (x, y, z) reversed, else None"""
+    return tuple(reversed(x.spacing)) if spacing is None and isinstance(x, Image) else spacing
 
 
 def _prepare_pair(y_pred: ArrayLike, y_ref: ArrayLike, spacing: Optional[Sequence[float]]):
     """Validate a volume pair (host only) -> (pred, ref, spacing_zyx (3 floats), spatial dims)."""
-    p, sp_p = _split(y_pred, spacing)
-    r, sp_r = _split(y_ref, spacing)
-    if p.dim() not in (2, 3):
-        raise ValueError(f"label volumes are 2-D or 3-D, got {p.dim()} dimensions")
+    p, sp_p = _raw(y_pred), _axis_spacing(y_pred, spacing)
+    r, sp_r = _raw(y_ref), _axis_spacing(y_ref, spacing)
+    ndim = len(p.shape)
+    if ndim not in (2, 3):
+        raise ValueError(f"label volumes are 2-D or 3-D, got {ndim} dimensions")
     if tuple(p.shape) != tuple(r.shape):
         raise ValueError(f"shape mismatch: prediction {tuple(p.shape)} vs reference {tuple(r.shape)}")
     sp = sp_p if sp_p is not None else sp_r
-    sp = [1.0] * p.dim() if sp is None else [float(s) for s in sp]
-    if len(sp) != p.dim():
-        raise ValueError(f"spacing has {len(sp)} entries for a {p.dim()}-D volume")
+    sp = [1.0] * ndim if sp is None else [float(s) for s in sp]
+    if len(sp) != ndim:
+        raise ValueError(f"spacing has {len(sp)} entries for a {ndim}-D volume")
     if not all(s > 0 and math.isfinite(s) for s in sp):
         raise ValueError(f"spacing must be positive and finite, got {sp}")
-    if p.is_floating_point() or r.is_floating_point() or p.is_complex():
+    if not (_is_integer(p) and _is_integer(r)):
         raise ValueError("label volumes must hold integers")
-    sp3 = ([1.0] + sp) if p.dim() == 2 else sp
-    return p, r, tuple(sp3), p.dim()
-
-
-def _to_device_labels(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
-    """label volume on the device in a type the kernels read in place (uint8 / int16 / int32)"""
-    if t.dtype == torch.bool:
-        t = t.to(torch.uint8)
-    elif t.dtype not in (torch.uint8, torch.int16, torch.int32):
-        t = t.to(torch.int32)
-    return t.to(dev).contiguous()
+    sp3 = ([1.0] + sp) if ndim == 2 else sp
+    return p, r, tuple(sp3), ndim
 
 
 def _lerp(a: float, b: float, t: float) -> float:
@@ -222,9 +200,9 @@ def _run(pred: torch.Tensor, ref: torch.Tensor, spacing_zyx, labels, k: int, per
 
 def _binary(y_pred: ArrayLike, y_ref: ArrayLike, spacing, kind: str) -> Dict[str, float]:
     p, r, sp, _ = _prepare_pair(y_pred, y_ref, spacing)
-    dev = _require_gpu()
-    p = (p.to(dev) != 0).to(torch.uint8).contiguous()
-    r = (r.to(dev) != 0).to(torch.uint8).contiguous()
+    dev = _require_gpu(_NEEDS_GPU)
+    p = (_tensor(p).to(dev) != 0).to(torch.uint8).contiguous()
+    r = (_tensor(r).to(dev) != 0).to(torch.uint8).contiguous()
     res, _, _ = _run(p, r, sp, [1], 2, None)
     one = res[1]
     if one["n_pred"] == 0 or one["n_ref"] == 0:
@@ -268,9 +246,9 @@ def surface_distances(pred_labels: ArrayLike, ref_labels: ArrayLike, num_classes
     p, r, sp, _ = _prepare_pair(pred_labels, ref_labels, spacing)
     if percentile is not None and not 0.0 <= float(percentile) <= 100.0:
         raise ValueError(f"percentile must lie in [0, 100], got {percentile}")
-    dev = _require_gpu()
-    p = _to_device_labels(p, dev)
-    r = _to_device_labels(r, dev)
+    dev = _require_gpu(_NEEDS_GPU)
+    p = _to_device(p, dev)
+    r = _to_device(r, dev)
     if p.dtype != r.dtype:
         p, r = p.to(torch.int32), r.to(torch.int32)
     if num_classes is None:
@@ -291,18 +269,17 @@ def surface_distances(pred_labels: ArrayLike, ref_labels: ArrayLike, num_classes
 def confusion_matrix(num_classes: int, y_pred: ArrayLike, y: ArrayLike) -> np.ndarray:
     """float64 ``[num_classes, num_classes]`` with ``cm[true, pred]`` (sklearn's convention; reference
     ``evaluation.py:96-125``).  Labels outside ``[0, num_classes)`` raise ``ValueError``."""
-    p, _ = _split(y_pred, None)
-    t, _ = _split(y, None)
+    p, t = _raw(y_pred), _raw(y)
     if tuple(p.shape) != tuple(t.shape):
         raise ValueError(f"shape mismatch: {tuple(p.shape)} vs {tuple(t.shape)}")
     k = int(num_classes)
     if k < 1:
         raise ValueError("num_classes must be positive")
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     from .. import ops
 
-    p = _to_device_labels(p.reshape(-1), dev)
-    t = _to_device_labels(t.reshape(-1), dev)
+    p = _to_device(p.reshape(-1), dev)
+    t = _to_device(t.reshape(-1), dev)
     if p.dtype != t.dtype:
         p, t = p.to(torch.int32), t.to(torch.int32)
     cm = torch.empty((k, k), dtype=torch.int64, device=dev)

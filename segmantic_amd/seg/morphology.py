@@ -37,31 +37,14 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from .transforms import (ArrayLike, _back, _channel_first, _check_applied, _check_labels, _Dict, _ops, _raw,
-                         _require_gpu, _restore, _to_device, _wrap)
+from .._arrays import ArrayLike, _back, _check_spacing, _raw, _require_gpu, _to_device, _wrap, _zyx
+from .transforms import _channel_first, _check_applied, _check_labels, _Dict, _ops, _restore
 
+_NEEDS_GPU = "segmantic_amd.seg.morphology needs an MI355X"
 BOX_MAX_LABELS = 1024          # label boxes come from one pass for labels below this; larger ones use the volume
 
 
 # ------------------------------------------------------------------ validation
-def _check_spacing(spacing, ndim: int) -> tuple:
-    if spacing is None:
-        return (1.0,) * ndim
-    if isinstance(spacing, (int, float, np.integer, np.floating)):
-        spacing = (spacing,) * ndim
-    sp = tuple(float(s) for s in spacing)
-    if len(sp) != ndim:
-        raise ValueError(f"spacing needs one entry per array axis ({ndim}), got {sp}")
-    if any(not (s > 0.0 and math.isfinite(s)) for s in sp):
-        raise ValueError(f"spacing must be positive and finite, got {sp}")
-    return sp
-
-
-def _zyx(sp: tuple) -> tuple:
-    """the three spacings the kernels take; a 2-D input repeats its y spacing for the absent axis"""
-    return sp if len(sp) == 3 else (sp[0],) + sp
-
-
 def _check_radius(radius, what: str = "radius") -> float:
     if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
         raise ValueError(f"{what} must be a number, got {radius!r}")
@@ -149,7 +132,7 @@ def distance_transform_edt(img: ArrayLike, sampling=None, return_distances: bool
     if len(shape) not in (2, 3) or 0 in shape or int(np.prod(shape, dtype=np.int64)) >= 2 ** 31:
         raise ValueError(f"distance_transform_edt: inputs are 2-D or 3-D with 1 .. 2^31 - 1 voxels, got shape {shape}")
     zyx = _zyx(_check_spacing(sampling, len(shape)))
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     ops = _ops()
     t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
     t = t.to(dev)
@@ -170,7 +153,7 @@ def nearest_label(labels: ArrayLike, spacing=None):
     """Every voxel takes the value of its nearest non-zero voxel (its own when it is non-zero); ties go to
     the smallest raster index.  A volume of zeros stays as it is."""
     a, zyx = _prepare(labels, spacing)
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     return _back(labels, _dilate(_to_device(a, dev), math.inf, zyx, None))
 
 
@@ -180,7 +163,7 @@ def expand_labels(labels: ArrayLike, distance=1, spacing=None):
     near, the voxel with the smallest raster index gives its label."""
     a, zyx = _prepare(labels, spacing)
     r = _check_radius(distance, "distance")
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     t = _to_device(a, dev)
     return _back(labels, t.clone() if r == 0.0 else _dilate(t, r, zyx, None))
 
@@ -191,7 +174,7 @@ def dilate_labels(labels: ArrayLike, radius, spacing=None, applied_labels: Optio
     a, zyx = _prepare(labels, spacing)
     r = _check_radius(radius)
     applied = _applied_nonzero(applied_labels)
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     t = _to_device(a, dev, check_range=applied is not None)
     if r == 0.0 or applied == []:
         return _back(labels, t.clone())
@@ -205,7 +188,7 @@ def erode_labels(labels: ArrayLike, radius, spacing=None, applied_labels: Option
     a, zyx = _prepare(labels, spacing)
     r = _check_radius(radius)
     applied = _applied_nonzero(applied_labels)
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     t = _to_device(a, dev, check_range=True)
     if r == 0.0 or applied == []:
         return _back(labels, t.clone())
@@ -217,7 +200,7 @@ def open_labels(labels: ArrayLike, radius, spacing=None, applied_labels: Optiona
     a, zyx = _prepare(labels, spacing)
     r = _check_radius(radius)
     applied = _applied_nonzero(applied_labels)
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     t = _to_device(a, dev, check_range=True)
     if r == 0.0 or applied == []:
         return _back(labels, t.clone())
@@ -230,7 +213,7 @@ def close_labels(labels: ArrayLike, radius, spacing=None, applied_labels: Option
     a, zyx = _prepare(labels, spacing)
     r = _check_radius(radius)
     applied = _applied_nonzero(applied_labels)
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     t = _to_device(a, dev, check_range=True)
     if r == 0.0 or applied == []:
         return _back(labels, t.clone())

@@ -41,26 +41,16 @@ chain produces label maps; there is no bundle-configuration hook.
 """
 from __future__ import annotations
 
-from typing import Dict, Hashable, Mapping, Optional, Sequence, Tuple, Union
+from typing import Dict, Hashable, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from ..image.processing import Image
-
-ArrayLike = Union[Image, np.ndarray, torch.Tensor]
+from .._arrays import MAX_LABEL, ArrayLike, Image, _back, _is_integer, _raw, _require_gpu, _to_device, _wrap
 
 MAX_VOXELS = 2 ** 31
-MAX_LABEL = 65535
 MAX_COMPONENTS = 8
-_NEEDS_GPU = "segmantic_amd.seg.transforms needs an MI355X; no GPU is visible and there is no CPU path"
-_IN_PLACE = (torch.uint8, torch.int16, torch.int32)
-
-
-def _require_gpu() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError(_NEEDS_GPU)
-    return torch.device("cuda", torch.cuda.current_device())
+_NEEDS_GPU = "segmantic_amd.seg.transforms needs an MI355X"
 
 
 def _ops():
@@ -69,20 +59,6 @@ def _ops():
 
 
 # ------------------------------------------------------------------ host-side validation and conversion
-def _raw(x: ArrayLike):
-    if isinstance(x, Image):
-        return x.data
-    if isinstance(x, (np.ndarray, torch.Tensor)):
-        return x
-    raise TypeError(f"expected an Image, a numpy array or a torch tensor, not {type(x).__name__}")
-
-
-def _is_integer(a) -> bool:
-    if isinstance(a, torch.Tensor):
-        return not (a.is_floating_point() or a.is_complex())
-    return a.dtype.kind in "biu"
-
-
 def _check_labels(x: ArrayLike, what: str = "labels"):
     """shape / dtype checks that need neither a copy nor the device -> the raw array"""
     a = _raw(x)
@@ -120,38 +96,6 @@ def _check_applied(applied_labels) -> Optional[list]:
     return out
 
 
-def _to_device(a, dev: torch.device, check_range: bool = False) -> torch.Tensor:
-    """contiguous device tensor of a type the kernels read in place.  ``check_range``: the class tables of the
-    clean-up transforms cover 0 .. MAX_LABEL; checking that is their one host synchronisation (uint8 needs none)"""
-    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
-    if t.dtype == torch.bool:
-        t = t.to(torch.uint8)
-    t = t.to(dev)
-    if check_range and t.dtype != torch.uint8:
-        lo, hi = torch.stack(torch.aminmax(t)).tolist()
-        if lo < 0 or hi > MAX_LABEL:
-            raise ValueError(f"label values must lie in 0 .. {MAX_LABEL}, the volume holds {lo} .. {hi}")
-    if t.dtype not in _IN_PLACE:
-        t = t.to(torch.int32)
-    return t.contiguous()
-
-
-def _wrap(x: ArrayLike, out: torch.Tensor):
-    """result in the form of the input: Image (geometry copied), numpy array, or tensor on the input's device"""
-    if isinstance(x, Image):
-        return Image(out.to(x.data.device), x.spacing, x.origin, x.direction)
-    if isinstance(x, np.ndarray):
-        return out.cpu().numpy()
-    return out.to(x.device)
-
-
-def _back(x: ArrayLike, out: torch.Tensor):
-    """like _wrap, in the input's dtype"""
-    a = _raw(x)
-    dt = torch.from_numpy(np.empty(0, a.dtype)).dtype if isinstance(a, np.ndarray) else a.dtype
-    return _wrap(x, out if out.dtype == dt else out.to(dt))
-
-
 # ------------------------------------------------------------------ functions
 def connected_components(labels: ArrayLike, connectivity: Optional[int] = None, background: Optional[int] = 0):
     """-> (components int32, n): the canonical component number ``1..n`` of every voxel (0 for voxels of no
@@ -161,7 +105,7 @@ def connected_components(labels: ArrayLike, connectivity: Optional[int] = None, 
     c = _check_connectivity(connectivity, len(a.shape))
     if background not in (0, None):
         raise ValueError(f"background must be 0 or None, got {background!r}")
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     ops = _ops()
     t = _to_device(a, dev)
     root = ops.cc_label(t, c, with_background=background is None)
@@ -173,7 +117,7 @@ def component_sizes(labels: ArrayLike, connectivity: Optional[int] = None):
     """-> int64 [n]: voxel counts of the components in canonical order."""
     a = _check_labels(labels)
     c = _check_connectivity(connectivity, len(a.shape))
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     ops = _ops()
     root = ops.cc_label(_to_device(a, dev), c)
     size = ops.cc_sizes(root).reshape(-1)
@@ -196,7 +140,7 @@ def keep_largest_connected_component(labels: ArrayLike, applied_labels: Optional
     if isinstance(num_components, bool) or int(num_components) != num_components or \
             not 1 <= int(num_components) <= MAX_COMPONENTS:
         raise ValueError(f"num_components must be an integer in 1 .. {MAX_COMPONENTS}, got {num_components!r}")
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     ops = _ops()
     t = _to_device(a, dev, check_range=True)
     if applied is not None:
@@ -222,7 +166,7 @@ def remove_small_objects(labels: ArrayLike, min_size: int = 64, connectivity: Op
     c = _check_connectivity(connectivity, len(a.shape))
     if isinstance(min_size, bool) or int(min_size) != min_size or int(min_size) < 0:
         raise ValueError(f"min_size must be an integer >= 0, got {min_size!r}")
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     ops = _ops()
     t = _to_device(a, dev, check_range=True)
     root = ops.cc_label(t, c)
@@ -235,7 +179,7 @@ def fill_holes(labels: ArrayLike, applied_labels: Optional[Sequence[int]] = None
     a = _check_labels(labels)
     c = _check_connectivity(connectivity, len(a.shape))
     applied = _check_applied(applied_labels)
-    dev = _require_gpu()
+    dev = _require_gpu(_NEEDS_GPU)
     ops = _ops()
     t = _to_device(a, dev, check_range=True)
     if applied is not None:
@@ -339,7 +283,7 @@ class MapLabels:
             raise ValueError(f"MapLabels: label maps must hold integers, got {a.dtype}")
         if int(np.prod(tuple(a.shape), dtype=np.int64)) == 0:
             raise ValueError("MapLabels: empty input")
-        dev = _require_gpu()
+        dev = _require_gpu(_NEEDS_GPU)
         ops = _ops()
         t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
         if t.dtype == torch.bool:
