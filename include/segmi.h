@@ -437,6 +437,14 @@ int segmi_sw_blend(int dtype, const void* cache, int k, int ldp, const int32_t* 
                    int win_hi, int rd, int rh, int rw, const float* importance, int d, int h, int w,
                    float* out_logits, int ldo, float* out_count, void* labels, int label_bytes,
                    int normalize, void* stream);
+/* Which kernel segmi_sw_blend takes for these arguments (launches nothing; both go through one choice):
+ * "sw_blend2_kernel<dt, G=g>" (at most two covering windows per dimension, every load issued up front),
+ * "sw_blend_kernel<dt, G=g>" (generic) or "sw_blend_scalar_kernel<dt, G=1>" (one channel per lane, labels from a
+ * second pass); G = channels per lane.  "invalid" for arguments segmi_sw_blend refuses outright.  The string is
+ * thread-local and valid until the thread's next call. */
+const char* segmi_sw_blend_kernel_name(int dtype, const void* cache, int k, int ldp, const int32_t* starts_z, int nz,
+                                       const int32_t* starts_y, int ny, const int32_t* starts_x, int nx, int rd,
+                                       int rh, int rw, const float* out_logits, int ldo);
 /* AsDiscrete(argmax=True), monai_unet.py:129-134,622,673 */
 int segmi_argmax(int dtype, const segmi_act* logits, void* labels, int label_bytes,
                  void* stream);

@@ -150,6 +150,7 @@ SIGNATURES = {
     "segmi_sw_finalize": (_i, [_AP, _P, _i, _P, _i, _P]),
     "segmi_sw_blend": (_i, [_i, _P, _i, _i, _P, _i, _P, _i, _P, _i, _i, _i, _i, _i, _i, _P, _i, _i, _i,
                             _P, _i, _P, _P, _i, _i, _P]),
+    "segmi_sw_blend_kernel_name": (C.c_char_p, [_i, _P, _i, _i, _P, _i, _P, _i, _P, _i, _i, _i, _i, _P, _i]),
     "segmi_argmax": (_i, [_i, _AP, _P, _i, _P]),
     "segmi_label_counts": (_i, [_P, _P, _i64, _i, _P, _P]),
     "segmi_resample3d": (_i, [_i, _P, _i, _i, _i, _P, _i, _i, _i, _P, _i, _d, _P]),

@@ -463,6 +463,33 @@ __global__ __launch_bounds__(256) void sw_blend2_kernel(
   }
 }
 
+// which blend kernel a call takes: `vec` = G (16 bytes of T) channels per lane, K / G a power of two <= 64, aligned rows;
+// `two` = at most two windows cover any coordinate in every dimension (start[i + 2] >= start[i] + roi) of an ascending,
+// gap-free schedule: the variant that issues all covering loads up front (41.8 vs 42.9 ms per volume with the generic
+// kernel).  segmi_sw_blend launches by this choice and segmi_sw_blend_kernel_name reports it.
+struct BlendChoice {
+  bool vec, two;
+  int g;            // channels per lane
+};
+static BlendChoice blend_choice(int dtype, const void* cache, int k, int ldp, const int32_t* const starts[3],
+                                const int nn[3], const int rr[3], const float* out_logits, int ldo) {
+  BlendChoice bc{};
+  const int gfull = 16 / dtype_size(dtype);
+  bc.vec = k % gfull == 0 && ldp % gfull == 0 && ((uintptr_t)cache % 16) == 0 &&
+           (!out_logits || (ldo % 4 == 0 && ((uintptr_t)out_logits % 16) == 0)) &&
+           (k / gfull) <= 64 && ((k / gfull) & (k / gfull - 1)) == 0;
+  bc.g = bc.vec ? gfull : 1;
+  bool two = bc.vec;            // the scalar lanes always run the generic kernel
+  for (int dd = 0; dd < 3 && two; ++dd)
+    for (int i = 0; i + 2 < nn[dd]; ++i)
+      if (starts[dd][i + 2] < starts[dd][i] + rr[dd]) { two = false; break; }
+  for (int dd = 0; dd < 3 && two; ++dd)          // ascending, gap-free coverage (MONAI's dense schedule)
+    for (int i = 0; i + 1 < nn[dd]; ++i)
+      if (starts[dd][i + 1] <= starts[dd][i] || starts[dd][i + 1] > starts[dd][i] + rr[dd]) { two = false; break; }
+  bc.two = two;
+  return bc;
+}
+
 }  // namespace segmi
 
 using namespace segmi;
@@ -654,29 +681,14 @@ int segmi_sw_blend(int dtype, const void* cache, int k, int ldp, const int32_t* 
   for (int i = 0; i < nz; ++i) sc.start[0][i] = starts_z[i];
   for (int i = 0; i < ny; ++i) sc.start[1][i] = starts_y[i];
   for (int i = 0; i < nx; ++i) sc.start[2][i] = starts_x[i];
-  const int es = dtype_size(dtype);
-  const int gfull = 16 / es;
-  const bool vec = k % gfull == 0 && ldp % gfull == 0 && ((uintptr_t)cache % 16) == 0 &&
-                   (!out_logits || (ldo % 4 == 0 && ((uintptr_t)out_logits % 16) == 0)) &&
-                   (k / gfull) <= 64 && ((k / gfull) & (k / gfull - 1)) == 0;
-  SEGMI_CHECK_ARG(vec || !labels || k <= 64,
-                  "sw_blend: the scalar path (K %% %d != 0) labels at most 64 classes", gfull);
+  const int32_t* const starts[3] = {starts_z, starts_y, starts_x};
+  const int nn[3] = {nz, ny, nx}, rr[3] = {rd, rh, rw};
+  const BlendChoice bc = blend_choice(dtype, cache, k, ldp, starts, nn, rr, out_logits, ldo);
+  const bool vec = bc.vec, two = bc.two;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t row_segs = (int64_t)d * h * (((int64_t)w * (vec ? k / gfull : k) + 255) / 256);
+  const int64_t row_segs = (int64_t)d * h * (((int64_t)w * (k / bc.g) + 255) / 256);
   SEGMI_CHECK_ARG(row_segs < (1ll << 31) && (int64_t)w * k < (1ll << 30), "sw_blend: volume too large");
   const int grid = (int)(row_segs < 16384 ? row_segs : 16384);
-  // at most two windows cover any coordinate in every dimension (start[i + 2] >= start[i] + roi): the variant that
-  // issues all covering loads up front (41.8 vs 42.9 ms per volume with the generic kernel)
-  bool two = true;
-  {
-    const int nn[3] = {nz, ny, nx}, rr[3] = {rd, rh, rw};
-    for (int dd = 0; dd < 3 && two; ++dd)
-      for (int i = 0; i + 2 < nn[dd]; ++i)
-        if (sc.start[dd][i + 2] < sc.start[dd][i] + rr[dd]) { two = false; break; }
-    for (int dd = 0; dd < 3 && two; ++dd)          // ascending, gap-free coverage (MONAI's dense schedule)
-      for (int i = 0; i + 1 < nn[dd]; ++i)
-        if (sc.start[dd][i + 1] <= sc.start[dd][i] || sc.start[dd][i + 1] > sc.start[dd][i] + rr[dd]) { two = false; break; }
-  }
 #define BLEND(TT, LL, GG)                                                                         \
   do {                                                                                            \
     if (two)                                                                                      \
@@ -724,6 +736,21 @@ int segmi_sw_blend(int dtype, const void* cache, int k, int ldp, const int32_t* 
 #undef BLEND
   SEGMI_LAUNCH_CHECK("sw_blend");
   return SEGMI_OK;
+}
+
+const char* segmi_sw_blend_kernel_name(int dtype, const void* cache, int k, int ldp, const int32_t* starts_z, int nz,
+                                       const int32_t* starts_y, int ny, const int32_t* starts_x, int nx, int rd,
+                                       int rh, int rw, const float* out_logits, int ldo) {
+  static thread_local char buf[64];
+  if (!dtype_ok(dtype) || !cache || !starts_z || !starts_y || !starts_x || k <= 0 || ldp < k || rd <= 0 || rh <= 0 ||
+      rw <= 0 || nz < 1 || ny < 1 || nx < 1 || nz > kMaxStarts || ny > kMaxStarts || nx > kMaxStarts)
+    return "invalid";
+  const int32_t* const starts[3] = {starts_z, starts_y, starts_x};
+  const int nn[3] = {nz, ny, nx}, rr[3] = {rd, rh, rw};
+  const BlendChoice bc = blend_choice(dtype, cache, k, ldp, starts, nn, rr, out_logits, ldo);
+  const char* dt = dtype == SEGMI_BF16 ? "bf16" : dtype == SEGMI_F16 ? "f16" : "f32";
+  snprintf(buf, sizeof buf, "sw_%s_kernel<%s, G=%d>", !bc.vec ? "blend_scalar" : bc.two ? "blend2" : "blend", dt, bc.g);
+  return buf;
 }
 
 int segmi_label_counts(const int32_t* pred, const int32_t* truth, int64_t n, int k,

@@ -656,6 +656,22 @@ def sw_blend(cache, starts_zyx, win_lo, win_hi, roi, d, h, w, importance=None, o
         "sw_blend")
 
 
+def sw_blend_kernel_name(cache, starts_zyx, win_lo, win_hi, roi, d, h, w, importance=None, out_logits=None,
+                         out_count=None, labels=None, normalize=True) -> str:
+    """The kernel ``sw_blend`` takes for these arguments (same signature; launches nothing):
+    ``sw_blend2_kernel<..>``, ``sw_blend_kernel<..>`` or ``sw_blend_scalar_kernel<..>``, with G = channels per lane."""
+    _require_device(cache)
+    if cache.dim() != 5 or cache.stride(4) != 1 or not cache.is_contiguous():
+        raise ValueError("sw_blend: cache must be a contiguous [slots, rd, rh, rw, K] tensor")
+    arrs = [np.ascontiguousarray(np.asarray(sv, dtype=np.int32)) for sv in starts_zyx]
+    ldo = out_logits.stride(-2) if out_logits is not None else 0
+    return lib.segmi_sw_blend_kernel_name(
+        dtype_code(cache), _ptr(cache), cache.shape[4], cache.stride(3),
+        arrs[0].ctypes.data_as(C.c_void_p), len(arrs[0]), arrs[1].ctypes.data_as(C.c_void_p),
+        len(arrs[1]), arrs[2].ctypes.data_as(C.c_void_p), len(arrs[2]),
+        int(roi[0]), int(roi[1]), int(roi[2]), _ptr(out_logits), int(ldo)).decode()
+
+
 def argmax(logits, labels) -> None:
     a = act(logits)
     check(lib.segmi_argmax(dtype_code(logits), C.byref(a), _ptr(labels),
