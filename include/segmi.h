@@ -357,6 +357,36 @@ int segmi_softmax_dice_bwd(int dtype, const segmi_act* logits, const float* labe
                            const float* coef, float grad_scale, const segmi_act* dlogits,
                            float* scratch, float* bias_grad, void* stream);
 
+/* Dice + cross-entropy on the same two passes:
+ *   loss = lambda_dice * Dice + lambda_ce * CE
+ *   Dice: the term above; include_background = 0 drops class 0 after the softmax (mean over n * (k - 1);
+ *         k = 1 is then refused).
+ *   CE:   torch cross_entropy(logits, labels, weight = class_weight, reduction = "mean") over all voxels of the
+ *         batch: sum_v w[y_v] * (-log p_{v,y_v}) / W with W = sum_v w[y_v] (batch-global; W = 0 gives NaN as in
+ *         torch).  -log p is formed as log sum_j exp(x_j - m) - (x_y - m), never as the log of a stored
+ *         probability.  lambda_ce = 0 switches the term off (no NaN from W = 0 then).
+ *   A voxel whose label lies outside [0, k) contributes to neither CE nor W (nor to the Dice target sums).
+ * class_weight: nullable DEVICE f32[k] (NULL = ones), entries finite and >= 0 (not checked on the device);
+ * lambda_dice, lambda_ce: finite and >= 0; n * k <= 1792 (the finalisation's LDS).  partials f32[segmi_dice_ce_chunks()][n][4][k]; coef f32[n][3][k]
+ * receives the backward coefficients: the Dice pair scaled by lambda_dice (zero for an excluded background)
+ * and c_k = lambda_ce * w_k / W; loss f32[1].  The lambdas, the weights and include_background reach the
+ * backward through coef alone:
+ *   dlogits_j = scale * [ lambda_dice * (Dice term) + c_y * (p_j - [j = y]) ],  scale = grad_scale or amp[0].
+ * scratch / bias_grad as for segmi_softmax_dice_bwd (scratch = the forward's 4-row partials buffer).  With
+ * lambda_dice = 1, lambda_ce = 0, include_background = 1 loss and dlogits are those of segmi_softmax_dice_fwd /
+ * _bwd bit for bit. */
+int segmi_dice_ce_chunks(const segmi_act* logits);
+int segmi_softmax_dice_ce_fwd(int dtype, const segmi_act* logits, const float* labels, float* partials,
+                              float* coef, float* loss, float smooth_nr, float smooth_dr, float lambda_dice,
+                              float lambda_ce, int include_background, const float* class_weight, void* stream);
+int segmi_softmax_dice_ce_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                              float grad_scale, const segmi_act* dlogits, float* scratch, float* bias_grad,
+                              void* stream);
+/* ... with the loss scale read from amp[0] on the device (see "dynamic loss scaling" below) */
+int segmi_softmax_dice_ce_bwd_amp(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                                  const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad,
+                                  void* stream);
+
 /* torch.optim.Adam / SGD semantics over one flat f32 arena, monai_unet.py:292-304,346, and
  * adabelief_pytorch.AdaBelief(rectify=False, fixed_decay=False), monai_unet.py:305-314.
  * Hyper-parameters are doubles, as the Python optimisers hold them: derived scalars (1 - beta,

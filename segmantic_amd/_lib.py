@@ -136,6 +136,10 @@ SIGNATURES = {
     "segmi_dice_chunks": (_i, [_AP]),
     "segmi_softmax_dice_fwd": (_i, [_i, _AP, _P, _P, _P, _P, _f, _f, _P]),
     "segmi_softmax_dice_bwd": (_i, [_i, _AP, _P, _P, _f, _AP, _P, _P, _P]),
+    "segmi_dice_ce_chunks": (_i, [_AP]),
+    "segmi_softmax_dice_ce_fwd": (_i, [_i, _AP, _P, _P, _P, _P, _f, _f, _f, _f, _i, _P, _P]),
+    "segmi_softmax_dice_ce_bwd": (_i, [_i, _AP, _P, _P, _f, _AP, _P, _P, _P]),
+    "segmi_softmax_dice_ce_bwd_amp": (_i, [_i, _AP, _P, _P, _P, _AP, _P, _P, _P]),
     "segmi_adam_step": (_i, [_P, _P, _P, _P, _P, _i64, _d, _d, _d, _d, _d, _i64, _f, _P]),
     "segmi_sgd_step": (_i, [_P, _P, _P, _i64, _d, _d, _d, _i, _f, _P]),
     "segmi_adabelief_step": (_i, [_P, _P, _P, _P, _i64, _d, _d, _d, _d, _d, _i, _i64, _f, _P]),

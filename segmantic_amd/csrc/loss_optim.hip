@@ -1,4 +1,5 @@
-// loss_optim.hip -- fused softmax + one-hot + Dice loss (forward / backward) and the
+// loss_optim.hip -- fused softmax + one-hot + Dice loss (forward / backward), its Dice + cross-entropy
+// extension (the CE template flag: same passes, one more partial / coefficient row), and the
 // flat-arena optimisers (Adam, SGD, AdaBelief).  HBM-bound: logits are read once per pass in
 // 16-byte vectors along the class axis (NDHWC keeps the K classes of a voxel contiguous), the
 // softmax lives in registers, reductions are two-stage and deterministic.
@@ -43,6 +44,75 @@ struct DiceFin {
   }
 };
 
+// Dice + cross-entropy: loss = lambda_dice * Dice + lambda_ce * CE.
+//   Dice: the term above; without the background class 0 is dropped and the mean runs over n * (k - 1).
+//   CE:   sum_v w[y_v] * (-log p_{v,y_v}) / W,  W = sum_v w[y_v] over the whole batch (torch's weighted mean);
+//         voxels whose label is outside [0, k) are in neither sum (they are in no row of the table).
+// sums: [n][4][k] = {intersection, sum p, sum t, sum of -log p_y over the voxels with y = k}
+// coef: [n][3][k] = {lambda_dice * Dice pair (0 for an excluded background), c_k = lambda_ce * w_k / W}
+struct DiceCEFin {
+  int n, k;
+  float smooth_nr, smooth_dr;
+  float lambda_dice, lambda_ce;
+  int include_background;
+  const float* weight;   // nullable: ones
+  float *coef, *loss;
+  __device__ void operator()(const double* sums, double* red) const {
+    const int tid = threadIdx.x;
+    double local = 0.0, num = 0.0, wsum = 0.0;
+    const int k0 = include_background ? 0 : 1;
+    const double nk = (double)n * (k - k0);
+    const double ld = (double)lambda_dice;
+    for (int o = tid; o < n * k; o += 256) {
+      const int b = o / k, j = o % k;
+      const double* q = sums + ((int64_t)b * 4) * k + j;
+      const double I = q[0], P = q[k], Tt = q[2 * k];
+      const double w = weight ? (double)weight[j] : 1.0;
+      num += w * q[3 * k];
+      wsum += w * Tt;
+      float* c = coef + ((int64_t)b * 3) * k + j;
+      if (j < k0) {
+        c[0] = 0.f;
+        c[k] = 0.f;
+        continue;
+      }
+      // f32 arithmetic as the reference does on the reduced sums
+      const float If = (float)I, Df = (float)Tt + (float)P;
+      const float f = 1.0f - (2.0f * If + smooth_nr) / (Df + smooth_dr);
+      local += (double)f;
+      const double den = (double)Df + (double)smooth_dr;
+      c[0] = (float)(ld * (-2.0 / den / nk));
+      c[k] = (float)(ld * ((2.0 * (double)If + (double)smooth_nr) / (den * den) / nk));
+    }
+    red[tid] = local;
+    red[256 + tid] = num;
+    red[512 + tid] = wsum;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) {
+        red[tid] += red[tid + o];
+        red[256 + tid] += red[256 + tid + o];
+        red[512 + tid] += red[512 + tid + o];
+      }
+      __syncthreads();
+    }
+    // lambda_ce = 0 switches the term off altogether: a batch without any weighted voxel (W = 0, CE = NaN
+    // by torch's rule) must not turn a pure Dice loss into NaN
+    const bool ce_on = lambda_ce != 0.f;
+    const double W = red[512];
+    for (int o = tid; o < n * k; o += 256) {
+      const int j = o % k;
+      const double w = weight ? (double)weight[j] : 1.0;
+      coef[((int64_t)(o / k) * 3 + 2) * k + j] = ce_on ? (float)((double)lambda_ce * w / W) : 0.f;
+    }
+    if (tid == 0) {
+      double total = ld * (red[0] / nk);
+      if (ce_on) total += (double)lambda_ce * (red[256] / W);
+      *loss = (float)total;
+    }
+  }
+};
+
 struct ChanSumFin {   // sums: [k] channel sums
   int k;
   float* db;
@@ -54,8 +124,8 @@ struct ChanSumFin {   // sums: [k] channel sums
 struct DiceParams {
   const void* logits;
   const float* labels;
-  float* partials;   // [n][chunks][3][k]
-  const float* coef; // [n][2][k]
+  float* partials;   // [chunks][n][3][k]; Dice + CE: [chunks][n][4][k]
+  const float* coef; // [n][2][k]; Dice + CE: [n][3][k]
   void* dlogits;
   int n, k, ld, ldd;
   int64_t vox;       // voxels per batch item
@@ -63,11 +133,12 @@ struct DiceParams {
   float grad_scale;
   const float* amp;  // nullable: {scale, found_inf} in device memory; scale replaces grad_scale
   float* bias_part;  // [n * chunks][k] per-workgroup channel sums of the written gradient (nullable)
-  // finalisation by the last workgroup of the launch (fin_tail.h): forward -> DiceFin over `partials`,
-  // backward -> ChanSumFin over `bias_part`
+  // finalisation by the last workgroup of the launch (fin_tail.h): forward -> DiceFin (Dice + CE: DiceCEFin)
+  // over `partials`, backward -> ChanSumFin over `bias_part`
   FinTail ft;
   DiceFin dfin;
   ChanSumFin cfin;
+  DiceCEFin cefin;
 };
 
 // VECLD: the caller has checked ONCE per workgroup (logits_vec_ok) that every voxel's class row is
@@ -123,10 +194,36 @@ __device__ __forceinline__ void softmax_inplace(int k, float (&v)[KMAX]) {
   for (int j = 0; j < KMAX; ++j) if (j < k) v[j] *= inv;
 }
 
+// softmax_inplace (the same operations in the same order: the probabilities keep their bits) that also returns
+// -log p_lab = log sum_j exp(x_j - m) - (x_lab - m), from the sum and the shifted logit and never from the stored
+// probability: a true class 200 below the maximum gives 200, not -log(0).  The sum lies in [1, k], so the hardware
+// log2 (v_log_f32) of the 16-bit path needs no denormal care; f32 keeps libm logf like its expf.  A label
+// outside [0, k) returns a value no caller uses.
+template <int KMAX, bool FAST>
+__device__ __forceinline__ float softmax_nll_inplace(int k, float (&v)[KMAX], int lab) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) if (j < k) m = fmaxf(m, v[j]);
+  float s = 0.f, xl = 0.f;
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) if (j < k) {
+    if (j == lab) xl = v[j] - m;
+    v[j] = FAST ? __builtin_amdgcn_exp2f((v[j] - m) * 1.4426950408889634f) : expf(v[j] - m);
+    s += v[j];
+  }
+  const float inv = 1.f / s;
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) if (j < k) v[j] *= inv;
+  return (FAST ? __builtin_amdgcn_logf(s) * 0.6931471805599453f : logf(s)) - xl;
+}
+
 // FULL: k == KMAX (16 / 32 / 64 labels): every per-channel predicate folds away at compile time
-template <typename T, int KMAX, bool FULL>
+// CE: Dice + cross-entropy -- a fourth partial row (sum of -log p_y over the voxels with y = k) and DiceCEFin;
+// CE = false is the Dice-only kernel, unchanged
+template <typename T, int KMAX, bool FULL, bool CE>
 __global__ __launch_bounds__(256) void dice_fwd_kernel(DiceParams p) {
-  __shared__ float red[4][3 * KMAX];
+  constexpr int ROWS = CE ? 4 : 3;
+  __shared__ float red[4][ROWS * KMAX];
   const int n = blockIdx.y, chunk = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t v0 = (int64_t)chunk * kDiceVox;
@@ -134,8 +231,13 @@ __global__ __launch_bounds__(256) void dice_fwd_kernel(DiceParams p) {
   const T* lg = (const T*)p.logits + (int64_t)n * p.vox * p.ld;
   const float* lb = p.labels + (int64_t)n * p.vox;
   float si[KMAX], sp[KMAX], stt[KMAX];
+  float snl[CE ? KMAX : 1];
 #pragma unroll
   for (int j = 0; j < KMAX; ++j) si[j] = sp[j] = stt[j] = 0.f;
+  if constexpr (CE) {
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) snl[j] = 0.f;
+  }
   // U voxels per trip with every load issued before the first softmax (one voxel per trip behind a
   // per-voxel alignment branch left the 32-byte loads exposed: 3.4 TB/s); the sums keep their voxel
   // order, so the partials keep their bits
@@ -152,13 +254,19 @@ __global__ __launch_bounds__(256) void dice_fwd_kernel(DiceParams p) {
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        softmax_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x[u]);
         const int lab = (int)lf[u];
+        float nll = 0.f;
+        if constexpr (CE) nll = softmax_nll_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x[u], lab);
+        else softmax_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x[u]);
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
           if (FULL || j < p.k) {
             sp[j] += x[u][j];
-            if (j == lab) { si[j] += x[u][j]; stt[j] += 1.f; }
+            if (j == lab) {
+              si[j] += x[u][j];
+              stt[j] += 1.f;
+              if constexpr (CE) snl[j] += nll;
+            }
           }
         }
       }
@@ -166,13 +274,19 @@ __global__ __launch_bounds__(256) void dice_fwd_kernel(DiceParams p) {
     for (; v < v1; v += 256) {
       float x[KMAX];
       load_logits<T, KMAX, VL>(lg + v * p.ld, FULL ? KMAX : p.k, x);
-      softmax_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x);
       const int lab = (int)lb[v];
+      float nll = 0.f;
+      if constexpr (CE) nll = softmax_nll_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x, lab);
+      else softmax_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x);
 #pragma unroll
       for (int j = 0; j < KMAX; ++j) {
         if (FULL || j < p.k) {
           sp[j] += x[j];
-          if (j == lab) { si[j] += x[j]; stt[j] += 1.f; }
+          if (j == lab) {
+            si[j] += x[j];
+            stt[j] += 1.f;
+            if constexpr (CE) snl[j] += nll;
+          }
         }
       }
     }
@@ -184,27 +298,37 @@ __global__ __launch_bounds__(256) void dice_fwd_kernel(DiceParams p) {
     if (FULL || j < p.k) {
       const float a = wave_sum(si[j]), b = wave_sum(sp[j]), c = wave_sum(stt[j]);
       if (lane == 0) { red[wave][j] = a; red[wave][KMAX + j] = b; red[wave][2 * KMAX + j] = c; }
+      if constexpr (CE) {
+        const float d = wave_sum(snl[j]);
+        if (lane == 0) red[wave][3 * KMAX + j] = d;
+      }
     }
   }
   __syncthreads();
-  if (tid < 3 * p.k) {
+  if (tid < ROWS * p.k) {
     const int which = tid / p.k, j = tid % p.k;
     const float s = red[0][which * KMAX + j] + red[1][which * KMAX + j] +
                     red[2][which * KMAX + j] + red[3][which * KMAX + j];
-    fin_store(&p.partials[(((int64_t)chunk * p.n + n) * 3 + which) * p.k + j], s);   // [chunk][n][3][k]
+    fin_store(&p.partials[(((int64_t)chunk * p.n + n) * ROWS + which) * p.k + j], s);   // [chunk][n][ROWS][k]
   }
   {
     extern __shared__ double dice_tail_lds[];
-    fin_tail_run<DiceFin, 256, offsetof(DiceParams, ft), offsetof(DiceParams, dfin)>(p.partials, dice_tail_lds);
+    if constexpr (CE)
+      fin_tail_run<DiceCEFin, 256, offsetof(DiceParams, ft), offsetof(DiceParams, cefin)>(p.partials, dice_tail_lds);
+    else
+      fin_tail_run<DiceFin, 256, offsetof(DiceParams, ft), offsetof(DiceParams, dfin)>(p.partials, dice_tail_lds);
   }
 }
 
-template <typename T, int KMAX, bool FULL>
+// CE: the third coefficient row c_k = lambda_ce * w_k / W adds c_y * (p_j - [j = y]) per class.  For j = y the
+// bracket is formed as -(sum of the other probabilities): p_y - 1 cancels when the voxel is classified well.
+template <typename T, int KMAX, bool FULL, bool CE>
 __global__ __launch_bounds__(256) void dice_bwd_kernel(DiceParams p) {
-  __shared__ float cf[2 * KMAX];
+  constexpr int ROWS = CE ? 3 : 2;
+  __shared__ float cf[ROWS * KMAX];
   const int n = blockIdx.y, chunk = blockIdx.x;
   const int tid = threadIdx.x;
-  if (tid < 2 * p.k) cf[(tid / p.k) * KMAX + tid % p.k] = p.coef[(int64_t)n * 2 * p.k + tid];
+  if (tid < ROWS * p.k) cf[(tid / p.k) * KMAX + tid % p.k] = p.coef[(int64_t)n * ROWS * p.k + tid];
   __syncthreads();
   const int64_t v0 = (int64_t)chunk * kDiceVox;
   const int64_t v1 = v0 + kDiceVox < p.vox ? v0 + kDiceVox : p.vox;
@@ -232,6 +356,14 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(DiceParams p) {
         dot = fmaf(x[j], dp[j], dot);
       }
     }
+    float cy = 0.f, rest = 0.f;    // CE term: cy * (p_j - [j = y]), cy = grad_scale * c_y (0 for a label outside [0, k))
+    if constexpr (CE) {
+      const bool in = (unsigned)lab < (unsigned)(FULL ? KMAX : p.k);
+      cy = in ? grad_scale * cf[2 * KMAX + (in ? lab : 0)] : 0.f;
+#pragma unroll
+      for (int j = 0; j < KMAX; ++j)
+        if ((FULL || j < p.k) && j != lab) rest += x[j];
+    }
     T* o = dl + v * p.ldd;
     if (vec_out) {
 #pragma unroll
@@ -239,7 +371,10 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(DiceParams p) {
         if (FULL || j < p.k) {
           f32x4 g4;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) g4[e] = (j + e < KMAX) ? grad_scale * x[j + e] * (dp[j + e] - dot) : 0.f;
+          for (int e = 0; e < 4; ++e) {
+            g4[e] = (j + e < KMAX) ? grad_scale * x[j + e] * (dp[j + e] - dot) : 0.f;
+            if constexpr (CE) if (j + e < KMAX) g4[e] += cy * (j + e == lab ? -rest : x[j + e]);
+          }
           store4<T>(o + j, g4);
 #pragma unroll
           for (int e = 0; e < 4; ++e)
@@ -250,7 +385,8 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(DiceParams p) {
 #pragma unroll
       for (int j = 0; j < KMAX; ++j)
         if (FULL || j < p.k) {
-          const float gv = grad_scale * x[j] * (dp[j] - dot);
+          float gv = grad_scale * x[j] * (dp[j] - dot);
+          if constexpr (CE) gv += cy * (j == lab ? -rest : x[j]);
           Elem<T>::st(o + j, gv);
           gsum[j] += gv;
         }
@@ -447,18 +583,18 @@ static inline int opt_blocks(int64_t n) {
   return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
 }
 
-template <typename T>
+template <typename T, bool CE>
 static int dice_dispatch(bool fwd, const DiceParams& p, hipStream_t st) {
   dim3 grid(p.chunks, p.n);
   const size_t lds = p.ft.on ? fin_tail_lds(p.ft.width, 256) : 0;
 #define DICE_K(KM)                                                                       \
   do {                                                                                   \
     if (p.k == KM) {                                                                     \
-      if (fwd) hipLaunchKernelGGL((dice_fwd_kernel<T, KM, true>), grid, 256, lds, st, p);  \
-      else hipLaunchKernelGGL((dice_bwd_kernel<T, KM, true>), grid, 256, lds, st, p);      \
+      if (fwd) hipLaunchKernelGGL((dice_fwd_kernel<T, KM, true, CE>), grid, 256, lds, st, p);  \
+      else hipLaunchKernelGGL((dice_bwd_kernel<T, KM, true, CE>), grid, 256, lds, st, p);      \
     } else {                                                                             \
-      if (fwd) hipLaunchKernelGGL((dice_fwd_kernel<T, KM, false>), grid, 256, lds, st, p); \
-      else hipLaunchKernelGGL((dice_bwd_kernel<T, KM, false>), grid, 256, lds, st, p);     \
+      if (fwd) hipLaunchKernelGGL((dice_fwd_kernel<T, KM, false, CE>), grid, 256, lds, st, p); \
+      else hipLaunchKernelGGL((dice_bwd_kernel<T, KM, false, CE>), grid, 256, lds, st, p);     \
     }                                                                                    \
   } while (0)
   if (p.k <= 4) DICE_K(4);
@@ -470,9 +606,10 @@ static int dice_dispatch(bool fwd, const DiceParams& p, hipStream_t st) {
   SEGMI_LAUNCH_CHECK("softmax_dice");
   return SEGMI_OK;
 }
+template <bool CE>
 static int dice_dispatch_dt(int dtype, bool fwd, const DiceParams& p, hipStream_t st) {
-  if (dtype == SEGMI_F32) return dice_dispatch<float>(fwd, p, st);
-  return dtype == SEGMI_F16 ? dice_dispatch<f16_t>(fwd, p, st) : dice_dispatch<bf16_t>(fwd, p, st);
+  if (dtype == SEGMI_F32) return dice_dispatch<float, CE>(fwd, p, st);
+  return dtype == SEGMI_F16 ? dice_dispatch<f16_t, CE>(fwd, p, st) : dice_dispatch<bf16_t, CE>(fwd, p, st);
 }
 
 }  // namespace segmi
@@ -507,11 +644,12 @@ int segmi_softmax_dice_fwd(int dtype, const segmi_act* logits, const float* labe
   // (fin_tail.h): rows = chunks, one row = [n][3][k]
   p.ft = fin_tail_make(p.chunks, p.n * 3 * p.k, (unsigned)p.chunks * (unsigned)p.n);
   p.dfin = DiceFin{p.n, p.k, smooth_nr, smooth_dr, coef, loss};
-  return dice_dispatch_dt(dtype, true, p, st);
+  return dice_dispatch_dt<false>(dtype, true, p, st);
 }
 
-static int dice_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef, float grad_scale,
-                    const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad, void* stream) {
+static int dice_bwd(bool ce, int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                    float grad_scale, const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad,
+                    void* stream) {
   SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_dice_bwd: bad dtype");
   SEGMI_CHECK_ARG(act_ok(logits) && act_ok(dlogits) && labels && coef &&
                       logits->n == dlogits->n && logits->d == dlogits->d &&
@@ -531,20 +669,66 @@ static int dice_bwd(int dtype, const segmi_act* logits, const float* labels, con
     p.ft = fin_tail_make(p.n * p.chunks, p.k, (unsigned)p.chunks * (unsigned)p.n);
     p.cfin = ChanSumFin{p.k, bias_grad};
   }
-  return dice_dispatch_dt(dtype, false, p, st);
+  return ce ? dice_dispatch_dt<true>(dtype, false, p, st) : dice_dispatch_dt<false>(dtype, false, p, st);
 }
 
 int segmi_softmax_dice_bwd(int dtype, const segmi_act* logits, const float* labels,
                            const float* coef, float grad_scale, const segmi_act* dlogits,
                            float* scratch, float* bias_grad, void* stream) {
-  return dice_bwd(dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
+  return dice_bwd(false, dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
 }
 
 int segmi_softmax_dice_bwd_amp(int dtype, const segmi_act* logits, const float* labels,
                                const float* coef, const float* amp, const segmi_act* dlogits,
                                float* scratch, float* bias_grad, void* stream) {
   SEGMI_CHECK_ARG(amp, "softmax_dice_bwd_amp: amp state missing");
-  return dice_bwd(dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
+  return dice_bwd(false, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
+}
+
+// ---- Dice + cross-entropy: 4-row partials, 3-row coefficients
+int segmi_dice_ce_chunks(const segmi_act* logits) {
+  if (!logits) return 0;
+  return dice_real_chunks(logits);
+}
+
+int segmi_softmax_dice_ce_fwd(int dtype, const segmi_act* logits, const float* labels, float* partials,
+                              float* coef, float* loss, float smooth_nr, float smooth_dr, float lambda_dice,
+                              float lambda_ce, int include_background, const float* class_weight, void* stream) {
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_dice_ce_fwd: bad dtype");
+  SEGMI_CHECK_ARG(act_ok(logits) && labels && partials && coef && loss, "softmax_dice_ce_fwd: bad arguments");
+  SEGMI_CHECK_ARG(lambda_dice >= 0.f && lambda_ce >= 0.f && __builtin_isfinite(lambda_dice) &&
+                      __builtin_isfinite(lambda_ce),
+                  "softmax_dice_ce_fwd: lambda_dice / lambda_ce must be finite and >= 0 (got %g, %g)",
+                  (double)lambda_dice, (double)lambda_ce);
+  SEGMI_CHECK_ARG(include_background || logits->c > 1,
+                  "softmax_dice_ce_fwd: include_background = 0 needs more than one class");
+  DiceParams p{};
+  p.logits = logits->data; p.labels = labels; p.partials = partials;
+  p.n = logits->n; p.k = logits->c; p.ld = logits->ld;
+  p.vox = (int64_t)logits->d * logits->h * logits->w;
+  p.chunks = dice_real_chunks(logits);
+  // the finalising workgroup folds one [n][4][k] row of doubles in LDS (fin_tail_lds): 64 KB per workgroup
+  SEGMI_CHECK_ARG(fin_tail_lds(p.n * 4 * p.k, 256) <= 64 * 1024,
+                  "softmax_dice_ce_fwd: batch %d x %d classes needs %zu bytes of LDS for the finalisation, the "
+                  "limit is 65536 (n * k <= 1792)", p.n, p.k, fin_tail_lds(p.n * 4 * p.k, 256));
+  // rows = chunks, one row = [n][4][k]; the last workgroup forms W, the loss and the coefficients in f64
+  p.ft = fin_tail_make(p.chunks, p.n * 4 * p.k, (unsigned)p.chunks * (unsigned)p.n);
+  p.cefin = DiceCEFin{p.n, p.k, smooth_nr, smooth_dr, lambda_dice, lambda_ce, include_background != 0,
+                      class_weight, coef, loss};
+  return dice_dispatch_dt<true>(dtype, true, p, (hipStream_t)stream);
+}
+
+int segmi_softmax_dice_ce_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                              float grad_scale, const segmi_act* dlogits, float* scratch, float* bias_grad,
+                              void* stream) {
+  return dice_bwd(true, dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
+}
+
+int segmi_softmax_dice_ce_bwd_amp(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                                  const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad,
+                                  void* stream) {
+  SEGMI_CHECK_ARG(amp, "softmax_dice_ce_bwd_amp: amp state missing");
+  return dice_bwd(true, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
 }
 
 int segmi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

@@ -537,6 +537,42 @@ def softmax_dice_bwd(logits, labels, coef, grad_scale, dlogits, scratch=None, bi
           "softmax_dice_bwd")
 
 
+def dice_ce_chunks(logits) -> int:
+    """chunks of the 4-row partials buffer f32 [chunks, n, 4, k] of the Dice + cross-entropy forward"""
+    a = act(logits)
+    return int(lib.segmi_dice_ce_chunks(C.byref(a)))
+
+
+def softmax_dice_ce_fwd(logits, labels, partials, coef, loss, smooth_nr=1e-5, smooth_dr=1e-5, lambda_dice=1.0,
+                        lambda_ce=1.0, include_background=True, class_weight=None) -> None:
+    """loss = lambda_dice * Dice + lambda_ce * CE (``segmi.h``); ``class_weight``: device f32[K] or None (ones);
+    ``coef`` f32[n, 3, k] carries everything the backward needs."""
+    a = act(logits)
+    if class_weight is not None and (class_weight.dtype != torch.float32 or class_weight.numel() != logits.shape[4]
+                                     or not class_weight.is_contiguous()):
+        raise ValueError(f"class_weight must be a contiguous float32 tensor of {logits.shape[4]} entries")
+    check(lib.segmi_softmax_dice_ce_fwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(partials), _ptr(coef),
+                                        _ptr(loss), smooth_nr, smooth_dr, float(lambda_dice), float(lambda_ce),
+                                        int(bool(include_background)), _ptr(class_weight), _stream()),
+          "softmax_dice_ce_fwd")
+
+
+def softmax_dice_ce_bwd(logits, labels, coef, grad_scale, dlogits, scratch=None, bias_grad=None) -> None:
+    """as ``softmax_dice_bwd`` with the 3-row coefficients of ``softmax_dice_ce_fwd``"""
+    a, b = act(logits), act(dlogits)
+    check(lib.segmi_softmax_dice_ce_bwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef),
+                                        float(grad_scale), C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
+          "softmax_dice_ce_bwd")
+
+
+def softmax_dice_ce_bwd_amp(logits, labels, coef, amp, dlogits, scratch=None, bias_grad=None) -> None:
+    """softmax_dice_ce_bwd with the loss scale read from ``amp[0]`` on the device."""
+    a, b = act(logits), act(dlogits)
+    check(lib.segmi_softmax_dice_ce_bwd_amp(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef), _ptr(amp),
+                                            C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
+          "softmax_dice_ce_bwd_amp")
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, beta1, beta2, eps,
               weight_decay, step, grad_scale=1.0) -> None:
     check(lib.segmi_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),

@@ -4,10 +4,16 @@
 reference ``src/segmantic/seg/monai_unet.py:128`` and called at ``:344`` / ``:357``;
 ``DiceMetric`` replaces ``monai.metrics.DiceMetric(include_background=False, reduction="mean")``
 (``:136-138``, ``:642-644``).
+
+``DiceCELoss`` (MONAI's ``DiceCELoss(to_onehot_y=True, softmax=True)``) adds a class-weighted cross-entropy
+term computed by the same two kernels, and both losses take ``include_background``.  Every loss object offers
+``forward_ndhwc`` / ``backward_ndhwc``, the explicit (no autograd graph) interface ``Net.training_step``
+drives; ``loss_from_config`` builds the object an ``optimizer["loss"]`` dictionary names.
 """
 from __future__ import annotations
 
-from typing import Optional
+import math
+from typing import Optional, Sequence
 
 import torch
 
@@ -74,42 +80,221 @@ def dice_backward(state: _DiceState, logits_ndhwc: torch.Tensor, grad_scale: flo
     return out
 
 
-class _DiceFn(torch.autograd.Function):
+class _DiceCEState:
+    """Scratch of the Dice + cross-entropy kernels (4-row partials, 3-row coefficients)."""
+
+    def __init__(self):
+        self.partials: Optional[torch.Tensor] = None
+        self.coef: Optional[torch.Tensor] = None
+        self.loss: Optional[torch.Tensor] = None
+        self.labels: Optional[torch.Tensor] = None
+        self.weight: Optional[torch.Tensor] = None
+        self._weight_key = None
+
+    def ensure(self, logits: torch.Tensor, weight: Optional[Sequence[float]]):
+        n, k = logits.shape[0], logits.shape[4]
+        chunks = ops.dice_ce_chunks(logits)
+        dev = logits.device
+        if self.partials is None or self.partials.shape != (chunks, n, 4, k) or self.partials.device != dev:
+            self.partials = torch.empty((chunks, n, 4, k), device=dev)      # the kernel's layout
+            self.coef = torch.empty((n, 3, k), device=dev)
+        # the device copy follows the values it was made from: ``DiceCELoss.weight`` may be edited between calls
+        key = None if weight is None else (tuple(float(v) for v in weight), dev)
+        if key != self._weight_key:
+            if key is not None and any(not math.isfinite(v) or v < 0.0 for v in key[0]):
+                raise ValueError(f"'class_weights' must be finite and >= 0 (got {list(key[0])})")
+            self.weight = None if weight is None else torch.tensor(key[0], dtype=torch.float32, device=dev)
+            self._weight_key = key
+        self.loss = torch.empty(1, device=dev)
+
+
+def dice_ce_forward(state: _DiceCEState, logits_ndhwc: torch.Tensor, labels: torch.Tensor, smooth_nr: float,
+                    smooth_dr: float, lambda_dice: float, lambda_ce: float, include_background: bool,
+                    weight: Optional[Sequence[float]]) -> torch.Tensor:
+    k = logits_ndhwc.shape[4]
+    if weight is not None and len(weight) != k:
+        raise ValueError(f"'class_weights' has {len(weight)} entries, the logits have {k} classes")
+    if not include_background and k == 1:
+        raise ValueError("include_background=False needs more than one class")
+    lab = labels.to(logits_ndhwc.device, torch.float32).contiguous().view(-1)
+    if lab.numel() != logits_ndhwc.numel() // k:
+        raise ValueError("label volume does not match logits")
+    state.ensure(logits_ndhwc, weight)
+    ops.softmax_dice_ce_fwd(logits_ndhwc, lab, state.partials, state.coef, state.loss, smooth_nr, smooth_dr,
+                            lambda_dice, lambda_ce, include_background, state.weight)
+    state.labels = lab
+    return state.loss.view(())
+
+
+def dice_ce_backward(state: _DiceCEState, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
+                     out: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
+                     amp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``dice_backward`` for the Dice + cross-entropy coefficients (same ``bias_grad`` / ``amp`` meaning)."""
+    if out is None or out.shape != logits_ndhwc.shape or out.dtype != logits_ndhwc.dtype:
+        out = torch.empty_like(logits_ndhwc)
+    scratch = state.partials if bias_grad is not None else None
+    if amp is not None:
+        ops.softmax_dice_ce_bwd_amp(logits_ndhwc, state.labels, state.coef, amp, out, scratch=scratch,
+                                    bias_grad=bias_grad)
+    else:
+        ops.softmax_dice_ce_bwd(logits_ndhwc, state.labels, state.coef, grad_scale, out, scratch=scratch,
+                                bias_grad=bias_grad)
+    return out
+
+
+class _LossFn(torch.autograd.Function):
+    """Bridges a loss object's explicit forward / backward into autograd for external training loops."""
+
     @staticmethod
     def forward(ctx, logits, labels, loss_mod):
         lg = as_ndhwc(logits)
         ctx.lg = lg
         ctx.mod = loss_mod
-        ctx.state = loss_mod._state
-        return dice_forward(loss_mod._state, lg, labels, loss_mod.smooth_nr, loss_mod.smooth_dr).clone()
+        return loss_mod.forward_ndhwc(lg, labels).clone()
 
     @staticmethod
     def backward(ctx, g):
         # g is the upstream scalar; fold it into the kernel on the host only when it is 1
-        d = dice_backward(ctx.state, ctx.lg, 1.0)
+        d = ctx.mod.backward_ndhwc(ctx.lg, 1.0)
         d = d.permute(0, 4, 1, 2, 3)
         gs = g.to(d.dtype)
         return (d if bool(gs == 1) else d * gs), None, None
 
 
-class DiceLoss(torch.nn.Module):
-    """Fused softmax + one-hot + Dice (MONAI defaults: include_background, smooth 1e-5, mean)."""
+class _FusedLoss(torch.nn.Module):
+    """What the two losses share: ``forward`` on logical [N,K,D,H,W] logits (autograd bridge or plain value)
+    over the subclass's ``forward_ndhwc`` / ``backward_ndhwc``."""
+
+    def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """logits [N,K,D,H,W] (float32/bfloat16/float16), labels [N,1,D,H,W] integer-valued."""
+        if logits.requires_grad and torch.is_grad_enabled():
+            return _LossFn.apply(logits, labels, self)
+        return self.forward_ndhwc(as_ndhwc(logits), labels).clone()
+
+
+def _check_lambda(name: str, v) -> float:
+    v = float(v)
+    if not (math.isfinite(v) and v >= 0.0):
+        raise ValueError(f"'{name}' must be finite and >= 0 (got {v})")
+    return v
+
+
+def _check_weight(weight) -> Optional[list]:
+    if weight is None:
+        return None
+    w = [float(v) for v in (weight.tolist() if isinstance(weight, torch.Tensor) else weight)]
+    if not w or any(not math.isfinite(v) or v < 0.0 for v in w):
+        raise ValueError(f"'class_weights' must be finite and >= 0 (got {w})")
+    return w
+
+
+class DiceLoss(_FusedLoss):
+    """Fused softmax + one-hot + Dice (MONAI defaults: include_background, smooth 1e-5, mean).
+    ``include_background=False`` drops class 0 after the softmax (mean over N * (K - 1)); it runs on the
+    Dice + cross-entropy kernels with ``lambda_ce = 0``, the default on the Dice-only kernels."""
 
     def __init__(self, to_onehot_y: bool = True, softmax: bool = True, smooth_nr: float = 1e-5,
-                 smooth_dr: float = 1e-5):
+                 smooth_dr: float = 1e-5, include_background: bool = True):
         super().__init__()
         if not (to_onehot_y and softmax):
             raise NotImplementedError("the HIP Dice kernel implements to_onehot_y=True, softmax=True "
                                       "(the configuration segmantic uses)")
         self.smooth_nr, self.smooth_dr = smooth_nr, smooth_dr
-        self._state = _DiceState()
+        self.include_background = bool(include_background)
+        self._state = _DiceState() if self.include_background else _DiceCEState()
 
-    def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        """logits [N,K,D,H,W] (float32/bfloat16/float16), labels [N,1,D,H,W] integer-valued."""
-        if logits.requires_grad and torch.is_grad_enabled():
-            return _DiceFn.apply(logits, labels, self)
-        lg = as_ndhwc(logits)
-        return dice_forward(self._state, lg, labels, self.smooth_nr, self.smooth_dr).clone()
+    def forward_ndhwc(self, logits_ndhwc: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """NDHWC logits (K real classes; the row stride may be larger) -> 0-d loss on the device"""
+        if self.include_background:
+            return dice_forward(self._state, logits_ndhwc, labels, self.smooth_nr, self.smooth_dr)
+        return dice_ce_forward(self._state, logits_ndhwc, labels, self.smooth_nr, self.smooth_dr, 1.0, 0.0,
+                               False, None)
+
+    def backward_ndhwc(self, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
+                       out: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
+                       amp: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dlogits of the last ``forward_ndhwc`` (see ``dice_backward`` for ``bias_grad`` / ``amp``)"""
+        fn = dice_backward if self.include_background else dice_ce_backward
+        return fn(self._state, logits_ndhwc, grad_scale, out, bias_grad=bias_grad, amp=amp)
+
+
+class DiceCELoss(_FusedLoss):
+    """``lambda_dice * Dice + lambda_ce * CE`` in the two passes of the Dice kernels (MONAI's ``DiceCELoss``
+    with ``to_onehot_y=True, softmax=True``).
+
+    Dice is ``DiceLoss`` (``include_background`` applies to this term only).  CE is
+    ``F.cross_entropy(logits, labels[:, 0].long(), weight=weight, reduction="mean")`` over every voxel of the
+    batch and all K classes: ``sum_v w[y_v] * -log p_{v,y_v} / W`` with ``W = sum_v w[y_v]`` batch-global (NaN when
+    ``W = 0``, as in torch).  A voxel whose label lies outside ``[0, K)`` contributes to neither CE nor ``W``
+    (nor to the Dice target sums).  ``weight``: K finite values >= 0 (its length is checked against the logits
+    at the first call).  Under data parallelism every rank normalises by its own ``W`` and the gradient
+    all-reduce averages the ranks, as torch DDP does with this loss."""
+
+    def __init__(self, include_background: bool = True, to_onehot_y: bool = True, softmax: bool = True,
+                 lambda_dice: float = 1.0, lambda_ce: float = 1.0, weight=None, smooth_nr: float = 1e-5,
+                 smooth_dr: float = 1e-5):
+        super().__init__()
+        if not (to_onehot_y and softmax):
+            raise NotImplementedError("the HIP Dice + cross-entropy kernels implement to_onehot_y=True, "
+                                      "softmax=True")
+        self.include_background = bool(include_background)
+        self.lambda_dice = _check_lambda("lambda_dice", lambda_dice)
+        self.lambda_ce = _check_lambda("lambda_ce", lambda_ce)
+        self.weight = _check_weight(weight)
+        self.smooth_nr, self.smooth_dr = smooth_nr, smooth_dr
+        self._state = _DiceCEState()
+
+    def forward_ndhwc(self, logits_ndhwc: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        return dice_ce_forward(self._state, logits_ndhwc, labels, self.smooth_nr, self.smooth_dr,
+                               self.lambda_dice, self.lambda_ce, self.include_background, self.weight)
+
+    def backward_ndhwc(self, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
+                       out: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
+                       amp: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return dice_ce_backward(self._state, logits_ndhwc, grad_scale, out, bias_grad=bias_grad, amp=amp)
+
+
+# ------------------------------------------------------------------ configuration
+LOSS_NAMES = ("Dice", "DiceCE", "CE")
+_LOSS_KEYS = {"Dice": ("name", "include_background"),
+              "DiceCE": ("name", "include_background", "lambda_dice", "lambda_ce", "class_weights"),
+              "CE": ("name", "lambda_ce", "class_weights")}
+
+
+def loss_from_config(cfg, num_classes: Optional[int] = None) -> torch.nn.Module:
+    """The loss object of ``optimizer["loss"]``: ``None`` -> ``DiceLoss()``; else a dictionary
+    ``{name: Dice | DiceCE | CE, include_background, lambda_dice, lambda_ce, class_weights}`` (``CE`` is
+    ``DiceCE`` with ``lambda_dice = 0``).  Raises ``ValueError`` naming the offending key; touches no device.
+    ``num_classes`` (when known) checks the length of ``class_weights``."""
+    if cfg is None:
+        return DiceLoss(to_onehot_y=True, softmax=True)
+    if not isinstance(cfg, dict):
+        raise ValueError(f"'loss' must be a dictionary with a 'name' in {LOSS_NAMES} (got {cfg!r})")
+    name = cfg.get("name", "Dice")
+    if name not in LOSS_NAMES:
+        raise ValueError(f"'loss': unknown 'name' {name!r}; expected one of {LOSS_NAMES}")
+    unknown = [k for k in cfg if k not in _LOSS_KEYS[name]]
+    if unknown:
+        raise ValueError(f"'loss': unknown key {unknown[0]!r} for name {name!r}; expected {_LOSS_KEYS[name]}")
+    include_background = cfg.get("include_background", True)
+    if not isinstance(include_background, bool):
+        raise ValueError(f"'loss': 'include_background' must be true or false (got {include_background!r})")
+    if not include_background and num_classes is not None and num_classes < 2:
+        raise ValueError("'loss': 'include_background' = false needs more than one class")
+    if name == "Dice":
+        return DiceLoss(to_onehot_y=True, softmax=True, include_background=include_background)
+    weights = cfg.get("class_weights")
+    if weights is not None:
+        if not isinstance(weights, (list, tuple)):
+            raise ValueError(f"'loss': 'class_weights' must be a list of numbers (got {weights!r})")
+        if num_classes is not None and len(weights) != num_classes:
+            raise ValueError(f"'loss': 'class_weights' has {len(weights)} entries, 'num_classes' is {num_classes}")
+    try:
+        return DiceCELoss(include_background=include_background,
+                          lambda_dice=0.0 if name == "CE" else cfg.get("lambda_dice", 1.0),
+                          lambda_ce=cfg.get("lambda_ce", 1.0), weight=weights)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"'loss': {e}") from e
 
 
 class DiceMetric:

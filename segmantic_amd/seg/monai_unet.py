@@ -10,6 +10,7 @@ IEEE fp16 storage with f32 accumulation, f32 master weights and dynamic loss sca
 ``precision=16`` AMP (``:424,533``) -- (``seg/amp.py``); ``False`` selects the exact-f32 MFMA path used for
 parity.
 """
+import copy
 import json
 import os
 import re
@@ -26,8 +27,7 @@ from ..image.labels import load_decathlon_tissuelist, load_tissue_list
 from .distributed import (GradSync, broadcast_buffers, env_world, init_distributed,
                           rank_device_index)
 from .inferers import SlidingWindowInferer, sliding_window_inference
-from .losses import (ConfusionMatrixMetric, DiceLoss, DiceMetric, as_ndhwc, dice_backward,
-                     dice_forward)
+from .losses import ConfusionMatrixMetric, DiceLoss, DiceMetric, as_ndhwc, loss_from_config
 from .optim import make_optimizer, make_scheduler
 from .unet import UNetEngine, UNetParams
 from .utils import make_device
@@ -96,6 +96,7 @@ class Net(torch.nn.Module):
                                  num_res_units=2, act=act, dropout=dropout)
         self.spatial_size = list(spatial_size) if spatial_size else [96] * 3
         self.loss_function = DiceLoss(to_onehot_y=True, softmax=True)
+        self._loss_cfg = (None,)          # the optimizer["loss"] entry loss_function was built from
         self.dice_metric = DiceMetric(num_classes, include_background=False)
         self.best_val_dice = 0.0
         self.best_val_epoch = 0.0
@@ -239,7 +240,17 @@ class Net(torch.nn.Module):
         return self._engine_for().window_views_ok(dtype)
 
     # ------------------------------------------------------------------ optimisers
+    def configure_loss(self):
+        """``self.loss_function`` from ``self.optimizer["loss"]`` (absent: the default ``DiceLoss``); a bad entry
+        raises ``ValueError`` naming its key.  The object is rebuilt only when the entry changed."""
+        cfg = (self.optimizer or {}).get("loss")
+        if self._loss_cfg != (cfg,):
+            self.loss_function = loss_from_config(cfg, self.num_classes)
+            self._loss_cfg = (copy.deepcopy(cfg),)
+        return self.loss_function
+
     def configure_optimizers(self):
+        self.configure_loss()
         eng = self._engine_for()
         self._opt = make_optimizer(self.optimizer, eng.flat, eng.flat_grad)
         self._sched = make_scheduler(self.lr_scheduling, self._opt)
@@ -264,8 +275,9 @@ class Net(torch.nn.Module):
 
     # ------------------------------------------------------------------ steps
     def training_step(self, batch, batch_idx=0):
-        """reference ``:339-348``: forward -> zero_grad -> Dice -> backward -> optimizer.step,
-        as explicit kernel sequences (no autograd graph)."""
+        """reference ``:339-348``: forward -> zero_grad -> loss -> backward -> optimizer.step,
+        as explicit kernel sequences (no autograd graph).  The loss is whatever ``self.loss_function`` is
+        (``configure_loss``), driven through its ``forward_ndhwc`` / ``backward_ndhwc``."""
         images, labels = batch["image"], batch["label"]
         eng = self._engine_for(images)
         # a one-launch BatchNorm backward of an earlier step that gave up its bounded wait wrote NaN gradients:
@@ -274,15 +286,14 @@ class Net(torch.nn.Module):
         with torch.cuda.device(eng.device):
             opt = self.optimizers()
             logits = eng.forward(images, train=True)
-            st = self.loss_function._state
-            loss = dice_forward(st, logits, labels, self.loss_function.smooth_nr,
-                                self.loss_function.smooth_dr)
-            # fp16: the Dice gradient is multiplied by the loss scale (device memory), and the weight gradients
+            loss_fn = self.loss_function
+            loss = loss_fn.forward_ndhwc(logits, labels)
+            # fp16: the loss gradient is multiplied by the loss scale (device memory), and the weight gradients
             # are not carried over the end of the step -- the Inf / NaN check must see the whole arena before
             # any of it is applied (all-or-nothing skip)
             scaler = self.grad_scaler() if eng.dtype == torch.float16 else None
-            dlogits = dice_backward(st, logits, 1.0, eng.dlogits_buffer(logits),
-                                    bias_grad=eng.top_bias_grad(), amp=scaler.amp if scaler else None)
+            dlogits = loss_fn.backward_ndhwc(logits, 1.0, eng.dlogits_buffer(logits),
+                                             bias_grad=eng.top_bias_grad(), amp=scaler.amp if scaler else None)
             if self._gsync is not None:
                 self._gsync.start()
             carried = eng.backward(dlogits, top_bias_done=True, carry=self._gsync is None and scaler is None)
@@ -431,6 +442,9 @@ def train(
     from .trainer import fit
 
     from . import launch
+    # the objective rides in optimizer["loss"]: a bad entry fails here, before any rank is started or any device
+    # call is made (the class-weight length is checked again once the class count is known)
+    loss_from_config((optimizer or {}).get("loss"), num_classes if num_classes > 0 else None)
     n_ranks = len(list(gpu_ids or []))
     if n_ranks > 1 and not launch.under_launcher():
         # several gpu_ids: one process per GPU, started from here as children of this process --
@@ -519,6 +533,7 @@ def train(
             if plan["spatial_size"] and not spatial_size:
                 net.spatial_size = [int(v) for v in plan["spatial_size"]]
     net.optimizer = optimizer
+    net.configure_loss()
     net.lr_scheduling = lr_scheduling
     net.cache_rate = cache_rate
     # True / False as before; "bf16" / "fp16" (YAML / JSON) select the 16-bit format; a bad string fails here
