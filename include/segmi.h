@@ -483,6 +483,35 @@ int segmi_argmax(int dtype, const segmi_act* logits, void* labels, int label_byt
 int segmi_label_counts(const int32_t* pred, const int32_t* truth, int64_t n, int k,
                        int64_t* counts, void* stream);
 
+/* ---------------------------------------------------------------- test-time augmentation */
+/* Mirror test-time augmentation and uncertainty read-out (no counterpart in the
+ * reference, the definitions are this project's).  2 <= K <= 512 everywhere.
+ *
+ * One pass: `logits` f32 [1][d][h][w][K] (ld >= K) is the network's result on the volume mirrored along
+ * the spatial axes whose bit is set in flip_mask (bit 0 = d, 1 = h, 2 = w).  For output voxel v the
+ * source voxel is u, u_a = n_a - 1 - v_a on the mirrored axes; with m = max_c l_c, e_c = expf(l_c - m),
+ * s = e_0 + e_1 + ... (ascending c) and p_c = e_c / s, acc[v][c] = p_c when `first`, else acc + p_c.
+ * acc: dense f32 [d][h][w][K].  One read of the logits and one read-modify-write of acc per pass; the
+ * caller fixes the pass order, so repeated runs are bit-identical. */
+int segmi_tta_accumulate(const segmi_act* logits, int flip_mask, float* acc, int first, void* stream);
+/* scores: non-negative f32, k channels (the accumulator, or what the inverse pre-processing chain made
+ * of it: all-zero voxels outside the crop, border voxels that sum to less than the pass count).  Per
+ * voxel s = sum_c scores_c (ascending c); s == 0: label 0, confidence 1, entropy 0, probabilities
+ * (1, 0, ...); otherwise q_c = scores_c / s, label = first maximum of q (the rule of segmi_argmax),
+ * confidence = q_label, entropy = -(sum_c q_c logf(q_c)) / logf(k) with 0 log 0 = 0, summed in ascending
+ * c and clamped to [0, 1].  labels: label_bytes 1 (k <= 256) or 4.  confidence, entropy (f32 per voxel)
+ * and probs_out (k channels, ld >= k) may each be NULL; probs_out may be `scores` itself. */
+int segmi_tta_finalize(const segmi_act* scores, int k, void* labels, int label_bytes, float* confidence,
+                       float* entropy, const segmi_act* probs_out, void* stream);
+/* Per label c < k: counts[c] (device i64) = voxels with that label, sums[c] (device f64) = the f64 sum
+ * of values over them (labels >= k are skipped; label_bytes 1 or 4; k <= 512).  Deterministic: fixed
+ * per-wave order, fixed-order fold by the workgroup that finishes last (csrc/fin_tail.h protocol on f64
+ * rows); repeated calls are bit-identical.  The partial tables live in library-owned device memory
+ * (4 per device, handed out round-robin: at most 4 calls of one device may be in flight on DIFFERENT
+ * streams; calls on one stream are unlimited). */
+int segmi_label_means(const void* labels, int label_bytes, const float* values, int64_t n, int k, double* sums,
+                      int64_t* counts, void* stream);
+
 /* ---------------------------------------------------------------- image ops ------------ */
 /* ITK ResampleImageFilter replacement, src/segmantic/image/processing.py:49-120.
  * index_map_host: 12 doubles, row-major 3x4 affine taking an output index (x,y,z,1) to the

@@ -157,6 +157,9 @@ SIGNATURES = {
     "segmi_sw_blend_kernel_name": (C.c_char_p, [_i, _P, _i, _i, _P, _i, _P, _i, _P, _i, _i, _i, _i, _P, _i]),
     "segmi_argmax": (_i, [_i, _AP, _P, _i, _P]),
     "segmi_label_counts": (_i, [_P, _P, _i64, _i, _P, _P]),
+    "segmi_tta_accumulate": (_i, [_AP, _i, _P, _i, _P]),
+    "segmi_tta_finalize": (_i, [_AP, _i, _P, _i, _P, _P, _AP, _P]),
+    "segmi_label_means": (_i, [_P, _i, _P, _i64, _i, _P, _P, _P]),
     "segmi_resample3d": (_i, [_i, _P, _i, _i, _i, _P, _i, _i, _i, _P, _i, _d, _P]),
     "segmi_normalize_workspace": (_i64, [_i, _i64]),
     "segmi_normalize_intensity": (_i, [_P, _i, _i64, _P, _P]),

@@ -86,8 +86,16 @@ def predict(
     spacing: List[float] = typer.Option([], "--spacing", help="if specified, the image is first resampled"),
     gpu_ids: List[int] = [0],
     datalist_key: str = "test",
+    tta: bool = typer.Option(False, "--tta/--no-tta", help="mirror test-time augmentation: average the class "
+                                                           "probabilities over the mirrored passes"),
+    tta_flips: str = typer.Option("all", "--tta-flips", help="'all' or passes separated by ',' with the axes of "
+                                                             "a pass joined by '+', 'none' = identity: none,0,1+2"),
+    save_uncertainty: bool = typer.Option(False, "--save-uncertainty",
+                                          help="write <stem>_entropy.nii.gz, <stem>_confidence.nii.gz per case "
+                                               "and uncertainty.csv"),
 ) -> None:
     """Predict segmentations"""
+    from ..seg.tta import parse_flips
     datalist = load_decathlon_datalist(datalist_file, data_list_key=datalist_key)
     test_images = [Path(d["image"]) for d in datalist]
     test_labels = [Path(d["label"]) for d in datalist if "label" in d]
@@ -97,7 +105,8 @@ def predict(
         tissue_dict = load_decathlon_tissuelist(datalist_file)
     _monai_unet().predict(model_file=model_file, test_images=test_images, test_labels=test_labels,
                           tissue_dict=tissue_dict, output_dir=results_dir, spacing=spacing,
-                          gpu_ids=gpu_ids)
+                          gpu_ids=gpu_ids, tta=tta, save_uncertainty=save_uncertainty,
+                          tta_flips=parse_flips(tta_flips))
 
 
 @app.command()

@@ -719,8 +719,70 @@ def label_counts(pred, truth, k, counts) -> None:
                                  _stream()), "label_counts")
 
 
+# ------------------------------------------------------------------ test-time augmentation
+_TTA_LABEL_BYTES = {torch.uint8: 1, torch.int32: 4}
+
+
+def tta_accumulate(logits, flip_mask: int, acc, first: bool) -> None:
+    """logits f32 NDHWC [1, d, h, w, K] of the pass run on the volume mirrored along the axes in ``flip_mask``
+    (bit 0 = d, 1 = h, 2 = w); acc dense f32 [d, h, w, K] receives (``first``) or adds the pass's softmax at the
+    un-mirrored voxel."""
+    if logits.dtype != torch.float32 or acc.dtype != torch.float32:
+        raise TypeError("tta_accumulate: float32 logits and accumulator")
+    a = act(logits)
+    _require_device(acc)
+    if not acc.is_contiguous() or tuple(acc.shape) != (a.d, a.h, a.w, a.c):
+        raise ValueError(f"tta_accumulate: acc must be a dense [d, h, w, K] tensor, got {tuple(acc.shape)} "
+                         f"for logits {tuple(logits.shape)}")
+    check(lib.segmi_tta_accumulate(C.byref(a), int(flip_mask), _ptr(acc), int(bool(first)), _stream()),
+          "tta_accumulate")
+
+
+def tta_finalize(scores, labels, confidence=None, entropy=None, probs_out=None) -> None:
+    """scores f32 NDHWC [n, d, h, w, K] (non-negative) -> labels uint8 / int32 [n, d, h, w] and, each optional,
+    confidence / entropy f32 [n, d, h, w] and the normalised probabilities (NDHWC; may be ``scores`` itself)."""
+    if scores.dtype != torch.float32:
+        raise TypeError("tta_finalize: float32 scores")
+    a = act(scores)
+    nvox = a.n * a.d * a.h * a.w
+    if labels.dtype not in _TTA_LABEL_BYTES:
+        raise TypeError("tta_finalize: labels must be uint8 or int32")
+    for t, what in ((labels, "labels"), (confidence, "confidence"), (entropy, "entropy")):
+        if t is not None and (t.numel() != nvox or not t.is_contiguous()):
+            raise ValueError(f"tta_finalize: {what} must be a dense tensor of {nvox} voxels")
+    for t, what in ((confidence, "confidence"), (entropy, "entropy")):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"tta_finalize: float32 {what}")
+    p = None
+    if probs_out is not None:
+        if probs_out.dtype != torch.float32:
+            raise TypeError("tta_finalize: float32 probs_out")
+        p = act(probs_out)
+    check(lib.segmi_tta_finalize(C.byref(a), a.c, _ptr(labels), _TTA_LABEL_BYTES[labels.dtype], _ptr(confidence),
+                                 _ptr(entropy), _ref(p), _stream()), "tta_finalize")
+
+
+def label_means(labels, values, k: int, sums=None, counts=None):
+    """Per label c < k: (sums f64 [k], counts i64 [k]) of ``values`` (f32) over the voxels of ``labels``
+    (uint8 / int32) with that label; deterministic, on the device."""
+    _require_device(labels)
+    if labels.dtype not in _TTA_LABEL_BYTES or values.dtype != torch.float32:
+        raise TypeError("label_means: uint8 / int32 labels and float32 values")
+    if labels.numel() != values.numel() or not labels.is_contiguous() or not values.is_contiguous():
+        raise ValueError("label_means: labels and values must be dense and of one size")
+    if sums is None:
+        sums = torch.empty(k, dtype=torch.float64, device=labels.device)
+    if counts is None:
+        counts = torch.empty(k, dtype=torch.int64, device=labels.device)
+    if sums.dtype != torch.float64 or counts.dtype != torch.int64 or sums.numel() != k or counts.numel() != k:
+        raise ValueError("label_means: sums f64 [k] and counts i64 [k]")
+    check(lib.segmi_label_means(_ptr(labels), _TTA_LABEL_BYTES[labels.dtype], _ptr(values), labels.numel(), int(k),
+                                _ptr(sums), _ptr(counts), _stream()), "label_means")
+    return sums, counts
+
+
 # ------------------------------------------------------------------ image ops
-_PIXEL = {torch.float32: 0, torch.uint8: 1, torch.int16: 2, torch.int32: 3, torch.uint16: 4}
+_PIXEL ={torch.float32: 0, torch.uint8: 1, torch.int16: 2, torch.int32: 3, torch.uint16: 4}
 
 
 def resample3d(src: torch.Tensor, out_size_zyx, index_map, nearest=False, default=0.0, border=False,

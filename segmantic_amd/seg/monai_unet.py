@@ -631,13 +631,22 @@ def predict(
     dropout: float = 0.0,
     spacing: Sequence[float] = [],
     gpu_ids: List[int] = [],
+    tta: bool = False,
+    save_uncertainty: bool = False,
+    tta_flips="all",
 ) -> None:
     """reference ``:551-725``: load checkpoint, sliding-window inference per volume, invert the
     pre-processing on the logits, argmax, save; with labels: per-volume / total Dice tables and the
     ``ConfusionMatrixMetric`` table (sensitivity, specificity, precision, accuracy).  Not
     reproduced: the per-volume ``*_confusion.png`` plots (matplotlib; out of scope).
     The class-Dice tables are headed by the K-1 foreground tissue names (the reference prints all K
-    names over the K-1 foreground values, one column off)."""
+    names over the K-1 foreground values, one column off).
+
+    ``tta``: mirror test-time augmentation (``seg/tta.py``; ``tta_flips`` = "all" or a list of axis tuples):
+    the class probabilities averaged over the mirrored passes, not the logits, go through the inverse chain
+    and are labelled in the source grid.  ``save_uncertainty``: also write ``<stem>_entropy.nii.gz``,
+    ``<stem>_confidence.nii.gz`` per case and one ``uncertainty.csv`` per run (with ``tta`` off: from the
+    identity pass alone).  With both off the path and its outputs are what they were without these options."""
     from . import launch
     from .pipeline import PredictPipeline
 
@@ -646,7 +655,9 @@ def predict(
         return _predict_in_ranks(len(gpu_ids), dict(
             model_file=model_file, test_images=test_images, test_labels=test_labels, output_dir=output_dir,
             tissue_dict=tissue_dict, channels=channels, strides=strides, dropout=dropout, spacing=spacing,
-            gpu_ids=gpu_ids))
+            gpu_ids=gpu_ids, tta=tta, save_uncertainty=save_uncertainty, tta_flips=tta_flips))
+    if save_uncertainty and not output_dir:
+        raise ValueError("segmantic_amd.predict: save_uncertainty needs an output_dir")
     model_file = Path(model_file)
     settings_json = model_file.with_suffix(".json")
     if settings_json.exists():
@@ -704,17 +715,24 @@ def predict(
     all_mean_dice = []
     class_dice_sum, class_dice_cnt = None, None
     per_volume = []            # (index in test_images, per-class Dice row): what a multi-rank run gathers
+    use_tta = bool(tta) or bool(save_uncertainty)
+    unc_rows = []              # (index in test_images, case, label, name, voxels, mean entropy, mean confidence)
     with torch.no_grad():
         for i, img_path in enumerate(test_images):
             if i % world != rank:
                 continue
             item = pipe.load(img_path, test_labels[i] if use_labels else None)
-            val_pred = inferer(item["image"][None], net)             # [1,K,D,H,W] f32 logits
-            label_vol = pipe.invert_and_discretize(val_pred[0], item)
-            if output_dir:
-                pipe.save(label_vol, item, output_dir)
+            if use_tta:
+                pred_lab = _predict_tta(net, pipe, item, i, tta_flips if tta else [()], save_uncertainty,
+                                        output_dir, tissue_names, unc_rows)
+            else:
+                val_pred = inferer(item["image"][None], net)             # [1,K,D,H,W] f32 logits
+                label_vol = pipe.invert_and_discretize(val_pred[0], item)
+                if output_dir:
+                    pipe.save(label_vol, item, output_dir)
             if use_labels:
-                pred_lab = _argmax_labels(val_pred)
+                if not use_tta:
+                    pred_lab = _argmax_labels(val_pred)
                 d = dice_metric(pred_lab, item["label"][None].long())
                 conf_matrix(pred_lab, item["label"][None].long())
                 dn = d.cpu().numpy()
@@ -727,6 +745,13 @@ def predict(
                 ok = (~np.isnan(dn[0])).astype(np.float64)
                 class_dice_sum = dz if class_dice_sum is None else class_dice_sum + dz
                 class_dice_cnt = ok if class_dice_cnt is None else class_dice_cnt + ok
+        if world > 1 and save_uncertainty:
+            import torch.distributed as dist
+            unc_parts = [None] * world
+            dist.all_gather_object(unc_parts, unc_rows)
+            unc_rows = [r for p in unc_parts for r in p]
+        if save_uncertainty and rank == 0:
+            _write_uncertainty_csv(output_dir / "uncertainty.csv", unc_rows)
         if world > 1:
             import torch.distributed as dist
             parts = [None] * world
@@ -763,6 +788,45 @@ def predict(
     # a process that goes on to train must not find it pinned beside its activations
     from .inferers import release_workspaces
     release_workspaces()
+
+
+def _predict_tta(net, pipe, item, index, flips, save_uncertainty, output_dir, tissue_names, unc_rows):
+    """One volume of ``predict`` with test-time augmentation and / or the uncertainty read-out: saves the label
+    volume (and the maps), appends the case's ``uncertainty.csv`` rows and returns the labels in the network's
+    grid ([1,1,D,H,W] int32) for the Dice and confusion tables."""
+    from .tta import mirror_tta_inference, uncertainty_summary
+    res = mirror_tta_inference(item["image"][None], net.spatial_size, 4, net, flips=flips)
+    K = res.probs.shape[1]
+    scores = pipe.invert_scores(res.probs[0], item)                 # NDHWC in the source grid
+    vox = tuple(scores.shape[1:4])
+    label_vol = torch.empty(vox, dtype=torch.uint8 if K <= 256 else torch.int32, device=scores.device)
+    ent = conf = None
+    if save_uncertainty:
+        ent = torch.empty(vox, dtype=torch.float32, device=scores.device)
+        conf = torch.empty(vox, dtype=torch.float32, device=scores.device)
+    ops.tta_finalize(scores, label_vol, conf, ent)
+    if output_dir:
+        pipe.save(label_vol, item, output_dir)
+    if save_uncertainty:
+        pipe.save_map(ent, item, output_dir, "entropy")
+        pipe.save_map(conf, item, output_dir, "confidence")
+        summ = uncertainty_summary(label_vol, ent, conf, K)
+        case = item["path"].name
+        for c in range(K):
+            unc_rows.append((index, case, c, tissue_names[c], int(summ["voxels"][c]),
+                             float(summ["mean_entropy"][c]), float(summ["mean_confidence"][c])))
+    return res.labels.to(torch.int32)
+
+
+def _write_uncertainty_csv(path: Path, rows) -> None:
+    """one row per case and label, cases in the order of ``test_images``"""
+    import csv
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["case", "label", "name", "voxels", "mean_entropy", "mean_confidence"])
+        for r in sorted(rows, key=lambda r: (r[0], r[2])):
+            w.writerow([r[1], r[2], r[3], r[4], repr(r[5]) if r[5] == r[5] else "nan",
+                        repr(r[6]) if r[6] == r[6] else "nan"])
 
 
 def _argmax_labels(logits: torch.Tensor) -> torch.Tensor:

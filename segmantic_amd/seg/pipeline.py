@@ -212,6 +212,26 @@ class PredictPipeline:
         ops.argmax(nd, lab)
         return lab
 
+    def invert_scores(self, scores: torch.Tensor, item: Dict) -> torch.Tensor:
+        """scores [K, x, y, z] (non-negative per-class scores, e.g. averaged probabilities) -> NDHWC
+        [1, x0, y0, z0, K] float32 in the source image's voxel grid: the inverse chain of
+        ``invert_and_discretize`` (inverse Spacing, un-crop with zeros, inverse orientation) without the
+        argmax.  Voxels outside the crop are all zero; ``ops.tta_finalize`` labels them background."""
+        sc = scores.float().contiguous()
+        if self.spacing:
+            sc = affine_resample(sc, item["affine"], item["affine_crop"], item["shape_crop"])
+        lo, hi, full = item["crop"]
+        out = torch.zeros((sc.shape[0],) + tuple(full), dtype=torch.float32, device=sc.device)
+        out[(slice(None),) + tuple(slice(l, h) for l, h in zip(lo, hi))] = sc
+        out = from_ras(out, item["ornt"])
+        return out.permute(1, 2, 3, 0).contiguous()[None]
+
+    def save_map(self, vol: torch.Tensor, item: Dict, output_dir: Path, postfix: str) -> Path:
+        """a float32 voxel map [x0, y0, z0] in the source grid -> <stem>_<postfix>.nii.gz with the source affine"""
+        out = Path(output_dir) / f"{strip_image_suffix(item['path'].name)}_{postfix}.nii.gz"
+        write_image(out, vol.float().cpu().numpy().transpose(2, 1, 0), item["affine0"])
+        return out
+
     def save(self, label_vol: torch.Tensor, item: Dict, output_dir: Path) -> Path:
         # MONAI SaveImaged(output_postfix="", separate_folder=False): <stem>.nii.gz (the default output_ext)
         out = Path(output_dir) / f"{strip_image_suffix(item['path'].name)}.nii.gz"
