@@ -28,6 +28,28 @@ value).  Where ``|ref|`` clears 65520 by more than the accumulation term the out
 ``±Inf`` with the sign of ``ref``; where it is below 65520 by that margin it must be finite and inside
 the bound; in the band between either is accepted.  A store that saturates to 65504 fails.  NaN in
 the output is never accepted unless ``ref`` is NaN.
+
+Other storage types.  ``bound``, ``ratio`` and ``assert_within`` take the storage type of the output
+(``"f16"``, the default, ``"bf16"`` or ``"f32"``, or the torch dtype).  Per element:
+
+    |got - ref| <= 1.05 * 2^-8  * |ref| + 2^-18 * A                  (bf16 output)
+    |got - ref| <= 1.05 * 2^-24 * |ref| + 2^-18 * A                  (f32 output, ``rounded=True``)
+    |got - ref| <=                        2^-18 * A                  (f32 accumulator: ``rounded=False``)
+
+* bf16 keeps 8 significand bits (7 stored and the implicit one): a value in [2^e, 2^(e+1)) lies on a grid of
+  spacing 2^(e-7), so rounding to nearest moves it by at most 2^(e-8) <= 2^-8 |v|.  A store that truncates
+  errs by up to a whole spacing, 2^-7 |v|, one-sidedly: on U(-1, 1) convolutions 18-24 % of its elements
+  leave this bound while its max-norm error (0.4-0.7 %) stays inside a 1.5 % gate.
+* f32 keeps 24 significand bits, so each rounding of a value to f32 moves it by at most 2^-24 |v|.  An f32
+  kernel rounds its operands nowhere; the term stands for the last f32 operation of the epilogue (bias,
+  PReLU or residual add) on the result, the earlier ones being part of the chain the ``A`` term covers.
+  Operands rounded through bf16 err by 2^-9 of a product each, 2^9 times the ``A`` term's unit.
+* The factor 1.05 is the same allowance as for fp16: the f32 sum may lie across a rounding boundary from
+  the float64 sum.  ``2^-18 A`` is the same f32 accumulation term: the accumulator is f32 for every type.
+* No absolute floor: the subnormal range of bf16 and f32 starts at 2^-126, far below these magnitudes.
+  Where the bound is 0 (``A == 0``: every product is zero) only the exact result is accepted.
+* No overflow band.  A non-finite output is accepted only where ``ref`` is non-finite: ``±Inf`` of the same
+  sign for an infinite ``ref``, NaN for a NaN ``ref``.
 """
 from __future__ import annotations
 
@@ -39,13 +61,32 @@ REL_ACC = 2.0 ** -18               # f32 accumulation, relative to A = op(|opera
 ABS_FLOOR = 2.0 ** -25             # half the fp16 subnormal spacing
 F16_OVERFLOW = 65520.0             # round-to-nearest-even threshold of fp16 overflow
 HALF_OUT_MIN_RATIO = 4.0           # a bf16-rounded output must exceed the bound by this factor
+REL_BF16 = 1.05 * 2.0 ** -8        # one bf16 output rounding (8 significand bits), with the same 5 % margin
+REL_F32 = 1.05 * 2.0 ** -24        # one f32 rounding of the result (24 significand bits), same margin
 
-__all__ = ["REL_HALF", "REL_ACC", "ABS_FLOOR", "F16_OVERFLOW", "HALF_OUT_MIN_RATIO", "bound", "ratio",
-           "assert_within", "conv_ref", "convT_ref", "wgrad_ref", "flush_f16_subnormals"]
+__all__ = ["REL_HALF", "REL_ACC", "ABS_FLOOR", "F16_OVERFLOW", "HALF_OUT_MIN_RATIO", "REL_BF16", "REL_F32",
+           "storage_of", "bound", "ratio", "assert_within", "conv_ref", "convT_ref", "wgrad_ref", "flush_f16_subnormals"]
 
 
-def bound(ref: torch.Tensor, absref: torch.Tensor, rounded: bool = True) -> torch.Tensor:
+_STORAGE = {"f16": "f16", "fp16": "f16", torch.float16: "f16", "bf16": "bf16", torch.bfloat16: "bf16",
+            "f32": "f32", "fp32": "f32", torch.float32: "f32"}
+_REL = {"bf16": REL_BF16, "f32": REL_F32}
+
+
+def storage_of(storage) -> str:
+    """'f16' / 'bf16' / 'f32' for a storage-type name or torch dtype"""
+    try:
+        return _STORAGE[storage]
+    except KeyError:
+        raise ValueError(f"unknown storage type {storage!r}: expected f16, bf16, f32 or their torch dtypes") from None
+
+
+def bound(ref: torch.Tensor, absref: torch.Tensor, rounded: bool = True, storage="f16") -> torch.Tensor:
     ref, absref = ref.double(), absref.double()
+    storage = storage_of(storage)
+    if storage != "f16":
+        b = REL_ACC * absref
+        return b + _REL[storage] * ref.abs() if rounded else b
     b = REL_ACC * absref + ABS_FLOOR
     if rounded:
         b = b + REL_HALF * ref.abs()
@@ -62,11 +103,31 @@ def _classify(ref, absref, rounded):
     return ref.abs() - slack >= F16_OVERFLOW, ref.abs() + slack < F16_OVERFLOW
 
 
-def ratio(got: torch.Tensor, ref: torch.Tensor, absref: torch.Tensor, rounded: bool = True) -> torch.Tensor:
+def _ratio_wide(got, ref, absref, rounded, storage):
+    """bf16 / f32 storage: no overflow band, no floor (a zero bound accepts the exact result only)"""
+    b = bound(ref, absref, rounded, storage)
+    zero, inf = torch.zeros_like(ref), torch.full_like(ref, float("inf"))
+    fin = torch.isfinite(ref) & torch.isfinite(got)
+    err = torch.where(fin, got - ref, zero).abs()
+    r = torch.where(b > 0, err / torch.where(b > 0, b, torch.ones_like(b)), torch.where(err == 0, zero, inf))
+    r = torch.where(torch.isnan(r), inf, r)                    # a NaN bound (NaN in A) accepts nothing
+    r = torch.where(torch.isfinite(got), r, inf)               # finite reference: the output must be finite
+    right_inf = torch.isinf(got) & (torch.sign(got) == torch.sign(ref))
+    r = torch.where(torch.isinf(ref), torch.where(right_inf, zero, inf), r)
+    return torch.where(torch.isnan(ref), torch.where(torch.isnan(got), zero, inf), r)
+
+
+def ratio(got: torch.Tensor, ref: torch.Tensor, absref: torch.Tensor, rounded: bool = True,
+          storage="f16") -> torch.Tensor:
     """Per-element |got - ref| / bound on the elements that must be finite; +inf where an element that
     must overflow is not ±Inf of the right sign, or where a finite element is not finite.  Elements in
-    the overflow band are 0 when they are ±Inf of the right sign or finite within the bound at 65504."""
+    the overflow band are 0 when they are ±Inf of the right sign or finite within the bound at 65504.
+    bf16 and f32 storage have no overflow band: +inf wherever the output is non-finite and the reference
+    is not non-finite in the same way, and wherever a zero bound is missed."""
     got, ref, absref = got.double().cpu(), ref.double().cpu(), absref.double().cpu()
+    storage = storage_of(storage)
+    if storage != "f16":
+        return _ratio_wide(got, ref, absref, rounded, storage)
     must_inf, must_fin = _classify(ref, absref, rounded)
     r = torch.zeros_like(ref)
     b = bound(ref, absref, rounded)
@@ -84,15 +145,16 @@ def ratio(got: torch.Tensor, ref: torch.Tensor, absref: torch.Tensor, rounded: b
     return r
 
 
-def assert_within(got, ref, absref, rounded: bool = True, what: str = "") -> float:
+def assert_within(got, ref, absref, rounded: bool = True, what: str = "", storage="f16") -> float:
     """Assert the bound on every element; returns the worst ratio (for reports)."""
-    r = ratio(got, ref, absref, rounded)
+    r = ratio(got, ref, absref, rounded, storage)
+    name = {"f16": "fp16", "bf16": "bf16", "f32": "f32"}[storage_of(storage)]
     worst = float(r.max()) if r.numel() else 0.0
     if not worst <= 1.0:
         bad = r > 1.0
         i = int(torch.argmax(torch.where(torch.isnan(r), torch.full_like(r, float("inf")), r)))
         g, f, a = got.double().cpu().flatten()[i], ref.double().cpu().flatten()[i], absref.double().cpu().flatten()[i]
-        raise AssertionError(f"{what}: {int(bad.sum())}/{r.numel()} elements outside the fp16 bound, worst "
+        raise AssertionError(f"{what}: {int(bad.sum())}/{r.numel()} elements outside the {name} bound, worst "
                              f"ratio {worst:.3g} at flat index {i}: got {float(g)!r}, ref {float(f)!r}, A {float(a)!r}")
     return worst
 

@@ -2,8 +2,9 @@
 UNet / DiceLoss reduce to, see oracle/unet_ref.py).  Tolerances are written next to each check:
 f32 kernels are exact-f32 MFMA chains (only the summation order differs from oneDNN), bf16
 kernels are compared against the oracle evaluated on bf16-rounded inputs.  fp16 kernels are compared the same
-way at a tighter tolerance and, where a test has a float64 reference of the same op, element by element against
-the bound of tests/helpers/lowp_bounds.py (one output rounding + f32 accumulation noise).
+way at a tighter tolerance.  Where a test has a float64 reference of the same op, every storage type (f32, bf16,
+fp16) is also held element by element to the bound of tests/helpers/lowp_bounds.py for that type (one output
+rounding + f32 accumulation noise); each such test reports its worst ratio with record_property.
 """
 import math
 import os
@@ -55,10 +56,34 @@ def tol(dtype):
     return F32_RTOL if dtype == torch.float32 else BF16_RTOL
 
 
-def f16_bound(dtype, got, ref, absref, what=""):
-    """fp16 only: every element of ``got`` (NCDHW) inside the lowp_bounds bound around the float64 ``ref``"""
-    if dtype == torch.float16:
-        lb.assert_within(got, ref, absref, what=what)
+_REPORT = []
+
+
+@pytest.fixture(autouse=True)
+def _ratio_report(record_property):
+    """elem_bound() reports the worst ratio of each check as a property of the running test"""
+    _REPORT.append(record_property)
+    yield
+    _REPORT.clear()
+
+
+def elem_bound(dtype, got, ref, absref, what="out", rounded=True):
+    """every element of ``got`` inside the lowp_bounds bound of the storage type ``dtype`` around the float64 ``ref``
+    (``rounded=False``: an f32 accumulator output of a kernel whose operands are stored as ``dtype``)"""
+    worst = lb.assert_within(got, ref, absref, rounded=rounded, what=what, storage=dtype)
+    if _REPORT:
+        _REPORT[0](f"worst ratio {what}", float(f"{worst:.4g}"))
+    return worst
+
+
+def wgrad_bound(dtype, x, dy, k, s, dw, db=None, what=""):
+    """dw (and db) of a weight-gradient kernel against lb.wgrad_ref on the operands it reads: f32 accumulator
+    outputs, so the bound is the accumulation term alone for every storage type"""
+    dw_ref, a_dw, db_ref, a_db = lb.wgrad_ref(q(x, dtype), q(dy, dtype), k, s)
+    for one in (dw if isinstance(dw, (list, tuple)) else [dw]):
+        elem_bound(dtype, one.cpu(), dw_ref, a_dw, what=f"dw{what}", rounded=False)
+    if db is not None:
+        elem_bound(dtype, db.cpu(), db_ref, a_db, what=f"db{what}", rounded=False)
 
 
 def epilogue64(ref, absref, alpha=None, res=None):
@@ -114,10 +139,9 @@ def test_conv3d_fwd(case, dtype):
     torch.cuda.synchronize()
     got = from_ndhwc(yd)
     assert relerr(got, ref) < tol(dtype)
-    if dtype == F16:
-        # the direct kernel reads the f32 weights as they are; the MFMA kernels (small-Cin included) round them
-        wq = w if "direct" in ops.conv3d_fwd_kernel_name(xd, yd, k, s) else q(w, dtype)
-        f16_bound(dtype, got, *lb.conv_ref(q(x, dtype), wq, b, stride=s, padding=(k - 1) // 2))
+    # the direct kernel reads the f32 weights as they are; the MFMA kernels (small-Cin included) round them
+    wq = w if "direct" in ops.conv3d_fwd_kernel_name(xd, yd, k, s) else q(w, dtype)
+    elem_bound(dtype, got, *lb.conv_ref(q(x, dtype), wq, b, stride=s, padding=(k - 1) // 2))
     # fused statistics: per-channel sum / sum of squares of the (pre-rounding) conv output
     ssum = stats[:, 0].double().sum(0).cpu()
     ssq = stats[:, 1].double().sum(0).cpu()
@@ -159,7 +183,7 @@ def test_conv3d_fwd_pair_equals_two_convs(dtype, cin, cout, stride, sp):
             assert torch.equal(st1[:real], st2[:real])
     ref = F.conv3d(q(x, dtype), q(wb, dtype), bb, stride=stride, padding=1)
     assert relerr(from_ndhwc(pb), ref) < tol(dtype)
-    f16_bound(dtype, from_ndhwc(pb), *lb.conv_ref(q(x, dtype), q(wb, dtype), bb, stride=stride, padding=1))
+    elem_bound(dtype, from_ndhwc(pb), *lb.conv_ref(q(x, dtype), q(wb, dtype), bb, stride=stride, padding=1))
     # MFMA-shaped layers do not qualify
     big = torch.empty((1, 4, 4, 4, 16), dtype=dtype, device=DEV)
     assert not ops.conv3d_pair_ok(big, big.clone(), big.clone())
@@ -240,8 +264,8 @@ def test_conv3d_epilogue_prelu_residual_and_views(dtype):
                    prelu_alpha=ad, residual=rd)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(big_out[..., 16:32]), ref) < tol(dtype)
-    f16_bound(dtype, from_ndhwc(big_out[..., 16:32]),
-              *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), alpha, q(r, dtype)))
+    elem_bound(dtype, from_ndhwc(big_out[..., 16:32]),
+               *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), alpha, q(r, dtype)))
     assert float(big_out[..., :16].float().abs().max()) == 0.0
 
 
@@ -305,9 +329,9 @@ def test_conv_ring3_dma_ring_ragged_and_segmented_shapes(n, sp, mode, dtype=torc
     assert bool(torch.isfinite(got).all())                          # every voxel written (the output started as NaN)
     assert relerr(got, ref) < tol(dtype)
     if mode == "plain":
-        f16_bound(dtype, got, *lb.conv_ref(q(x, dtype), q(w, dtype)))
+        elem_bound(dtype, got, *lb.conv_ref(q(x, dtype), q(w, dtype)))
     elif mode == "alpha_res_stats":
-        f16_bound(dtype, got, *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), 0.3, q(r, dtype)))
+        elem_bound(dtype, got, *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), 0.3, q(r, dtype)))
 
 
 @pytest.mark.parametrize("n,sp,mode", [(4, (18, 64, 120), "tf_identity"), (1, (64, 64, 128), "tf_identity"),
@@ -335,7 +359,7 @@ def test_conv3d_ring_kernel_epilogue(dtype):
                    residual=rd, stats=stats)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(yd), ref) < tol(dtype)
-    f16_bound(dtype, from_ndhwc(yd), *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), 0.3, q(r, dtype)))
+    elem_bound(dtype, from_ndhwc(yd), *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), 0.3, q(r, dtype)))
     ssum = stats[:, 0].double().sum(0).cpu()
     assert float((ssum - raw.double().sum((0, 2, 3, 4))).abs().max()) / (raw.numel() / c) < \
         (1e-5 if dtype == torch.float32 else 2e-2) * float(raw.abs().max())
@@ -361,7 +385,7 @@ def test_conv3d_ksplit_kernel_epilogue(dtype):
                    prelu_alpha=torch.tensor([0.3], device=DEV), residual=rd, stats=stats)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(yd), ref) < tol(dtype)
-    f16_bound(dtype, from_ndhwc(yd), *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), 0.3, q(r, dtype)))
+    elem_bound(dtype, from_ndhwc(yd), *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), 0.3, q(r, dtype)))
     ssum = stats[:, 0].double().sum(0).cpu()
     assert float((ssum - raw.double().sum((0, 2, 3, 4))).abs().max()) / (raw.numel() / cout) < \
         (1e-5 if dtype == torch.float32 else 2e-2) * float(raw.abs().max())
@@ -389,7 +413,7 @@ def test_conv3d_ring_kernel_identity_residual(dtype, c, sp):
     torch.cuda.synchronize()
     assert torch.equal(y1, y2)
     assert relerr(from_ndhwc(y1), ref) < tol(dtype)
-    f16_bound(dtype, from_ndhwc(y1), *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), None, q(x, dtype)))
+    elem_bound(dtype, from_ndhwc(y1), *epilogue64(*lb.conv_ref(q(x, dtype), q(w, dtype), b), None, q(x, dtype)))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -407,9 +431,8 @@ def test_conv3d_dgrad_s1(case, dtype):
     ops.conv3d_fwd(dyd, dxd, packed, wd, 1, None, 3, 1)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(dxd), ref) < tol(dtype)
-    if dtype == F16:
-        wq = q(w, dtype) if packed is not None else w
-        f16_bound(dtype, from_ndhwc(dxd), *lb.convT_ref(q(dy, dtype), wq, stride=1, padding=1, output_padding=0))
+    wq = q(w, dtype) if packed is not None else w
+    elem_bound(dtype, from_ndhwc(dxd), *lb.convT_ref(q(dy, dtype), wq, stride=1, padding=1, output_padding=0))
 
 
 CONVT_CASES = [
@@ -469,9 +492,8 @@ def test_convT3d_fwd(case, dtype):
     ops.convT3d_fwd(xd, yd, packed, wd, bd, stats=stats)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(yd), ref) < tol(dtype)
-    if dtype == F16:
-        wq = q(w, dtype) if packed is not None else w
-        f16_bound(dtype, from_ndhwc(yd), *lb.convT_ref(q(x, dtype), wq, b, output_padding=0 if odd else 1))
+    wq = q(w, dtype) if packed is not None else w
+    elem_bound(dtype, from_ndhwc(yd), *lb.convT_ref(q(x, dtype), wq, b, output_padding=0 if odd else 1))
     ssum = stats[:, 0].double().sum(0).cpu()
     rs = ref.double().sum((0, 2, 3, 4))
     assert float((ssum - rs).abs().max()) / (ref.numel() / cout) < (1e-5 if dtype == torch.float32 else 2e-2) * float(ref.abs().max())
@@ -499,7 +521,7 @@ def test_convT3d_epilogue_prelu_residual(case, dtype):
     ops.convT3d_fwd(xd, yd, packed, wd, b.to(DEV), prelu_alpha=alpha.to(DEV), residual=rd)
     torch.cuda.synchronize()
     assert relerr(from_ndhwc(yd), ref) < tol(dtype)
-    f16_bound(dtype, from_ndhwc(yd), *epilogue64(*lb.convT_ref(q(x, dtype), q(w, dtype), b), 0.2, q(res, dtype)))
+    elem_bound(dtype, from_ndhwc(yd), *epilogue64(*lb.convT_ref(q(x, dtype), q(w, dtype), b), 0.2, q(res, dtype)))
 
 
 WGRAD_CASES = [
@@ -542,6 +564,7 @@ def test_conv3d_wgrad(case, dtype):
     # bf16 inputs are exact products in f32; only summation order differs
     assert relerr(dw.cpu(), w0.grad) < 5e-5
     assert relerr(db.cpu(), b0.grad) < 5e-5
+    wgrad_bound(dtype, x, dy, k, s, dw, db)
 
 
 @pytest.mark.parametrize("case", [(16, 16, 3, 1, (32, 32, 32), 2), (32, 64, 3, 2, (16, 16, 16), 2)])
@@ -570,6 +593,7 @@ def test_wgrad_grid_budget_changes_the_partition_not_the_gradient(case, dtype=to
         assert relerr(dw.cpu(), w0.grad) < 5e-5, cus
         got[cus] = dw.cpu()
     assert float((got[0] - got[64]).abs().max()) <= 1e-4 * float(got[0].abs().max())
+    wgrad_bound(dtype, x, dy, k, s, [got[cus] for cus in (0, 128, 64, 8)])      # every partition, one reference
     if "SEGMI_WGRAD_CUS" not in os.environ:
         assert sizes[8] < sizes[0]          # fewer slabs for a smaller budget
 
@@ -591,9 +615,57 @@ def test_convT3d_wgrad_via_conv_wgrad(dtype):
     xd, dyd = to_ndhwc(x, dtype), to_ndhwc(dy, dtype)
     dw = torch.empty_like(w0, device=DEV)
     ws = torch.empty(ops.conv3d_wgrad_workspace(dyd, xd, 3, 2), dtype=torch.uint8, device=DEV)
-    ops.conv3d_wgrad(dyd, xd, dw, None, 3, 2, ws)
+    db = torch.empty(cin, device=DEV)
+    ops.conv3d_wgrad(dyd, xd, dw, db, 3, 2, ws)
     torch.cuda.synchronize()
     assert relerr(dw.cpu(), w0.grad) < 5e-5
+    # the same identity in float64: the roles of x and dy swap, so the "bias gradient" is the channel sum of x
+    wgrad_bound(dtype, dy, x, 3, 2, dw, db)
+
+
+def bn_fwd_ref64(x, scale, shift, alpha, res=None, mask=None):
+    """y = prelu((x scale + shift) mask) + res in float64 on the operands bn_act_fwd reads (x and res in their storage
+    type, the f32 scale / shift the finalisation wrote), and A: the same formula on the absolute value of each term.
+    The kernel rounds four times (the fma, the dropout factor, the slope, the residual add), each by at most 2^-24 of
+    a value bounded by A: inside the 2^-18 A of the bound.  PReLU is continuous in z, so a z whose f32 sign differs
+    from the float64 one (|z| within rounding of 0) changes nothing."""
+    v = lambda t: t.double().view(1, -1, 1, 1, 1)
+    z, az = x.double() * v(scale) + v(shift), x.double().abs() * v(scale).abs() + v(shift).abs()
+    if mask is not None:
+        z, az = z * mask.double(), az * mask.double()
+    ref, a = torch.where(z > 0, z, alpha * z), az * max(1.0, abs(alpha))
+    if res is not None:
+        ref, a = ref + res.double(), a + res.double().abs()
+    return ref, a
+
+
+def bn_bwd_bound(dtype, got, dy, x, mean, invstd, gamma, beta, alpha, coef, mask=None, what="dx"):
+    """dx = gamma invstd (dz - c0 - xhat c1), dz = dy [z > 0] + alpha dy [z <= 0] (times the dropout factor), in
+    float64 on the operands bn_act_bwd_apply reads (x, dy in their storage type; mean, invstd, c0, c1 as the launches
+    before it wrote them in f32), with A = |gamma invstd| (|dz| + |c0| + (|x| + |mean|) |invstd| |c1|).  The kernel
+    rounds seven times (x - mean, xhat, gamma invstd, alpha dy, dz - c0, the fma, the product), each by at most 2^-24
+    of a value bounded by A.  The side of PReLU is decided on the kernel's f32 z = xhat gamma + beta (three roundings,
+    <= 2^-22 of |xhat gamma| + |beta|): where the float64 z is within 2^-21 of that magnitude of zero, either side is
+    the correct result and the better of the two ratios counts."""
+    v = lambda t: t.double().view(1, -1, 1, 1, 1)
+    dy, x = dy.double(), x.double()
+    m = 1.0 if mask is None else mask.double()
+    xh, axh = (x - v(mean)) * v(invstd), (x.abs() + v(mean).abs()) * v(invstd).abs()
+    z, az = (xh * v(gamma) + v(beta)) * m, (axh * v(gamma).abs() + v(beta).abs()) * m
+    k = v(gamma) * v(invstd)
+
+    def dx_of(neg):
+        dz = torch.where(neg, alpha * dy, dy) * m
+        return k * (dz - v(coef[0]) - xh * v(coef[1])), k.abs() * (dz.abs() + v(coef[0]).abs() + axh * v(coef[1]).abs())
+
+    neg = ~(z > 0)
+    r = lb.ratio(got, *dx_of(neg), storage=dtype)
+    either = z.abs() <= 2.0 ** -21 * az
+    r = torch.where(either, torch.minimum(r, lb.ratio(got, *dx_of(~neg), storage=dtype)), r)
+    worst = float(r.max())
+    if _REPORT:
+        _REPORT[0](f"worst ratio {what}", float(f"{worst:.4g}"))
+    assert worst <= 1.0, f"{what}: {int((r > 1).sum())}/{r.numel()} elements outside the bound, worst ratio {worst:.3g}"
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -628,6 +700,8 @@ def test_bn_prelu_fwd_bwd(dtype, c):
     t = tol(dtype)
     assert relerr(from_ndhwc(yd), y.detach()) < t
     assert relerr(rmd.cpu(), rm) < 1e-5 and relerr(rvd.cpu(), rv) < 1e-5
+    elem_bound(dtype, from_ndhwc(yd), *bn_fwd_ref64(q(x, dtype), scale.cpu(), shift.cpu(), float(alpha), q(res, dtype)),
+               what="y")
     # backward
     dyd = to_ndhwc(dy, dtype)
     rrows = ops.bn_act_bwd_rows(xd)
@@ -643,6 +717,8 @@ def test_bn_prelu_fwd_bwd(dtype, c):
     assert relerr(dbt.cpu(), b0.grad) < 1e-4
     assert relerr(da.cpu(), a0.grad) < 1e-4
     assert relerr(from_ndhwc(dxd), xq.grad) < (1e-4 if dtype == torch.float32 else 1.5e-2)
+    bn_bwd_bound(dtype, from_ndhwc(dxd), q(dy, dtype), q(x, dtype), mean.cpu(), invstd.cpu(), gamma, beta, float(alpha),
+                 coef.cpu())
 
 
 def _drop_mask(numel, p, seed):
@@ -695,6 +771,7 @@ def test_bn_dropout_prelu_fwd_bwd(c, dtype=torch.float32):
     got = from_ndhwc(yd)
     assert torch.equal(got == 0, (mask == 0) | (y.detach() == 0))     # the very same voxels are dropped
     assert relerr(got, y.detach()) < (1e-5 if dtype == torch.float32 else tol(dtype))
+    elem_bound(dtype, got, *bn_fwd_ref64(x, scale.cpu(), shift.cpu(), float(alpha), None, mask), what="y")
     dyd = to_ndhwc(dy, dtype)
     rrows = ops.bn_act_bwd_rows(xd)
     rp = torch.empty((rrows, 3, c), device=DEV)
@@ -709,6 +786,7 @@ def test_bn_dropout_prelu_fwd_bwd(c, dtype=torch.float32):
     assert relerr(dbt.cpu(), b0.grad) < 1e-4
     assert relerr(da.cpu(), a0.grad) < 1e-4
     assert relerr(from_ndhwc(dxd), xq.grad) < (1e-4 if dtype == torch.float32 else tol(dtype))
+    bn_bwd_bound(dtype, from_ndhwc(dxd), dy, x, mean.cpu(), invstd.cpu(), gamma, beta, float(alpha), coef.cpu(), mask)
     # p = 0 is the identity (no mask evaluated)
     y0 = torch.empty_like(xd)
     ops.bn_act_fwd(xd, y0, scale, shift, ad, None, dropout=(0.0, seed))
@@ -720,6 +798,11 @@ def test_bn_dropout_prelu_fwd_bwd(c, dtype=torch.float32):
 @pytest.mark.parametrize("c", [3, 16, 64])
 def test_bn_dropout_prelu_fwd_bwd_f16(c):
     test_bn_dropout_prelu_fwd_bwd(c, dtype=F16)
+
+
+@pytest.mark.parametrize("c", [3, 16, 64])
+def test_bn_dropout_prelu_fwd_bwd_bf16(c):
+    test_bn_dropout_prelu_fwd_bwd(c, dtype=torch.bfloat16)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -1402,12 +1485,14 @@ def test_wave_specialised_wgrad_matches_torch(case, dtype=torch.bfloat16):
     torch.cuda.synchronize()
     assert relerr(dw.cpu(), w0.grad) < 5e-5
     assert relerr(db.cpu(), b0.grad) < 5e-5
+    dw_full, db_full = dw.cpu(), db.cpu()
     # a channel-slice view (ld > c) of a wider buffer as X: the buffer descriptor covers the view
     wide = torch.zeros(xd.shape[:4] + (2 * cin,), dtype=dtype, device=DEV)
     wide[..., cin:] = xd
     ops.conv3d_wgrad(wide[..., cin:], dyd, dw, None, k, s, ws)
     torch.cuda.synchronize()
     assert relerr(dw.cpu(), w0.grad) < 5e-5
+    wgrad_bound(dtype, x, dy, k, s, [dw_full, dw.cpu()], db_full)
     # the fused input transform (segmi_in_affine) on the wave-specialised path: same bits as the
     # weight gradient of the separately normalised tensor
     scale = (rnd((cin,), 333).abs() + 0.5).to(DEV)
