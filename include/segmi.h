@@ -542,6 +542,22 @@ int segmi_warp_crop_patches(const segmi_act* image, const float* label, const in
                             const uint8_t* flips_host, int count, const double* index_map_host,
                             int dst_dtype, const segmi_act* out_image, float* out_label,
                             void* stream);
+/* segmi_warp_crop_patches with a smooth non-rigid deformation composed into the same gather (DESIGN.md
+ * section 18).  The field lives in the index space of the augmented volume: a patch voxel goes (flip, crop
+ * origin) -> integer augmented index a -> a' = a + u(a) -> index_map_host (as above; NULL = identity) ->
+ * image trilinear with border clamping, label nearest; the SpatialPadd region is decided on the integer a
+ * and written as 0.  u is a uniform cubic B-spline, tensor product over the three axes: `control` is a
+ * DEVICE array of f32 displacements in voxels laid out [3][n0][n1][n2] (component and grid axes both in
+ * (z, y, x) order).  For an axis of extent dim > 1: t = i (n - 3) / (dim - 1), k = min(floor(t), n - 4),
+ * f = t - k, and the four uniform cubic B-spline basis functions of f weigh control points k .. k+3, so the
+ * volume spans the n - 3 interior spans exactly.  An axis of extent 1 uses t = 0 and its displacement
+ * component is 0.  4 <= n0, n1, n2 and n0 * n1 * n2 <= 4096 (the grid is staged in LDS, 48 KB at most):
+ * SEGMI_EINVAL otherwise.  1..16 crops per call; allocates nothing and does not synchronise; the control array
+ * must stay valid until the kernel has run on `stream`. */
+int segmi_elastic_warp_crop_patches(const segmi_act* image, const float* label, const int32_t* starts_host,
+                                    const uint8_t* flips_host, int count, const double* index_map_host,
+                                    const float* control, int n0, int n1, int n2, int dst_dtype,
+                                    const segmi_act* out_image, float* out_label, void* stream);
 /* Intensity augmentation of monai_unet.py:205-208 on `count` dense f32 NDHWC patches
  * [count][rd][rh][rw][c], in place, in the reference's order: RandAdjustContrastd (gamma),
  * RandHistogramShiftd (nctrl floating control points in [0,1] per patch, ascending),

@@ -3,6 +3,8 @@
 //                  composed into ONE gather: patch voxel -> (flip, crop origin) -> augmented-space
 //                  index -> 3x4 affine -> continuous source index; image trilinear with border
 //                  clamping, label nearest; the SpatialPad region (outside the volume) is 0.
+//   * elastic_warp_crop : the same gather with a cubic B-spline displacement field (control grid in
+//                  LDS) added to the augmented index before the affine map.
 //   * patch_minmax / adjust_contrast / histogram_shift / bias_field : RandAdjustContrastd,
 //                  RandHistogramShiftd, RandBiasFieldd on f32 patches, in place.
 // All HBM-bound elementwise / gather kernels.
@@ -18,6 +20,44 @@ struct WarpList {
   unsigned char flip[kMaxCrops];
   float m[12];   // augmented index (x,y,z,1) -> source index (x,y,z), row-major 3x4
 };
+
+// One patch voxel of the warp gather: the (possibly fractional) augmented index (ax, ay, az) of a voxel
+// inside the augmented volume -> 3x4 affine -> clamped source position -> trilinear image (C channels
+// stored at o) and nearest label (returned).  Shared by the affine and the elastic kernel.
+template <typename TD>
+__device__ __forceinline__ float warp_sample(const float* __restrict__ img, const float* __restrict__ lab,
+                                             const WarpList& wl, int w, float ax, float ay, float az,
+                                             int D, int H, int W, int C, int ldi, TD* __restrict__ o) {
+  float cx = wl.m[0] * ax + wl.m[1] * ay + wl.m[2] * az + wl.m[3];
+  float cy = wl.m[4] * ax + wl.m[5] * ay + wl.m[6] * az + wl.m[7];
+  float cz = wl.m[8] * ax + wl.m[9] * ay + wl.m[10] * az + wl.m[11];
+  // padding_mode="border": clamp the sample position into the volume
+  cx = fminf(fmaxf(cx, 0.f), (float)(W - 1));
+  cy = fminf(fmaxf(cy, 0.f), (float)(H - 1));
+  cz = fminf(fmaxf(cz, 0.f), (float)(D - 1));
+  const int x0 = (int)cx, y0 = (int)cy, z0 = (int)cz;
+  const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1,
+            z1 = z0 + 1 < D ? z0 + 1 : D - 1;
+  const float fx = cx - x0, fy = cy - y0, fz = cz - z0;
+  const int64_t base = (int64_t)wl.b[w] * D;
+  const int64_t r00 = ((base + z0) * H + y0) * W, r01 = ((base + z0) * H + y1) * W;
+  const int64_t r10 = ((base + z1) * H + y0) * W, r11 = ((base + z1) * H + y1) * W;
+  for (int c = 0; c < C; ++c) {
+    const float v000 = img[(r00 + x0) * ldi + c], v001 = img[(r00 + x1) * ldi + c];
+    const float v010 = img[(r01 + x0) * ldi + c], v011 = img[(r01 + x1) * ldi + c];
+    const float v100 = img[(r10 + x0) * ldi + c], v101 = img[(r10 + x1) * ldi + c];
+    const float v110 = img[(r11 + x0) * ldi + c], v111 = img[(r11 + x1) * ldi + c];
+    const float a0 = v000 + fx * (v001 - v000), a1 = v010 + fx * (v011 - v010);
+    const float a2 = v100 + fx * (v101 - v100), a3 = v110 + fx * (v111 - v110);
+    const float b0 = a0 + fy * (a1 - a0), b1 = a2 + fy * (a3 - a2);
+    Elem<TD>::st(o + c, b0 + fz * (b1 - b0));
+  }
+  if (!lab) return 0.f;
+  const int nx = (int)(cx + 0.5f) < W ? (int)(cx + 0.5f) : W - 1;
+  const int ny = (int)(cy + 0.5f) < H ? (int)(cy + 0.5f) : H - 1;
+  const int nz = (int)(cz + 0.5f) < D ? (int)(cz + 0.5f) : D - 1;
+  return lab[((base + nz) * H + ny) * W + nx];
+}
 
 template <typename TD>
 __global__ void warp_crop_kernel(const float* __restrict__ img, const float* __restrict__ lab,
@@ -41,36 +81,91 @@ __global__ void warp_crop_kernel(const float* __restrict__ img, const float* __r
     if (!in) {
       for (int c = 0; c < C; ++c) Elem<TD>::st(oimg + e * ldo + c, 0.f);
     } else {
-      float cx = wl.m[0] * ax + wl.m[1] * ay + wl.m[2] * az + wl.m[3];
-      float cy = wl.m[4] * ax + wl.m[5] * ay + wl.m[6] * az + wl.m[7];
-      float cz = wl.m[8] * ax + wl.m[9] * ay + wl.m[10] * az + wl.m[11];
-      // padding_mode="border": clamp the sample position into the volume
-      cx = fminf(fmaxf(cx, 0.f), (float)(W - 1));
-      cy = fminf(fmaxf(cy, 0.f), (float)(H - 1));
-      cz = fminf(fmaxf(cz, 0.f), (float)(D - 1));
-      const int x0 = (int)cx, y0 = (int)cy, z0 = (int)cz;
-      const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1,
-                z1 = z0 + 1 < D ? z0 + 1 : D - 1;
-      const float fx = cx - x0, fy = cy - y0, fz = cz - z0;
-      const int64_t base = (int64_t)wl.b[w] * D;
-      const int64_t r00 = ((base + z0) * H + y0) * W, r01 = ((base + z0) * H + y1) * W;
-      const int64_t r10 = ((base + z1) * H + y0) * W, r11 = ((base + z1) * H + y1) * W;
-      for (int c = 0; c < C; ++c) {
-        const float v000 = img[(r00 + x0) * ldi + c], v001 = img[(r00 + x1) * ldi + c];
-        const float v010 = img[(r01 + x0) * ldi + c], v011 = img[(r01 + x1) * ldi + c];
-        const float v100 = img[(r10 + x0) * ldi + c], v101 = img[(r10 + x1) * ldi + c];
-        const float v110 = img[(r11 + x0) * ldi + c], v111 = img[(r11 + x1) * ldi + c];
-        const float a0 = v000 + fx * (v001 - v000), a1 = v010 + fx * (v011 - v010);
-        const float a2 = v100 + fx * (v101 - v100), a3 = v110 + fx * (v111 - v110);
-        const float b0 = a0 + fy * (a1 - a0), b1 = a2 + fy * (a3 - a2);
-        Elem<TD>::st(oimg + e * ldo + c, b0 + fz * (b1 - b0));
+      lv = warp_sample<TD>(img, lab, wl, w, (float)ax, (float)ay, (float)az, D, H, W, C, ldi, oimg + e * ldo);
+    }
+    if (olab) olab[e] = lv;
+  }
+}
+
+// ---- elastic deformation composed into the same gather
+// The field lives in the index space of the augmented volume: a' = a + u(a), source = M a'.  u is a
+// uniform cubic B-spline over a control grid [3][n0][n1][n2] of displacements in voxels (component
+// and grid axes in (z, y, x) = (d0, d1, d2) order); the volume [0, dim - 1] spans the n - 3 interior
+// spans of an axis: t = i (n - 3) / (dim - 1), k = min(floor(t), n - 4), f = t - k.
+constexpr int kMaxControl = 4096;   // n0 * n1 * n2: three f32 planes = 48 KB of LDS at most
+
+struct ElasticGrid {
+  int n[3];       // control points along z, y, x
+  float s[3];     // (n - 3) / (dim - 1), 0 for an axis of extent 1
+};
+
+// Span and weights of control points k+1..k+3 for index i; the weight of point k is never formed:
+// the four weights sum to 1, and the sums below are written as p0 + sum_j w_j (p_j - p0), so a
+// constant grid gives that constant exactly.
+__device__ __forceinline__ int bspline_span(int i, float s, int n, float (&w)[3]) {
+  const float t = (float)i * s;
+  int k = (int)t;
+  if (k > n - 4) k = n - 4;
+  const float f = t - (float)k, f2 = f * f, f3 = f2 * f;
+  w[0] = (3.f * f3 - 6.f * f2 + 4.f) * (1.f / 6.f);
+  w[1] = (-3.f * f3 + 3.f * f2 + 3.f * f + 1.f) * (1.f / 6.f);
+  w[2] = f3 * (1.f / 6.f);
+  return k;
+}
+__device__ __forceinline__ float bspline_mix(float p0, float p1, float p2, float p3, const float (&w)[3]) {
+  return p0 + w[0] * (p1 - p0) + w[1] * (p2 - p0) + w[2] * (p3 - p0);
+}
+
+template <typename TD>
+__global__ __launch_bounds__(256) void elastic_warp_crop_kernel(
+    const float* __restrict__ img, const float* __restrict__ lab, const float* __restrict__ ctrl,
+    WarpList wl, ElasticGrid eg, int D, int H, int W, int C, int ldi, TD* __restrict__ oimg,
+    float* __restrict__ olab, int rd, int rh, int rw, int ldo) {
+  extern __shared__ __attribute__((aligned(16))) char dsm[];
+  float* g = reinterpret_cast<float*>(dsm);          // [3][n0][n1][n2]
+  const int ncp = eg.n[0] * eg.n[1] * eg.n[2];
+  for (int i = threadIdx.x; i < 3 * ncp; i += 256) g[i] = ctrl[i];
+  __syncthreads();
+  const int64_t per = (int64_t)rd * rh * rw;
+  const int64_t total = per * wl.n;
+  for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    int64_t t = e;
+    const int x = t % rw; t /= rw;
+    const int y = t % rh; t /= rh;
+    const int z = t % rd;
+    const int w = (int)(t / rd);
+    const unsigned char f = wl.flip[w];
+    const int az = wl.z[w] + ((f & 1) ? rd - 1 - z : z);
+    const int ay = wl.y[w] + ((f & 2) ? rh - 1 - y : y);
+    const int ax = wl.x[w] + ((f & 4) ? rw - 1 - x : x);
+    const bool in = (unsigned)az < (unsigned)D && (unsigned)ay < (unsigned)H && (unsigned)ax < (unsigned)W;
+    float lv = 0.f;
+    if (!in) {
+      for (int c = 0; c < C; ++c) Elem<TD>::st(oimg + e * ldo + c, 0.f);
+    } else {
+      float wz[3], wy[3], wx[3];
+      const int kz = bspline_span(az, eg.s[0], eg.n[0], wz);
+      const int ky = bspline_span(ay, eg.s[1], eg.n[1], wy);
+      const int kx = bspline_span(ax, eg.s[2], eg.n[2], wx);
+      float u[3];
+      for (int comp = 0; comp < 3; ++comp) {
+        const float* p = g + comp * ncp + (kz * eg.n[1] + ky) * eg.n[2] + kx;
+        float rz[4];
+        for (int a = 0; a < 4; ++a) {
+          float ry[4];
+          for (int b = 0; b < 4; ++b) {
+            const float* q = p + (a * eg.n[1] + b) * eg.n[2];
+            ry[b] = bspline_mix(q[0], q[1], q[2], q[3], wx);
+          }
+          rz[a] = bspline_mix(ry[0], ry[1], ry[2], ry[3], wy);
+        }
+        u[comp] = bspline_mix(rz[0], rz[1], rz[2], rz[3], wz);
       }
-      if (lab) {
-        const int nx = (int)(cx + 0.5f) < W ? (int)(cx + 0.5f) : W - 1;
-        const int ny = (int)(cy + 0.5f) < H ? (int)(cy + 0.5f) : H - 1;
-        const int nz = (int)(cz + 0.5f) < D ? (int)(cz + 0.5f) : D - 1;
-        lv = lab[((base + nz) * H + ny) * W + nx];
-      }
+      // an axis of extent 1 (the depth of a 2-D network) does not move
+      const float pz = D > 1 ? (float)az + u[0] : (float)az;
+      const float py = H > 1 ? (float)ay + u[1] : (float)ay;
+      const float px = W > 1 ? (float)ax + u[2] : (float)ax;
+      lv = warp_sample<TD>(img, lab, wl, w, px, py, pz, D, H, W, C, ldi, oimg + e * ldo);
     }
     if (olab) olab[e] = lv;
   }
@@ -231,6 +326,58 @@ int segmi_warp_crop_patches(const segmi_act* image, const float* label, const in
                        image->d, image->h, image->w, image->c, image->ld, (bf16_t*)out_image->data,
                        out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
   SEGMI_LAUNCH_CHECK("warp_crop_patches");
+  return SEGMI_OK;
+}
+
+int segmi_elastic_warp_crop_patches(const segmi_act* image, const float* label, const int32_t* starts_host,
+                                    const uint8_t* flips_host, int count, const double* index_map_host,
+                                    const float* control, int n0, int n1, int n2, int dst_dtype,
+                                    const segmi_act* out_image, float* out_label, void* stream) {
+  SEGMI_CHECK_ARG(act_ok(image) && act_ok(out_image) && starts_host && control,
+                  "elastic_warp_crop_patches: bad arguments");
+  SEGMI_CHECK_ARG(count > 0 && count <= kMaxCrops && out_image->n >= count && out_image->c == image->c,
+                  "elastic_warp_crop_patches: 1..%d crops per call", kMaxCrops);
+  SEGMI_CHECK_ARG(dtype_ok(dst_dtype), "elastic_warp_crop_patches: bad dtype");
+  SEGMI_CHECK_ARG(n0 >= 4 && n1 >= 4 && n2 >= 4 && (int64_t)n0 * n1 * n2 <= kMaxControl,
+                  "elastic_warp_crop_patches: control grid %d x %d x %d (at least 4 points per axis, at most %d "
+                  "in all)", n0, n1, n2, kMaxControl);
+  WarpList wl{};
+  wl.n = count;
+  for (int i = 0; i < count; ++i) {
+    wl.b[i] = starts_host[4 * i]; wl.z[i] = starts_host[4 * i + 1];
+    wl.y[i] = starts_host[4 * i + 2]; wl.x[i] = starts_host[4 * i + 3];
+    wl.flip[i] = flips_host ? flips_host[i] : 0;
+    SEGMI_CHECK_ARG(wl.b[i] >= 0 && wl.b[i] < image->n,
+                    "elastic_warp_crop_patches: volume index out of range");
+  }
+  for (int i = 0; i < 12; ++i)
+    wl.m[i] = index_map_host ? (float)index_map_host[i] : (i % 5 == 0 ? 1.f : 0.f);   // NULL = identity
+  ElasticGrid eg{};
+  const int dims[3] = {image->d, image->h, image->w}, ns[3] = {n0, n1, n2};
+  for (int a = 0; a < 3; ++a) {
+    eg.n[a] = ns[a];
+    eg.s[a] = dims[a] > 1 ? (float)((double)(ns[a] - 3) / (double)(dims[a] - 1)) : 0.f;
+  }
+  const int64_t total = (int64_t)count * out_image->d * out_image->h * out_image->w;
+  const int grid = grid_1d(total, 8192);
+  const size_t lds = (size_t)3 * n0 * n1 * n2 * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  if (dst_dtype == SEGMI_F32)
+    hipLaunchKernelGGL(elastic_warp_crop_kernel<float>, grid, 256, lds, st, (const float*)image->data, label,
+                       control, wl, eg, image->d, image->h, image->w, image->c, image->ld,
+                       (float*)out_image->data, out_label, out_image->d, out_image->h, out_image->w,
+                       out_image->ld);
+  else if (dst_dtype == SEGMI_F16)
+    hipLaunchKernelGGL(elastic_warp_crop_kernel<f16_t>, grid, 256, lds, st, (const float*)image->data, label,
+                       control, wl, eg, image->d, image->h, image->w, image->c, image->ld,
+                       (f16_t*)out_image->data, out_label, out_image->d, out_image->h, out_image->w,
+                       out_image->ld);
+  else
+    hipLaunchKernelGGL(elastic_warp_crop_kernel<bf16_t>, grid, 256, lds, st, (const float*)image->data, label,
+                       control, wl, eg, image->d, image->h, image->w, image->c, image->ld,
+                       (bf16_t*)out_image->data, out_label, out_image->d, out_image->h, out_image->w,
+                       out_image->ld);
+  SEGMI_LAUNCH_CHECK("elastic_warp_crop_patches");
   return SEGMI_OK;
 }
 

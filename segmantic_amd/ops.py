@@ -861,6 +861,32 @@ def warp_crop_patches(image, label, starts, flips, index_map, out_image, out_lab
               "warp_crop_patches")
 
 
+def elastic_warp_crop_patches(image, label, starts, flips, index_map, control, out_image, out_label) -> None:
+    """warp_crop_patches with a cubic B-spline displacement field added to the augmented index before
+    the affine map (``index_map`` None = identity).  ``control``: contiguous f32 device tensor
+    [3, n0, n1, n2] of displacements in voxels."""
+    from .seg.augment import ELASTIC_MAX_CONTROL      # kMaxControl; seg.augment is numpy-only and imports nothing of ops
+    _require_device(control)
+    if control.dtype != torch.float32 or control.dim() != 4 or control.shape[0] != 3 or not control.is_contiguous():
+        raise ValueError("elastic_warp_crop_patches: contiguous float32 [3, n0, n1, n2] control grid expected")
+    n0, n1, n2 = (int(v) for v in control.shape[1:])
+    if min(n0, n1, n2) < 4 or n0 * n1 * n2 > ELASTIC_MAX_CONTROL:
+        raise ValueError(f"elastic_warp_crop_patches: control grid {n0} x {n1} x {n2}: at least 4 points per axis "
+                         f"and at most {ELASTIC_MAX_CONTROL} in all")
+    a = act(image)
+    m = None if index_map is None else np.ascontiguousarray(np.asarray(index_map, dtype=np.float64).reshape(12))
+    mp = None if m is None else m.ctypes.data_as(C.c_void_p)
+    for i in range(0, len(starts), AUG_MAX_PATCHES):
+        arr, p = _starts(starts[i:i + AUG_MAX_PATCHES], 4)
+        n = arr.shape[0]
+        b = act(out_image[i:i + n])
+        _fl, flp = _flips_arg(flips, i, n)
+        check(lib.segmi_elastic_warp_crop_patches(C.byref(a), _ptr(label), p, flp, n, mp, _ptr(control), n0, n1, n2,
+                                                  dtype_code(out_image), C.byref(b),
+                                                  _ptr(_rows(out_label, i, n)), _stream()),
+              "elastic_warp_crop_patches")
+
+
 def _host_arrays():
     keep = []
 

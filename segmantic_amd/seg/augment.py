@@ -19,6 +19,24 @@ MONAI's transforms do and composes the spatial ones into one index map:
   the flips (``flip_params``; the Gibbs mask is mirrored inside ``ops.kspace_augment``), which
   gives the same patch without a separate flip pass.
 
+* ``augment_elastic`` (not in the reference; off by default): a smooth non-rigid deformation composed
+  into the same gather (``segmi_elastic_warp_crop_patches``).  The field lives in
+  the index space of the augmented volume, so every crop of one volume in one batch shares it, as
+  they share the affine map.  ``n = (n0, n1, n2) >= 4`` control points along (d0, d1, d2) carry a
+  displacement in voxels each; the displacement is the uniform cubic B-spline, tensor product over the
+  axes: for an axis of extent ``dim > 1``, ``t = i (n_a - 3) / (dim - 1)``, ``k = min(floor(t),
+  n_a - 4)``, ``f = t - k``, and the four uniform cubic B-spline basis functions of ``f`` weigh control
+  points ``k .. k+3``; the volume spans the ``n_a - 3`` interior spans and ``h_a = (dim - 1) / (n_a - 3)``
+  is the control spacing in voxels.  An axis of extent 1 uses ``t = 0`` and its displacement component
+  is 0.  A patch voxel's integer augmented index ``a`` becomes ``a' = a + u(a)`` and the source index
+  is ``M a'`` (``M`` = the affine pull-back, or the identity); clamping, trilinear image, nearest label
+  and the SpatialPad region (decided on the integer ``a``) are those of the affine gather.  The
+  control displacements of component ``a`` are U(-A_a, A_a), ``A_a = max_displacement`` (default
+  ``0.12 h_a``).  The derivative of a cubic B-spline is a convex combination of neighbouring control
+  differences, so ``|du_a/di_b| <= 2 A_a / h_b``; ``L = max_a sum_b 2 A_a / h_b < 1`` is required (the
+  default gives 0.72): then ``I + grad u`` is invertible and ``forward_point_elastic`` contracts at rate L.
+  At most 4096 control points (three f32 planes in LDS).
+
 Spatial axes: the cached volumes are [C, d0, d1, d2]; ``range_x`` rotates about d0, ``range_y``
 about d1, ``range_z`` about d2, as MONAI names the axes of a channel-first array.
 """
@@ -83,6 +101,134 @@ def forward_point(m_d012: np.ndarray, pt) -> np.ndarray:
     """Source index -> index in the augmented volume (inverse of the pull-back map)."""
     inv = np.linalg.inv(m_d012)
     return (inv @ np.array([pt[0], pt[1], pt[2], 1.0]))[:3]
+
+
+ELASTIC_MAX_CONTROL = 4096          # control points of one field: three f32 planes = 48 KB of LDS
+_ELASTIC_KEYS = ("prob", "control_points", "max_displacement")
+
+
+def _triple(v, what, kind):
+    vals = list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * 3
+    if len(vals) != 3:
+        raise ValueError(f"augment_elastic: '{what}' must be one value or one per axis (d0, d1, d2), got {v!r}")
+    out = []
+    for x in vals:
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or (
+                kind is int and float(x) != int(x)):
+            raise ValueError(f"augment_elastic: '{what}' must be {'an integer' if kind is int else 'a number'}"
+                             f" or three of them, got {v!r}")
+        out.append(kind(x))
+    return tuple(out)
+
+
+def elastic_config(value) -> Optional[dict]:
+    """The ``augment_elastic`` option in normal form: None when off (False / None), else
+    ``{"prob": float, "control_points": (n0, n1, n2), "max_displacement": None | (a0, a1, a2)}``.
+    ``True`` = ``prob 0.2``, ``control_points 7``, ``max_displacement`` 0.12 control spacings.  Unknown keys
+    and out-of-range values raise ``ValueError``; what depends on a volume's extents (the no-fold
+    condition) is checked by ``elastic_amplitudes``."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        value = {}
+    if not isinstance(value, dict):
+        raise ValueError(f"augment_elastic must be False, True or a dictionary with keys {_ELASTIC_KEYS}, "
+                         f"got {value!r}")
+    unknown = [k for k in value if k not in _ELASTIC_KEYS]
+    if unknown:
+        raise ValueError(f"augment_elastic: unknown keys {unknown}; accepted: {list(_ELASTIC_KEYS)}")
+    prob = value.get("prob", 0.2)
+    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 <= float(prob) <= 1.0:
+        raise ValueError(f"augment_elastic: 'prob' must be a probability in [0, 1], got {prob!r}")
+    n = _triple(value.get("control_points", 7), "control_points", int)
+    if min(n) < 4:
+        raise ValueError(f"augment_elastic: 'control_points' needs at least 4 points per axis (one cubic span), "
+                         f"got {n}")
+    if n[0] * n[1] * n[2] > ELASTIC_MAX_CONTROL:
+        raise ValueError(f"augment_elastic: 'control_points' {n} = {n[0] * n[1] * n[2]} points, more than the "
+                         f"{ELASTIC_MAX_CONTROL} the kernel holds in LDS")
+    amp = value.get("max_displacement")
+    if amp is not None:
+        amp = _triple(amp, "max_displacement", float)
+        if not all(np.isfinite(a) and a >= 0.0 for a in amp):
+            raise ValueError(f"augment_elastic: 'max_displacement' must be finite and >= 0 (voxels), got {amp}")
+    return {"prob": float(prob), "control_points": n, "max_displacement": amp}
+
+
+def elastic_amplitudes(shape, cfg: dict) -> Tuple[np.ndarray, float]:
+    """(A, L): the displacement amplitude per component in voxels and the bound
+    ``L = max_a sum_b 2 A_a / h_b`` of ``|grad u|`` for a volume of extents ``shape``.  Raises unless
+    ``L < 1`` (the field could fold).  An axis of extent 1 carries no displacement and no derivative."""
+    shape = [int(v) for v in shape]
+    n = cfg["control_points"]
+    live = np.array([d > 1 for d in shape])
+    h = np.array([(d - 1) / (k - 3) if d > 1 else np.inf for d, k in zip(shape, n)], dtype=np.float64)
+    if cfg["max_displacement"] is None:
+        amp = np.where(live, 0.12 * np.where(live, h, 0.0), 0.0)
+    else:
+        amp = np.where(live, np.asarray(cfg["max_displacement"], dtype=np.float64), 0.0)
+    lip = float(np.max(2.0 * amp * np.sum(1.0 / h)))
+    if not lip < 1.0:
+        raise ValueError(f"augment_elastic: 'max_displacement' {tuple(float(a) for a in amp)} voxels with control "
+                         f"spacing {tuple(float(v) for v in h)} voxels (volume {tuple(shape)}, control_points "
+                         f"{tuple(n)}) gives max_a sum_b 2 A_a / h_b = {lip:.3f} >= 1: the deformation could fold; "
+                         f"lower 'max_displacement' or use fewer control points")
+    return amp, lip
+
+
+def draw_elastic(rng: np.random.RandomState, shape, cfg: dict) -> Optional[np.ndarray]:
+    """Control displacements [3, n0, n1, n2] f32 (components and grid axes in (d0, d1, d2) order) of one
+    volume's field, or None when it did not fire (then nothing but the one ``rand()`` is drawn)."""
+    if not rng.rand() < cfg["prob"]:
+        return None
+    amp, _lip = elastic_amplitudes(shape, cfg)
+    n = cfg["control_points"]
+    return np.stack([rng.uniform(-a, a, size=n) for a in amp]).astype(np.float32)
+
+
+def _bspline_basis(f: np.ndarray) -> np.ndarray:
+    """the four uniform cubic B-spline basis functions of f, stacked on a new first axis"""
+    return np.stack([(1.0 - f) ** 3, 3.0 * f ** 3 - 6.0 * f ** 2 + 4.0,
+                     -3.0 * f ** 3 + 3.0 * f ** 2 + 3.0 * f + 1.0, f ** 3]) / 6.0
+
+
+def elastic_displacement(ctrl: np.ndarray, shape, points) -> np.ndarray:
+    """u at ``points`` [..., 3] (indices of the augmented volume in (d0, d1, d2) order, float64; a
+    position outside the volume takes the displacement of the nearest position inside)."""
+    ctrl = np.asarray(ctrl, dtype=np.float64)
+    pts = np.asarray(points, dtype=np.float64)
+    n = ctrl.shape[1:]
+    ks, ws = [], []
+    for a in range(3):
+        dim = int(shape[a])
+        t = np.clip(pts[..., a], 0.0, dim - 1.0) * (n[a] - 3) / (dim - 1) if dim > 1 else np.zeros(pts.shape[:-1])
+        k = np.minimum(np.floor(t).astype(np.int64), n[a] - 4)
+        ks.append(k)
+        ws.append(_bspline_basis(t - k))
+    u = np.zeros(pts.shape[:-1] + (3,))
+    for i in range(4):
+        for j in range(4):
+            for l in range(4):
+                w = ws[0][i] * ws[1][j] * ws[2][l]
+                u += w[..., None] * np.moveaxis(ctrl[:, ks[0] + i, ks[1] + j, ks[2] + l], 0, -1)
+    u[..., [int(shape[a]) <= 1 for a in range(3)]] = 0.0
+    return u
+
+
+def forward_point_elastic(m_d012: Optional[np.ndarray], ctrl: np.ndarray, shape, pt) -> np.ndarray:
+    """Source index -> index in the augmented volume under the composed map ``s = M (p + u(p))``
+    (``m_d012`` None = identity): the fixed point of ``p = M^-1 s - u(p)``, iterated in float64 from
+    ``M^-1 s`` until the update is below 1e-9 voxel.  The no-fold condition makes it a contraction."""
+    q = np.asarray(pt, dtype=np.float64)[:3] if m_d012 is None else forward_point(m_d012, pt)
+    p = q.copy()
+    for _ in range(1000):
+        nxt = q - elastic_displacement(ctrl, shape, p)
+        done = float(np.abs(nxt - p).max()) < 1e-9
+        p = nxt
+        if done:
+            return p
+    raise RuntimeError("augment_elastic: the crop centre's fixed-point iteration did not converge in 1000 steps "
+                       "(the field's gradient bound is too close to 1)")
 
 
 def draw_intensity(rng: np.random.RandomState, n: int, roi=None):

@@ -113,6 +113,17 @@ class Net(torch.nn.Module):
 
     # ------------------------------------------------------------------ properties
     @property
+    def augment_elastic(self):
+        """False, or the validated ``{prob, control_points, max_displacement}`` of the elastic deformation
+        (``seg/augment.py``).  Assigning ``True`` or a dictionary validates it on the spot."""
+        return self.__dict__.get("_augment_elastic") or False
+
+    @augment_elastic.setter
+    def augment_elastic(self, value):
+        from .augment import elastic_config
+        self.__dict__["_augment_elastic"] = elastic_config(value)
+
+    @property
     def num_classes(self):
         return self._model.out_channels
 
@@ -445,6 +456,8 @@ def train(
     # the objective rides in optimizer["loss"]: a bad entry fails here, before any rank is started or any device
     # call is made (the class-weight length is checked again once the class count is known)
     loss_from_config((optimizer or {}).get("loss"), num_classes if num_classes > 0 else None)
+    from .augment import elastic_config
+    elastic_config((augmentation or {}).get("augment_elastic", False))     # a bad entry fails here too
     n_ranks = len(list(gpu_ids or []))
     if n_ranks > 1 and not launch.under_launcher():
         # several gpu_ids: one process per GPU, started from here as children of this process --
@@ -492,9 +505,14 @@ def train(
     else:
         raise ValueError("Either provide a dataset file, or an image_dir, labels_dir pair.")
     net.config_preprocessing = preprocessing
-    net.config_augmentation = augmentation
     net.augment_intensity = augment_intensity
     net.augment_spatial = augment_spatial
+    # the elastic deformation is not in the reference's schema, whose keys this signature keeps: it rides in
+    # the augmentation dictionary as "augment_elastic" (False / True / {prob, control_points,
+    # max_displacement}) beside the bundle's Compose, as the objective rides in optimizer["loss"]
+    augmentation = dict(augmentation or {})
+    net.augment_elastic = augmentation.pop("augment_elastic", False)
+    net.config_augmentation = augmentation        # the bundle dictionary alone, as it is parsed below
     net.num_samples = num_samples
     # MONAI-bundle dictionaries (reference prepare_data, :232-262): resolved with the reference's
     # parser context and mapped onto the on-device pipeline; transforms it cannot express raise here

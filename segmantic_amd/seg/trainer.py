@@ -23,7 +23,8 @@ import torch
 
 from .. import ops
 from . import streams
-from .augment import draw_intensity, draw_spatial, flip_params, forward_point, to_index_map_xyz
+from .augment import (draw_elastic, draw_intensity, draw_spatial, elastic_amplitudes, elastic_config, flip_params,
+                      forward_point, forward_point_elastic, to_index_map_xyz)
 from .distributed import broadcast_buffers, env_world, init_distributed
 from .pipeline import PredictPipeline
 
@@ -76,13 +77,16 @@ class CachedVolumes:
 
 
 def crop_centers(rng: np.random.RandomState, item: Dict, roi, num_samples: int, num_classes: int,
-                 spatial: Optional[np.ndarray] = None, cache: Optional[CachedVolumes] = None):
+                 spatial: Optional[np.ndarray] = None, cache: Optional[CachedVolumes] = None,
+                 elastic: Optional[np.ndarray] = None):
     """MONAI ``generate_label_classes_crop_centers`` + ``correct_crop_centers`` with
     ratios = [0, 1, 1, ...] (background never chosen as a centre, monai_unet.py:201).
 
     ``spatial`` (the pull-back map of ``augment.draw_spatial``): the centre voxel is drawn from the
     stored label's class lists and carried into the augmented volume, where the reference would
-    have drawn it from the resampled label."""
+    have drawn it from the resampled label.  ``elastic`` (the control displacements of
+    ``augment.draw_elastic``): the deformation in front of that map is inverted as well
+    (``augment.forward_point_elastic``)."""
     shape = list(item["label"].shape[1:])
     ratios = np.array([0.0 if c == 0 else 1.0 for c in range(num_classes)])
     counts = np.asarray(item["class_counts"])
@@ -101,7 +105,10 @@ def crop_centers(rng: np.random.RandomState, item: Dict, roi, num_samples: int, 
     else:
         flat = item["class_all"][torch.from_numpy(where).to(item["class_all"].device)].cpu().numpy()
     centers = np.stack(np.unravel_index(flat, shape), 1)
-    if spatial is not None:
+    if elastic is not None:
+        centers = np.stack([np.rint(forward_point_elastic(spatial, elastic, shape, c)).astype(np.int64)
+                            for c in centers])
+    elif spatial is not None:
         centers = np.stack([np.rint(forward_point(spatial, c)).astype(np.int64) for c in centers])
     starts = []
     for ctr in centers:
@@ -135,20 +142,24 @@ def draw_batch(net, cache: CachedVolumes, vol_ids, rng) -> List[Dict]:
     """The host half of ``make_batch``: every random draw of one batch, in the order the sampler
     has always made them (``bench.py``'s fit mode and the prefetcher's bit-identity rely on it).
 
-    One record per volume: ``vid``, ``spatial`` (pull-back map or None), ``starts`` (crop origins),
+    One record per volume: ``vid``, ``spatial`` (pull-back map or None), ``elastic`` (f32 control
+    displacements [3, n0, n1, n2] or None; drawn directly after ``spatial``, and only with
+    ``augment_elastic`` on: with it off not one extra random number is consumed), ``starts`` (crop origins),
     ``flips`` (bit 0 = d0, bit 1 = d1, bit 2 = d2) and ``intensity`` (the five parameter tuples of
     ``augment.draw_intensity`` as the reference draws them, i.e. for the UNflipped patch; or None)."""
     roi = list(net.spatial_size)
     fp = float(getattr(net, "flip_prob", 0.2))
+    ecfg = elastic_config(getattr(net, "augment_elastic", False))
     records = []
     for vid in vol_ids:
         it = cache.items[vid]
         spatial = draw_spatial(rng, it["label"].shape[1:]) if net.augment_spatial else None
-        starts = crop_centers(rng, it, roi, net.num_samples, net.num_classes, spatial, cache)
+        elastic = draw_elastic(rng, it["label"].shape[1:], ecfg) if ecfg is not None else None
+        starts = crop_centers(rng, it, roi, net.num_samples, net.num_classes, spatial, cache, elastic)
         flips = [(int(rng.rand() < fp)) | (int(rng.rand() < fp) << 1) | (int(rng.rand() < fp) << 2)
                  for _ in starts]
         intensity = draw_intensity(rng, len(starts), roi) if net.augment_intensity else None
-        records.append({"vid": vid, "spatial": spatial, "starts": starts, "flips": flips,
+        records.append({"vid": vid, "spatial": spatial, "elastic": elastic, "starts": starts, "flips": flips,
                         "intensity": intensity})
     return records
 
@@ -156,7 +167,9 @@ def draw_batch(net, cache: CachedVolumes, vol_ids, rng) -> List[Dict]:
 def apply_batch(net, cache: CachedVolumes, records: List[Dict], out: Optional[Dict] = None) -> Dict:
     """The device half of ``make_batch``: the crops of ``draw_batch``'s records, flipped in the gather,
     then the intensity and k-space transforms with their parameters mirrored by the flips
-    (``augment.flip_params``), which gives the reference's order crop -> intensity -> k-space -> flip."""
+    (``augment.flip_params``), which gives the reference's order crop -> intensity -> k-space -> flip.
+    A record with an ``elastic`` field goes through ``ops.elastic_warp_crop_patches`` (with the affine map or
+    the identity); what follows the gather is the same."""
     roi = list(net.spatial_size)
     dev = net.device
     imgs, labs = [], []
@@ -174,7 +187,14 @@ def apply_batch(net, cache: CachedVolumes, records: List[Dict], out: Optional[Di
             out_i = torch.empty((len(starts), roi[0], roi[1], roi[2], C), dtype=torch.float32, device=dev)
             out_l = torch.empty((len(starts), roi[0], roi[1], roi[2]), dtype=torch.float32, device=dev)
         row += len(starts)
-        if spatial is None:
+        if rec.get("elastic") is not None:
+            # the control grid is uploaded on the current stream, in front of the gather that reads it (a plain
+            # copy from pageable memory: the host array is free again when the call returns)
+            ctrl = torch.from_numpy(np.ascontiguousarray(rec["elastic"], dtype=np.float32)).to(dev)
+            ops.elastic_warp_crop_patches(src, it["label_dhw"], [[0] + s for s in starts], flips,
+                                          None if spatial is None else to_index_map_xyz(spatial), ctrl,
+                                          out_i, out_l)
+        elif spatial is None:
             ops.crop_patches(src, it["label_dhw"], [[0] + s for s in starts], flips, out_i, out_l)
         else:
             ops.warp_crop_patches(src, it["label_dhw"], [[0] + s for s in starts], flips,
@@ -401,6 +421,10 @@ def fit(net, output_dir: Path, max_epochs: int, early_stop_patience: int, gpu_id
     spacing = list(getattr(net, "train_spacing", []) or [])
     ln = bool(getattr(net, "train_spacing_label_nearest", False))
     train_cache = CachedVolumes(net.dataset.training_files(), device, net.num_classes, spacing, ln)
+    ecfg = elastic_config(getattr(net, "augment_elastic", False))
+    if ecfg is not None:                          # the no-fold condition depends on the extents: fail before step 1
+        for it in train_cache.items:
+            elastic_amplitudes(it["label"].shape[1:], ecfg)
     val_cache = CachedVolumes(net.dataset.validation_files(), device, net.num_classes, spacing, ln)
 
     prefetch = BatchPrefetcher(net, train_cache)

@@ -139,6 +139,14 @@ def _check(comp, allowed, what):
         raise ValueError(f"'{what}' must resolve to a Compose of transforms, got {type(comp).__name__}")
     flat = comp.flatten()
     for t in flat:
+        if isinstance(t, TransformSpec) and t.name.startswith(("Rand3DElastic", "Rand2DElastic")):
+            # MONAI's field is Gaussian-smoothed per-voxel noise (sigma_range, magnitude_range); the device's
+            # elastic deformation is a cubic B-spline over a coarse control grid -- another field, so no mapping
+            raise ValueError(
+                f"'{what}': transform {t.target!r} is refused: MONAI's elastic field is Gaussian-smoothed per-voxel "
+                f"noise, while segmantic_amd's on-device elastic deformation is a cubic B-spline over a control grid; "
+                f"mapping one onto the other would silently change what the bundle means.  Drop the transform and "
+                f"set the 'augment_elastic' option ({{prob, control_points, max_displacement}}) instead")
         if not isinstance(t, TransformSpec) or t.name not in allowed:
             raise ValueError(
                 f"'{what}': transform {getattr(t, 'target', t)!r} is not available in segmantic_amd's on-device "
