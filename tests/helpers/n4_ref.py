@@ -122,6 +122,61 @@ def evaluate(lattice, shape):
     return out
 
 
+def _axis_weights_f64(n, lat):
+    """(span [n], weights [n, 4]) as csrc/n4.hip's axis_weights: products written out, {1, 0, 0, 0} when
+    the axis has no spline dimension"""
+    if lat == 1:
+        w = np.zeros((n, 4))
+        w[:, 0] = 1.0
+        return np.zeros(n, np.int64), w
+    m = lat - 3
+    i = np.arange(n, dtype=np.float64)
+    u = i / float(n - 1) * float(m) if n > 1 else np.zeros(n)
+    s = np.minimum(np.floor(u), m - 1).astype(np.int64)
+    t = u - s
+    t2 = t * t
+    t3 = t2 * t
+    w = np.stack([(1.0 - t) * (1.0 - t) * (1.0 - t) / 6.0, (3.0 * t3 - 6.0 * t2 + 4.0) / 6.0,
+                  (-3.0 * t3 + 3.0 * t2 + 3.0 * t + 1.0) / 6.0, t3 / 6.0], axis=-1)
+    return s, w
+
+
+def evaluate_f32(lattice, shape):
+    """n4_full_kernel's arithmetic: the z / y weights fold the [Lz, Ly, Lx] lattice into one row of Lx
+    coefficients per (z, y) in f64, rounded to f32; then u = f32(x) f32(m / (nx - 1)), the cubic weights
+    and the four-tap sum, left to right, all in f32.  `shape` is (nz, ny, nx); returns f32 [nz, ny, nx]."""
+    lat = np.asarray(lattice, np.float64)
+    nz, ny, nx = shape
+    Lz, Ly, Lx = lat.shape
+    sz, wz = _axis_weights_f64(nz, Lz)
+    sy, wy = _axis_weights_f64(ny, Ly)
+    acc = np.zeros((nz, ny, Lx))
+    for a in range(4):
+        iz = np.minimum(sz + a, Lz - 1)
+        for b in range(4):
+            iy = np.minimum(sy + b, Ly - 1)
+            acc = acc + (wz[:, a][:, None] * wy[:, b][None, :])[:, :, None] * lat[iz[:, None], iy[None, :], :]
+    q = acc.astype(np.float32)
+    if Lx == 1:
+        return np.broadcast_to(q, (nz, ny, nx)).copy()
+    f = np.float32
+    m = Lx - 3
+    scale = f(float(m) / float(nx - 1)) if nx > 1 else f(0.0)
+    u = np.arange(nx).astype(np.float32) * scale
+    s = np.minimum(np.floor(u).astype(np.int64), m - 1)
+    t = u - s.astype(np.float32)
+    t2 = t * t
+    t3 = t2 * t
+    one = f(1.0)
+    w0 = (one - t) * (one - t) * (one - t) / f(6.0)
+    w1 = (f(3.0) * t3 - f(6.0) * t2 + f(4.0)) / f(6.0)
+    w2 = (f(-3.0) * t3 + f(3.0) * t2 + f(3.0) * t + one) / f(6.0)
+    w3 = t3 / f(6.0)
+    out = w0 * q[:, :, s] + w1 * q[:, :, s + 1] + w2 * q[:, :, s + 2] + w3 * q[:, :, s + 3]
+    assert out.dtype == np.float32
+    return out
+
+
 def refine_axis(P, ax):
     P = np.moveaxis(np.asarray(P, np.float64), ax, 0)
     L = P.shape[0]
@@ -227,6 +282,66 @@ def sharpen(u, bins=200, fwhm=0.15, noise=0.01):
     return E, S
 
 
+HIST_FIX = 4294967296.0  # 2^32: the kernel's histogram weights are whole multiples of 2^-32
+
+
+def sharpen_direct(u, bins=200, fwhm=0.15, noise=0.01):
+    """`sharpen` with the arithmetic of csrc/n4.hip (its two declared departures from the FFT form): the
+    splat weights are rint(w 2^32) / 2^32, summed exactly as integers, and F^, g = IDFT(G), U~ and the two
+    F-convolutions are direct f64 sums over the P points, each sum running in the kernel's index order
+    (one term after the other, no pairwise grouping).  Returns (E [bins], sharpened values)."""
+    u = np.asarray(u, np.float64)
+    lo, hi = float(u.min()), float(u.max())
+    slope = (hi - lo) / (bins - 1)
+    c = np.maximum((u - lo) / slope, 0.0)
+    fi = np.floor(c)
+    i = np.where(fi < bins - 1, fi, bins - 1).astype(np.int64)
+    f1 = np.minimum(c - i, 1.0)
+    H = np.zeros(bins, np.int64)
+    np.add.at(H, i, np.rint((1.0 - f1) * HIST_FIX).astype(np.int64))
+    ok = i + 1 < bins
+    np.add.at(H, i[ok] + 1, np.rint(f1[ok] * HIST_FIX).astype(np.int64))
+    P = padded_size(bins)
+    off = (P - bins) // 2
+    mask = P - 1
+    idx = np.arange(P)
+    V = np.zeros(P)
+    V[off:off + bins] = H.astype(np.float64) / HIST_FIX
+    fw = fwhm / slope
+    e = 4.0 * math.log(2.0) / (fw * fw)
+    s = 2.0 * math.sqrt(math.log(2.0) / math.pi) / fw
+    cs = np.cos(2.0 * np.pi * idx / P)
+    cs[[0, P // 2]] = 1.0, -1.0
+    cs[[P // 4, 3 * P // 4]] = 0.0  # cospi is exact at the quarter points
+    nn = np.where(idx <= P // 2, idx, P - idx).astype(np.float64)
+    F = s * np.exp(-e * nn * nn)
+    fh = np.zeros(P)
+    for n in range(P):
+        fh = fh + F[n] * cs[(n * idx) & mask]
+    G = fh / (fh * fh + noise)
+    a = np.zeros(P)
+    for k in range(P):
+        a = a + G[k] * cs[(idx * k) & mask]
+    g = a / P
+    a = np.zeros(P)
+    for m in range(off, off + bins):
+        a = a + V[m] * g[(idx - m) & mask]
+    Ut = np.where(a > 0.0, a, 0.0)
+    xU = (lo + (idx - off).astype(np.float64) * slope) * Ut
+    nb = off + np.arange(bins)
+    num = np.zeros(bins)
+    den = np.zeros(bins)
+    for m in range(P):
+        f = F[(nb - m) & mask]
+        num = num + xU[m] * f
+        den = den + Ut[m] * f
+    E = np.where(den != 0, num / np.where(den != 0, den, 1.0), 0.0)
+    last = fi >= bins - 1
+    ic = np.where(last, bins - 2, fi).astype(np.int64)
+    S = np.where(last, E[bins - 1], E[ic] + (E[ic + 1] - E[ic]) * (c - fi))
+    return E, S
+
+
 # ------------------------------------------------------------------ N4
 def fit_set(img, mask):
     v = np.asarray(img, np.float64)
@@ -235,8 +350,11 @@ def fit_set(img, mask):
 
 
 def n4(img, mask, iterations=(50, 50, 50, 50), control_points=4, bins=200, fwhm=0.15, noise=0.01,
-       threshold=0.001):
-    """the whole N4 fit on the (already shrunk) image: (lattice, field on the grid, elapsed per level, CV)"""
+       threshold=0.001, sharpen_fn=None, trace=False):
+    """the whole N4 fit on the (already shrunk) image: (lattice, field on the grid, elapsed per level, CV);
+    `sharpen_fn` is `sharpen` (the default) or `sharpen_direct`; with `trace`, a fifth value: per level, the
+    CV after every iteration"""
+    sharpen_fn = sharpen_fn or sharpen
     img = np.asarray(img, np.float64)
     valid = fit_set(img, mask)
     if valid.sum() < 2:
@@ -247,25 +365,29 @@ def n4(img, mask, iterations=(50, 50, 50, 50), control_points=4, bins=200, fwhm=
     spans = control_points - 3
     lattice = np.zeros(lattice_shape(img.shape, spans))
     field = np.zeros(img.shape)
-    elapsed = []
+    elapsed, cvs = [], []
     cv = math.inf
     for lev, max_it in enumerate(iterations):
         if lev > 0:
             lattice = refine(lattice)
             spans *= 2
         it, cv = 0, math.inf
+        cvs.append([])
         while it < max_it and cv > threshold:
             U = L - field
-            _, S = sharpen(U[valid], bins, fwhm, noise)
+            _, S = sharpen_fn(U[valid], bins, fwhm, noise)
             r = np.zeros(img.shape)
             r[valid] = U[valid] - S
             lattice = lattice + ba_fit(r, valid, spans)
             new = evaluate(lattice, img.shape)
             e = np.exp(field[valid] - new[valid])
             cv = float(np.std(e, ddof=1) / np.mean(e))
+            cvs[-1].append(cv)
             field = new
             it += 1
         elapsed.append(it)
+    if trace:
+        return lattice, field, elapsed, cv, cvs
     return lattice, field, elapsed, cv
 
 
@@ -276,6 +398,19 @@ def median_filter(x):
     stack = []
     for off in np.ndindex(*(3,) * x.ndim):
         stack.append(p[tuple(slice(o, o + n) for o, n in zip(off, x.shape))])
+    return np.median(np.stack(stack), axis=0)
+
+
+def median_filter_slab(x, z0, z1):
+    """planes [z0, z1) of median_filter(x) for a [z, y, x] volume, from those planes and their real
+    neighbours only (replicate borders at the volume's own ends): a large volume checked slab by slab"""
+    x = np.asarray(x)
+    nz = x.shape[0]
+    a, b = max(z0 - 1, 0), min(z1 + 1, nz)
+    p = np.pad(np.asarray(x[a:b], np.float64), ((int(z0 == 0), int(z1 == nz)), (1, 1), (1, 1)), mode="edge")
+    stack = []
+    for off in np.ndindex(3, 3, 3):
+        stack.append(p[off[0]:off[0] + z1 - z0, off[1]:off[1] + x.shape[1], off[2]:off[2] + x.shape[2]])
     return np.median(np.stack(stack), axis=0)
 
 
