@@ -1,4 +1,6 @@
-// augment.hip -- on-device training augmentation (reference src/segmantic/seg/monai_unet.py:178-217):
+// augment.hip -- the training sampler's gathers and the on-device training augmentation (reference
+// src/segmantic/seg/monai_unet.py:178-217).  The three gathers share one patch list and one per-voxel prologue:
+//   * crop       : SpatialPadd + RandCropByLabelClassesd + RandFlipd, a plain copy / conversion.
 //   * warp_crop  : RandRotated x3 + RandZoomd + SpatialPadd + RandCropByLabelClassesd + RandFlipd
 //                  composed into ONE gather: patch voxel -> (flip, crop origin) -> augmented-space
 //                  index -> 3x4 affine -> continuous source index; image trilinear with border
@@ -14,12 +16,56 @@ namespace segmi {
 
 constexpr int kMaxCrops = 16;
 
-struct WarpList {
+// the patches of one call: volume index and origin in the augmented volume, flip bits (1 = z, 2 = y, 4 = x)
+struct PatchList {
   int n;
   int b[kMaxCrops], z[kMaxCrops], y[kMaxCrops], x[kMaxCrops];
   unsigned char flip[kMaxCrops];
+};
+struct WarpList {
+  PatchList p;
   float m[12];   // augmented index (x,y,z,1) -> source index (x,y,z), row-major 3x4
 };
+
+// The prologue of the three gathers: output element e -> patch w, its volume b and the index (az, ay, ax) in
+// the augmented volume of the voxel it takes, the flip applied; `in` says whether that index lies inside the
+// volume (outside is the SpatialPad region: zero).  The result is returned by value and carries b because
+// that is the form hipcc compiles to the instructions of the three hand-written prologues it replaced.
+struct PatchVoxel {
+  int w, b, az, ay, ax;
+  bool in;
+};
+__device__ __forceinline__ PatchVoxel patch_voxel(const PatchList& pl, int64_t e, int rd, int rh, int rw, int D,
+                                                  int H, int W) {
+  int64_t t = e;
+  const int x = t % rw; t /= rw;
+  const int y = t % rh; t /= rh;
+  const int z = t % rd;
+  const int w = (int)(t / rd);
+  const unsigned char f = pl.flip[w];
+  const int az = pl.z[w] + ((f & 1) ? rd - 1 - z : z);
+  const int ay = pl.y[w] + ((f & 2) ? rh - 1 - y : y);
+  const int ax = pl.x[w] + ((f & 4) ? rw - 1 - x : x);
+  const bool in = (unsigned)az < (unsigned)D && (unsigned)ay < (unsigned)H && (unsigned)ax < (unsigned)W;
+  return PatchVoxel{w, pl.b[w], az, ay, ax, in};
+}
+
+// The plain cropper.  It moved here from sliding.hip, which is compiled with -ffp-contract=off while this file
+// is not: the kernel copies and converts and does no floating-point arithmetic, so there is nothing to
+// contract and the move cannot change a bit.
+template <typename TD>
+__global__ void crop_kernel(const float* __restrict__ img, const float* __restrict__ lab, PatchList pl,
+                            int D, int H, int W, int C, int ldi, TD* __restrict__ oimg,
+                            float* __restrict__ olab, int rd, int rh, int rw, int ldo) {
+  const int64_t per = (int64_t)rd * rh * rw;
+  const int64_t total = per * pl.n;
+  for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const PatchVoxel v = patch_voxel(pl, e, rd, rh, rw, D, H, W);
+    const int64_t gv = (((int64_t)v.b * D + v.az) * H + v.ay) * W + v.ax;
+    for (int c = 0; c < C; ++c) Elem<TD>::st(oimg + e * ldo + c, v.in ? img[gv * ldi + c] : 0.f);
+    if (olab) olab[e] = (v.in && lab) ? lab[gv] : 0.f;
+  }
+}
 
 // One patch voxel of the warp gather: the (possibly fractional) augmented index (ax, ay, az) of a voxel
 // inside the augmented volume -> 3x4 affine -> clamped source position -> trilinear image (C channels
@@ -39,7 +85,7 @@ __device__ __forceinline__ float warp_sample(const float* __restrict__ img, cons
   const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1,
             z1 = z0 + 1 < D ? z0 + 1 : D - 1;
   const float fx = cx - x0, fy = cy - y0, fz = cz - z0;
-  const int64_t base = (int64_t)wl.b[w] * D;
+  const int64_t base = (int64_t)wl.p.b[w] * D;
   const int64_t r00 = ((base + z0) * H + y0) * W, r01 = ((base + z0) * H + y1) * W;
   const int64_t r10 = ((base + z1) * H + y0) * W, r11 = ((base + z1) * H + y1) * W;
   for (int c = 0; c < C; ++c) {
@@ -65,23 +111,15 @@ __global__ void warp_crop_kernel(const float* __restrict__ img, const float* __r
                                  TD* __restrict__ oimg, float* __restrict__ olab, int rd, int rh,
                                  int rw, int ldo) {
   const int64_t per = (int64_t)rd * rh * rw;
-  const int64_t total = per * wl.n;
+  const int64_t total = per * wl.p.n;
   for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    int64_t t = e;
-    const int x = t % rw; t /= rw;
-    const int y = t % rh; t /= rh;
-    const int z = t % rd;
-    const int w = (int)(t / rd);
-    const unsigned char f = wl.flip[w];
-    const int az = wl.z[w] + ((f & 1) ? rd - 1 - z : z);
-    const int ay = wl.y[w] + ((f & 2) ? rh - 1 - y : y);
-    const int ax = wl.x[w] + ((f & 4) ? rw - 1 - x : x);
-    const bool in = (unsigned)az < (unsigned)D && (unsigned)ay < (unsigned)H && (unsigned)ax < (unsigned)W;
+    const PatchVoxel v = patch_voxel(wl.p, e, rd, rh, rw, D, H, W);
     float lv = 0.f;
-    if (!in) {
+    if (!v.in) {
       for (int c = 0; c < C; ++c) Elem<TD>::st(oimg + e * ldo + c, 0.f);
     } else {
-      lv = warp_sample<TD>(img, lab, wl, w, (float)ax, (float)ay, (float)az, D, H, W, C, ldi, oimg + e * ldo);
+      lv = warp_sample<TD>(img, lab, wl, v.w, (float)v.ax, (float)v.ay, (float)v.az, D, H, W, C, ldi,
+                           oimg + e * ldo);
     }
     if (olab) olab[e] = lv;
   }
@@ -127,26 +165,17 @@ __global__ __launch_bounds__(256) void elastic_warp_crop_kernel(
   for (int i = threadIdx.x; i < 3 * ncp; i += 256) g[i] = ctrl[i];
   __syncthreads();
   const int64_t per = (int64_t)rd * rh * rw;
-  const int64_t total = per * wl.n;
+  const int64_t total = per * wl.p.n;
   for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    int64_t t = e;
-    const int x = t % rw; t /= rw;
-    const int y = t % rh; t /= rh;
-    const int z = t % rd;
-    const int w = (int)(t / rd);
-    const unsigned char f = wl.flip[w];
-    const int az = wl.z[w] + ((f & 1) ? rd - 1 - z : z);
-    const int ay = wl.y[w] + ((f & 2) ? rh - 1 - y : y);
-    const int ax = wl.x[w] + ((f & 4) ? rw - 1 - x : x);
-    const bool in = (unsigned)az < (unsigned)D && (unsigned)ay < (unsigned)H && (unsigned)ax < (unsigned)W;
+    const PatchVoxel v = patch_voxel(wl.p, e, rd, rh, rw, D, H, W);
     float lv = 0.f;
-    if (!in) {
+    if (!v.in) {
       for (int c = 0; c < C; ++c) Elem<TD>::st(oimg + e * ldo + c, 0.f);
     } else {
       float wz[3], wy[3], wx[3];
-      const int kz = bspline_span(az, eg.s[0], eg.n[0], wz);
-      const int ky = bspline_span(ay, eg.s[1], eg.n[1], wy);
-      const int kx = bspline_span(ax, eg.s[2], eg.n[2], wx);
+      const int kz = bspline_span(v.az, eg.s[0], eg.n[0], wz);
+      const int ky = bspline_span(v.ay, eg.s[1], eg.n[1], wy);
+      const int kx = bspline_span(v.ax, eg.s[2], eg.n[2], wx);
       float u[3];
       for (int comp = 0; comp < 3; ++comp) {
         const float* p = g + comp * ncp + (kz * eg.n[1] + ky) * eg.n[2] + kx;
@@ -162,10 +191,10 @@ __global__ __launch_bounds__(256) void elastic_warp_crop_kernel(
         u[comp] = bspline_mix(rz[0], rz[1], rz[2], rz[3], wz);
       }
       // an axis of extent 1 (the depth of a 2-D network) does not move
-      const float pz = D > 1 ? (float)az + u[0] : (float)az;
-      const float py = H > 1 ? (float)ay + u[1] : (float)ay;
-      const float px = W > 1 ? (float)ax + u[2] : (float)ax;
-      lv = warp_sample<TD>(img, lab, wl, w, px, py, pz, D, H, W, C, ldi, oimg + e * ldo);
+      const float pz = D > 1 ? (float)v.az + u[0] : (float)v.az;
+      const float py = H > 1 ? (float)v.ay + u[1] : (float)v.ay;
+      const float px = W > 1 ? (float)v.ax + u[2] : (float)v.ax;
+      lv = warp_sample<TD>(img, lab, wl, v.w, px, py, pz, D, H, W, C, ldi, oimg + e * ldo);
     }
     if (olab) olab[e] = lv;
   }
@@ -281,9 +310,26 @@ __global__ void bias_field_kernel(float* __restrict__ x, int rd, int rh, int rw,
   }
 }
 
-static inline int grid_1d(int64_t total, int cap) {
-  const int64_t b = cdiv64(total, 256);
-  return (int)(b > cap ? cap : (b < 1 ? 1 : b));
+// The patch list of one sampler call from starts_host (b, z, y, x per patch) and flips_host (nullable), after the
+// checks the three entry points share; `what` is the caller's name in the error text.
+static int fill_patches(const char* what, const segmi_act* image, const segmi_act* out_image,
+                        const int32_t* starts_host, const uint8_t* flips_host, int count, int dst_dtype,
+                        PatchList& pl) {
+  SEGMI_CHECK_ARG(count > 0 && count <= kMaxCrops && out_image->n >= count && out_image->c == image->c,
+                  "%s: 1..%d crops per call", what, kMaxCrops);
+  SEGMI_CHECK_ARG(dtype_ok(dst_dtype), "%s: bad dtype", what);
+  pl.n = count;
+  for (int i = 0; i < count; ++i) {
+    pl.b[i] = starts_host[4 * i]; pl.z[i] = starts_host[4 * i + 1];
+    pl.y[i] = starts_host[4 * i + 2]; pl.x[i] = starts_host[4 * i + 3];
+    pl.flip[i] = flips_host ? flips_host[i] : 0;
+    SEGMI_CHECK_ARG(pl.b[i] >= 0 && pl.b[i] < image->n, "%s: volume index out of range", what);
+  }
+  return SEGMI_OK;
+}
+// workgroups of a gather that writes `count` patches shaped like out_image
+static inline int patch_grid(int count, const segmi_act* out_image) {
+  return grid_1d((int64_t)count * out_image->d * out_image->h * out_image->w, 8192);
 }
 
 }  // namespace segmi
@@ -292,39 +338,39 @@ using namespace segmi;
 
 extern "C" {
 
+int segmi_crop_patches(const segmi_act* image, const float* label, const int32_t* starts_host,
+                       const uint8_t* flips_host, int count, int dst_dtype,
+                       const segmi_act* out_image, float* out_label, void* stream) {
+  SEGMI_CHECK_ARG(act_ok(image) && act_ok(out_image) && starts_host, "crop_patches: bad arguments");
+  PatchList pl{};
+  const int rc = fill_patches("crop_patches", image, out_image, starts_host, flips_host, count, dst_dtype, pl);
+  if (rc) return rc;
+#define CROP(T)                                                                                               \
+  hipLaunchKernelGGL(crop_kernel<T>, patch_grid(count, out_image), 256, 0, (hipStream_t)stream,               \
+                     (const float*)image->data, label, pl, image->d, image->h, image->w, image->c, image->ld, \
+                     (T*)out_image->data, out_label, out_image->d, out_image->h, out_image->w, out_image->ld)
+  SEGMI_BY_DTYPE(dst_dtype, CROP);
+#undef CROP
+  SEGMI_LAUNCH_CHECK("crop_patches");
+  return SEGMI_OK;
+}
+
 int segmi_warp_crop_patches(const segmi_act* image, const float* label, const int32_t* starts_host,
                             const uint8_t* flips_host, int count, const double* index_map_host,
                             int dst_dtype, const segmi_act* out_image, float* out_label,
                             void* stream) {
   SEGMI_CHECK_ARG(act_ok(image) && act_ok(out_image) && starts_host && index_map_host,
                   "warp_crop_patches: bad arguments");
-  SEGMI_CHECK_ARG(count > 0 && count <= kMaxCrops && out_image->n >= count && out_image->c == image->c,
-                  "warp_crop_patches: 1..%d crops per call", kMaxCrops);
-  SEGMI_CHECK_ARG(dtype_ok(dst_dtype), "warp_crop_patches: bad dtype");
   WarpList wl{};
-  wl.n = count;
-  for (int i = 0; i < count; ++i) {
-    wl.b[i] = starts_host[4 * i]; wl.z[i] = starts_host[4 * i + 1];
-    wl.y[i] = starts_host[4 * i + 2]; wl.x[i] = starts_host[4 * i + 3];
-    wl.flip[i] = flips_host ? flips_host[i] : 0;
-    SEGMI_CHECK_ARG(wl.b[i] >= 0 && wl.b[i] < image->n, "warp_crop_patches: volume index out of range");
-  }
+  const int rc = fill_patches("warp_crop_patches", image, out_image, starts_host, flips_host, count, dst_dtype, wl.p);
+  if (rc) return rc;
   for (int i = 0; i < 12; ++i) wl.m[i] = (float)index_map_host[i];
-  const int64_t total = (int64_t)count * out_image->d * out_image->h * out_image->w;
-  const int grid = grid_1d(total, 8192);
-  hipStream_t st = (hipStream_t)stream;
-  if (dst_dtype == SEGMI_F32)
-    hipLaunchKernelGGL(warp_crop_kernel<float>, grid, 256, 0, st, (const float*)image->data, label, wl,
-                       image->d, image->h, image->w, image->c, image->ld, (float*)out_image->data,
-                       out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
-  else if (dst_dtype == SEGMI_F16)
-    hipLaunchKernelGGL(warp_crop_kernel<f16_t>, grid, 256, 0, st, (const float*)image->data, label, wl,
-                       image->d, image->h, image->w, image->c, image->ld, (f16_t*)out_image->data,
-                       out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
-  else
-    hipLaunchKernelGGL(warp_crop_kernel<bf16_t>, grid, 256, 0, st, (const float*)image->data, label, wl,
-                       image->d, image->h, image->w, image->c, image->ld, (bf16_t*)out_image->data,
-                       out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
+#define WARP(T)                                                                                               \
+  hipLaunchKernelGGL(warp_crop_kernel<T>, patch_grid(count, out_image), 256, 0, (hipStream_t)stream,          \
+                     (const float*)image->data, label, wl, image->d, image->h, image->w, image->c, image->ld, \
+                     (T*)out_image->data, out_label, out_image->d, out_image->h, out_image->w, out_image->ld)
+  SEGMI_BY_DTYPE(dst_dtype, WARP);
+#undef WARP
   SEGMI_LAUNCH_CHECK("warp_crop_patches");
   return SEGMI_OK;
 }
@@ -335,21 +381,13 @@ int segmi_elastic_warp_crop_patches(const segmi_act* image, const float* label, 
                                     const segmi_act* out_image, float* out_label, void* stream) {
   SEGMI_CHECK_ARG(act_ok(image) && act_ok(out_image) && starts_host && control,
                   "elastic_warp_crop_patches: bad arguments");
-  SEGMI_CHECK_ARG(count > 0 && count <= kMaxCrops && out_image->n >= count && out_image->c == image->c,
-                  "elastic_warp_crop_patches: 1..%d crops per call", kMaxCrops);
-  SEGMI_CHECK_ARG(dtype_ok(dst_dtype), "elastic_warp_crop_patches: bad dtype");
   SEGMI_CHECK_ARG(n0 >= 4 && n1 >= 4 && n2 >= 4 && (int64_t)n0 * n1 * n2 <= kMaxControl,
                   "elastic_warp_crop_patches: control grid %d x %d x %d (at least 4 points per axis, at most %d "
                   "in all)", n0, n1, n2, kMaxControl);
   WarpList wl{};
-  wl.n = count;
-  for (int i = 0; i < count; ++i) {
-    wl.b[i] = starts_host[4 * i]; wl.z[i] = starts_host[4 * i + 1];
-    wl.y[i] = starts_host[4 * i + 2]; wl.x[i] = starts_host[4 * i + 3];
-    wl.flip[i] = flips_host ? flips_host[i] : 0;
-    SEGMI_CHECK_ARG(wl.b[i] >= 0 && wl.b[i] < image->n,
-                    "elastic_warp_crop_patches: volume index out of range");
-  }
+  const int rc = fill_patches("elastic_warp_crop_patches", image, out_image, starts_host, flips_host, count,
+                              dst_dtype, wl.p);
+  if (rc) return rc;
   for (int i = 0; i < 12; ++i)
     wl.m[i] = index_map_host ? (float)index_map_host[i] : (i % 5 == 0 ? 1.f : 0.f);   // NULL = identity
   ElasticGrid eg{};
@@ -358,25 +396,14 @@ int segmi_elastic_warp_crop_patches(const segmi_act* image, const float* label, 
     eg.n[a] = ns[a];
     eg.s[a] = dims[a] > 1 ? (float)((double)(ns[a] - 3) / (double)(dims[a] - 1)) : 0.f;
   }
-  const int64_t total = (int64_t)count * out_image->d * out_image->h * out_image->w;
-  const int grid = grid_1d(total, 8192);
   const size_t lds = (size_t)3 * n0 * n1 * n2 * sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
-  if (dst_dtype == SEGMI_F32)
-    hipLaunchKernelGGL(elastic_warp_crop_kernel<float>, grid, 256, lds, st, (const float*)image->data, label,
-                       control, wl, eg, image->d, image->h, image->w, image->c, image->ld,
-                       (float*)out_image->data, out_label, out_image->d, out_image->h, out_image->w,
-                       out_image->ld);
-  else if (dst_dtype == SEGMI_F16)
-    hipLaunchKernelGGL(elastic_warp_crop_kernel<f16_t>, grid, 256, lds, st, (const float*)image->data, label,
-                       control, wl, eg, image->d, image->h, image->w, image->c, image->ld,
-                       (f16_t*)out_image->data, out_label, out_image->d, out_image->h, out_image->w,
-                       out_image->ld);
-  else
-    hipLaunchKernelGGL(elastic_warp_crop_kernel<bf16_t>, grid, 256, lds, st, (const float*)image->data, label,
-                       control, wl, eg, image->d, image->h, image->w, image->c, image->ld,
-                       (bf16_t*)out_image->data, out_label, out_image->d, out_image->h, out_image->w,
-                       out_image->ld);
+#define ELASTIC(T)                                                                                            \
+  hipLaunchKernelGGL(elastic_warp_crop_kernel<T>, patch_grid(count, out_image), 256, lds, (hipStream_t)stream, \
+                     (const float*)image->data, label, control, wl, eg, image->d, image->h, image->w, image->c, \
+                     image->ld, (T*)out_image->data, out_label, out_image->d, out_image->h, out_image->w,      \
+                     out_image->ld)
+  SEGMI_BY_DTYPE(dst_dtype, ELASTIC);
+#undef ELASTIC
   SEGMI_LAUNCH_CHECK("elastic_warp_crop_patches");
   return SEGMI_OK;
 }

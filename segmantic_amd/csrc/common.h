@@ -315,6 +315,61 @@ static inline int dtype_size(int dtype) { return dtype == SEGMI_F32 ? 4 : 2; }
 static inline bool dtype_ok(int dtype) { return dtype == SEGMI_F32 || dtype == SEGMI_BF16 || dtype == SEGMI_F16; }
 // the 16-bit storage formats: every kernel family, fast path and shape gate treats them alike
 static inline bool dtype_h16(int dtype) { return dtype == SEGMI_BF16 || dtype == SEGMI_F16; }
+static inline const char* dtype_name(int dtype) { return dtype == SEGMI_BF16 ? "bf16" : dtype == SEGMI_F16 ? "f16" : "f32"; }
+
+// ------------------------------------------------------------------ launch dispatch
+// Every launcher picks its kernel instantiation through these, so a launch is written once per call site
+// with T in place of the casts.  All of them fail closed: a code outside the list sets the error and returns
+// SEGMI_EINVAL from the enclosing function before anything is launched -- no branch means "everything else".
+// F(T, extra...) with the storage type of `dtype`
+#define SEGMI_BY_DTYPE(dtype, F, ...)                                              \
+  do {                                                                             \
+    if ((dtype) == SEGMI_F32) { F(float, ##__VA_ARGS__); }                         \
+    else if ((dtype) == SEGMI_F16) { F(::segmi::f16_t, ##__VA_ARGS__); }           \
+    else if ((dtype) == SEGMI_BF16) { F(::segmi::bf16_t, ##__VA_ARGS__); }         \
+    else SEGMI_CHECK_ARG(false, "unknown dtype code %d", (int)(dtype));            \
+  } while (0)
+
+// F(TS, TD, extra...) for a converting copy: f32 with any type, a 16-bit type with itself or with f32
+static inline bool dtype_pair_ok(int s, int d) {
+  return dtype_ok(s) && dtype_ok(d) && (s == d || s == SEGMI_F32 || d == SEGMI_F32);
+}
+#define SEGMI_BY_DTYPE_PAIR(s, d, F, ...)                                                                    \
+  do {                                                                                                       \
+    if ((s) == SEGMI_F32 && (d) == SEGMI_F32) { F(float, float, ##__VA_ARGS__); }                            \
+    else if ((s) == SEGMI_F32 && (d) == SEGMI_BF16) { F(float, ::segmi::bf16_t, ##__VA_ARGS__); }            \
+    else if ((s) == SEGMI_BF16 && (d) == SEGMI_F32) { F(::segmi::bf16_t, float, ##__VA_ARGS__); }            \
+    else if ((s) == SEGMI_BF16 && (d) == SEGMI_BF16) { F(::segmi::bf16_t, ::segmi::bf16_t, ##__VA_ARGS__); } \
+    else if ((s) == SEGMI_F32 && (d) == SEGMI_F16) { F(float, ::segmi::f16_t, ##__VA_ARGS__); }              \
+    else if ((s) == SEGMI_F16 && (d) == SEGMI_F32) { F(::segmi::f16_t, float, ##__VA_ARGS__); }              \
+    else if ((s) == SEGMI_F16 && (d) == SEGMI_F16) { F(::segmi::f16_t, ::segmi::f16_t, ##__VA_ARGS__); }     \
+    else SEGMI_CHECK_ARG(false, "unsupported dtype pair %d -> %d", (int)(s), (int)(d));                      \
+  } while (0)
+
+// F(L, extra...) with the label type whose width is `lb` bytes.  A call site names its own types where its
+// kernels differ (the blend stores 2-byte labels as uint16_t, test-time augmentation has no 2-byte labels).
+#define SEGMI_LABEL_CASE(lb, L, F, ...) if ((lb) == (int)sizeof(L)) { F(L, ##__VA_ARGS__); }
+#define SEGMI_BAD_LABEL(lb) SEGMI_CHECK_ARG(false, "unsupported label_bytes %d", (int)(lb))
+#define SEGMI_BY_LABEL_AS(lb, L1, L2, L4, F, ...)           \
+  do {                                                      \
+    SEGMI_LABEL_CASE(lb, L1, F, ##__VA_ARGS__)              \
+    else SEGMI_LABEL_CASE(lb, L2, F, ##__VA_ARGS__)         \
+    else SEGMI_LABEL_CASE(lb, L4, F, ##__VA_ARGS__)         \
+    else SEGMI_BAD_LABEL(lb);                               \
+  } while (0)
+#define SEGMI_BY_LABEL_14(lb, F, ...)                       \
+  do {                                                      \
+    SEGMI_LABEL_CASE(lb, uint8_t, F, ##__VA_ARGS__)         \
+    else SEGMI_LABEL_CASE(lb, int32_t, F, ##__VA_ARGS__)    \
+    else SEGMI_BAD_LABEL(lb);                               \
+  } while (0)
+#define LV_BY_LABEL(lb, F, ...) SEGMI_BY_LABEL_AS(lb, uint8_t, int16_t, int32_t, F, ##__VA_ARGS__)
+
+// workgroups of 256 threads for `total` items, at most `cap` (the kernels stride over the rest), at least 1
+static inline int grid_1d(int64_t total, int cap) {
+  const int64_t b = cdiv64(total, 256);
+  return (int)(b > cap ? cap : (b < 1 ? 1 : b));
+}
 
 // ------------------------------------------------------------------ fragment-pack geometry
 // k-slot enumeration shared by the pack kernels and the MFMA kernels.

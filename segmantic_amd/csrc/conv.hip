@@ -18,14 +18,19 @@ int conv_mfma_f16(const ConvParams& p, int ksize, int stride, hipStream_t st);
 int convt_mfma_f32(const ConvTParams& p, hipStream_t st);
 int convt_mfma_bf16(const ConvTParams& p, hipStream_t st);
 int convt_mfma_f16(const ConvTParams& p, hipStream_t st);
-// the MFMA families by storage format
+// the MFMA families by storage format: one translation unit and one function name per type, so the choice
+// is spelled out here instead of going through SEGMI_BY_DTYPE; it fails closed all the same
 static inline int conv_mfma_dt(int dtype, const ConvParams& p, int ksize, int stride, hipStream_t st) {
   if (dtype == SEGMI_F32) return conv_mfma_f32(p, ksize, stride, st);
-  return dtype == SEGMI_F16 ? conv_mfma_f16(p, ksize, stride, st) : conv_mfma_bf16(p, ksize, stride, st);
+  if (dtype == SEGMI_F16) return conv_mfma_f16(p, ksize, stride, st);
+  SEGMI_CHECK_ARG(dtype == SEGMI_BF16, "conv3d: unknown dtype code %d", dtype);
+  return conv_mfma_bf16(p, ksize, stride, st);
 }
 static inline int convt_mfma_dt(int dtype, const ConvTParams& p, hipStream_t st) {
   if (dtype == SEGMI_F32) return convt_mfma_f32(p, st);
-  return dtype == SEGMI_F16 ? convt_mfma_f16(p, st) : convt_mfma_bf16(p, st);
+  if (dtype == SEGMI_F16) return convt_mfma_f16(p, st);
+  SEGMI_CHECK_ARG(dtype == SEGMI_BF16, "convT3d: unknown dtype code %d", dtype);
+  return convt_mfma_bf16(p, st);
 }
 int bn_stats_launch(int dtype, const segmi_act* x, float* partials, hipStream_t st, const BiasFin* bias_fin = nullptr);
 int bn_stats_rows_for(const segmi_act* x);
@@ -257,7 +262,7 @@ const char* segmi_conv3d_fwd_kernel_name(int dtype, const segmi_act* in, const s
                                          int ksize, int stride) {
   static thread_local char buf[96];
   if (!act_ok(in) || !act_ok(out)) return "invalid";
-  const char* dt = dtype == SEGMI_BF16 ? "bf16" : dtype == SEGMI_F16 ? "f16" : "f32";
+  const char* dt = dtype_name(dtype);
   if (mfma_ok(in->c, out->c)) {
     const int ck = pick_ck(dtype, in->c);
     if (conv_ring_ok(dtype, in->c, ksize, stride, out)) {
@@ -415,11 +420,8 @@ int segmi_conv3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, const
   p.N = in->n; p.Di = in->d; p.Hi = in->h; p.Wi = in->w; p.Do = out->d; p.Ho = out->h;
   p.Wo = out->w; p.Cin = in->c; p.Cout = out->c; p.ldi = in->ld; p.ldo = out->ld;
   p.ldr = residual ? residual->ld : 0; p.ks = ksize; p.stride = stride; p.kind = w_kind;
-  const int64_t total = act_voxels(out) * out->c;
-  int blocks = (int)(cdiv64(total, 256) > 8192 ? 8192 : cdiv64(total, 256));
-  if (dtype == SEGMI_F32) hipLaunchKernelGGL(conv_direct_kernel<float>, blocks, 256, 0, st, p);
-  else if (dtype == SEGMI_F16) hipLaunchKernelGGL(conv_direct_kernel<f16_t>, blocks, 256, 0, st, p);
-  else hipLaunchKernelGGL(conv_direct_kernel<bf16_t>, blocks, 256, 0, st, p);
+#define DIRECT(T, KERN) hipLaunchKernelGGL(KERN<T>, grid_1d(act_voxels(out) * out->c, 8192), 256, 0, st, p)
+  SEGMI_BY_DTYPE(dtype, DIRECT, conv_direct_kernel);
   SEGMI_LAUNCH_CHECK("conv3d_fwd(direct)");
   if (stats_partials) {
     SEGMI_CHECK_ARG(!prelu_alpha && !residual,
@@ -484,11 +486,8 @@ int segmi_convT3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, cons
   p.N = in->n; p.Di = in->d; p.Hi = in->h; p.Wi = in->w; p.Do = out->d; p.Ho = out->h;
   p.Wo = out->w; p.Cin = in->c; p.Cout = out->c; p.ldi = in->ld; p.ldo = out->ld;
   p.ldr = residual ? residual->ld : 0; p.ks = 3; p.stride = 2; p.kind = 2;
-  const int64_t total = act_voxels(out) * out->c;
-  int blocks = (int)(cdiv64(total, 256) > 8192 ? 8192 : cdiv64(total, 256));
-  if (dtype == SEGMI_F32) hipLaunchKernelGGL(convt_direct_kernel<float>, blocks, 256, 0, st, p);
-  else if (dtype == SEGMI_F16) hipLaunchKernelGGL(convt_direct_kernel<f16_t>, blocks, 256, 0, st, p);
-  else hipLaunchKernelGGL(convt_direct_kernel<bf16_t>, blocks, 256, 0, st, p);
+  SEGMI_BY_DTYPE(dtype, DIRECT, convt_direct_kernel);
+#undef DIRECT
   SEGMI_LAUNCH_CHECK("convT3d_fwd(direct)");
   if (stats_partials) {
     SEGMI_CHECK_ARG(!prelu_alpha && !residual,

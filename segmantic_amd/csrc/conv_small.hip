@@ -548,7 +548,7 @@ int conv_small_fwd(int dtype, const segmi_act* in, const segmi_act* out, const f
   }
   if (out2) { p.out2 = out2->data; p.w2 = w2; p.bias2 = bias2; p.ldo2 = out2->ld; }
   p.vec = in->c == 1 && in->ld == 1 && in->w % 4 == 0 &&
-          ((uintptr_t)in->data % (4 * (dtype == SEGMI_F32 ? 4 : 2))) == 0;
+          ((uintptr_t)in->data % (4 * dtype_size(dtype))) == 0;
   if (win) SEGMI_CHECK_ARG(p.vec, "conv3d: window views need the 4-element staging path");
   p.in = in->data; p.out = out->data; p.w = w; p.bias = bias; p.alpha = alpha;
   p.res = res ? res->data : nullptr; p.ldr = res ? res->ld : 0; p.stats = stats;
@@ -556,14 +556,10 @@ int conv_small_fwd(int dtype, const segmi_act* in, const segmi_act* out, const f
   p.Cout = out->c; p.ldi = in->ld; p.ldo = out->ld;
   p.tz = cdiv(out->d, 4); p.ty = cdiv(out->h, 8); p.tx = cdiv(out->w, 16);
   SEGMI_CHECK_ARG((int64_t)p.N * p.tz * p.ty * p.tx < (1ll << 31), "conv3d: too many tiles");
-  if (dtype == SEGMI_F32)
-    return stride == 2 ? launch_small_fwd_cin<float, 2>(p, in->c, st)
-                       : launch_small_fwd_cin<float, 1>(p, in->c, st);
-  if (dtype == SEGMI_F16)
-    return stride == 2 ? launch_small_fwd_cin<f16_t, 2>(p, in->c, st)
-                       : launch_small_fwd_cin<f16_t, 1>(p, in->c, st);
-  return stride == 2 ? launch_small_fwd_cin<bf16_t, 2>(p, in->c, st)
-                     : launch_small_fwd_cin<bf16_t, 1>(p, in->c, st);
+#define SMALL_FWD(T) \
+  return stride == 2 ? launch_small_fwd_cin<T, 2>(p, in->c, st) : launch_small_fwd_cin<T, 1>(p, in->c, st)
+  SEGMI_BY_DTYPE(dtype, SMALL_FWD);
+#undef SMALL_FWD
 }
 
 int conv_small_wgrad_slabs(const segmi_act* dy) {
@@ -609,14 +605,10 @@ int conv_small_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float* 
   p.tz = cdiv(dy->d, 2); p.ty = cdiv(dy->h, 8); p.tx = cdiv(dy->w, 16);
   p.ntiles = dy->n * p.tz * p.ty * p.tx;
   const int grid = conv_small_wgrad_slabs(dy);
-  if (dtype == SEGMI_F32)
-    return stride == 2 ? launch_small_wgrad_cin<float, 2>(p, x->c, grid, st)
-                       : launch_small_wgrad_cin<float, 1>(p, x->c, grid, st);
-  if (dtype == SEGMI_F16)
-    return stride == 2 ? launch_small_wgrad_cin<f16_t, 2>(p, x->c, grid, st)
-                       : launch_small_wgrad_cin<f16_t, 1>(p, x->c, grid, st);
-  return stride == 2 ? launch_small_wgrad_cin<bf16_t, 2>(p, x->c, grid, st)
-                     : launch_small_wgrad_cin<bf16_t, 1>(p, x->c, grid, st);
+#define SMALL_WGRAD(T) \
+  return stride == 2 ? launch_small_wgrad_cin<T, 2>(p, x->c, grid, st) : launch_small_wgrad_cin<T, 1>(p, x->c, grid, st)
+  SEGMI_BY_DTYPE(dtype, SMALL_WGRAD);
+#undef SMALL_WGRAD
 }
 
 }  // namespace segmi

@@ -1,6 +1,6 @@
 // labelvol.h -- the foundation shared by the label-volume translation units (distance, components,
 // morphology, surfaces, decimate; landmarks, n4 and nyul take the pieces that apply): workspace carving,
-// the label-type dispatch, the host argument checks, the capped grid size, the host-table uploader and the
+// the host argument checks, the capped grid size, the host-table uploader and the
 // workgroup scan.  Everything here is integer arithmetic or a bare comparison, so the header means the same
 // in the units compiled with -ffp-contract=off and in those compiled without it.
 #pragma once
@@ -17,15 +17,6 @@ struct LvCarver {
   size_t off = 0;                                // bytes carved so far: the total after the last take()
   size_t take(size_t bytes) { const size_t at = off; off += lv_align256(bytes); return at; }
 };
-
-// ------------------------------------------------------------------ label-type dispatch
-// F(T, extra...) for the storage type of label_bytes 1 / 2 / 4 (checked by LV_CHECK_LABEL_BYTES)
-#define LV_BY_LABEL(lb, F, ...)                              \
-  do {                                                       \
-    if ((lb) == 1) F(uint8_t, ##__VA_ARGS__);                \
-    else if ((lb) == 2) F(int16_t, ##__VA_ARGS__);           \
-    else F(int32_t, ##__VA_ARGS__);                          \
-  } while (0)
 
 // ------------------------------------------------------------------ host argument checks
 static inline bool lv_voxels_ok(int d, int h, int w) {
@@ -63,10 +54,7 @@ static inline bool lv_spacing_ok(const F* s) {
 
 // ------------------------------------------------------------------ launches
 // workgroups for n items at `per` items each, at most `cap` (the kernels stride over the rest), at least 1
-static inline int lv_grid(int64_t n, int per, int cap) {
-  const int64_t g = cdiv64(n, per);
-  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
-}
+static inline int lv_grid(int64_t n, int per, int cap) { return grid_1d(cdiv64(n, per) * 256, cap); }
 
 // A host table reaches the device through kernel arguments, N entries per launch: no staging buffer, no
 // copy that would have to outlive the call.  sink(i, e) receives entry i of the table.

@@ -578,10 +578,7 @@ __global__ void amp_update_kernel(float* amp, int32_t* tracker, int64_t* step, f
   amp[1] = 0.f;
 }
 
-static inline int opt_blocks(int64_t n) {
-  const int64_t b = cdiv64(n, 256);
-  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
+constexpr int kOptCap = 2048;   // workgroups of an optimiser step
 
 template <typename T, bool CE>
 static int dice_dispatch(bool fwd, const DiceParams& p, hipStream_t st) {
@@ -608,8 +605,9 @@ static int dice_dispatch(bool fwd, const DiceParams& p, hipStream_t st) {
 }
 template <bool CE>
 static int dice_dispatch_dt(int dtype, bool fwd, const DiceParams& p, hipStream_t st) {
-  if (dtype == SEGMI_F32) return dice_dispatch<float, CE>(fwd, p, st);
-  return dtype == SEGMI_F16 ? dice_dispatch<f16_t, CE>(fwd, p, st) : dice_dispatch<bf16_t, CE>(fwd, p, st);
+#define DICE_T(T) return dice_dispatch<T, CE>(fwd, p, st)
+  SEGMI_BY_DTYPE(dtype, DICE_T);
+#undef DICE_T
 }
 
 }  // namespace segmi
@@ -740,7 +738,7 @@ int segmi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_
   const double bc2 = 1.0 - pow(beta2, (double)step);
   const float step_size = (float)(lr / bc1);
   const float bc2_sqrt = (float)sqrt(bc2);
-  hipLaunchKernelGGL(adam_kernel, opt_blocks(n), 256, 0, (hipStream_t)stream, param, grad,
+  hipLaunchKernelGGL(adam_kernel, grid_1d(n, kOptCap), 256, 0, (hipStream_t)stream, param, grad,
                      exp_avg, exp_avg_sq, max_exp_avg_sq, n, (float)(1.0 - beta1), (float)beta2,
                      (float)(1.0 - beta2), (float)eps, (float)weight_decay, step_size, bc2_sqrt,
                      grad_scale);
@@ -752,7 +750,7 @@ int segmi_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t
                    double momentum, double weight_decay, int first_step, float grad_scale,
                    void* stream) {
   SEGMI_CHECK_ARG(param && grad && n > 0 && (momentum == 0.0 || momentum_buf), "sgd: bad arguments");
-  hipLaunchKernelGGL(sgd_kernel, opt_blocks(n), 256, 0, (hipStream_t)stream, param, grad,
+  hipLaunchKernelGGL(sgd_kernel, grid_1d(n, kOptCap), 256, 0, (hipStream_t)stream, param, grad,
                      momentum_buf, n, (float)lr, (float)momentum, (float)weight_decay, first_step,
                      grad_scale);
   SEGMI_LAUNCH_CHECK("sgd");
@@ -766,7 +764,7 @@ int segmi_adabelief_step(float* param, const float* grad, float* exp_avg, float*
   SEGMI_CHECK_ARG(param && grad && exp_avg && exp_avg_var && n > 0 && step > 0, "adabelief: bad arguments");
   const double bc1 = 1.0 - pow(beta1, (double)step);
   const double bc2 = 1.0 - pow(beta2, (double)step);
-  hipLaunchKernelGGL(adabelief_kernel, opt_blocks(n), 256, 0, (hipStream_t)stream, param, grad,
+  hipLaunchKernelGGL(adabelief_kernel, grid_1d(n, kOptCap), 256, 0, (hipStream_t)stream, param, grad,
                      exp_avg, exp_avg_var, n, (float)(1.0 - lr * weight_decay), (float)beta1,
                      (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
                      (float)weight_decay, weight_decouple, (float)(lr / bc1), (float)sqrt(bc2),
@@ -777,7 +775,7 @@ int segmi_adabelief_step(float* param, const float* grad, float* exp_avg, float*
 
 int segmi_amp_check_finite(const float* grad, int64_t n, float* amp, void* stream) {
   SEGMI_CHECK_ARG(grad && amp && n > 0, "amp_check_finite: bad arguments");
-  hipLaunchKernelGGL(amp_check_kernel, opt_blocks(n), 256, 0, (hipStream_t)stream, grad, n, amp);
+  hipLaunchKernelGGL(amp_check_kernel, grid_1d(n, kOptCap), 256, 0, (hipStream_t)stream, grad, n, amp);
   SEGMI_LAUNCH_CHECK("amp_check_finite");
   return SEGMI_OK;
 }
@@ -796,7 +794,7 @@ int segmi_adam_step_amp(float* param, const float* grad, float* exp_avg, float* 
                         double eps, double weight_decay, const float* amp, const int64_t* step,
                         float grad_scale, void* stream) {
   SEGMI_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n > 0 && amp && step, "adam_amp: bad arguments");
-  hipLaunchKernelGGL(adam_amp_kernel, opt_blocks(n), 256, 0, (hipStream_t)stream, param, grad, exp_avg,
+  hipLaunchKernelGGL(adam_amp_kernel, grid_1d(n, kOptCap), 256, 0, (hipStream_t)stream, param, grad, exp_avg,
                      exp_avg_sq, max_exp_avg_sq, n, lr, beta1, beta2, (float)eps, (float)weight_decay, amp, step,
                      grad_scale);
   SEGMI_LAUNCH_CHECK("adam_amp");
@@ -808,7 +806,7 @@ int segmi_sgd_step_amp(float* param, const float* grad, float* momentum_buf, int
                        float grad_scale, void* stream) {
   SEGMI_CHECK_ARG(param && grad && n > 0 && (momentum == 0.0 || momentum_buf) && amp && step,
                   "sgd_amp: bad arguments");
-  hipLaunchKernelGGL(sgd_amp_kernel, opt_blocks(n), 256, 0, (hipStream_t)stream, param, grad, momentum_buf, n,
+  hipLaunchKernelGGL(sgd_amp_kernel, grid_1d(n, kOptCap), 256, 0, (hipStream_t)stream, param, grad, momentum_buf, n,
                      (float)lr, (float)momentum, (float)weight_decay, amp, step, grad_scale);
   SEGMI_LAUNCH_CHECK("sgd_amp");
   return SEGMI_OK;
@@ -819,7 +817,7 @@ int segmi_adabelief_step_amp(float* param, const float* grad, float* exp_avg, fl
                              double weight_decay, int weight_decouple, const float* amp,
                              const int64_t* step, float grad_scale, void* stream) {
   SEGMI_CHECK_ARG(param && grad && exp_avg && exp_avg_var && n > 0 && amp && step, "adabelief_amp: bad arguments");
-  hipLaunchKernelGGL(adabelief_amp_kernel, opt_blocks(n), 256, 0, (hipStream_t)stream, param, grad, exp_avg,
+  hipLaunchKernelGGL(adabelief_amp_kernel, grid_1d(n, kOptCap), 256, 0, (hipStream_t)stream, param, grad, exp_avg,
                      exp_avg_var, n, lr, beta1, beta2, (float)eps, weight_decay, weight_decouple, amp, step,
                      grad_scale);
   SEGMI_LAUNCH_CHECK("adabelief_amp");

@@ -160,19 +160,14 @@ int bn_stats_launch(int dtype, const segmi_act* x, float* partials, hipStream_t 
     p.fin_on = 1; p.biasfin = *bias_fin;
     lds = fin_tail_arm(p, dim3(rows), 256, 2 * x->c, 0);
   }
-  if (v4) {
-    if (dtype == SEGMI_F32) hipLaunchKernelGGL((bn_stats_kernel<float, 4>), rows, 256, lds, st, p);
-    else if (dtype == SEGMI_F16) hipLaunchKernelGGL((bn_stats_kernel<f16_t, 4>), rows, 256, lds, st, p);
-    else hipLaunchKernelGGL((bn_stats_kernel<bf16_t, 4>), rows, 256, lds, st, p);
-  } else if (x->c <= 256) {
-    if (dtype == SEGMI_F32) hipLaunchKernelGGL((bn_stats_kernel<float, 1>), rows, 256, lds, st, p);
-    else if (dtype == SEGMI_F16) hipLaunchKernelGGL((bn_stats_kernel<f16_t, 1>), rows, 256, lds, st, p);
-    else hipLaunchKernelGGL((bn_stats_kernel<bf16_t, 1>), rows, 256, lds, st, p);
-  } else {
-    if (dtype == SEGMI_F32) hipLaunchKernelGGL(bn_stats_wide_kernel<float>, rows, 256, 0, st, p);
-    else if (dtype == SEGMI_F16) hipLaunchKernelGGL(bn_stats_wide_kernel<f16_t>, rows, 256, 0, st, p);
-    else hipLaunchKernelGGL(bn_stats_wide_kernel<bf16_t>, rows, 256, 0, st, p);
-  }
+#define BN_STATS(T)                                                                           \
+  do {                                                                                        \
+    if (v4) hipLaunchKernelGGL((bn_stats_kernel<T, 4>), rows, 256, lds, st, p);               \
+    else if (x->c <= 256) hipLaunchKernelGGL((bn_stats_kernel<T, 1>), rows, 256, lds, st, p); \
+    else hipLaunchKernelGGL(bn_stats_wide_kernel<T>, rows, 256, 0, st, p);                    \
+  } while (0)
+  SEGMI_BY_DTYPE(dtype, BN_STATS);
+#undef BN_STATS
   SEGMI_LAUNCH_CHECK("bn_stats");
   if (bias_fin && !tail) {
     const int width = 2 * x->c;
@@ -622,10 +617,7 @@ __global__ void ndhwc_to_nchw_kernel(const T* __restrict__ s, float* __restrict_
   }
 }
 
-static inline int ew_blocks(int64_t total) {
-  const int64_t b = cdiv64(total, 256);
-  return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
-}
+constexpr int kEwCap = 4096;   // workgroups of an elementwise pass
 
 static inline bool same_shape(const segmi_act* a, const segmi_act* b) {
   return a->n == b->n && a->d == b->d && a->h == b->h && a->w == b->w && a->c == b->c;
@@ -635,19 +627,13 @@ static inline bool same_shape(const segmi_act* a, const segmi_act* b) {
 
 using namespace segmi;
 
-#define DISPATCH_TV(KERN, dtype, v4, grid, lds, st, p)                                        \
-  do {                                                                                        \
-    if (dtype == SEGMI_F32) {                                                                 \
-      if (v4) hipLaunchKernelGGL((KERN<float, 4>), grid, 256, lds, st, p);                    \
-      else hipLaunchKernelGGL((KERN<float, 1>), grid, 256, lds, st, p);                       \
-    } else if (dtype == SEGMI_F16) {                                                          \
-      if (v4) hipLaunchKernelGGL((KERN<f16_t, 4>), grid, 256, lds, st, p);                    \
-      else hipLaunchKernelGGL((KERN<f16_t, 1>), grid, 256, lds, st, p);                       \
-    } else {                                                                                  \
-      if (v4) hipLaunchKernelGGL((KERN<bf16_t, 4>), grid, 256, lds, st, p);                   \
-      else hipLaunchKernelGGL((KERN<bf16_t, 1>), grid, 256, lds, st, p);                      \
-    }                                                                                         \
+// KERN<T, 4> where every row takes 16-byte accesses, KERN<T, 1> otherwise
+#define LAUNCH_TV(T, KERN, v4, grid, lds, st, p)                        \
+  do {                                                                  \
+    if (v4) hipLaunchKernelGGL((KERN<T, 4>), grid, 256, lds, st, p);    \
+    else hipLaunchKernelGGL((KERN<T, 1>), grid, 256, lds, st, p);       \
   } while (0)
+#define DISPATCH_TV(KERN, dtype, ...) SEGMI_BY_DTYPE(dtype, LAUNCH_TV, KERN, __VA_ARGS__)
 
 extern "C" {
 
@@ -699,7 +685,7 @@ int segmi_bn_act_fwd(int dtype, const segmi_act* x, const segmi_act* y, const fl
   p.ldr = residual ? residual->ld : 0;
   p.p0 = scale; p.p1 = shift; p.alpha = prelu_alpha;
   const bool v4 = vec4_ok(x, dtype) && vec4_ok(y, dtype) && (!residual || vec4_ok(residual, dtype));
-  const int grid = ew_blocks(p.nvox * (x->c / (v4 ? 4 : 1)));
+  const int grid = grid_1d(p.nvox * (x->c / (v4 ? 4 : 1)), kEwCap);
   DISPATCH_TV(bn_act_fwd_kernel, dtype, v4, grid, 2 * x->c * sizeof(float), (hipStream_t)stream, p);
   SEGMI_LAUNCH_CHECK("bn_act_fwd");
   return SEGMI_OK;
@@ -770,7 +756,7 @@ int segmi_bn_act_bwd_apply(int dtype, const segmi_act* dy, const segmi_act* x,
   p.ldx = x->ld; p.ldy = dy->ld; p.ldo = dx->ld;
   p.p0 = mean; p.p1 = invstd; p.p2 = gamma; p.p3 = beta; p.alpha = prelu_alpha; p.coef = coef;
   const bool v4 = vec4_ok(x, dtype) && vec4_ok(dy, dtype) && vec4_ok(dx, dtype);
-  const int grid = ew_blocks(p.nvox * (x->c / (v4 ? 4 : 1)));
+  const int grid = grid_1d(p.nvox * (x->c / (v4 ? 4 : 1)), kEwCap);
   DISPATCH_TV(bn_act_bwd_apply_kernel, dtype, v4, grid, 6 * x->c * sizeof(float), (hipStream_t)stream, p);
   SEGMI_LAUNCH_CHECK("bn_act_bwd_apply");
   return SEGMI_OK;
@@ -784,8 +770,12 @@ static inline size_t fused_lds_bytes(int c) {
   return fold > tail ? fold : tail;
 }
 // workgroups of this kernel the CURRENT device holds at once (occupancy query x compute units, <= 256), per
-// dtype and LDS size; 0 = it cannot hold one
+// dtype and LDS size; below 1 = it cannot hold one
 static int fused_capacity(int dtype, size_t lds) {
+  const void* fn = nullptr;
+#define FUSED_FN(T) fn = reinterpret_cast<const void*>(bn_act_bwd_fused_kernel<T>)
+  SEGMI_BY_DTYPE(dtype, FUSED_FN);
+#undef FUSED_FN
   static std::mutex mu;
   static std::map<std::tuple<int, int, size_t>, int> cache;
   int dev = 0;
@@ -795,9 +785,6 @@ static int fused_capacity(int dtype, size_t lds) {
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
   int per_cu = 0, cus = 0;
-  const void* fn = dtype == SEGMI_F32   ? reinterpret_cast<const void*>(bn_act_bwd_fused_kernel<float>)
-                   : dtype == SEGMI_F16 ? reinterpret_cast<const void*>(bn_act_bwd_fused_kernel<f16_t>)
-                                        : reinterpret_cast<const void*>(bn_act_bwd_fused_kernel<bf16_t>);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kFusedThreads, lds) != hipSuccess) per_cu = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
   (void)hipGetLastError();
@@ -877,9 +864,9 @@ int segmi_bn_act_bwd_fused(int dtype, const segmi_act* dy, const segmi_act* x, c
   p.no_publish = g_fused_no_publish.load(std::memory_order_relaxed);
   p.tmo = g_fused_tmo_dev;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == SEGMI_F32) hipLaunchKernelGGL(bn_act_bwd_fused_kernel<float>, rows, kFusedThreads, lds, st, p);
-  else if (dtype == SEGMI_F16) hipLaunchKernelGGL(bn_act_bwd_fused_kernel<f16_t>, rows, kFusedThreads, lds, st, p);
-  else hipLaunchKernelGGL(bn_act_bwd_fused_kernel<bf16_t>, rows, kFusedThreads, lds, st, p);
+#define FUSED(T) hipLaunchKernelGGL(bn_act_bwd_fused_kernel<T>, rows, kFusedThreads, lds, st, p)
+  SEGMI_BY_DTYPE(dtype, FUSED);
+#undef FUSED
   SEGMI_LAUNCH_CHECK("bn_act_bwd_fused");
   return SEGMI_OK;
 }
@@ -904,52 +891,43 @@ int segmi_fused_test_hook(unsigned poll_limit, int no_publish) {
 int segmi_cast_copy(int src_dtype, const segmi_act* src, int dst_dtype, const segmi_act* dst,
                     void* stream) {
   SEGMI_CHECK_ARG(act_ok(src) && act_ok(dst) && same_shape(src, dst), "cast_copy: shape mismatch");
+  SEGMI_CHECK_ARG(dtype_pair_ok(src_dtype, dst_dtype), "cast_copy: bad dtypes");
   const int64_t nvox = act_voxels(src);
-  const int grid = ew_blocks(nvox * src->c);
+  const int grid = grid_1d(nvox * src->c, kEwCap);
   hipStream_t st = (hipStream_t)stream;
-  if (src_dtype == SEGMI_F32 && dst_dtype == SEGMI_F32)
-    hipLaunchKernelGGL((cast_copy_kernel<float, float>), grid, 256, 0, st, (const float*)src->data, (float*)dst->data, nvox, src->c, src->ld, dst->ld);
-  else if (src_dtype == SEGMI_F32 && dst_dtype == SEGMI_BF16)
-    hipLaunchKernelGGL((cast_copy_kernel<float, bf16_t>), grid, 256, 0, st, (const float*)src->data, (bf16_t*)dst->data, nvox, src->c, src->ld, dst->ld);
-  else if (src_dtype == SEGMI_BF16 && dst_dtype == SEGMI_F32)
-    hipLaunchKernelGGL((cast_copy_kernel<bf16_t, float>), grid, 256, 0, st, (const bf16_t*)src->data, (float*)dst->data, nvox, src->c, src->ld, dst->ld);
-  else if (src_dtype == SEGMI_BF16 && dst_dtype == SEGMI_BF16)
-    hipLaunchKernelGGL((cast_copy_kernel<bf16_t, bf16_t>), grid, 256, 0, st, (const bf16_t*)src->data, (bf16_t*)dst->data, nvox, src->c, src->ld, dst->ld);
-  else if (src_dtype == SEGMI_F32 && dst_dtype == SEGMI_F16)
-    hipLaunchKernelGGL((cast_copy_kernel<float, f16_t>), grid, 256, 0, st, (const float*)src->data, (f16_t*)dst->data, nvox, src->c, src->ld, dst->ld);
-  else if (src_dtype == SEGMI_F16 && dst_dtype == SEGMI_F32)
-    hipLaunchKernelGGL((cast_copy_kernel<f16_t, float>), grid, 256, 0, st, (const f16_t*)src->data, (float*)dst->data, nvox, src->c, src->ld, dst->ld);
-  else if (src_dtype == SEGMI_F16 && dst_dtype == SEGMI_F16)
-    hipLaunchKernelGGL((cast_copy_kernel<f16_t, f16_t>), grid, 256, 0, st, (const f16_t*)src->data, (f16_t*)dst->data, nvox, src->c, src->ld, dst->ld);
-  else SEGMI_CHECK_ARG(false, "cast_copy: bad dtypes");
+#define CAST_COPY(TS, TD)                                                                                  \
+  hipLaunchKernelGGL((cast_copy_kernel<TS, TD>), grid, 256, 0, st, (const TS*)src->data, (TD*)dst->data, nvox, \
+                     src->c, src->ld, dst->ld)
+  SEGMI_BY_DTYPE_PAIR(src_dtype, dst_dtype, CAST_COPY);
+#undef CAST_COPY
   SEGMI_LAUNCH_CHECK("cast_copy");
   return SEGMI_OK;
 }
 
 int segmi_nchw_to_ndhwc(const float* src, int dst_dtype, const segmi_act* dst, void* stream) {
   SEGMI_CHECK_ARG(src && act_ok(dst), "nchw_to_ndhwc: bad arguments");
+  SEGMI_CHECK_ARG(dtype_ok(dst_dtype), "nchw_to_ndhwc: bad dtype");
   const int64_t vox = (int64_t)dst->d * dst->h * dst->w;
-  const int grid = ew_blocks((int64_t)dst->n * vox * dst->c);
-  if (dst_dtype == SEGMI_F32)
-    hipLaunchKernelGGL(nchw_to_ndhwc_kernel<float>, grid, 256, 0, (hipStream_t)stream, src, (float*)dst->data, dst->n, dst->c, vox, dst->ld);
-  else if (dst_dtype == SEGMI_F16)
-    hipLaunchKernelGGL(nchw_to_ndhwc_kernel<f16_t>, grid, 256, 0, (hipStream_t)stream, src, (f16_t*)dst->data, dst->n, dst->c, vox, dst->ld);
-  else
-    hipLaunchKernelGGL(nchw_to_ndhwc_kernel<bf16_t>, grid, 256, 0, (hipStream_t)stream, src, (bf16_t*)dst->data, dst->n, dst->c, vox, dst->ld);
+  const int grid = grid_1d((int64_t)dst->n * vox * dst->c, kEwCap);
+#define TO_NDHWC(T)                                                                                         \
+  hipLaunchKernelGGL(nchw_to_ndhwc_kernel<T>, grid, 256, 0, (hipStream_t)stream, src, (T*)dst->data, dst->n, \
+                     dst->c, vox, dst->ld)
+  SEGMI_BY_DTYPE(dst_dtype, TO_NDHWC);
+#undef TO_NDHWC
   SEGMI_LAUNCH_CHECK("nchw_to_ndhwc");
   return SEGMI_OK;
 }
 
 int segmi_ndhwc_to_nchw(int src_dtype, const segmi_act* src, float* dst, void* stream) {
   SEGMI_CHECK_ARG(dst && act_ok(src), "ndhwc_to_nchw: bad arguments");
+  SEGMI_CHECK_ARG(dtype_ok(src_dtype), "ndhwc_to_nchw: bad dtype");
   const int64_t vox = (int64_t)src->d * src->h * src->w;
-  const int grid = ew_blocks((int64_t)src->n * vox * src->c);
-  if (src_dtype == SEGMI_F32)
-    hipLaunchKernelGGL(ndhwc_to_nchw_kernel<float>, grid, 256, 0, (hipStream_t)stream, (const float*)src->data, dst, src->n, src->c, vox, src->ld);
-  else if (src_dtype == SEGMI_F16)
-    hipLaunchKernelGGL(ndhwc_to_nchw_kernel<f16_t>, grid, 256, 0, (hipStream_t)stream, (const f16_t*)src->data, dst, src->n, src->c, vox, src->ld);
-  else
-    hipLaunchKernelGGL(ndhwc_to_nchw_kernel<bf16_t>, grid, 256, 0, (hipStream_t)stream, (const bf16_t*)src->data, dst, src->n, src->c, vox, src->ld);
+  const int grid = grid_1d((int64_t)src->n * vox * src->c, kEwCap);
+#define TO_NCHW(T)                                                                                          \
+  hipLaunchKernelGGL(ndhwc_to_nchw_kernel<T>, grid, 256, 0, (hipStream_t)stream, (const T*)src->data, dst, \
+                     src->n, src->c, vox, src->ld)
+  SEGMI_BY_DTYPE(src_dtype, TO_NCHW);
+#undef TO_NCHW
   SEGMI_LAUNCH_CHECK("ndhwc_to_nchw");
   return SEGMI_OK;
 }

@@ -1,5 +1,6 @@
 // sliding.hip -- sliding-window inference data movement (gather / ordered blend / finalise),
-// channel argmax, label overlap counts and the on-device patch cropper.  All HBM-bound.
+// channel argmax and label overlap counts.  All HBM-bound.  (The training sampler's patch cropper lives
+// with the other sampler gathers in augment.hip.)
 #include <type_traits>
 
 #include "common.h"
@@ -7,6 +8,7 @@
 namespace segmi {
 
 constexpr int kMaxWin = 16;
+constexpr int kSwGrid = 8192;   // workgroup cap of the strided 1-D kernels
 
 struct WinList {
   int n;
@@ -325,39 +327,6 @@ __global__ void label_counts_kernel(const int32_t* __restrict__ pred, const int3
     if (hist[i]) atomicAdd(&counts[i], (unsigned long long)hist[i]);
 }
 
-struct CropList {
-  int n;
-  int b[kMaxWin], z[kMaxWin], y[kMaxWin], x[kMaxWin];
-  unsigned char flip[kMaxWin];
-};
-
-template <typename TD>
-__global__ void crop_kernel(const float* __restrict__ img, const float* __restrict__ lab, CropList cl,
-                            int D, int H, int W, int C, int ldi, TD* __restrict__ oimg,
-                            float* __restrict__ olab, int rd, int rh, int rw, int ldo) {
-  const int64_t per = (int64_t)rd * rh * rw;
-  const int64_t total = per * cl.n;
-  for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    int64_t t = e;
-    const int x = t % rw; t /= rw;
-    const int y = t % rh; t /= rh;
-    const int z = t % rd;
-    const int w = t / rd;
-    const unsigned char f = cl.flip[w];
-    const int sz = (f & 1) ? rd - 1 - z : z, sy = (f & 2) ? rh - 1 - y : y, sx = (f & 4) ? rw - 1 - x : x;
-    const int gz = cl.z[w] + sz, gy = cl.y[w] + sy, gx = cl.x[w] + sx;
-    const bool in = (unsigned)gz < (unsigned)D && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-    const int64_t gv = (((int64_t)cl.b[w] * D + gz) * H + gy) * W + gx;
-    for (int c = 0; c < C; ++c) Elem<TD>::st(oimg + e * ldo + c, in ? img[gv * ldi + c] : 0.f);
-    if (olab) olab[e] = (in && lab) ? lab[gv] : 0.f;
-  }
-}
-
-static inline int grid_for(int64_t total) {
-  const int64_t b = cdiv64(total, 256);
-  return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
-
 
 // The same blend for schedules in which at most TWO windows cover a coordinate in every dimension (overlap <= 0.5:
 // BASELINE config 3 and the reference's defaults): the <= 8 covering windows of a voxel are located first (z, y:
@@ -502,46 +471,31 @@ int segmi_sw_gather(int dtype_src, const segmi_act* image, int img_index,
   SEGMI_CHECK_ARG(act_ok(image) && act_ok(windows) && starts_host, "sw_gather: bad arguments");
   SEGMI_CHECK_ARG(nwin > 0 && nwin <= kMaxWin && windows->n >= nwin, "sw_gather: 1..%d windows per call", kMaxWin);
   SEGMI_CHECK_ARG(img_index >= 0 && img_index < image->n && image->c == windows->c, "sw_gather: image index / channels");
+  SEGMI_CHECK_ARG(dtype_pair_ok(dtype_src, dst_dtype), "sw_gather: bad dtypes");
   WinList wl{};
   wl.n = nwin;
   for (int i = 0; i < nwin; ++i) { wl.z[i] = starts_host[3 * i]; wl.y[i] = starts_host[3 * i + 1]; wl.x[i] = starts_host[3 * i + 2]; }
   const int es = dtype_size(dtype_src);
   const char* base = (const char*)image->data + (int64_t)img_index * image->d * image->h * image->w * image->ld * es;
   const int64_t total = (int64_t)nwin * windows->d * windows->h * windows->w * windows->c;
-  const int grid = grid_for(total);
   hipStream_t st = (hipStream_t)stream;
-#define GATHER(TS, TD)                                                                          \
-  hipLaunchKernelGGL((sw_gather_kernel<TS, TD>), grid, 256, 0, st, (const TS*)base,             \
-                     (TD*)windows->data, wl, image->d, image->h, image->w, image->c, image->ld, \
-                     windows->d, windows->h, windows->w, windows->ld)
-  const int des = dtype_size(dst_dtype);
-  if (image->c == 1 && windows->ld == 1 && windows->w % 4 == 0 && ((uintptr_t)windows->data % (4 * des)) == 0) {
-    const int g4 = grid_for(total / 4);
-#define GATHER4(TS, TD)                                                                          \
-    hipLaunchKernelGGL((sw_gather4_kernel<TS, TD>), g4, 256, 0, st, (const TS*)base,              \
-                       (TD*)windows->data, wl, image->d, image->h, image->w, image->ld,          \
-                       windows->d, windows->h, windows->w)
-    if (dtype_src == SEGMI_F32 && dst_dtype == SEGMI_F32) GATHER4(float, float);
-    else if (dtype_src == SEGMI_F32 && dst_dtype == SEGMI_BF16) GATHER4(float, bf16_t);
-    else if (dtype_src == SEGMI_BF16 && dst_dtype == SEGMI_BF16) GATHER4(bf16_t, bf16_t);
-    else if (dtype_src == SEGMI_BF16 && dst_dtype == SEGMI_F32) GATHER4(bf16_t, float);
-    else if (dtype_src == SEGMI_F32 && dst_dtype == SEGMI_F16) GATHER4(float, f16_t);
-    else if (dtype_src == SEGMI_F16 && dst_dtype == SEGMI_F16) GATHER4(f16_t, f16_t);
-    else if (dtype_src == SEGMI_F16 && dst_dtype == SEGMI_F32) GATHER4(f16_t, float);
-    else SEGMI_CHECK_ARG(false, "sw_gather: bad dtypes");
+  if (image->c == 1 && windows->ld == 1 && windows->w % 4 == 0 &&
+      ((uintptr_t)windows->data % (4 * dtype_size(dst_dtype))) == 0) {
+    const int g4 = grid_1d(total / 4, kSwGrid);
+#define GATHER4(TS, TD)                                                                                      \
+  hipLaunchKernelGGL((sw_gather4_kernel<TS, TD>), g4, 256, 0, st, (const TS*)base, (TD*)windows->data, wl, \
+                     image->d, image->h, image->w, image->ld, windows->d, windows->h, windows->w)
+    SEGMI_BY_DTYPE_PAIR(dtype_src, dst_dtype, GATHER4);
 #undef GATHER4
-    SEGMI_LAUNCH_CHECK("sw_gather");
-    return SEGMI_OK;
-  }
-  if (dtype_src == SEGMI_F32 && dst_dtype == SEGMI_F32) GATHER(float, float);
-  else if (dtype_src == SEGMI_F32 && dst_dtype == SEGMI_BF16) GATHER(float, bf16_t);
-  else if (dtype_src == SEGMI_BF16 && dst_dtype == SEGMI_BF16) GATHER(bf16_t, bf16_t);
-  else if (dtype_src == SEGMI_BF16 && dst_dtype == SEGMI_F32) GATHER(bf16_t, float);
-  else if (dtype_src == SEGMI_F32 && dst_dtype == SEGMI_F16) GATHER(float, f16_t);
-  else if (dtype_src == SEGMI_F16 && dst_dtype == SEGMI_F16) GATHER(f16_t, f16_t);
-  else if (dtype_src == SEGMI_F16 && dst_dtype == SEGMI_F32) GATHER(f16_t, float);
-  else SEGMI_CHECK_ARG(false, "sw_gather: bad dtypes");
+  } else {
+    const int grid = grid_1d(total, kSwGrid);
+#define GATHER(TS, TD)                                                                                       \
+  hipLaunchKernelGGL((sw_gather_kernel<TS, TD>), grid, 256, 0, st, (const TS*)base, (TD*)windows->data, wl, \
+                     image->d, image->h, image->w, image->c, image->ld, windows->d, windows->h, windows->w, \
+                     windows->ld)
+    SEGMI_BY_DTYPE_PAIR(dtype_src, dst_dtype, GATHER);
 #undef GATHER
+  }
   SEGMI_LAUNCH_CHECK("sw_gather");
   return SEGMI_OK;
 }
@@ -567,26 +521,16 @@ int segmi_sw_scatter_add(int dtype, const segmi_act* pred, const int32_t* starts
   if (z1 <= z0 || y1 <= y0 || x1 <= x0) return SEGMI_OK;
   const int bd = z1 - z0, bh = y1 - y0, bw = x1 - x0;
   hipStream_t st = (hipStream_t)stream;
-  const int es = dtype_size(dtype);
-  if (acc->c % 4 == 0 && acc->ld % 4 == 0 && pred->ld % 4 == 0 && ((uintptr_t)acc->data % 16) == 0 &&
-      ((uintptr_t)pred->data % (4 * es)) == 0) {
-    const int g4 = grid_for((int64_t)bd * bh * bw * (acc->c / 4));
-    if (dtype == SEGMI_F32)
-      hipLaunchKernelGGL(sw_scatter4_kernel<float>, g4, 256, 0, st, (const float*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
-    else if (dtype == SEGMI_F16)
-      hipLaunchKernelGGL(sw_scatter4_kernel<f16_t>, g4, 256, 0, st, (const f16_t*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
-    else
-      hipLaunchKernelGGL(sw_scatter4_kernel<bf16_t>, g4, 256, 0, st, (const bf16_t*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
-    SEGMI_LAUNCH_CHECK("sw_scatter_add");
-    return SEGMI_OK;
-  }
-  const int grid = grid_for((int64_t)bd * bh * bw * acc->c);
-  if (dtype == SEGMI_F32)
-    hipLaunchKernelGGL(sw_scatter_kernel<float>, grid, 256, 0, st, (const float*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
-  else if (dtype == SEGMI_F16)
-    hipLaunchKernelGGL(sw_scatter_kernel<f16_t>, grid, 256, 0, st, (const f16_t*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
-  else
-    hipLaunchKernelGGL(sw_scatter_kernel<bf16_t>, grid, 256, 0, st, (const bf16_t*)pred->data, wl, importance, (float*)acc->data, cnt, acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, bd, bh, bw);
+  const bool v4 = acc->c % 4 == 0 && acc->ld % 4 == 0 && pred->ld % 4 == 0 && ((uintptr_t)acc->data % 16) == 0 &&
+                  ((uintptr_t)pred->data % (4 * dtype_size(dtype))) == 0;
+  const int grid = grid_1d((int64_t)bd * bh * bw * (v4 ? acc->c / 4 : acc->c), kSwGrid);
+#define SCATTER(T, KERN)                                                                                      \
+  hipLaunchKernelGGL(KERN<T>, grid, 256, 0, st, (const T*)pred->data, wl, importance, (float*)acc->data, cnt, \
+                     acc->d, acc->h, acc->w, acc->c, acc->ld, pred->d, pred->h, pred->w, pred->ld, z0, y0, x0, \
+                     bd, bh, bw)
+  if (v4) SEGMI_BY_DTYPE(dtype, SCATTER, sw_scatter4_kernel);
+  else SEGMI_BY_DTYPE(dtype, SCATTER, sw_scatter_kernel);
+#undef SCATTER
   SEGMI_LAUNCH_CHECK("sw_scatter_add");
   return SEGMI_OK;
 }
@@ -595,48 +539,16 @@ static int argmax_launch(int dtype, const segmi_act* lg, const float* cnt, int w
                          void* labels, int label_bytes, hipStream_t st) {
   const int64_t nvox = act_voxels(lg);
   float* wb = write_back ? (float*)lg->data : nullptr;
-  const int es = dtype_size(dtype);
   const int tpv = lg->c / 4;
-  if (lg->c % 4 == 0 && tpv >= 1 && tpv <= 64 && (tpv & (tpv - 1)) == 0 && lg->ld % 4 == 0 &&
-      ((uintptr_t)lg->data % (4 * es)) == 0) {
-    const int g4 = grid_for(nvox * tpv);
-#define ARGMAX4(T, L)                                                                      \
-  hipLaunchKernelGGL((argmax4_kernel<T, L>), g4, 256, 0, st, (const T*)lg->data, cnt, wb, \
-                     (L*)labels, nvox, lg->c, lg->ld)
-    if (dtype == SEGMI_F32) {
-      if (label_bytes == 1) ARGMAX4(float, uint8_t);
-      else if (label_bytes == 2) ARGMAX4(float, int16_t);
-      else ARGMAX4(float, int32_t);
-    } else if (dtype == SEGMI_F16) {
-      if (label_bytes == 1) ARGMAX4(f16_t, uint8_t);
-      else if (label_bytes == 2) ARGMAX4(f16_t, int16_t);
-      else ARGMAX4(f16_t, int32_t);
-    } else {
-      if (label_bytes == 1) ARGMAX4(bf16_t, uint8_t);
-      else if (label_bytes == 2) ARGMAX4(bf16_t, int16_t);
-      else ARGMAX4(bf16_t, int32_t);
-    }
-#undef ARGMAX4
-    SEGMI_LAUNCH_CHECK("argmax");
-    return SEGMI_OK;
-  }
-  const int grid = grid_for(nvox);
-#define ARGMAX(T, L)                                                                     \
-  hipLaunchKernelGGL((argmax_kernel<T, L>), grid, 256, 0, st, (const T*)lg->data, cnt, wb, \
-                     (L*)labels, nvox, lg->c, lg->ld)
-  if (dtype == SEGMI_F32) {
-    if (label_bytes == 1) ARGMAX(float, uint8_t);
-    else if (label_bytes == 2) ARGMAX(float, int16_t);
-    else ARGMAX(float, int32_t);
-  } else if (dtype == SEGMI_F16) {
-    if (label_bytes == 1) ARGMAX(f16_t, uint8_t);
-    else if (label_bytes == 2) ARGMAX(f16_t, int16_t);
-    else ARGMAX(f16_t, int32_t);
-  } else {
-    if (label_bytes == 1) ARGMAX(bf16_t, uint8_t);
-    else if (label_bytes == 2) ARGMAX(bf16_t, int16_t);
-    else ARGMAX(bf16_t, int32_t);
-  }
+  const bool v4 = lg->c % 4 == 0 && tpv >= 1 && tpv <= 64 && (tpv & (tpv - 1)) == 0 && lg->ld % 4 == 0 &&
+                  ((uintptr_t)lg->data % (4 * dtype_size(dtype))) == 0;
+  const int grid = grid_1d(v4 ? nvox * tpv : nvox, kSwGrid);
+#define ARGMAX(L, T, KERN)                                                                                   \
+  hipLaunchKernelGGL((KERN<T, L>), grid, 256, 0, st, (const T*)lg->data, cnt, wb, (L*)labels, nvox, lg->c, lg->ld)
+#define ARGMAX_T(T, KERN) LV_BY_LABEL(label_bytes, ARGMAX, T, KERN)
+  if (v4) SEGMI_BY_DTYPE(dtype, ARGMAX_T, argmax4_kernel);
+  else SEGMI_BY_DTYPE(dtype, ARGMAX_T, argmax_kernel);
+#undef ARGMAX_T
 #undef ARGMAX
   SEGMI_LAUNCH_CHECK("argmax");
   return SEGMI_OK;
@@ -689,52 +601,29 @@ int segmi_sw_blend(int dtype, const void* cache, int k, int ldp, const int32_t* 
   const int64_t row_segs = (int64_t)d * h * (((int64_t)w * (k / bc.g) + 255) / 256);
   SEGMI_CHECK_ARG(row_segs < (1ll << 31) && (int64_t)w * k < (1ll << 30), "sw_blend: volume too large");
   const int grid = (int)(row_segs < 16384 ? row_segs : 16384);
-#define BLEND(TT, LL, GG)                                                                         \
-  do {                                                                                            \
-    if (two)                                                                                      \
-      hipLaunchKernelGGL((sw_blend2_kernel<TT, LL, GG>), grid, 256, 0, st, (const TT*)cache, sc, win_lo, \
-                         win_hi, importance, out_logits, out_count, (LL*)labels, d, h, w, k, ldo, rd, \
-                         rh, rw, ldp, normalize);                                                 \
-    else                                                                                          \
-      hipLaunchKernelGGL((sw_blend_kernel<TT, LL, GG>), grid, 256, 0, st, (const TT*)cache, sc, win_lo, \
-                         win_hi, importance, out_logits, out_count, (LL*)labels, d, h, w, k, ldo, rd, \
-                         rh, rw, ldp, normalize);                                                 \
+  // labels come from the vector kernels only: the scalar lanes (one channel each) write the logits, and the
+  // labels (if wanted) come from a second pass over them
+  SEGMI_CHECK_ARG(vec || !labels || out_logits, "sw_blend: the scalar path labels from the written logits");
+#define BLEND(L, T, KERN, G)                                                                                  \
+  hipLaunchKernelGGL((KERN<T, L, G>), grid, 256, 0, st, (const T*)cache, sc, win_lo, win_hi, importance,      \
+                     out_logits, out_count, vec ? (L*)labels : nullptr, d, h, w, k, ldo, rd, rh, rw, ldp, normalize)
+#define BLEND_L(T, KERN) SEGMI_BY_LABEL_AS(lb, uint8_t, uint16_t, int32_t, BLEND, T, KERN, (int)(16 / sizeof(T)))
+#define BLEND_T(T)                                                \
+  do {                                                            \
+    if (!vec) BLEND(int32_t, T, sw_blend_kernel, 1);              \
+    else if (two) BLEND_L(T, sw_blend2_kernel);                   \
+    else BLEND_L(T, sw_blend_kernel);                             \
   } while (0)
-  if (vec) {
-    if (dtype == SEGMI_F16) {
-      if (label_bytes == 1) BLEND(f16_t, uint8_t, 8);
-      else if (label_bytes == 2) BLEND(f16_t, uint16_t, 8);
-      else BLEND(f16_t, int32_t, 8);
-    } else if (dtype == SEGMI_BF16) {
-      if (label_bytes == 1) BLEND(bf16_t, uint8_t, 8);
-      else if (label_bytes == 2) BLEND(bf16_t, uint16_t, 8);
-      else BLEND(bf16_t, int32_t, 8);
-    } else {
-      if (label_bytes == 1) BLEND(float, uint8_t, 4);
-      else if (label_bytes == 2) BLEND(float, uint16_t, 4);
-      else BLEND(float, int32_t, 4);
-    }
-  } else {
-    // scalar lanes: one channel each; labels (if wanted) come from a second pass over the logits
-    SEGMI_CHECK_ARG(!labels || out_logits, "sw_blend: the scalar path labels from the written logits");
-    if (dtype == SEGMI_F16) hipLaunchKernelGGL((sw_blend_kernel<f16_t, int32_t, 1>), grid, 256, 0, st,
-        (const f16_t*)cache, sc, win_lo, win_hi, importance, out_logits, out_count, (int32_t*)nullptr,
-        d, h, w, k, ldo, rd, rh, rw, ldp, normalize);
-    else if (dtype == SEGMI_BF16) hipLaunchKernelGGL((sw_blend_kernel<bf16_t, int32_t, 1>), grid, 256, 0, st,
-        (const bf16_t*)cache, sc, win_lo, win_hi, importance, out_logits, out_count, (int32_t*)nullptr,
-        d, h, w, k, ldo, rd, rh, rw, ldp, normalize);
-    else hipLaunchKernelGGL((sw_blend_kernel<float, int32_t, 1>), grid, 256, 0, st,
-        (const float*)cache, sc, win_lo, win_hi, importance, out_logits, out_count, (int32_t*)nullptr,
-        d, h, w, k, ldo, rd, rh, rw, ldp, normalize);
-    SEGMI_LAUNCH_CHECK("sw_blend");
-    if (labels) {
-      segmi_act lg{out_logits, 1, d, h, w, k, ldo};
-      return argmax_launch(SEGMI_F32, &lg, nullptr, 0, labels, label_bytes, st);
-    }
-    return SEGMI_OK;
-  }
+  const int lb = labels ? label_bytes : 4;   // without labels the width is not checked and does not matter
+  SEGMI_BY_DTYPE(dtype, BLEND_T);
+#undef BLEND_T
+#undef BLEND_L
 #undef BLEND
   SEGMI_LAUNCH_CHECK("sw_blend");
+  if (!vec && labels) {
+    segmi_act lg{out_logits, 1, d, h, w, k, ldo};
+    return argmax_launch(SEGMI_F32, &lg, nullptr, 0, labels, label_bytes, st);
+  }
   return SEGMI_OK;
 }
 
@@ -748,8 +637,7 @@ const char* segmi_sw_blend_kernel_name(int dtype, const void* cache, int k, int 
   const int32_t* const starts[3] = {starts_z, starts_y, starts_x};
   const int nn[3] = {nz, ny, nx}, rr[3] = {rd, rh, rw};
   const BlendChoice bc = blend_choice(dtype, cache, k, ldp, starts, nn, rr, out_logits, ldo);
-  const char* dt = dtype == SEGMI_BF16 ? "bf16" : dtype == SEGMI_F16 ? "f16" : "f32";
-  snprintf(buf, sizeof buf, "sw_%s_kernel<%s, G=%d>", !bc.vec ? "blend_scalar" : bc.two ? "blend2" : "blend", dt, bc.g);
+  snprintf(buf, sizeof buf, "sw_%s_kernel<%s, G=%d>", !bc.vec ? "blend_scalar" : bc.two ? "blend2" : "blend", dtype_name(dtype), bc.g);
   return buf;
 }
 
@@ -761,37 +649,10 @@ int segmi_label_counts(const int32_t* pred, const int32_t* truth, int64_t n, int
     set_error("label_counts: memset failed");
     return SEGMI_ELAUNCH;
   }
-  const int grid = grid_for(n) > 1024 ? 1024 : grid_for(n);
+  const int grid = grid_1d(n, 1024);
   hipLaunchKernelGGL(label_counts_kernel, grid, 256, (size_t)k * 3 * 4, st, pred, truth, n, k,
                      (unsigned long long*)counts);
   SEGMI_LAUNCH_CHECK("label_counts");
-  return SEGMI_OK;
-}
-
-int segmi_crop_patches(const segmi_act* image, const float* label, const int32_t* starts_host,
-                       const uint8_t* flips_host, int count, int dst_dtype,
-                       const segmi_act* out_image, float* out_label, void* stream) {
-  SEGMI_CHECK_ARG(act_ok(image) && act_ok(out_image) && starts_host, "crop_patches: bad arguments");
-  SEGMI_CHECK_ARG(count > 0 && count <= kMaxWin && out_image->n >= count && out_image->c == image->c,
-                  "crop_patches: 1..%d crops per call", kMaxWin);
-  CropList cl{};
-  cl.n = count;
-  for (int i = 0; i < count; ++i) {
-    cl.b[i] = starts_host[4 * i]; cl.z[i] = starts_host[4 * i + 1];
-    cl.y[i] = starts_host[4 * i + 2]; cl.x[i] = starts_host[4 * i + 3];
-    cl.flip[i] = flips_host ? flips_host[i] : 0;
-    SEGMI_CHECK_ARG(cl.b[i] >= 0 && cl.b[i] < image->n, "crop_patches: volume index out of range");
-  }
-  const int64_t total = (int64_t)count * out_image->d * out_image->h * out_image->w;
-  const int grid = grid_for(total);
-  hipStream_t st = (hipStream_t)stream;
-  if (dst_dtype == SEGMI_F32)
-    hipLaunchKernelGGL(crop_kernel<float>, grid, 256, 0, st, (const float*)image->data, label, cl, image->d, image->h, image->w, image->c, image->ld, (float*)out_image->data, out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
-  else if (dst_dtype == SEGMI_F16)
-    hipLaunchKernelGGL(crop_kernel<f16_t>, grid, 256, 0, st, (const float*)image->data, label, cl, image->d, image->h, image->w, image->c, image->ld, (f16_t*)out_image->data, out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
-  else
-    hipLaunchKernelGGL(crop_kernel<bf16_t>, grid, 256, 0, st, (const float*)image->data, label, cl, image->d, image->h, image->w, image->c, image->ld, (bf16_t*)out_image->data, out_label, out_image->d, out_image->h, out_image->w, out_image->ld);
-  SEGMI_LAUNCH_CHECK("crop_patches");
   return SEGMI_OK;
 }
 

@@ -18,7 +18,7 @@
 namespace segmi {
 
 constexpr int kTtaMaxK = 512;
-constexpr int kTtaMaxGrid = 8192;      // workgroups of 256 threads, the cap of sliding.hip's grid_for
+constexpr int kTtaMaxGrid = 8192;      // workgroups of 256 threads, the cap sliding.hip uses too
 constexpr int kTtaScalarK = 32;        // channels a lane of the scalar layout keeps in registers
 
 // first maximal index wins (the rule of segmi_argmax; scores are finite, no NaN handling needed)
@@ -511,11 +511,8 @@ int segmi_tta_finalize(const segmi_act* scores, int k, void* labels, int label_b
   p.K = k; p.ld = scores->ld; p.ldp = probs_out ? probs_out->ld : 0;
   const int layout = tta_layout(k, p.sc, p.ld, p.probs, p.ldp);
   hipStream_t st = (hipStream_t)stream;
-#define FIN_BY_LABEL(KERNEL, GRID, ...)                                                                 \
-  do {                                                                                                  \
-    if (label_bytes == 1) hipLaunchKernelGGL((KERNEL<uint8_t __VA_ARGS__>), GRID, 256, 0, st, p);        \
-    else hipLaunchKernelGGL((KERNEL<int32_t __VA_ARGS__>), GRID, 256, 0, st, p);                         \
-  } while (0)
+#define FIN(L, KERNEL, GRID, ...) hipLaunchKernelGGL((KERNEL<L, ##__VA_ARGS__>), GRID, 256, 0, st, p)
+#define FIN_BY_LABEL(KERNEL, GRID, ...) SEGMI_BY_LABEL_14(label_bytes, FIN, KERNEL, GRID, ##__VA_ARGS__)
   if (layout == kLayoutVec) {
     // the flat voxel list as rows of 2^16 voxels: the lanes of a voxel stay together, no 64-bit division
     const int64_t roww = p.nvox < 65536 ? p.nvox : 65536;
@@ -528,14 +525,13 @@ int segmi_tta_finalize(const segmi_act* scores, int k, void* labels, int label_b
   } else {
     const int grid = tta_grid((p.nvox + 3) / 4);
     const int nj = (k + 63) / 64;
-#define COMMA ,
-    if (nj <= 1) FIN_BY_LABEL(tta_finalize_wave_kernel, grid, COMMA 1);
-    else if (nj <= 2) FIN_BY_LABEL(tta_finalize_wave_kernel, grid, COMMA 2);
-    else if (nj <= 4) FIN_BY_LABEL(tta_finalize_wave_kernel, grid, COMMA 4);
-    else FIN_BY_LABEL(tta_finalize_wave_kernel, grid, COMMA 8);
-#undef COMMA
+    if (nj <= 1) FIN_BY_LABEL(tta_finalize_wave_kernel, grid, 1);
+    else if (nj <= 2) FIN_BY_LABEL(tta_finalize_wave_kernel, grid, 2);
+    else if (nj <= 4) FIN_BY_LABEL(tta_finalize_wave_kernel, grid, 4);
+    else FIN_BY_LABEL(tta_finalize_wave_kernel, grid, 8);
   }
 #undef FIN_BY_LABEL
+#undef FIN
   SEGMI_LAUNCH_CHECK("tta_finalize");
   return SEGMI_OK;
 }
@@ -562,8 +558,9 @@ int segmi_label_means(const void* labels, int label_bytes, const float* values, 
   p.pcnt = (unsigned long long*)(ws + (size_t)kLmCells * 8);
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)k * 4 * 16;
-  if (label_bytes == 1) hipLaunchKernelGGL(label_means_kernel<uint8_t>, grid, 256, lds, st, p);
-  else hipLaunchKernelGGL(label_means_kernel<int32_t>, grid, 256, lds, st, p);
+#define LABEL_MEANS(L) hipLaunchKernelGGL(label_means_kernel<L>, grid, 256, lds, st, p)
+  SEGMI_BY_LABEL_14(label_bytes, LABEL_MEANS);
+#undef LABEL_MEANS
   SEGMI_LAUNCH_CHECK("label_means");
   return SEGMI_OK;
 }

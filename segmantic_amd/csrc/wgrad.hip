@@ -209,6 +209,7 @@ int64_t segmi_conv3d_wgrad_workspace(int dtype, const segmi_act* x, const segmi_
 }
 
 int segmi_bias_grad(int dtype, const segmi_act* dy, float* db, void* workspace, void* stream) {
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "bias_grad: bad dtype");
   SEGMI_CHECK_ARG(act_ok(dy) && db && workspace, "bias_grad: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   // the channel sums are folded by the last workgroup of the statistics launch (fin_tail.h): one launch, not two
@@ -262,12 +263,12 @@ int segmi_conv3d_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float
     p.N = x->n; p.Dx = x->d; p.Hx = x->h; p.Wx = x->w; p.Dy = dy->d; p.Hy = dy->h; p.Wy = dy->w;
     p.Cin = x->c; p.Cout = dy->c; p.ldx = x->ld; p.ldy = dy->ld; p.ks = ksize; p.stride = stride;
     p.nvox = act_voxels(dy); p.chunk = 512;
-    if (dtype == SEGMI_F32) hipLaunchKernelGGL(wgrad_direct_kernel<float>, slabs, 256, 0, st, p);
-    else if (dtype == SEGMI_F16) hipLaunchKernelGGL(wgrad_direct_kernel<f16_t>, slabs, 256, 0, st, p);
-    else hipLaunchKernelGGL(wgrad_direct_kernel<bf16_t>, slabs, 256, 0, st, p);
+#define WG_DIRECT(T) hipLaunchKernelGGL(wgrad_direct_kernel<T>, slabs, 256, 0, st, p)
+    SEGMI_BY_DTYPE(dtype, WG_DIRECT);
+#undef WG_DIRECT
     SEGMI_LAUNCH_CHECK("conv3d_wgrad(direct)");
   }
-  const int rb = (int)(cdiv64(nout, 256) > 2048 ? 2048 : cdiv64(nout, 256));
+  const int rb = grid_1d(nout, 2048);
   float* gsum = (float*)((char*)workspace + align256((int64_t)slabs * nout * 4));
   if (slabs > 2 * kSlabGroups) {
     const int fb = (int)(cdiv64(nout, 64) > 4096 ? 4096 : cdiv64(nout, 64));

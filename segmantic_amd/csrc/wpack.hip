@@ -207,6 +207,7 @@ int64_t segmi_wpack_bytes(int dtype, int kind, int cin_k, int cout_k, int ksize)
 int segmi_wpack(int dtype, int kind, const float* w_src, const float* scale, int cin_k,
                 int cout_k, int ksize, void* packed, void* stream) {
   SEGMI_CHECK_ARG(w_src && packed, "wpack: null pointer");
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "wpack: bad dtype %d", dtype);
   SEGMI_CHECK_ARG(cin_k > 0 && cout_k > 0 && cin_k % 16 == 0 && cout_k % 16 == 0,
                   "wpack: MFMA packs need cin %% 16 == 0 and cout %% 16 == 0 (got %d, %d)",
                   cin_k, cout_k);
@@ -217,32 +218,19 @@ int segmi_wpack(int dtype, int kind, const float* w_src, const float* scale, int
   if (kind == 2) {
     PackGeom g = pack_geom(dtype, cin_k, cout_k, 1);
     dim3 grid(64, 8);
-    if (dtype == SEGMI_F32)
-      hipLaunchKernelGGL(wpack_convT_kernel<float>, grid, 256, 0, st, w_src, scale,
-                         (float*)packed, cin_k, cout_k, g.CK, g.SPT, g.nchunks, g.ntiles);
-    else if (dtype == SEGMI_F16)
-      hipLaunchKernelGGL(wpack_convT_kernel<f16_t>, grid, 256, 0, st, w_src, scale,
-                         (f16_t*)packed, cin_k, cout_k, g.CK, g.SPT, g.nchunks, g.ntiles);
-    else
-      hipLaunchKernelGGL(wpack_convT_kernel<bf16_t>, grid, 256, 0, st, w_src, scale,
-                         (bf16_t*)packed, cin_k, cout_k, g.CK, g.SPT, g.nchunks, g.ntiles);
+#define WPACK_T(T)                                                                                   \
+  hipLaunchKernelGGL(wpack_convT_kernel<T>, grid, 256, 0, st, w_src, scale, (T*)packed, cin_k, cout_k, \
+                     g.CK, g.SPT, g.nchunks, g.ntiles)
+    SEGMI_BY_DTYPE(dtype, WPACK_T);
+#undef WPACK_T
   } else {
     PackGeom g = pack_geom(dtype, cin_k, cout_k, ksize * ksize * ksize);
     int64_t total = wpack_elems(dtype, kind, cin_k, cout_k, ksize);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    if (dtype == SEGMI_F32)
-      hipLaunchKernelGGL(wpack_conv_kernel<float>, blocks, 256, 0, st, w_src, scale,
-                         (float*)packed, kind, cin_k, cout_k, g.ntaps, g.CK, g.SPT, g.nsteps,
-                         g.ntiles, total);
-    else if (dtype == SEGMI_F16)
-      hipLaunchKernelGGL(wpack_conv_kernel<f16_t>, blocks, 256, 0, st, w_src, scale,
-                         (f16_t*)packed, kind, cin_k, cout_k, g.ntaps, g.CK, g.SPT, g.nsteps,
-                         g.ntiles, total);
-    else
-      hipLaunchKernelGGL(wpack_conv_kernel<bf16_t>, blocks, 256, 0, st, w_src, scale,
-                         (bf16_t*)packed, kind, cin_k, cout_k, g.ntaps, g.CK, g.SPT, g.nsteps,
-                         g.ntiles, total);
+#define WPACK(T)                                                                                       \
+  hipLaunchKernelGGL(wpack_conv_kernel<T>, grid_1d(total, 2048), 256, 0, st, w_src, scale, (T*)packed, kind, \
+                     cin_k, cout_k, g.ntaps, g.CK, g.SPT, g.nsteps, g.ntiles, total)
+    SEGMI_BY_DTYPE(dtype, WPACK);
+#undef WPACK
   }
   SEGMI_LAUNCH_CHECK("wpack");
   return SEGMI_OK;
@@ -276,12 +264,9 @@ int segmi_wpack_batch(int dtype, const segmi_wpack_desc* descs_host, int ndesc,
     }
   }
   dim3 grid(64, ndesc);
-  if (dtype == SEGMI_F32)
-    hipLaunchKernelGGL(wpack_batch_kernel<float>, grid, 256, 0, st, descs_dev);
-  else if (dtype == SEGMI_F16)
-    hipLaunchKernelGGL(wpack_batch_kernel<f16_t>, grid, 256, 0, st, descs_dev);
-  else
-    hipLaunchKernelGGL(wpack_batch_kernel<bf16_t>, grid, 256, 0, st, descs_dev);
+#define WPACK_BATCH(T) hipLaunchKernelGGL(wpack_batch_kernel<T>, grid, 256, 0, st, descs_dev)
+  SEGMI_BY_DTYPE(dtype, WPACK_BATCH);
+#undef WPACK_BATCH
   SEGMI_LAUNCH_CHECK("wpack_batch");
   return SEGMI_OK;
 }

@@ -821,44 +821,34 @@ def normalize_intensity_(x: torch.Tensor) -> torch.Tensor:
 AUG_MAX_PATCHES = 16    # patches per segmi_crop_patches / warp_crop / intensity / kspace call (kMaxCrops)
 
 
-def _flips_arg(flips, i, n):
-    if flips is None:
-        return None, None
-    fl = np.ascontiguousarray(np.asarray(flips, dtype=np.uint8).reshape(-1)[i:i + n])
-    return fl, fl.ctypes.data_as(C.c_void_p)
-
-
-def _rows(x, i, n):
-    return None if x is None else x[i:i + n]
+def _patch_chunks(name, native, image, label, starts, flips, out_image, out_label) -> None:
+    """The chunk loop of the three sampler gathers, one launch per 16 patches.  ``native(a, label, starts, flips,
+    n, dst_dtype, out, out_label)`` is the library call, given the arguments every one of them takes."""
+    a = act(image)
+    fl = None if flips is None else np.asarray(flips, dtype=np.uint8).reshape(-1)
+    for i in range(0, len(starts), AUG_MAX_PATCHES):
+        arr, p = _starts(starts[i:i + AUG_MAX_PATCHES], 4)
+        n = arr.shape[0]
+        b = act(out_image[i:i + n])
+        f = None if fl is None else np.ascontiguousarray(fl[i:i + n])
+        check(native(C.byref(a), _ptr(label), p, None if f is None else f.ctypes.data_as(C.c_void_p), n,
+                     dtype_code(out_image), C.byref(b), _ptr(None if out_label is None else out_label[i:i + n])),
+              name)
 
 
 def crop_patches(image, label, starts, flips, out_image, out_label) -> None:
     """``len(starts)`` crops (any number: one launch per 16) of ``image`` / ``label`` into
     ``out_image`` / ``out_label``."""
-    a = act(image)
-    for i in range(0, len(starts), AUG_MAX_PATCHES):
-        arr, p = _starts(starts[i:i + AUG_MAX_PATCHES], 4)
-        n = arr.shape[0]
-        b = act(out_image[i:i + n])
-        _fl, flp = _flips_arg(flips, i, n)
-        check(lib.segmi_crop_patches(C.byref(a), _ptr(label), p, flp, n,
-                                     dtype_code(out_image), C.byref(b), _ptr(_rows(out_label, i, n)),
-                                     _stream()), "crop_patches")
+    _patch_chunks("crop_patches", lambda a, lab, p, fl, n, dt, b, ol: lib.segmi_crop_patches(
+        a, lab, p, fl, n, dt, b, ol, _stream()), image, label, starts, flips, out_image, out_label)
 
 
 def warp_crop_patches(image, label, starts, flips, index_map, out_image, out_label) -> None:
     """crop_patches with a 3x4 affine (augmented index (x,y,z,1) -> source index) composed in."""
-    a = act(image)
     m = np.ascontiguousarray(np.asarray(index_map, dtype=np.float64).reshape(12))
-    for i in range(0, len(starts), AUG_MAX_PATCHES):
-        arr, p = _starts(starts[i:i + AUG_MAX_PATCHES], 4)
-        n = arr.shape[0]
-        b = act(out_image[i:i + n])
-        _fl, flp = _flips_arg(flips, i, n)
-        check(lib.segmi_warp_crop_patches(C.byref(a), _ptr(label), p, flp, n,
-                                          m.ctypes.data_as(C.c_void_p), dtype_code(out_image),
-                                          C.byref(b), _ptr(_rows(out_label, i, n)), _stream()),
-              "warp_crop_patches")
+    _patch_chunks("warp_crop_patches", lambda a, lab, p, fl, n, dt, b, ol: lib.segmi_warp_crop_patches(
+        a, lab, p, fl, n, m.ctypes.data_as(C.c_void_p), dt, b, ol, _stream()),
+        image, label, starts, flips, out_image, out_label)
 
 
 def elastic_warp_crop_patches(image, label, starts, flips, index_map, control, out_image, out_label) -> None:
@@ -873,18 +863,12 @@ def elastic_warp_crop_patches(image, label, starts, flips, index_map, control, o
     if min(n0, n1, n2) < 4 or n0 * n1 * n2 > ELASTIC_MAX_CONTROL:
         raise ValueError(f"elastic_warp_crop_patches: control grid {n0} x {n1} x {n2}: at least 4 points per axis "
                          f"and at most {ELASTIC_MAX_CONTROL} in all")
-    a = act(image)
     m = None if index_map is None else np.ascontiguousarray(np.asarray(index_map, dtype=np.float64).reshape(12))
     mp = None if m is None else m.ctypes.data_as(C.c_void_p)
-    for i in range(0, len(starts), AUG_MAX_PATCHES):
-        arr, p = _starts(starts[i:i + AUG_MAX_PATCHES], 4)
-        n = arr.shape[0]
-        b = act(out_image[i:i + n])
-        _fl, flp = _flips_arg(flips, i, n)
-        check(lib.segmi_elastic_warp_crop_patches(C.byref(a), _ptr(label), p, flp, n, mp, _ptr(control), n0, n1, n2,
-                                                  dtype_code(out_image), C.byref(b),
-                                                  _ptr(_rows(out_label, i, n)), _stream()),
-              "elastic_warp_crop_patches")
+    _patch_chunks("elastic_warp_crop_patches",
+                  lambda a, lab, p, fl, n, dt, b, ol: lib.segmi_elastic_warp_crop_patches(
+                      a, lab, p, fl, n, mp, _ptr(control), n0, n1, n2, dt, b, ol, _stream()),
+                  image, label, starts, flips, out_image, out_label)
 
 
 def _host_arrays():

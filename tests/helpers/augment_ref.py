@@ -1,5 +1,4 @@
-"""Float64 numpy references of the training augmentation (seg/augment.py, csrc/augment.hip,
-crop_kernel in csrc/sliding.hip), written from MONAI's documented semantics of the transforms the
+"""Float64 numpy references of the training augmentation (seg/augment.py, csrc/augment.hip), written from MONAI's documented semantics of the transforms the
 reference pipeline composes: SpatialPad + RandCropByLabelClasses + RandFlip, the rotate / zoom
 index map (the project's one-resample form), AdjustContrast, HistogramShift, BiasField, GibbsNoise
 and KSpaceSpikeNoise.

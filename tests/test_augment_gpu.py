@@ -1,5 +1,5 @@
 """The training-batch augmentation kernels against the float64 references of
-tests/helpers/augment_ref.py, at the shapes and edges the sampler reaches: crop_kernel (sliding.hip),
+tests/helpers/augment_ref.py, at the shapes and edges the sampler reaches: crop_kernel,
 warp_crop_kernel, the intensity kernels and the k-space DFT (augment.hip), and the whole
 ``trainer.make_batch`` chain against ``augment_ref.reference_chain`` for the same draws.
 
