@@ -523,6 +523,37 @@ int segmi_label_means(const void* labels, int label_bytes, const float* values, 
 int segmi_resample3d(int pixel, const void* src, int sx, int sy, int sz, void* dst, int dx,
                      int dy, int dz, const double* index_map_host, int interp,
                      double default_value, void* stream);
+/* The two high-quality interpolators of the resampler (csrc/resample_hq.hip).  Arrays,
+ * pixel codes, index_map_host, the inside test -0.5 <= c < n - 0.5, `border` (0 / 1: clamp the continuous index
+ * to [0, n-1] first), default_value and the saturate-then-truncate output cast are those of segmi_resample3d; an
+ * axis of extent 1 (the 2-D case) is accepted everywhere.  The evaluate and vote kernels launch at most
+ * SEGMI_RESAMPLE_HQ_GRID_CAP workgroups of 256 threads and stride over the rest of the output. */
+#define SEGMI_RESAMPLE_HQ_GRID_CAP 2048
+/* Cubic B-spline (sitkBSpline), in two steps so that one coefficient volume serves several output grids.
+ * segmi_bspline_prefilter: native pixels -> float64 coefficients `coef` (device, [sz][sy][sx], the
+ * segmi_bspline_workspace(sx, sy, sz) = 8 sx sy sz bytes): the separable recursive filter with pole sqrt(3) - 2 and
+ * gain 6 per axis, along x, then y, then z, whole-sample mirror boundaries, the causal start taken from the mirror
+ * sum over the whole line (lines longer than 57 samples: its first 56 terms, the rest lying below 2^-106 of the
+ * line's largest sample); a line of length 1 is copied.  What scipy.ndimage.spline_filter(order=3, mode="mirror")
+ * computes. */
+int64_t segmi_bspline_workspace(int sx, int sy, int sz);
+int segmi_bspline_prefilter(int pixel, const void* src, int sx, int sy, int sz, double* coef, void* stream);
+/* segmi_resample3d_bspline: evaluates `coef` at every output voxel.  Per axis f = floor(c), t = c - f, weights
+ * (1-t)^3/6, (3t^3-6t^2+4)/6, (-3t^3+3t^2+3t+1)/6, t^3/6 on taps f-1 .. f+2 folded by the whole-sample mirror
+ * (period 2(n-1); extent 1: every tap is sample 0); the 64 products are summed in f64, x innermost and z outermost,
+ * and cast to `pixel`.  Equals scipy.ndimage.map_coordinates(order=3, mode="mirror") in float64. */
+int segmi_resample3d_bspline(const double* coef, int sx, int sy, int sz, int pixel, void* dst, int dx, int dy, int dz,
+                             const double* index_map_host, int border, double default_value, void* stream);
+/* Label-Gaussian (sitkLabelGaussian) as an exact integer vote.  sigma_xyz_host: 3 doubles, the Gaussian's sigma per
+ * axis (x, y, z) in input voxels, each > 0; alpha > 0; radius R = ceil(alpha * sigma) per axis, refused beyond 8.
+ * Per axis i0 = floor(c + 0.5), taps i in [i0 - R, i0 + R] that lie in [0, n-1], weight
+ * w(i) = 0.5 (erf(((i + 0.5) - c) inv) - erf(((i - 0.5) - c) inv)) with inv = 1 / (sigma sqrt 2), quantised to
+ * q(i) = floor(w(i) 2^18 + 0.5).  A voxel weighs qz qy qx; a label's score is the int64 sum over the window's voxels
+ * that carry it; the output is the label with the largest score, the smallest label value among equal scores.
+ * f32 labels are compared as numbers (NaN is not supported).  Any number of distinct labels per window. */
+int segmi_resample3d_label_gaussian(int pixel, const void* src, int sx, int sy, int sz, void* dst, int dx, int dy,
+                                    int dz, const double* index_map_host, const double* sigma_xyz_host, double alpha,
+                                    int border, double default_value, void* stream);
 /* NormalizeIntensityd(channel_wise=True), monai_unet.py:164: in-place (x-mean)/std per channel
  * of a [c][nvox] f32 array.  workspace >= segmi_normalize_workspace(c, nvox) bytes. */
 int64_t segmi_normalize_workspace(int c, int64_t nvox);

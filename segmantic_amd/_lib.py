@@ -161,6 +161,10 @@ SIGNATURES = {
     "segmi_tta_finalize": (_i, [_AP, _i, _P, _i, _P, _P, _AP, _P]),
     "segmi_label_means": (_i, [_P, _i, _P, _i64, _i, _P, _P, _P]),
     "segmi_resample3d": (_i, [_i, _P, _i, _i, _i, _P, _i, _i, _i, _P, _i, _d, _P]),
+    "segmi_bspline_workspace": (_i64, [_i, _i, _i]),
+    "segmi_bspline_prefilter": (_i, [_i, _P, _i, _i, _i, _P, _P]),
+    "segmi_resample3d_bspline": (_i, [_P, _i, _i, _i, _i, _P, _i, _i, _i, _P, _i, _d, _P]),
+    "segmi_resample3d_label_gaussian": (_i, [_i, _P, _i, _i, _i, _P, _i, _i, _i, _P, _P, _d, _i, _d, _P]),
     "segmi_normalize_workspace": (_i64, [_i, _i64]),
     "segmi_normalize_intensity": (_i, [_P, _i, _i64, _P, _P]),
     "segmi_crop_patches": (_i, [_AP, _P, _P, _P, _i, _i, _AP, _P, _P]),

@@ -1,8 +1,10 @@
 """Drop-in for ``segmantic.image.processing`` (reference ``src/segmantic/image/processing.py``)
 without SimpleITK: a minimal ``Image`` (voxel tensor + spacing / origin / direction, the subset of
 ``sitk.Image`` the reference touches) and ``resample`` / ``apply_transform`` /
-``resample_to_ref`` running the ITK-semantics HIP kernel (``segmi_resample3d``) instead of ITK's
-CPU ``ResampleImageFilter``.  ``make_image / extract_slices / pad / crop_center / crop`` are host
+``resample_to_ref`` running the ITK-semantics HIP kernels (``segmi_resample3d``, and for the
+``sitkBSpline`` / ``sitkLabelGaussian`` interpolators ``segmi_resample3d_bspline`` /
+``segmi_resample3d_label_gaussian``) instead of ITK's CPU ``ResampleImageFilter``.  ``read_image`` /
+``write_image`` carry an ``Image`` to and from a file.  ``make_image / extract_slices / pad / crop_center / crop`` are host
 metadata / slicing helpers, as in the reference (``:10-46, :123-156``).
 """
 from __future__ import annotations
@@ -18,6 +20,9 @@ sitkUInt8, sitkInt16, sitkUInt16, sitkInt32, sitkFloat32 = "uint8", "int16", "ui
 _TORCH = {"uint8": torch.uint8, "int16": torch.int16, "uint16": torch.uint16, "int32": torch.int32,
           "float32": torch.float32}
 _NAME = {v: k for k, v in _TORCH.items()}
+# interpolators (names follow SimpleITK)
+sitkLinear, sitkNearestNeighbor, sitkBSpline, sitkLabelGaussian = "linear", "nearest", "bspline", "label-gaussian"
+_INTERPOLATORS = (sitkLinear, sitkNearestNeighbor, sitkBSpline, sitkLabelGaussian)
 
 
 class Image:
@@ -144,12 +149,35 @@ def _index_map(moving: Image, out_spacing, out_origin, out_direction, transform)
     return m
 
 
+def _interpolator(nearest: bool, interpolator, sigma, alpha) -> str:
+    """The interpolator a call asks for, checked on the host: ``None`` means what ``nearest`` says."""
+    if interpolator is None:
+        interpolator = sitkNearestNeighbor if nearest else sitkLinear
+    if interpolator not in _INTERPOLATORS:
+        raise ValueError(f"unknown interpolator {interpolator!r}: one of {', '.join(_INTERPOLATORS)}")
+    if nearest and interpolator != sitkNearestNeighbor:
+        raise ValueError(f"nearest=True contradicts interpolator={interpolator!r}")
+    if interpolator != sitkLabelGaussian and not (np.all(np.asarray(sigma) == 1.0) and alpha == 2.0):
+        raise ValueError(f"sigma / alpha belong to interpolator={sitkLabelGaussian!r}, not to {interpolator!r}")
+    if interpolator == sitkLabelGaussian:
+        sg = np.asarray(sigma, np.float64)
+        if sg.shape not in ((), (2,), (3,)) or not np.all(sg > 0) or not alpha > 0:
+            raise ValueError(f"sigma (a number or one per axis) and alpha must be positive, got {sigma!r}, {alpha!r}")
+    return interpolator
+
+
 def _resample_to_grid(moving: Image, size, spacing, origin, direction, transform, nearest: bool,
-                      device=None) -> Image:
+                      device=None, interpolator=None, sigma=1.0, alpha=2.0) -> Image:
     from .. import ops
+    interpolator = _interpolator(nearest, interpolator, sigma, alpha)
     nd = moving.GetDimension()
     if nd not in (2, 3):
         raise ValueError("resample supports 2D / 3D images")
+    sg = np.asarray(sigma, np.float64)
+    if sg.ndim and sg.shape != (nd,):
+        raise ValueError(f"sigma has {sg.size} entries for a {nd}-D image")
+    sg = np.broadcast_to(sg, (nd,))
+    sg = np.concatenate([sg, np.full(3 - nd, sg.min())])      # 2-D: the z axis has extent 1, its sigma is idle
     dev = device or (moving.data.device if moving.data.is_cuda else torch.device("cuda:0"))
     if not torch.cuda.is_available():
         raise RuntimeError("segmantic_amd resample runs on an MI355X (no CPU path)")
@@ -160,7 +188,12 @@ def _resample_to_grid(moving: Image, size, spacing, origin, direction, transform
         out_zyx = (1, int(size[1]), int(size[0]))
     else:
         out_zyx = (int(size[2]), int(size[1]), int(size[0]))
-    dst = ops.resample3d(src, out_zyx, m, nearest=nearest, default=0.0)
+    if interpolator == sitkBSpline:
+        dst = ops.resample3d_bspline(src, out_zyx, m, default=0.0)
+    elif interpolator == sitkLabelGaussian:
+        dst = ops.resample3d_label_gaussian(src, out_zyx, m, sigma=sg, alpha=alpha, default=0.0)
+    else:
+        dst = ops.resample3d(src, out_zyx, m, nearest=interpolator == sitkNearestNeighbor, default=0.0)
     if nd == 2:
         dst = dst[0]
     if not moving.data.is_cuda and device is None:
@@ -168,30 +201,75 @@ def _resample_to_grid(moving: Image, size, spacing, origin, direction, transform
     return Image(dst, spacing, origin, direction)
 
 
-def resample(image: Image, target_spacing: Sequence[float], nearest: bool = False) -> Image:
+def resample(image: Image, target_spacing: Sequence[float], nearest: bool = False, *, interpolator=None,
+             sigma=1.0, alpha=2.0) -> Image:
     """resample (2D/3D) image to a target spacing (reference ``:49-71``): size' =
     ceil(size * spacing / target), same origin / direction, identity transform, default pixel 0,
-    output pixel type = input pixel type."""
+    output pixel type = input pixel type.  ``interpolator``: ``sitkLinear``, ``sitkNearestNeighbor``,
+    ``sitkBSpline`` or ``sitkLabelGaussian`` (``None``: what ``nearest`` says); ``sigma`` (in voxels of
+    ``image``, a number or one per axis x, y[, z]) and ``alpha`` shape the label-Gaussian window."""
+    _interpolator(nearest, interpolator, sigma, alpha)
     size = list(image.GetSize())
     spacing = list(image.GetSpacing())
     for d in range(image.GetDimension()):
         size[d] = math.ceil(size[d] * spacing[d] / target_spacing[d])
         spacing[d] = float(target_spacing[d])
     return _resample_to_grid(image, size, spacing, image.GetOrigin(), image.GetDirection(), None,
-                             nearest)
+                             nearest, interpolator=interpolator, sigma=sigma, alpha=alpha)
 
 
 def apply_transform(moving_image: Image, fixed_image: Image, transform: Optional[np.ndarray],
-                    nearest: bool) -> Image:
+                    nearest: bool, *, interpolator=None, sigma=1.0, alpha=2.0) -> Image:
     """Resample ``moving_image`` onto the grid of ``fixed_image``; ``transform`` (homogeneous
-    (d+1)x(d+1) matrix or None = identity) maps fixed -> moving physical points (``:74-98``)."""
+    (d+1)x(d+1) matrix or None = identity) maps fixed -> moving physical points (``:74-98``).
+    ``interpolator`` / ``sigma`` / ``alpha`` as in ``resample``."""
     return _resample_to_grid(moving_image, fixed_image.GetSize(), fixed_image.GetSpacing(),
-                             fixed_image.GetOrigin(), fixed_image.GetDirection(), transform, nearest)
+                             fixed_image.GetOrigin(), fixed_image.GetDirection(), transform, nearest,
+                             interpolator=interpolator, sigma=sigma, alpha=alpha)
 
 
-def resample_to_ref(moving_image: Image, fixed_image: Image, nearest: bool) -> Image:
+def resample_to_ref(moving_image: Image, fixed_image: Image, nearest: bool, *, interpolator=None, sigma=1.0,
+                    alpha=2.0) -> Image:
     """resample (2D/3D) image to a reference grid (reference ``:101-120``)."""
-    return apply_transform(moving_image, fixed_image, None, nearest)
+    return apply_transform(moving_image, fixed_image, None, nearest, interpolator=interpolator, sigma=sigma,
+                           alpha=alpha)
+
+
+_LPS_TO_RAS = np.diag([-1.0, -1.0, 1.0, 1.0])
+
+
+def read_image(path) -> Image:
+    """Read a NIfTI / MetaImage / NRRD file (``data.imageio``) as an ``Image``.  The file's RAS affine becomes ITK's
+    LPS geometry: spacing = the length of each voxel axis, direction = the unit axes as columns, origin = the
+    position of voxel 0.  A 2-D file gives a 2-D image with the in-plane 2 x 2 part of that geometry.  float64
+    voxels are narrowed to float32; other pixel types than the five of ``Image`` are refused."""
+    from ..data import imageio
+    arr, affine = imageio.read_image(path)
+    if arr.dtype == np.float64:
+        arr = arr.astype(np.float32)
+    if arr.dtype.name not in _TORCH:
+        raise ValueError(f"{path}: pixel type {arr.dtype} is not one of {', '.join(_TORCH)}")
+    if arr.ndim not in (2, 3):
+        raise ValueError(f"{path}: {arr.ndim}-D data; images are 2-D or 3-D")
+    nd = arr.ndim
+    a = _LPS_TO_RAS @ np.asarray(affine, np.float64)
+    spacing = np.sqrt((a[:nd, :nd] ** 2).sum(0))
+    spacing[spacing == 0] = 1.0
+    return Image(arr, spacing, a[:nd, 3], (a[:nd, :nd] / spacing).reshape(-1))
+
+
+def write_image(image: Image, path) -> None:
+    """Write an ``Image`` to a NIfTI / MetaImage / NRRD file: the inverse of ``read_image`` (a 2-D image is written
+    as a 2-D NIfTI, and as a single slice in the formats that are 3-D only)."""
+    from ..data import imageio
+    nd = image.GetDimension()
+    a = np.eye(4)
+    a[:nd, :nd] = np.asarray(image.direction, np.float64).reshape(nd, nd) * np.asarray(image.spacing, np.float64)
+    a[:nd, 3] = image.origin
+    arr = image.numpy()
+    if nd == 2 and not str(path).lower().endswith((".nii", ".nii.gz")):
+        arr = arr[None]
+    imageio.write_image(path, arr, _LPS_TO_RAS @ a)
 
 
 def pad(image: Image, target_size: Sequence[int], value: float = 0) -> Image:

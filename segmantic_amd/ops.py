@@ -804,6 +804,71 @@ def resample3d(src: torch.Tensor, out_size_zyx, index_map, nearest=False, defaul
     return dst
 
 
+# workgroups x threads one launch of the B-spline evaluate / label-Gaussian kernels covers before it strides
+# (SEGMI_RESAMPLE_HQ_GRID_CAP in include/segmi.h)
+RESAMPLE_HQ_GRID_LANES = 2048 * 256
+
+
+def _resample_args(name: str, src: torch.Tensor, out_size_zyx, index_map):
+    _require_device(src)
+    if src.dim() != 3 or not src.is_contiguous():
+        raise ValueError(f"{name} expects a contiguous [z,y,x] tensor")
+    if src.dtype not in _PIXEL:
+        raise TypeError(f"{name}: unsupported pixel type {src.dtype}")
+    dz, dy, dx = (int(v) for v in out_size_zyx)
+    dst = torch.empty((dz, dy, dx), dtype=src.dtype, device=src.device)
+    m = np.ascontiguousarray(np.asarray(index_map, dtype=np.float64).reshape(12))
+    return dst, m
+
+
+def bspline_coefficients(src: torch.Tensor) -> torch.Tensor:
+    """Cubic B-spline coefficients of src [z,y,x] (any pixel type) as a float64 tensor of the same shape: the
+    recursive prefilter with whole-sample mirror boundaries (``scipy.ndimage.spline_filter(order=3, mode="mirror")``)."""
+    _require_device(src)
+    if src.dim() != 3 or not src.is_contiguous():
+        raise ValueError("bspline_coefficients expects a contiguous [z,y,x] tensor")
+    if src.dtype not in _PIXEL:
+        raise TypeError(f"bspline_coefficients: unsupported pixel type {src.dtype}")
+    sz, sy, sx = src.shape
+    coef = torch.empty(int(lib.segmi_bspline_workspace(sx, sy, sz)) // 8, dtype=torch.float64,
+                       device=src.device).view(sz, sy, sx)
+    check(lib.segmi_bspline_prefilter(_PIXEL[src.dtype], _ptr(src), sx, sy, sz, _ptr(coef), _stream()),
+          "bspline_prefilter")
+    return coef
+
+
+def resample3d_bspline(src: torch.Tensor, out_size_zyx, index_map, default=0.0, border=False, coef=None):
+    """``resample3d`` with cubic B-spline interpolation (``map_coordinates(order=3, mode="mirror")``).  ``coef``:
+    the result of ``bspline_coefficients(src)``, to resample one image onto several grids without refiltering."""
+    dst, m = _resample_args("resample3d_bspline", src, out_size_zyx, index_map)
+    if coef is None:
+        coef = bspline_coefficients(src)
+    _require_device(coef)
+    if coef.dtype != torch.float64 or coef.shape != src.shape or not coef.is_contiguous() or coef.device != src.device:
+        raise ValueError("resample3d_bspline: coef must be the contiguous float64 result of bspline_coefficients(src)")
+    sz, sy, sx = src.shape
+    dz, dy, dx = dst.shape
+    check(lib.segmi_resample3d_bspline(_ptr(coef), sx, sy, sz, _PIXEL[src.dtype], _ptr(dst), dx, dy, dz,
+                                       m.ctypes.data_as(C.c_void_p), 1 if border else 0, float(default), _stream()),
+          "resample3d_bspline")
+    return dst
+
+
+def resample3d_label_gaussian(src: torch.Tensor, out_size_zyx, index_map, sigma=1.0, alpha=2.0, default=0.0,
+                              border=False):
+    """``resample3d`` of a label map with the label-Gaussian vote.  ``sigma``: a number or (x, y, z), in input
+    voxels; the window radius is ceil(alpha * sigma) per axis (at most 8)."""
+    dst, m = _resample_args("resample3d_label_gaussian", src, out_size_zyx, index_map)
+    sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (3,)))
+    sz, sy, sx = src.shape
+    dz, dy, dx = dst.shape
+    check(lib.segmi_resample3d_label_gaussian(_PIXEL[src.dtype], _ptr(src), sx, sy, sz, _ptr(dst), dx, dy, dz,
+                                              m.ctypes.data_as(C.c_void_p), sg.ctypes.data_as(C.c_void_p),
+                                              float(alpha), 1 if border else 0, float(default), _stream()),
+          "resample3d_label_gaussian")
+    return dst
+
+
 def normalize_intensity_(x: torch.Tensor) -> torch.Tensor:
     """in-place channel-wise (x-mean)/std of a contiguous f32 [C, ...] tensor."""
     _require_device(x)
