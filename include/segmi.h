@@ -616,6 +616,39 @@ int segmi_kspace_augment(float* patches, int count, int rd, int rh, int rw, int 
                          const uint8_t* spike_on_host, const int32_t* spike_loc_host,
                          const float* spike_u_host, const uint8_t* flips_host, void* workspace,
                          void* stream);
+/* The `augment_degrade` training augmentation (not in the reference) on the same patch
+ * layout [count][rd][rh][rw][c], in the order noise, blur, brightness, lowres; one draw per patch is shared by
+ * its channels.  Each *_on_host (uint8[count], nullable = skip the transform) selects the patches of a transform;
+ * the draws are the caller's.
+ *   noise      : x[e] += sqrt(variance) * g(seed, e), e = ((z*rh + y)*rw + x)*c + ch the element index in its
+ *                patch, seed_host uint32[count].  g is Box-Muller over a counter hash, k = 2e + j (j = 0, 1) in
+ *                uint32 arithmetic: h = k*0x9E3779B1 ^ seed; h ^= h>>16; h *= 0x7feb352d; h ^= h>>15;
+ *                h *= 0x846ca68b; h ^= h>>16; u1 = ((h_0>>8) + 1) 2^-24, u2 = (h_1>>8) 2^-24,
+ *                g = sqrt(-2 ln u1) cos(2 pi u2).  variance_host >= 0.
+ *   blur       : separable Gaussian over the spatial axes of extent > 1, sigma_host in voxels,
+ *                R = floor(4 sigma + 0.5) <= 8, w_k = exp(-k^2 / (2 sigma^2)) normalised to sum 1 (computed here in
+ *                double, used as f32), scipy's `reflect` border for any R, also R larger than the extent.
+ *   brightness : x *= multiplier_host.
+ *   lowres     : coarse_host int32[count][3] = the coarse extents m (z, y, x), 1 <= m <= extent.  Nearest
+ *                down, linear up, as one gather: coarse sample j is the fine voxel src(j) = floor((2j+1) n / (2m));
+ *                fine voxel i has t = clamp((i + 0.5) m/n - 0.5, 0, m-1), j0 = min(floor(t), max(m-2, 0)),
+ *                f = t - j0 and the value (1-f) v[src(j0)] + f v[src(min(j0+1, m-1))] along that axis, tensor
+ *                product over the axes.  An axis with m == n passes through; m == n on every axis leaves the
+ *                patch's bits as they are.
+ * Blur and lowres are out of place (patches <-> workspace); the noise is added where the first step loads, the
+ * brightness multiplies where the last step stores; a patch with neither takes one in-place pass.  Only
+ * selected patches are touched; nothing is launched when no flag is set.  1..16 patches per call, each of fewer
+ * than 2^31 elements; lowres takes extents with rd + rh + rw <= 4096.  Allocates nothing and does not
+ * synchronise.  workspace >= segmi_degrade_workspace(count, rd, rh, rw, c) bytes; it may be NULL only when no
+ * patch is selected for blur or lowres.  SEGMI_EINVAL names what is out of range.  Non-finite inputs are not
+ * supported. */
+int64_t segmi_degrade_workspace(int count, int rd, int rh, int rw, int c);
+int segmi_degrade_augment(float* patches, int count, int rd, int rh, int rw, int c,
+                          const uint8_t* noise_on_host, const float* variance_host, const uint32_t* seed_host,
+                          const uint8_t* blur_on_host, const float* sigma_host,
+                          const uint8_t* bright_on_host, const float* multiplier_host,
+                          const uint8_t* lowres_on_host, const int32_t* coarse_host, void* workspace,
+                          void* stream);
 
 /* ---------------------------------------------------------------- model ensembles ------ */
 /* Combination of `models` (<= 16) predictions over n elements, monai_unet.py:848-1004.

@@ -177,6 +177,8 @@ SIGNATURES = {
     "segmi_ensemble_select": (_i, [_P, _i, _P, _P, _i, _i64, _P, _P]),
     "segmi_kspace_workspace": (_i64, [_i, _i, _i, _i]),
     "segmi_kspace_augment": (_i, [_P, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "segmi_degrade_workspace": (_i64, [_i, _i, _i, _i, _i]),
+    "segmi_degrade_augment": (_i, [_P, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "segmi_label_boxes": (_i, [_P, _P, _i, _i, _i, _i, _i, _P, _P, _P]),
     "segmi_edt_workspace_bytes": (_i64, [_i, _i, _i]),
     "segmi_edt_sq": (_i, [_P, _i, _i, _i, _i, _i, _i, _i, _P, _P, _P, _P, C.c_size_t, _P]),

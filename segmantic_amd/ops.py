@@ -1003,6 +1003,49 @@ def kspace_augment(patches, gibbs=None, spike=None, flips=None) -> None:
                                        arr(flips, np.uint8, i, n), _ptr(ws), _stream()), "kspace_augment")
 
 
+DEGRADE_MAX_RADIUS = 8      # blur radius floor(4 sigma + 0.5) the kernel stages (kMaxRadius): sigma <= 2.0
+
+
+def degrade_augment(patches, noise=None, blur=None, brightness=None, lowres=None) -> None:
+    """In-place noise / blur / brightness / low-resolution augmentation (``augment_degrade``)
+    on f32 NDHWC patches, in that order.
+
+    noise = (on uint8[n], variance f32[n], seed uint32[n]); blur = (on, sigma f32[n], voxels);
+    brightness = (on, multiplier f32[n]); lowres = (on, m int32[n][3], the coarse extents (d0, d1, d2)).
+    None skips a transform.  Any n: one call per 16 patches; the workspace is allocated only when a blur or
+    a lowres fires."""
+    _require_device(patches)
+    if patches.dtype != torch.float32 or patches.dim() != 5 or not patches.is_contiguous():
+        raise ValueError("degrade_augment: dense float32 [n, d, h, w, c] patches expected")
+    N, rd, rh, rw, c = patches.shape
+    non, var, seed = noise if noise is not None else (None, None, None)
+    bon, sigma = blur if blur is not None else (None, None)
+    ron, mult = brightness if brightness is not None else (None, None)
+    lon, coarse = lowres if lowres is not None else (None, None)
+    if bon is not None:
+        bad = [float(s) for o, s in zip(np.asarray(bon), np.asarray(sigma, dtype=np.float64))
+               if o and not (s > 0.0 and np.floor(4.0 * s + 0.5) <= DEGRADE_MAX_RADIUS)]
+        if bad:
+            raise ValueError(f"degrade_augment: blur sigma {bad}: 0 < sigma and a radius floor(4 sigma + 0.5) of at "
+                             f"most {DEGRADE_MAX_RADIUS} (sigma <= 2.0) expected")
+    ws = None
+    for i in range(0, N, AUG_MAX_PATCHES):
+        n = min(AUG_MAX_PATCHES, N - i)
+        fired = [np.asarray(o)[i:i + n].astype(bool) for o in (non, bon, ron, lon) if o is not None]
+        if not any(f.any() for f in fired):
+            continue
+        if ws is None and any(np.asarray(o)[i:i + n].any() for o in (bon, lon) if o is not None):
+            ws = torch.empty(int(lib.segmi_degrade_workspace(min(N, AUG_MAX_PATCHES), rd, rh, rw, c)),
+                             dtype=torch.uint8, device=patches.device)
+        arr = _host_arrays()
+        check(lib.segmi_degrade_augment(_ptr(patches[i:i + n]), n, rd, rh, rw, c, arr(non, np.uint8, i, n),
+                                        arr(var, np.float32, i, n), arr(seed, np.uint32, i, n),
+                                        arr(bon, np.uint8, i, n), arr(sigma, np.float32, i, n),
+                                        arr(ron, np.uint8, i, n), arr(mult, np.float32, i, n),
+                                        arr(lon, np.uint8, i, n), arr(coarse, np.int32, i, n), _ptr(ws), _stream()),
+              "degrade_augment")
+
+
 def _ptr_table(tensors, dtype):
     for t in tensors:
         _require_device(t)

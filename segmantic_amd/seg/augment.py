@@ -37,6 +37,15 @@ MONAI's transforms do and composes the spatial ones into one index map:
   default gives 0.72): then ``I + grad u`` is invertible and ``forward_point_elastic`` contracts at rate L.
   At most 4096 control points (three f32 planes in LDS).
 
+* ``augment_degrade`` (not in the reference; off by default): additive Gaussian noise, Gaussian blur, a
+  brightness multiplier and simulated low resolution, in that order, on the f32 patches as the gather
+  wrote them (flipped already), before the intensity transforms (``segmi_degrade_augment``, DESIGN.md
+  section 20).  One draw per patch is shared by its channels; the label is never touched.  Noise:
+  ``x[e] += sqrt(variance) g(seed, e)`` with ``g`` a counter-hash Box-Muller normal of the element index.
+  Blur: separable Gaussian, ``sigma`` in voxels, radius ``floor(4 sigma + 0.5) <= 8``, scipy's ``reflect``
+  border.  Brightness: ``x *= multiplier``.  Lowres: nearest down onto ``m = max(1, floor(n zoom + 0.5))``
+  samples per axis, linear back up.  ``degrade_config`` validates the option, ``draw_degrade`` draws it.
+
 Spatial axes: the cached volumes are [C, d0, d1, d2]; ``range_x`` rotates about d0, ``range_y``
 about d1, ``range_z`` about d2, as MONAI names the axes of a channel-first array.
 """
@@ -229,6 +238,111 @@ def forward_point_elastic(m_d012: Optional[np.ndarray], ctrl: np.ndarray, shape,
             return p
     raise RuntimeError("augment_elastic: the crop centre's fixed-point iteration did not converge in 1000 steps "
                        "(the field's gradient bound is too close to 1)")
+
+
+DEGRADE_MAX_SIGMA = 2.0             # blur radius floor(4 sigma + 0.5) <= 8, the halo the kernel stages
+_DEGRADE_DEFAULTS = {
+    "noise": {"prob": 0.1, "variance": (0.0, 0.1)},
+    "blur": {"prob": 0.2, "sigma": (0.5, 1.0)},
+    "brightness": {"prob": 0.15, "multiplier": (0.75, 1.25)},
+    "lowres": {"prob": 0.25, "zoom": (0.5, 1.0)},
+}
+
+
+def _number(x) -> bool:
+    return not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating))
+
+
+def _degrade_entry(name: str, value) -> Optional[dict]:
+    """one transform of ``augment_degrade`` in normal form: None (off) or ``{prob, <range field>: (lo, hi)}``"""
+    defaults = _DEGRADE_DEFAULTS[name]
+    field = next(k for k in defaults if k != "prob")
+    if value is None or value is False:
+        return None
+    if value is True:
+        value = {}
+    if not isinstance(value, dict):
+        raise ValueError(f"augment_degrade: '{name}' must be false, true or a dictionary with keys "
+                         f"{list(defaults)}, got {value!r}")
+    unknown = [k for k in value if k not in defaults]
+    if unknown:
+        raise ValueError(f"augment_degrade: '{name}': unknown keys {unknown}; accepted: {list(defaults)}")
+    prob = value.get("prob", defaults["prob"])
+    if not _number(prob) or not 0.0 <= float(prob) <= 1.0:
+        raise ValueError(f"augment_degrade: '{name}.prob' must be a probability in [0, 1], got {prob!r}")
+    rng = value.get(field, defaults[field])
+    ok = isinstance(rng, (list, tuple, np.ndarray)) and len(rng) == 2 and all(_number(v) for v in rng)
+    if not ok or not all(np.isfinite(float(v)) for v in rng) or float(rng[0]) > float(rng[1]):
+        raise ValueError(f"augment_degrade: '{name}.{field}' must be two finite ascending numbers [low, high], "
+                         f"got {rng!r}")
+    lo, hi = float(rng[0]), float(rng[1])
+    if name == "noise" and lo < 0.0:
+        raise ValueError(f"augment_degrade: 'noise.variance' must be >= 0, got {rng!r}")
+    if name == "blur" and (lo <= 0.0 or hi > DEGRADE_MAX_SIGMA):
+        raise ValueError(f"augment_degrade: 'blur.sigma' must lie in (0, {DEGRADE_MAX_SIGMA}] voxels (the kernel "
+                         f"stages a halo of floor(4 sigma + 0.5) <= 8 voxels), got {rng!r}")
+    if name == "lowres" and (lo <= 0.0 or hi > 1.0):
+        raise ValueError(f"augment_degrade: 'lowres.zoom' must lie in (0, 1], got {rng!r}")
+    return {"prob": float(prob), field: (lo, hi)}
+
+
+def degrade_config(value) -> Optional[dict]:
+    """The ``augment_degrade`` option in normal form: None when off (False / None, or every transform off),
+    else a dictionary with the four keys ``noise``, ``blur``, ``brightness``, ``lowres``, each None (that
+    transform is off and draws nothing) or ``{"prob": float, <field>: (low, high)}`` with the field
+    ``variance`` / ``sigma`` (voxels) / ``multiplier`` / ``zoom``.  ``True`` = all four with the defaults
+    ``{0.1, [0, 0.1]}``, ``{0.2, [0.5, 1.0]}``, ``{0.15, [0.75, 1.25]}``, ``{0.25, [0.5, 1.0]}``.  In a dictionary a
+    missing key means that transform's defaults, ``False`` switches it off, ``True`` means its defaults and a
+    dictionary overrides single fields.  Unknown keys and out-of-range values raise ``ValueError`` by name."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        value = {}
+    if not isinstance(value, dict):
+        raise ValueError(f"augment_degrade must be False, True or a dictionary with keys {list(_DEGRADE_DEFAULTS)}, "
+                         f"got {value!r}")
+    unknown = [k for k in value if k not in _DEGRADE_DEFAULTS]
+    if unknown:
+        raise ValueError(f"augment_degrade: unknown keys {unknown}; accepted: {list(_DEGRADE_DEFAULTS)}")
+    cfg = {name: _degrade_entry(name, value.get(name, True)) for name in _DEGRADE_DEFAULTS}
+    return cfg if any(v is not None for v in cfg.values()) else None
+
+
+def lowres_extents(roi, zoom) -> np.ndarray:
+    """coarse extents int32[n, 3] for patch extents ``roi`` and zooms [n]: ``max(1, floor(extent zoom + 0.5))``,
+    1 for an axis of extent 1"""
+    z = np.asarray(zoom, dtype=np.float64).reshape(-1, 1)
+    ext = np.asarray([int(r) for r in roi], dtype=np.float64).reshape(1, 3)
+    m = np.maximum(1.0, np.floor(ext * z + 0.5))
+    return np.where(ext > 1, np.minimum(m, ext), 1.0).astype(np.int32)
+
+
+def draw_degrade(rng: np.random.RandomState, n: int, roi, cfg: dict) -> dict:
+    """Per-patch draws of ``augment_degrade`` for ``ops.degrade_augment``, vectorised over the ``n`` patches, per
+    enabled transform and in this order: ``noise`` = (on, variance, seed uint32), ``blur`` = (on, sigma),
+    ``brightness`` = (on, multiplier), ``lowres`` = (on, zoom, m int32[n, 3]); a transform that is off is None
+    and draws nothing.  Each transform draws ``rand(n) < prob``, then ``uniform(range, n)`` (kept as f32, the
+    value the device is given); noise also ``randint(0, 2**32, n)``."""
+    out = {"noise": None, "blur": None, "brightness": None, "lowres": None}
+    c = cfg["noise"]
+    if c is not None:
+        on = (rng.rand(n) < c["prob"]).astype(np.uint8)
+        var = rng.uniform(c["variance"][0], c["variance"][1], n).astype(np.float32)
+        out["noise"] = (on, var, rng.randint(0, 2 ** 32, n, dtype=np.uint32))
+    c = cfg["blur"]
+    if c is not None:
+        on = (rng.rand(n) < c["prob"]).astype(np.uint8)
+        out["blur"] = (on, rng.uniform(c["sigma"][0], c["sigma"][1], n).astype(np.float32))
+    c = cfg["brightness"]
+    if c is not None:
+        on = (rng.rand(n) < c["prob"]).astype(np.uint8)
+        out["brightness"] = (on, rng.uniform(c["multiplier"][0], c["multiplier"][1], n).astype(np.float32))
+    c = cfg["lowres"]
+    if c is not None:
+        on = (rng.rand(n) < c["prob"]).astype(np.uint8)
+        zoom = rng.uniform(c["zoom"][0], c["zoom"][1], n).astype(np.float32)
+        out["lowres"] = (on, zoom, lowres_extents(roi, zoom))
+    return out
 
 
 def draw_intensity(rng: np.random.RandomState, n: int, roi=None):

@@ -124,6 +124,17 @@ class Net(torch.nn.Module):
         self.__dict__["_augment_elastic"] = elastic_config(value)
 
     @property
+    def augment_degrade(self):
+        """False, or the validated ``{noise, blur, brightness, lowres}`` of the noise / blur / brightness /
+        low-resolution augmentation (``seg/augment.py``).  Assigning ``True`` or a dictionary validates it on the spot."""
+        return self.__dict__.get("_augment_degrade") or False
+
+    @augment_degrade.setter
+    def augment_degrade(self, value):
+        from .augment import degrade_config
+        self.__dict__["_augment_degrade"] = degrade_config(value)
+
+    @property
     def num_classes(self):
         return self._model.out_channels
 
@@ -456,8 +467,9 @@ def train(
     # the objective rides in optimizer["loss"]: a bad entry fails here, before any rank is started or any device
     # call is made (the class-weight length is checked again once the class count is known)
     loss_from_config((optimizer or {}).get("loss"), num_classes if num_classes > 0 else None)
-    from .augment import elastic_config
+    from .augment import degrade_config, elastic_config
     elastic_config((augmentation or {}).get("augment_elastic", False))     # a bad entry fails here too
+    degrade_config((augmentation or {}).get("augment_degrade", False))
     n_ranks = len(list(gpu_ids or []))
     if n_ranks > 1 and not launch.under_launcher():
         # several gpu_ids: one process per GPU, started from here as children of this process --
@@ -509,9 +521,11 @@ def train(
     net.augment_spatial = augment_spatial
     # the elastic deformation is not in the reference's schema, whose keys this signature keeps: it rides in
     # the augmentation dictionary as "augment_elastic" (False / True / {prob, control_points,
-    # max_displacement}) beside the bundle's Compose, as the objective rides in optimizer["loss"]
+    # max_displacement}) beside the bundle's Compose, as the objective rides in optimizer["loss"]; so does
+    # "augment_degrade" (False / True / {noise, blur, brightness, lowres})
     augmentation = dict(augmentation or {})
     net.augment_elastic = augmentation.pop("augment_elastic", False)
+    net.augment_degrade = augmentation.pop("augment_degrade", False)
     net.config_augmentation = augmentation        # the bundle dictionary alone, as it is parsed below
     net.num_samples = num_samples
     # MONAI-bundle dictionaries (reference prepare_data, :232-262): resolved with the reference's

@@ -23,8 +23,8 @@ import torch
 
 from .. import ops
 from . import streams
-from .augment import (draw_elastic, draw_intensity, draw_spatial, elastic_amplitudes, elastic_config, flip_params,
-                      forward_point, forward_point_elastic, to_index_map_xyz)
+from .augment import (degrade_config, draw_degrade, draw_elastic, draw_intensity, draw_spatial, elastic_amplitudes,
+                      elastic_config, flip_params, forward_point, forward_point_elastic, to_index_map_xyz)
 from .distributed import broadcast_buffers, env_world, init_distributed
 from .pipeline import PredictPipeline
 
@@ -145,11 +145,14 @@ def draw_batch(net, cache: CachedVolumes, vol_ids, rng) -> List[Dict]:
     One record per volume: ``vid``, ``spatial`` (pull-back map or None), ``elastic`` (f32 control
     displacements [3, n0, n1, n2] or None; drawn directly after ``spatial``, and only with
     ``augment_elastic`` on: with it off not one extra random number is consumed), ``starts`` (crop origins),
-    ``flips`` (bit 0 = d0, bit 1 = d1, bit 2 = d2) and ``intensity`` (the five parameter tuples of
-    ``augment.draw_intensity`` as the reference draws them, i.e. for the UNflipped patch; or None)."""
+    ``flips`` (bit 0 = d0, bit 1 = d1, bit 2 = d2), ``intensity`` (the five parameter tuples of
+    ``augment.draw_intensity`` as the reference draws them, i.e. for the UNflipped patch; or None) and
+    ``degrade`` (the draws of ``augment.draw_degrade``, made directly after ``intensity`` and only with
+    ``augment_degrade`` on; they are for the patch as the gather writes it, flipped; or None)."""
     roi = list(net.spatial_size)
     fp = float(getattr(net, "flip_prob", 0.2))
     ecfg = elastic_config(getattr(net, "augment_elastic", False))
+    dcfg = degrade_config(getattr(net, "augment_degrade", False))
     records = []
     for vid in vol_ids:
         it = cache.items[vid]
@@ -159,8 +162,9 @@ def draw_batch(net, cache: CachedVolumes, vol_ids, rng) -> List[Dict]:
         flips = [(int(rng.rand() < fp)) | (int(rng.rand() < fp) << 1) | (int(rng.rand() < fp) << 2)
                  for _ in starts]
         intensity = draw_intensity(rng, len(starts), roi) if net.augment_intensity else None
+        degrade = draw_degrade(rng, len(starts), roi, dcfg) if dcfg is not None else None
         records.append({"vid": vid, "spatial": spatial, "elastic": elastic, "starts": starts, "flips": flips,
-                        "intensity": intensity})
+                        "intensity": intensity, "degrade": degrade})
     return records
 
 
@@ -169,7 +173,8 @@ def apply_batch(net, cache: CachedVolumes, records: List[Dict], out: Optional[Di
     then the intensity and k-space transforms with their parameters mirrored by the flips
     (``augment.flip_params``), which gives the reference's order crop -> intensity -> k-space -> flip.
     A record with an ``elastic`` field goes through ``ops.elastic_warp_crop_patches`` (with the affine map or
-    the identity); what follows the gather is the same."""
+    the identity); what follows the gather is the same.  A record with ``degrade`` draws gets noise, blur,
+    brightness and low resolution (``ops.degrade_augment``) between the gather and the intensity transforms."""
     roi = list(net.spatial_size)
     dev = net.device
     imgs, labs = [], []
@@ -199,6 +204,10 @@ def apply_batch(net, cache: CachedVolumes, records: List[Dict], out: Optional[Di
         else:
             ops.warp_crop_patches(src, it["label_dhw"], [[0] + s for s in starts], flips,
                                   to_index_map_xyz(spatial), out_i, out_l)
+        if rec.get("degrade") is not None:
+            dg = rec["degrade"]
+            ops.degrade_augment(out_i, dg["noise"], dg["blur"], dg["brightness"],
+                                None if dg["lowres"] is None else (dg["lowres"][0], dg["lowres"][2]))
         if rec["intensity"] is not None:
             con, hist, bias, gibbs, spike = flip_params(rec["intensity"], flips, roi)
             ops.intensity_augment(out_i, con, hist, bias)

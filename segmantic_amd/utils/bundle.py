@@ -147,6 +147,15 @@ def _check(comp, allowed, what):
                 f"noise, while segmantic_amd's on-device elastic deformation is a cubic B-spline over a control grid; "
                 f"mapping one onto the other would silently change what the bundle means.  Drop the transform and "
                 f"set the 'augment_elastic' option ({{prob, control_points, max_displacement}}) instead")
+        if isinstance(t, TransformSpec) and t.name.startswith(("RandGaussianNoise", "RandGaussianSmooth",
+                                                               "RandScaleIntensity")):
+            # MONAI draws these per call from its own generator (and the noise per voxel from it); the device's
+            # noise / blur / brightness take other draws -- a different stream of batches, so no mapping
+            raise ValueError(
+                f"'{what}': transform {t.target!r} is refused: MONAI's draws for it differ from those of "
+                f"segmantic_amd's on-device noise / blur / brightness / low-resolution augmentation, so mapping one "
+                f"onto the other would silently change what the bundle means.  Drop the transform and set the "
+                f"'augment_degrade' option ({{noise, blur, brightness, lowres}}) instead")
         if not isinstance(t, TransformSpec) or t.name not in allowed:
             raise ValueError(
                 f"'{what}': transform {getattr(t, 'target', t)!r} is not available in segmantic_amd's on-device "
