@@ -387,6 +387,52 @@ int segmi_softmax_dice_ce_bwd_amp(int dtype, const segmi_act* logits, const floa
                                   const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad,
                                   void* stream);
 
+/* Tversky / focal Tversky on the Dice passes.  With I, P, T the per-(n, k) sums of the Dice
+ * forward (intersection, sum p, sum t; softmax over all k classes):
+ *   TI = (I + smooth_nr) / (I + alpha (P - I) + beta (T - I) + smooth_dr)
+ *   loss = mean over the included (n, k) of (1 - TI)^exponent
+ * alpha weighs false positives, beta false negatives (MONAI's TverskyLoss); include_background = 0 drops class 0
+ * after the softmax (mean over n * (k - 1); k = 1 is then refused).  alpha, beta: finite, >= 0, alpha + beta > 0;
+ * exponent in (0, 3] (0.75 is the focal Tversky loss with gamma = 4/3); n * k <= 1792.  Term and coefficients are
+ * formed in f64 on the f64 sums.  Where 1 - TI <= 0 (possible only through rounding or smooth_nr > smooth_dr) the
+ * term AND its gradient coefficients are 0.  With alpha = beta = 0.5, exponent = 1 and both smooths s / 2 the value is
+ * the Dice loss with smooth s.
+ * partials f32[segmi_dice_ce_chunks()][n][3][k]; coef f32[n][2][k] receives {d loss / d I, d loss / d P} (zero for an
+ * excluded background); loss f32[1].  The backward is the Dice backward on that pair (same kernels, same scratch /
+ * bias_grad rule with scratch = this forward's partials): dlogits = scale * dLoss/dlogits, scale = grad_scale or
+ * amp[0].  A label outside [0, k) is in no class row. */
+int segmi_softmax_tversky_fwd(int dtype, const segmi_act* logits, const float* labels, float* partials, float* coef,
+                              float* loss, float smooth_nr, float smooth_dr, float alpha, float beta, float exponent,
+                              int include_background, void* stream);
+int segmi_softmax_tversky_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                              float grad_scale, const segmi_act* dlogits, float* scratch, float* bias_grad,
+                              void* stream);
+int segmi_softmax_tversky_bwd_amp(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                                  const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad,
+                                  void* stream);
+
+/* Dice + focal cross-entropy on the Dice + cross-entropy passes:
+ *   loss = lambda_dice * Dice + lambda_focal * Focal
+ *   Focal = sum_v w[y_v] * q_v^gamma * nll_v / W,  nll_v = -log p_{v,y_v} as segmi_softmax_dice_ce_fwd forms it,
+ *           q_v = 1 - p_{v,y_v} formed as the sum of the other probabilities (q = 0 contributes 0), W = sum_v w[y_v]
+ *           batch-global: the cross-entropy term's normaliser (W = 0 gives NaN; lambda_focal = 0 switches the term off).
+ * gamma: 0 or in [1, 5].  gamma = 0 runs the Dice + cross-entropy kernels themselves: loss and dlogits are those of
+ * segmi_softmax_dice_ce_fwd / _bwd with lambda_ce = lambda_focal bit for bit.  f32 uses powf / logf, the 16-bit types
+ * the hardware log2 / exp2.  Buffers, class_weight, include_background, the label rule and n * k <= 1792 as for
+ * segmi_softmax_dice_ce_fwd (partials f32[segmi_dice_ce_chunks()][n][4][k], coef f32[n][3][k]).  The backward needs
+ * the same gamma; per voxel it adds  scale * g_v * c_y * (p_j - [j = y]),  g_v = q^gamma + gamma q^(gamma-1) nll_v p_y,
+ * with nll_v recomputed. */
+int segmi_softmax_dice_focal_fwd(int dtype, const segmi_act* logits, const float* labels, float* partials,
+                                 float* coef, float* loss, float smooth_nr, float smooth_dr, float lambda_dice,
+                                 float lambda_focal, float gamma, int include_background, const float* class_weight,
+                                 void* stream);
+int segmi_softmax_dice_focal_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                                 float gamma, float grad_scale, const segmi_act* dlogits, float* scratch,
+                                 float* bias_grad, void* stream);
+int segmi_softmax_dice_focal_bwd_amp(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                                     float gamma, const float* amp, const segmi_act* dlogits, float* scratch,
+                                     float* bias_grad, void* stream);
+
 /* torch.optim.Adam / SGD semantics over one flat f32 arena, monai_unet.py:292-304,346, and
  * adabelief_pytorch.AdaBelief(rectify=False, fixed_decay=False), monai_unet.py:305-314.
  * Hyper-parameters are doubles, as the Python optimisers hold them: derived scalars (1 - beta,

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Loss forward / backward kernels in isolation at the benchmark shape (B=8 x 128^3, K=16), cold caches:
-Dice and Dice + cross-entropy, bf16 and f32, the backward with the fused bias gradient (as ``Net.training_step``
-runs it).  The two losses alternate inside every repetition, so both see the same machine state.
+Dice, Dice + cross-entropy, Tversky and Dice + focal, bf16 and f32, the backward with the fused bias gradient (as
+``Net.training_step`` runs it).  The losses alternate inside every repetition, so all see the same machine state.
 
 Byte model (what each pass has to move): forward = logits + labels read; backward = logits + labels read and
 dlogits written.  The partial rows, coefficients and bias sums are a few hundred KB and are left out.
 
-    python scripts/dice_bench.py [--reps 20] [--json]
+    python scripts/dice_bench.py [--reps 20] [--json] [--losses Dice,DiceCE]
 """
 import argparse
 import json
@@ -16,7 +16,7 @@ import sys
 import torch
 
 sys.path.insert(0, ".")
-from segmantic_amd.seg.losses import DiceCELoss, DiceLoss  # noqa: E402
+from segmantic_amd.seg.losses import DiceCELoss, DiceFocalLoss, DiceLoss, TverskyLoss  # noqa: E402
 
 DEV = "cuda:0"
 N, S, K = 8, 128, 16
@@ -32,6 +32,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--json", action="store_true", help="one JSON line per (dtype, loss, pass)")
+    ap.add_argument("--losses", default="Dice,DiceCE,Tversky,DiceFocal", help="comma-separated subset, in this order")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("dice_bench needs an MI355X")
@@ -42,7 +43,10 @@ def main():
         lg = torch.randn((N, S, S, S, K), device=DEV, generator=g).to(dtype)
         out = torch.empty_like(lg)
         bias = torch.empty(K, device=DEV)
-        losses = {"Dice": DiceLoss(), "DiceCE": DiceCELoss(weight=[0.5] + [1.0] * (K - 1))}
+        weight = [0.5] + [1.0] * (K - 1)
+        losses = {"Dice": DiceLoss(), "DiceCE": DiceCELoss(weight=weight),
+                  "Tversky": TverskyLoss(exponent=0.75), "DiceFocal": DiceFocalLoss(gamma=2.0, weight=weight)}
+        losses = {name: losses[name] for name in args.losses.split(",")}
         passes = {}
         for name, mod in losses.items():
             passes[name, "fwd"] = (lambda m=mod: m.forward_ndhwc(lg, lab), False)
@@ -71,10 +75,10 @@ def main():
             if args.json:
                 print(json.dumps(row))
             else:
-                print(f"{row['dtype']:>8} {name:>6} {which}: median {med:8.1f} us  [{ts[0]:8.1f} .. {ts[-1]:8.1f}]  "
+                print(f"{row['dtype']:>8} {name:>9} {which}: median {med:8.1f} us  [{ts[0]:8.1f} .. {ts[-1]:8.1f}]  "
                       f"{row['tb_per_s']:.2f} TB/s of the byte model")
         for name, mod in losses.items():
-            print(f"{str(dtype).replace('torch.', ''):>8} {name:>6} loss {float(mod.forward_ndhwc(lg, lab)):.6f}")
+            print(f"{str(dtype).replace('torch.', ''):>8} {name:>9} loss {float(mod.forward_ndhwc(lg, lab)):.6f}")
 
 
 if __name__ == "__main__":

@@ -140,6 +140,12 @@ SIGNATURES = {
     "segmi_softmax_dice_ce_fwd": (_i, [_i, _AP, _P, _P, _P, _P, _f, _f, _f, _f, _i, _P, _P]),
     "segmi_softmax_dice_ce_bwd": (_i, [_i, _AP, _P, _P, _f, _AP, _P, _P, _P]),
     "segmi_softmax_dice_ce_bwd_amp": (_i, [_i, _AP, _P, _P, _P, _AP, _P, _P, _P]),
+    "segmi_softmax_tversky_fwd": (_i, [_i, _AP, _P, _P, _P, _P, _f, _f, _f, _f, _f, _i, _P]),
+    "segmi_softmax_tversky_bwd": (_i, [_i, _AP, _P, _P, _f, _AP, _P, _P, _P]),
+    "segmi_softmax_tversky_bwd_amp": (_i, [_i, _AP, _P, _P, _P, _AP, _P, _P, _P]),
+    "segmi_softmax_dice_focal_fwd": (_i, [_i, _AP, _P, _P, _P, _P, _f, _f, _f, _f, _f, _i, _P, _P]),
+    "segmi_softmax_dice_focal_bwd": (_i, [_i, _AP, _P, _P, _f, _f, _AP, _P, _P, _P]),
+    "segmi_softmax_dice_focal_bwd_amp": (_i, [_i, _AP, _P, _P, _f, _P, _AP, _P, _P, _P]),
     "segmi_adam_step": (_i, [_P, _P, _P, _P, _P, _i64, _d, _d, _d, _d, _d, _i64, _f, _P]),
     "segmi_sgd_step": (_i, [_P, _P, _P, _i64, _d, _d, _d, _i, _f, _P]),
     "segmi_adabelief_step": (_i, [_P, _P, _P, _P, _i64, _d, _d, _d, _d, _d, _i, _i64, _f, _P]),

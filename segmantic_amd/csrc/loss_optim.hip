@@ -1,5 +1,6 @@
 // loss_optim.hip -- fused softmax + one-hot + Dice loss (forward / backward), its Dice + cross-entropy
-// extension (the CE template flag: same passes, one more partial / coefficient row), and the
+// extension (LossMode kDiceCE: same passes, one more partial / coefficient row), the Tversky and Dice + focal
+// losses on the same passes (kTversky, kFocal: DESIGN.md section 21), and the
 // flat-arena optimisers (Adam, SGD, AdaBelief).  HBM-bound: logits are read once per pass in
 // 16-byte vectors along the class axis (NDHWC keeps the K classes of a voxel contiguous), the
 // softmax lives in registers, reductions are two-stage and deterministic.
@@ -113,6 +114,54 @@ struct DiceCEFin {
   }
 };
 
+// Tversky / focal Tversky: per (n, k), all in f64 on the reduced sums,
+//   TI = (I + smooth_nr) / (I + alpha (P - I) + beta (T - I) + smooth_dr),  loss = mean of (1 - TI)^exponent
+// over the included (n, k); where 1 - TI <= 0 the term and its coefficients are 0.
+// sums: [n][3][k] as DiceFin; coef: [n][2][k] = {d loss / d I, d loss / d P} (0 for an excluded background), the
+// pair dice_bwd_kernel applies: d loss / d p_{v,k} = coef[0][k] [y_v = k] + coef[1][k]
+struct TverskyFin {
+  int n, k;
+  float smooth_nr, smooth_dr;
+  float alpha, beta, exponent;
+  int include_background;
+  float *coef, *loss;
+  __device__ void operator()(const double* sums, double* red) const {
+    const int tid = threadIdx.x;
+    double local = 0.0;
+    const int k0 = include_background ? 0 : 1;
+    const double nk = (double)n * (k - k0);
+    const double a = (double)alpha, bt = (double)beta, e = (double)exponent;
+    for (int o = tid; o < n * k; o += 256) {
+      const int b = o / k, j = o % k;
+      const double* q = sums + ((int64_t)b * 3) * k + j;
+      const double I = q[0], P = q[k], Tt = q[2 * k];
+      float* c = coef + ((int64_t)b * 2) * k + j;
+      double cI = 0.0, cP = 0.0;
+      if (j >= k0) {
+        const double num = I + (double)smooth_nr;
+        const double den = I + a * (P - I) + bt * (Tt - I) + (double)smooth_dr;
+        const double u = 1.0 - num / den;
+        if (u > 0.0) {
+          // d (u^e) / d TI = -e u^(e - 1);  d TI / d I = (den - num (1 - alpha - beta)) / den^2,  d TI / d P = -alpha num / den^2
+          const double dt = exponent == 1.f ? -1.0 : -e * pow(u, e - 1.0);
+          local += exponent == 1.f ? u : pow(u, e);
+          cI = dt * (den - num * (1.0 - a - bt)) / (den * den) / nk;
+          cP = dt * (-a * num) / (den * den) / nk;
+        }
+      }
+      c[0] = (float)cI;
+      c[k] = (float)cP;
+    }
+    red[tid] = local;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) red[tid] += red[tid + o];
+      __syncthreads();
+    }
+    if (tid == 0) *loss = (float)(red[0] / nk);
+  }
+};
+
 struct ChanSumFin {   // sums: [k] channel sums
   int k;
   float* db;
@@ -139,6 +188,17 @@ struct DiceParams {
   DiceFin dfin;
   ChanSumFin cfin;
   DiceCEFin cefin;
+  float gamma;       // kFocal: the focusing exponent, in [1, 5] (0 runs the kDiceCE kernels)
+  TverskyFin tfin;
+};
+
+// which loss a kernel instantiation computes.  kDice and kDiceCE are the kernels as they were before the other two
+// existed: everything the later modes add sits behind `if constexpr`
+enum LossMode : int {
+  kDice = 0,     // 3 partial rows, DiceFin, 2 coefficient rows
+  kDiceCE = 1,   // + a fourth partial row (sum of -log p_y) and DiceCEFin, 3 coefficient rows
+  kTversky = 2,  // the kDice forward with TverskyFin; its backward IS the kDice backward
+  kFocal = 3,    // kDiceCE with q^gamma * -log p_y in the fourth row and the focal factor on the backward's c_y
 };
 
 // VECLD: the caller has checked ONCE per workgroup (logits_vec_ok) that every voxel's class row is
@@ -217,11 +277,32 @@ __device__ __forceinline__ float softmax_nll_inplace(int k, float (&v)[KMAX], in
   return (FAST ? __builtin_amdgcn_logf(s) * 0.6931471805599453f : logf(s)) - xl;
 }
 
+// x^g for x >= 0 and g > 0 (0 at x = 0): libm powf for f32; the 16-bit paths use v_log_f32 / v_exp_f32 like the rest
+// of their softmax (log2(0) = -inf, g * -inf = -inf, exp2(-inf) = 0)
+template <bool FAST>
+__device__ __forceinline__ float pow_pos(float x, float g) {
+  return FAST ? __builtin_amdgcn_exp2f(g * __builtin_amdgcn_logf(x)) : powf(x, g);
+}
+
+// q^gamma with q = 1 - p_lab formed as the sum of the other probabilities (1 - p cancels when the voxel is classified
+// well; q = 0 gives 0).  A label outside [0, k) returns a value no caller uses.
+template <int KMAX, bool FULL, bool FAST>
+__device__ __forceinline__ float focal_q_pow(int k, const float (&pr)[KMAX], int lab, float gamma) {
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j)
+    if ((FULL || j < k) && j != lab) q += pr[j];
+  return pow_pos<FAST>(q, gamma);
+}
+
 // FULL: k == KMAX (16 / 32 / 64 labels): every per-channel predicate folds away at compile time
 // CE: Dice + cross-entropy -- a fourth partial row (sum of -log p_y over the voxels with y = k) and DiceCEFin;
 // CE = false is the Dice-only kernel, unchanged
-template <typename T, int KMAX, bool FULL, bool CE>
+// kFocal: the fourth row receives q^gamma * -log p_y, q = the sum of the other probabilities (as the backward's `rest`)
+template <typename T, int KMAX, bool FULL, int MODE>
 __global__ __launch_bounds__(256) void dice_fwd_kernel(DiceParams p) {
+  constexpr bool CE = MODE == kDiceCE || MODE == kFocal;
+  constexpr bool FOCAL = MODE == kFocal;
   constexpr int ROWS = CE ? 4 : 3;
   __shared__ float red[4][ROWS * KMAX];
   const int n = blockIdx.y, chunk = blockIdx.x;
@@ -258,6 +339,7 @@ __global__ __launch_bounds__(256) void dice_fwd_kernel(DiceParams p) {
         float nll = 0.f;
         if constexpr (CE) nll = softmax_nll_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x[u], lab);
         else softmax_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x[u]);
+        if constexpr (FOCAL) nll *= focal_q_pow<KMAX, FULL, sizeof(T) == 2>(p.k, x[u], lab, p.gamma);
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
           if (FULL || j < p.k) {
@@ -278,6 +360,7 @@ __global__ __launch_bounds__(256) void dice_fwd_kernel(DiceParams p) {
       float nll = 0.f;
       if constexpr (CE) nll = softmax_nll_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x, lab);
       else softmax_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x);
+      if constexpr (FOCAL) nll *= focal_q_pow<KMAX, FULL, sizeof(T) == 2>(p.k, x, lab, p.gamma);
 #pragma unroll
       for (int j = 0; j < KMAX; ++j) {
         if (FULL || j < p.k) {
@@ -315,6 +398,8 @@ __global__ __launch_bounds__(256) void dice_fwd_kernel(DiceParams p) {
     extern __shared__ double dice_tail_lds[];
     if constexpr (CE)
       fin_tail_run<DiceCEFin, 256, offsetof(DiceParams, ft), offsetof(DiceParams, cefin)>(p.partials, dice_tail_lds);
+    else if constexpr (MODE == kTversky)
+      fin_tail_run<TverskyFin, 256, offsetof(DiceParams, ft), offsetof(DiceParams, tfin)>(p.partials, dice_tail_lds);
     else
       fin_tail_run<DiceFin, 256, offsetof(DiceParams, ft), offsetof(DiceParams, dfin)>(p.partials, dice_tail_lds);
   }
@@ -322,8 +407,13 @@ __global__ __launch_bounds__(256) void dice_fwd_kernel(DiceParams p) {
 
 // CE: the third coefficient row c_k = lambda_ce * w_k / W adds c_y * (p_j - [j = y]) per class.  For j = y the
 // bracket is formed as -(sum of the other probabilities): p_y - 1 cancels when the voxel is classified well.
-template <typename T, int KMAX, bool FULL, bool CE>
+// kFocal: d Focal_v / d x_j = g_v * c_y * (p_j - [j = y]) with g_v = q^gamma + gamma q^(gamma - 1) nll p_y: the CE term
+// with cy multiplied by g_v; nll is recomputed as the forward formed it (softmax_nll_inplace keeps the probabilities' bits)
+template <typename T, int KMAX, bool FULL, int MODE>
 __global__ __launch_bounds__(256) void dice_bwd_kernel(DiceParams p) {
+  static_assert(MODE != kTversky, "the Tversky backward is the kDice kernel");
+  constexpr bool CE = MODE == kDiceCE || MODE == kFocal;
+  constexpr bool FOCAL = MODE == kFocal;
   constexpr int ROWS = CE ? 3 : 2;
   __shared__ float cf[ROWS * KMAX];
   const int n = blockIdx.y, chunk = blockIdx.x;
@@ -345,8 +435,27 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(DiceParams p) {
     float x[KMAX];
     if (vec_in) load_logits<T, KMAX, true>(lg + v * p.ld, FULL ? KMAX : p.k, x);
     else load_logits<T, KMAX, false>(lg + v * p.ld, FULL ? KMAX : p.k, x);
-    softmax_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x);
+    float nll = 0.f;
+    if constexpr (FOCAL) nll = softmax_nll_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x, (int)lb[v]);
+    else softmax_inplace<KMAX, sizeof(T) == 2>(FULL ? KMAX : p.k, x);
     const int lab = (int)lb[v];
+    float fg = 0.f, fq = 0.f;        // kFocal: g_v and q_v, formed here so that only two scalars live through the Dice part
+    if constexpr (FOCAL) {
+      float py = 0.f, q = 0.f;       // q: the sum the CE term calls `rest`
+#pragma unroll
+      for (int j = 0; j < KMAX; ++j)
+        if (FULL || j < p.k) {
+          if (j == lab) py = x[j];
+          else q += x[j];
+        }
+      // q^(gamma - 1) is 1 for gamma = 1 whatever q is (0 * log2(0) would be NaN)
+      const float qg1 = p.gamma == 1.f ? 1.f : pow_pos<sizeof(T) == 2>(q, p.gamma - 1.f);
+      fg = fmaf(p.gamma * qg1, nll * py, qg1 * q);
+      fq = q;
+      // keep the scheduler from spreading this block over the Dice part: the ragged 64-class instantiations sit at
+      // the register limit, and fp16 spilled without it
+      __builtin_amdgcn_sched_barrier(0);
+    }
     float dot = 0.f;
     float dp[KMAX];
 #pragma unroll
@@ -360,9 +469,14 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(DiceParams p) {
     if constexpr (CE) {
       const bool in = (unsigned)lab < (unsigned)(FULL ? KMAX : p.k);
       cy = in ? grad_scale * cf[2 * KMAX + (in ? lab : 0)] : 0.f;
+      if constexpr (FOCAL) {
+        rest = fq;
+        cy *= fg;
+      } else {
 #pragma unroll
-      for (int j = 0; j < KMAX; ++j)
-        if ((FULL || j < p.k) && j != lab) rest += x[j];
+        for (int j = 0; j < KMAX; ++j)
+          if ((FULL || j < p.k) && j != lab) rest += x[j];
+      }
     }
     T* o = dl + v * p.ldd;
     if (vec_out) {
@@ -580,18 +694,19 @@ __global__ void amp_update_kernel(float* amp, int32_t* tracker, int64_t* step, f
 
 constexpr int kOptCap = 2048;   // workgroups of an optimiser step
 
-template <typename T, bool CE>
+template <typename T, int MODE>
 static int dice_dispatch(bool fwd, const DiceParams& p, hipStream_t st) {
+  constexpr int BMODE = MODE == kTversky ? (int)kDice : MODE;   // backward instantiation
   dim3 grid(p.chunks, p.n);
   const size_t lds = p.ft.on ? fin_tail_lds(p.ft.width, 256) : 0;
 #define DICE_K(KM)                                                                       \
   do {                                                                                   \
     if (p.k == KM) {                                                                     \
-      if (fwd) hipLaunchKernelGGL((dice_fwd_kernel<T, KM, true, CE>), grid, 256, lds, st, p);  \
-      else hipLaunchKernelGGL((dice_bwd_kernel<T, KM, true, CE>), grid, 256, lds, st, p);      \
+      if (fwd) hipLaunchKernelGGL((dice_fwd_kernel<T, KM, true, MODE>), grid, 256, lds, st, p);  \
+      else hipLaunchKernelGGL((dice_bwd_kernel<T, KM, true, BMODE>), grid, 256, lds, st, p);      \
     } else {                                                                             \
-      if (fwd) hipLaunchKernelGGL((dice_fwd_kernel<T, KM, false, CE>), grid, 256, lds, st, p); \
-      else hipLaunchKernelGGL((dice_bwd_kernel<T, KM, false, CE>), grid, 256, lds, st, p);     \
+      if (fwd) hipLaunchKernelGGL((dice_fwd_kernel<T, KM, false, MODE>), grid, 256, lds, st, p); \
+      else hipLaunchKernelGGL((dice_bwd_kernel<T, KM, false, BMODE>), grid, 256, lds, st, p);     \
     }                                                                                    \
   } while (0)
   if (p.k <= 4) DICE_K(4);
@@ -603,9 +718,9 @@ static int dice_dispatch(bool fwd, const DiceParams& p, hipStream_t st) {
   SEGMI_LAUNCH_CHECK("softmax_dice");
   return SEGMI_OK;
 }
-template <bool CE>
+template <int MODE>
 static int dice_dispatch_dt(int dtype, bool fwd, const DiceParams& p, hipStream_t st) {
-#define DICE_T(T) return dice_dispatch<T, CE>(fwd, p, st)
+#define DICE_T(T) return dice_dispatch<T, MODE>(fwd, p, st)
   SEGMI_BY_DTYPE(dtype, DICE_T);
 #undef DICE_T
 }
@@ -642,12 +757,12 @@ int segmi_softmax_dice_fwd(int dtype, const segmi_act* logits, const float* labe
   // (fin_tail.h): rows = chunks, one row = [n][3][k]
   p.ft = fin_tail_make(p.chunks, p.n * 3 * p.k, (unsigned)p.chunks * (unsigned)p.n);
   p.dfin = DiceFin{p.n, p.k, smooth_nr, smooth_dr, coef, loss};
-  return dice_dispatch_dt<false>(dtype, true, p, st);
+  return dice_dispatch_dt<kDice>(dtype, true, p, st);
 }
 
-static int dice_bwd(bool ce, int dtype, const segmi_act* logits, const float* labels, const float* coef,
+static int dice_bwd(int mode, int dtype, const segmi_act* logits, const float* labels, const float* coef,
                     float grad_scale, const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad,
-                    void* stream) {
+                    void* stream, float gamma = 0.f) {
   SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_dice_bwd: bad dtype");
   SEGMI_CHECK_ARG(act_ok(logits) && act_ok(dlogits) && labels && coef &&
                       logits->n == dlogits->n && logits->d == dlogits->d &&
@@ -660,6 +775,7 @@ static int dice_bwd(bool ce, int dtype, const segmi_act* logits, const float* la
   p.chunks = dice_real_chunks(logits);
   p.grad_scale = grad_scale;
   p.amp = amp;
+  p.gamma = gamma;
   SEGMI_CHECK_ARG(!bias_grad || scratch, "softmax_dice_bwd: bias_grad needs the scratch buffer");
   p.bias_part = bias_grad ? scratch : nullptr;
   hipStream_t st = (hipStream_t)stream;
@@ -667,20 +783,21 @@ static int dice_bwd(bool ce, int dtype, const segmi_act* logits, const float* la
     p.ft = fin_tail_make(p.n * p.chunks, p.k, (unsigned)p.chunks * (unsigned)p.n);
     p.cfin = ChanSumFin{p.k, bias_grad};
   }
-  return ce ? dice_dispatch_dt<true>(dtype, false, p, st) : dice_dispatch_dt<false>(dtype, false, p, st);
+  if (mode == kFocal) return dice_dispatch_dt<kFocal>(dtype, false, p, st);
+  return mode == kDiceCE ? dice_dispatch_dt<kDiceCE>(dtype, false, p, st) : dice_dispatch_dt<kDice>(dtype, false, p, st);
 }
 
 int segmi_softmax_dice_bwd(int dtype, const segmi_act* logits, const float* labels,
                            const float* coef, float grad_scale, const segmi_act* dlogits,
                            float* scratch, float* bias_grad, void* stream) {
-  return dice_bwd(false, dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
+  return dice_bwd(kDice, dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
 }
 
 int segmi_softmax_dice_bwd_amp(int dtype, const segmi_act* logits, const float* labels,
                                const float* coef, const float* amp, const segmi_act* dlogits,
                                float* scratch, float* bias_grad, void* stream) {
   SEGMI_CHECK_ARG(amp, "softmax_dice_bwd_amp: amp state missing");
-  return dice_bwd(false, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
+  return dice_bwd(kDice, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
 }
 
 // ---- Dice + cross-entropy: 4-row partials, 3-row coefficients
@@ -713,20 +830,116 @@ int segmi_softmax_dice_ce_fwd(int dtype, const segmi_act* logits, const float* l
   p.ft = fin_tail_make(p.chunks, p.n * 4 * p.k, (unsigned)p.chunks * (unsigned)p.n);
   p.cefin = DiceCEFin{p.n, p.k, smooth_nr, smooth_dr, lambda_dice, lambda_ce, include_background != 0,
                       class_weight, coef, loss};
-  return dice_dispatch_dt<true>(dtype, true, p, (hipStream_t)stream);
+  return dice_dispatch_dt<kDiceCE>(dtype, true, p, (hipStream_t)stream);
 }
 
 int segmi_softmax_dice_ce_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef,
                               float grad_scale, const segmi_act* dlogits, float* scratch, float* bias_grad,
                               void* stream) {
-  return dice_bwd(true, dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
+  return dice_bwd(kDiceCE, dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
 }
 
 int segmi_softmax_dice_ce_bwd_amp(int dtype, const segmi_act* logits, const float* labels, const float* coef,
                                   const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad,
                                   void* stream) {
   SEGMI_CHECK_ARG(amp, "softmax_dice_ce_bwd_amp: amp state missing");
-  return dice_bwd(true, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
+  return dice_bwd(kDiceCE, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
+}
+
+// ---- Tversky: the Dice forward with TverskyFin; the backward is the Dice backward on its coefficient pair
+int segmi_softmax_tversky_fwd(int dtype, const segmi_act* logits, const float* labels, float* partials, float* coef,
+                              float* loss, float smooth_nr, float smooth_dr, float alpha, float beta, float exponent,
+                              int include_background, void* stream) {
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_tversky_fwd: bad dtype");
+  SEGMI_CHECK_ARG(act_ok(logits) && labels && partials && coef && loss, "softmax_tversky_fwd: bad arguments");
+  SEGMI_CHECK_ARG(alpha >= 0.f && beta >= 0.f && __builtin_isfinite(alpha) && __builtin_isfinite(beta) &&
+                      alpha + beta > 0.f,
+                  "softmax_tversky_fwd: alpha / beta must be finite and >= 0 with alpha + beta > 0 (got %g, %g)",
+                  (double)alpha, (double)beta);
+  SEGMI_CHECK_ARG(exponent > 0.f && exponent <= 3.f, "softmax_tversky_fwd: exponent must lie in (0, 3] (got %g)",
+                  (double)exponent);
+  SEGMI_CHECK_ARG(include_background || logits->c > 1,
+                  "softmax_tversky_fwd: include_background = 0 needs more than one class");
+  DiceParams p{};
+  p.logits = logits->data; p.labels = labels; p.partials = partials;
+  p.n = logits->n; p.k = logits->c; p.ld = logits->ld;
+  p.vox = (int64_t)logits->d * logits->h * logits->w;
+  p.chunks = dice_real_chunks(logits);
+  // the limit of the Dice + cross-entropy finalisation, so that one batch / class bound holds for every configurable loss
+  SEGMI_CHECK_ARG(fin_tail_lds(p.n * 4 * p.k, 256) <= 64 * 1024,
+                  "softmax_tversky_fwd: batch %d x %d classes is beyond the finalisation's LDS (n * k <= 1792)",
+                  p.n, p.k);
+  p.ft = fin_tail_make(p.chunks, p.n * 3 * p.k, (unsigned)p.chunks * (unsigned)p.n);
+  p.tfin = TverskyFin{p.n, p.k, smooth_nr, smooth_dr, alpha, beta, exponent, include_background != 0, coef, loss};
+  return dice_dispatch_dt<kTversky>(dtype, true, p, (hipStream_t)stream);
+}
+
+int segmi_softmax_tversky_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                              float grad_scale, const segmi_act* dlogits, float* scratch, float* bias_grad,
+                              void* stream) {
+  return dice_bwd(kDice, dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
+}
+
+int segmi_softmax_tversky_bwd_amp(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                                  const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad,
+                                  void* stream) {
+  SEGMI_CHECK_ARG(amp, "softmax_tversky_bwd_amp: amp state missing");
+  return dice_bwd(kDice, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
+}
+
+// ---- Dice + focal: the Dice + cross-entropy passes with the focal factor; gamma = 0 IS Dice + cross-entropy
+static bool focal_gamma_ok(float gamma) { return gamma == 0.f || (gamma >= 1.f && gamma <= 5.f); }
+
+int segmi_softmax_dice_focal_fwd(int dtype, const segmi_act* logits, const float* labels, float* partials,
+                                 float* coef, float* loss, float smooth_nr, float smooth_dr, float lambda_dice,
+                                 float lambda_focal, float gamma, int include_background, const float* class_weight,
+                                 void* stream) {
+  SEGMI_CHECK_ARG(focal_gamma_ok(gamma), "softmax_dice_focal_fwd: gamma must be 0 or lie in [1, 5] (got %g)",
+                  (double)gamma);
+  if (gamma == 0.f)
+    return segmi_softmax_dice_ce_fwd(dtype, logits, labels, partials, coef, loss, smooth_nr, smooth_dr, lambda_dice,
+                                     lambda_focal, include_background, class_weight, stream);
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_dice_focal_fwd: bad dtype");
+  SEGMI_CHECK_ARG(act_ok(logits) && labels && partials && coef && loss, "softmax_dice_focal_fwd: bad arguments");
+  SEGMI_CHECK_ARG(lambda_dice >= 0.f && lambda_focal >= 0.f && __builtin_isfinite(lambda_dice) &&
+                      __builtin_isfinite(lambda_focal),
+                  "softmax_dice_focal_fwd: lambda_dice / lambda_focal must be finite and >= 0 (got %g, %g)",
+                  (double)lambda_dice, (double)lambda_focal);
+  SEGMI_CHECK_ARG(include_background || logits->c > 1,
+                  "softmax_dice_focal_fwd: include_background = 0 needs more than one class");
+  DiceParams p{};
+  p.logits = logits->data; p.labels = labels; p.partials = partials;
+  p.n = logits->n; p.k = logits->c; p.ld = logits->ld;
+  p.vox = (int64_t)logits->d * logits->h * logits->w;
+  p.chunks = dice_real_chunks(logits);
+  p.gamma = gamma;
+  SEGMI_CHECK_ARG(fin_tail_lds(p.n * 4 * p.k, 256) <= 64 * 1024,
+                  "softmax_dice_focal_fwd: batch %d x %d classes needs %zu bytes of LDS for the finalisation, the "
+                  "limit is 65536 (n * k <= 1792)", p.n, p.k, fin_tail_lds(p.n * 4 * p.k, 256));
+  p.ft = fin_tail_make(p.chunks, p.n * 4 * p.k, (unsigned)p.chunks * (unsigned)p.n);
+  // the finalisation is the Dice + cross-entropy one: the fourth row holds the focal sums, lambda_focal is its lambda
+  p.cefin = DiceCEFin{p.n, p.k, smooth_nr, smooth_dr, lambda_dice, lambda_focal, include_background != 0,
+                      class_weight, coef, loss};
+  return dice_dispatch_dt<kFocal>(dtype, true, p, (hipStream_t)stream);
+}
+
+int segmi_softmax_dice_focal_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                                 float gamma, float grad_scale, const segmi_act* dlogits, float* scratch,
+                                 float* bias_grad, void* stream) {
+  SEGMI_CHECK_ARG(focal_gamma_ok(gamma), "softmax_dice_focal_bwd: gamma must be 0 or lie in [1, 5] (got %g)",
+                  (double)gamma);
+  return dice_bwd(gamma == 0.f ? (int)kDiceCE : (int)kFocal, dtype, logits, labels, coef, grad_scale, nullptr, dlogits,
+                  scratch, bias_grad, stream, gamma);
+}
+
+int segmi_softmax_dice_focal_bwd_amp(int dtype, const segmi_act* logits, const float* labels, const float* coef,
+                                     float gamma, const float* amp, const segmi_act* dlogits, float* scratch,
+                                     float* bias_grad, void* stream) {
+  SEGMI_CHECK_ARG(focal_gamma_ok(gamma), "softmax_dice_focal_bwd_amp: gamma must be 0 or lie in [1, 5] (got %g)",
+                  (double)gamma);
+  SEGMI_CHECK_ARG(amp, "softmax_dice_focal_bwd_amp: amp state missing");
+  return dice_bwd(gamma == 0.f ? (int)kDiceCE : (int)kFocal, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch,
+                  bias_grad, stream, gamma);
 }
 
 int segmi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

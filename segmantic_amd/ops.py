@@ -573,6 +573,63 @@ def softmax_dice_ce_bwd_amp(logits, labels, coef, amp, dlogits, scratch=None, bi
           "softmax_dice_ce_bwd_amp")
 
 
+def softmax_tversky_fwd(logits, labels, partials, coef, loss, smooth_nr=1e-5, smooth_dr=1e-5, alpha=0.3, beta=0.7,
+                        exponent=1.0, include_background=True) -> None:
+    """loss = mean (1 - TI)^exponent (``segmi.h``); ``partials`` f32 [dice_ce_chunks, n, 3, k], ``coef`` f32 [n, 2, k]"""
+    a = act(logits)
+    check(lib.segmi_softmax_tversky_fwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(partials), _ptr(coef),
+                                        _ptr(loss), smooth_nr, smooth_dr, float(alpha), float(beta), float(exponent),
+                                        int(bool(include_background)), _stream()),
+          "softmax_tversky_fwd")
+
+
+def softmax_tversky_bwd(logits, labels, coef, grad_scale, dlogits, scratch=None, bias_grad=None) -> None:
+    """as ``softmax_dice_bwd`` with the coefficient pair of ``softmax_tversky_fwd``"""
+    a, b = act(logits), act(dlogits)
+    check(lib.segmi_softmax_tversky_bwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef),
+                                        float(grad_scale), C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
+          "softmax_tversky_bwd")
+
+
+def softmax_tversky_bwd_amp(logits, labels, coef, amp, dlogits, scratch=None, bias_grad=None) -> None:
+    """softmax_tversky_bwd with the loss scale read from ``amp[0]`` on the device."""
+    a, b = act(logits), act(dlogits)
+    check(lib.segmi_softmax_tversky_bwd_amp(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef), _ptr(amp),
+                                            C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
+          "softmax_tversky_bwd_amp")
+
+
+def softmax_dice_focal_fwd(logits, labels, partials, coef, loss, smooth_nr=1e-5, smooth_dr=1e-5, lambda_dice=1.0,
+                           lambda_focal=1.0, gamma=2.0, include_background=True, class_weight=None) -> None:
+    """loss = lambda_dice * Dice + lambda_focal * Focal (``segmi.h``); buffers as ``softmax_dice_ce_fwd``;
+    ``gamma = 0`` runs the Dice + cross-entropy kernels."""
+    a = act(logits)
+    if class_weight is not None and (class_weight.dtype != torch.float32 or class_weight.numel() != logits.shape[4]
+                                     or not class_weight.is_contiguous()):
+        raise ValueError(f"class_weight must be a contiguous float32 tensor of {logits.shape[4]} entries")
+    check(lib.segmi_softmax_dice_focal_fwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(partials), _ptr(coef),
+                                           _ptr(loss), smooth_nr, smooth_dr, float(lambda_dice), float(lambda_focal),
+                                           float(gamma), int(bool(include_background)), _ptr(class_weight),
+                                           _stream()),
+          "softmax_dice_focal_fwd")
+
+
+def softmax_dice_focal_bwd(logits, labels, coef, gamma, grad_scale, dlogits, scratch=None, bias_grad=None) -> None:
+    """as ``softmax_dice_ce_bwd`` with the forward's ``gamma``"""
+    a, b = act(logits), act(dlogits)
+    check(lib.segmi_softmax_dice_focal_bwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef), float(gamma),
+                                           float(grad_scale), C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
+          "softmax_dice_focal_bwd")
+
+
+def softmax_dice_focal_bwd_amp(logits, labels, coef, gamma, amp, dlogits, scratch=None, bias_grad=None) -> None:
+    """softmax_dice_focal_bwd with the loss scale read from ``amp[0]`` on the device."""
+    a, b = act(logits), act(dlogits)
+    check(lib.segmi_softmax_dice_focal_bwd_amp(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef), float(gamma),
+                                               _ptr(amp), C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
+          "softmax_dice_focal_bwd_amp")
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, beta1, beta2, eps,
               weight_decay, step, grad_scale=1.0) -> None:
     check(lib.segmi_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),

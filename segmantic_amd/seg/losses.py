@@ -9,6 +9,8 @@ reference ``src/segmantic/seg/monai_unet.py:128`` and called at ``:344`` / ``:35
 term computed by the same two kernels, and both losses take ``include_background``.  Every loss object offers
 ``forward_ndhwc`` / ``backward_ndhwc``, the explicit (no autograd graph) interface ``Net.training_step``
 drives; ``loss_from_config`` builds the object an ``optimizer["loss"]`` dictionary names.
+
+``TverskyLoss`` and ``DiceFocalLoss`` answer class imbalance on the same two passes.
 """
 from __future__ import annotations
 
@@ -162,7 +164,7 @@ class _LossFn(torch.autograd.Function):
 
 
 class _FusedLoss(torch.nn.Module):
-    """What the two losses share: ``forward`` on logical [N,K,D,H,W] logits (autograd bridge or plain value)
+    """What the losses share: ``forward`` on logical [N,K,D,H,W] logits (autograd bridge or plain value)
     over the subclass's ``forward_ndhwc`` / ``backward_ndhwc``."""
 
     def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
@@ -254,17 +256,156 @@ class DiceCELoss(_FusedLoss):
         return dice_ce_backward(self._state, logits_ndhwc, grad_scale, out, bias_grad=bias_grad, amp=amp)
 
 
+class _TverskyState:
+    """Scratch of the Tversky kernels (3-row partials in the kernel's layout, the Dice backward's coefficient pair)."""
+
+    def __init__(self):
+        self.partials: Optional[torch.Tensor] = None
+        self.coef: Optional[torch.Tensor] = None
+        self.loss: Optional[torch.Tensor] = None
+        self.labels: Optional[torch.Tensor] = None
+
+    def ensure(self, logits: torch.Tensor):
+        n, k = logits.shape[0], logits.shape[4]
+        chunks = ops.dice_ce_chunks(logits)
+        dev = logits.device
+        if self.partials is None or self.partials.shape != (chunks, n, 3, k) or self.partials.device != dev:
+            self.partials = torch.empty((chunks, n, 3, k), device=dev)
+            self.coef = torch.empty((n, 2, k), device=dev)
+        self.loss = torch.empty(1, device=dev)
+
+
+def _check_range(name: str, v, ok, what: str) -> float:
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"'{name}' must be a number (got {v!r})") from None
+    if not (math.isfinite(v) and ok(v)):
+        raise ValueError(f"'{name}' must {what} (got {v})")
+    return v
+
+
+class TverskyLoss(_FusedLoss):
+    """Tversky / focal Tversky loss on the Dice kernels (MONAI's ``TverskyLoss(to_onehot_y=True, softmax=True)``
+    raised to ``exponent``): per (n, k) ``TI = (I + smooth_nr) / (I + alpha (P - I) + beta (T - I) + smooth_dr)``,
+    ``loss = mean (1 - TI) ** exponent``.  ``alpha`` weighs false positives, ``beta`` false negatives; the defaults
+    0.3 / 0.7 are Salehi et al.'s, ``exponent = 0.75`` is Abraham and Khan's focal Tversky loss (gamma = 4/3).
+    ``include_background=False`` drops class 0 after the softmax as ``DiceLoss`` does."""
+
+    def __init__(self, include_background: bool = True, to_onehot_y: bool = True, softmax: bool = True,
+                 alpha: float = 0.3, beta: float = 0.7, exponent: float = 1.0, smooth_nr: float = 1e-5,
+                 smooth_dr: float = 1e-5):
+        super().__init__()
+        if not (to_onehot_y and softmax):
+            raise NotImplementedError("the HIP Tversky kernels implement to_onehot_y=True, softmax=True")
+        self.include_background = bool(include_background)
+        self.alpha = _check_range("alpha", alpha, lambda v: v >= 0.0, "be finite and >= 0")
+        self.beta = _check_range("beta", beta, lambda v: v >= 0.0, "be finite and >= 0")
+        if not self.alpha + self.beta > 0.0:
+            raise ValueError(f"'alpha' + 'beta' must be > 0 (got {self.alpha}, {self.beta})")
+        self.exponent = _check_range("exponent", exponent, lambda v: 0.0 < v <= 3.0, "lie in (0, 3]")
+        self.smooth_nr, self.smooth_dr = smooth_nr, smooth_dr
+        self._state = _TverskyState()
+
+    def forward_ndhwc(self, logits_ndhwc: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        k = logits_ndhwc.shape[4]
+        if not self.include_background and k == 1:
+            raise ValueError("include_background=False needs more than one class")
+        lab = labels.to(logits_ndhwc.device, torch.float32).contiguous().view(-1)
+        if lab.numel() != logits_ndhwc.numel() // k:
+            raise ValueError("label volume does not match logits")
+        st = self._state
+        st.ensure(logits_ndhwc)
+        ops.softmax_tversky_fwd(logits_ndhwc, lab, st.partials, st.coef, st.loss, self.smooth_nr, self.smooth_dr,
+                                self.alpha, self.beta, self.exponent, self.include_background)
+        st.labels = lab
+        return st.loss.view(())
+
+    def backward_ndhwc(self, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
+                       out: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
+                       amp: Optional[torch.Tensor] = None) -> torch.Tensor:
+        st = self._state
+        if out is None or out.shape != logits_ndhwc.shape or out.dtype != logits_ndhwc.dtype:
+            out = torch.empty_like(logits_ndhwc)
+        scratch = st.partials if bias_grad is not None else None
+        if amp is not None:
+            ops.softmax_tversky_bwd_amp(logits_ndhwc, st.labels, st.coef, amp, out, scratch=scratch,
+                                        bias_grad=bias_grad)
+        else:
+            ops.softmax_tversky_bwd(logits_ndhwc, st.labels, st.coef, grad_scale, out, scratch=scratch,
+                                    bias_grad=bias_grad)
+        return out
+
+
+class DiceFocalLoss(_FusedLoss):
+    """``lambda_dice * Dice + lambda_focal * Focal`` in the two passes of the Dice + cross-entropy kernels.
+
+    ``Focal = sum_v w[y_v] * (1 - p_{v,y_v}) ** gamma * -log p_{v,y_v} / W`` with ``W = sum_v w[y_v]`` batch-global,
+    the normaliser of ``DiceCELoss``'s cross-entropy term (Lin et al.'s focal loss on the softmax; MONAI's
+    ``DiceFocalLoss`` averages over N * K * V elements instead, a constant factor).  ``gamma`` is 0 or in [1, 5];
+    ``gamma = 0`` is ``DiceCELoss`` bit for bit.  ``weight``, ``include_background`` and the label rule as there."""
+
+    def __init__(self, include_background: bool = True, to_onehot_y: bool = True, softmax: bool = True,
+                 lambda_dice: float = 1.0, lambda_focal: float = 1.0, gamma: float = 2.0, weight=None,
+                 smooth_nr: float = 1e-5, smooth_dr: float = 1e-5):
+        super().__init__()
+        if not (to_onehot_y and softmax):
+            raise NotImplementedError("the HIP Dice + focal kernels implement to_onehot_y=True, softmax=True")
+        self.include_background = bool(include_background)
+        self.lambda_dice = _check_lambda("lambda_dice", lambda_dice)
+        self.lambda_focal = _check_lambda("lambda_focal", lambda_focal)
+        self.gamma = _check_range("gamma", gamma, lambda v: v == 0.0 or 1.0 <= v <= 5.0, "be 0 or lie in [1, 5]")
+        self.weight = _check_weight(weight)
+        self.smooth_nr, self.smooth_dr = smooth_nr, smooth_dr
+        self._state = _DiceCEState()
+
+    def forward_ndhwc(self, logits_ndhwc: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        k = logits_ndhwc.shape[4]
+        if self.weight is not None and len(self.weight) != k:
+            raise ValueError(f"'class_weights' has {len(self.weight)} entries, the logits have {k} classes")
+        if not self.include_background and k == 1:
+            raise ValueError("include_background=False needs more than one class")
+        lab = labels.to(logits_ndhwc.device, torch.float32).contiguous().view(-1)
+        if lab.numel() != logits_ndhwc.numel() // k:
+            raise ValueError("label volume does not match logits")
+        st = self._state
+        st.ensure(logits_ndhwc, self.weight)
+        ops.softmax_dice_focal_fwd(logits_ndhwc, lab, st.partials, st.coef, st.loss, self.smooth_nr, self.smooth_dr,
+                                   self.lambda_dice, self.lambda_focal, self.gamma, self.include_background, st.weight)
+        st.labels = lab
+        st.gamma = self.gamma           # the backward differentiates the forward that ran
+        return st.loss.view(())
+
+    def backward_ndhwc(self, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
+                       out: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
+                       amp: Optional[torch.Tensor] = None) -> torch.Tensor:
+        st = self._state
+        if out is None or out.shape != logits_ndhwc.shape or out.dtype != logits_ndhwc.dtype:
+            out = torch.empty_like(logits_ndhwc)
+        scratch = st.partials if bias_grad is not None else None
+        if amp is not None:
+            ops.softmax_dice_focal_bwd_amp(logits_ndhwc, st.labels, st.coef, st.gamma, amp, out, scratch=scratch,
+                                           bias_grad=bias_grad)
+        else:
+            ops.softmax_dice_focal_bwd(logits_ndhwc, st.labels, st.coef, st.gamma, grad_scale, out, scratch=scratch,
+                                       bias_grad=bias_grad)
+        return out
+
+
 # ------------------------------------------------------------------ configuration
-LOSS_NAMES = ("Dice", "DiceCE", "CE")
+LOSS_NAMES = ("Dice", "DiceCE", "CE", "Tversky", "DiceFocal")
 _LOSS_KEYS = {"Dice": ("name", "include_background"),
               "DiceCE": ("name", "include_background", "lambda_dice", "lambda_ce", "class_weights"),
-              "CE": ("name", "lambda_ce", "class_weights")}
+              "CE": ("name", "lambda_ce", "class_weights"),
+              "Tversky": ("name", "include_background", "alpha", "beta", "exponent"),
+              "DiceFocal": ("name", "include_background", "lambda_dice", "lambda_focal", "gamma", "class_weights")}
 
 
 def loss_from_config(cfg, num_classes: Optional[int] = None) -> torch.nn.Module:
     """The loss object of ``optimizer["loss"]``: ``None`` -> ``DiceLoss()``; else a dictionary
     ``{name: Dice | DiceCE | CE, include_background, lambda_dice, lambda_ce, class_weights}`` (``CE`` is
-    ``DiceCE`` with ``lambda_dice = 0``).  Raises ``ValueError`` naming the offending key; touches no device.
+    ``DiceCE`` with ``lambda_dice = 0``), ``{name: Tversky, include_background, alpha, beta, exponent}`` or
+    ``{name: DiceFocal, include_background, lambda_dice, lambda_focal, gamma, class_weights}``.  Raises ``ValueError`` naming the offending key; touches no device.
     ``num_classes`` (when known) checks the length of ``class_weights``."""
     if cfg is None:
         return DiceLoss(to_onehot_y=True, softmax=True)
@@ -283,6 +424,12 @@ def loss_from_config(cfg, num_classes: Optional[int] = None) -> torch.nn.Module:
         raise ValueError("'loss': 'include_background' = false needs more than one class")
     if name == "Dice":
         return DiceLoss(to_onehot_y=True, softmax=True, include_background=include_background)
+    if name == "Tversky":
+        try:
+            return TverskyLoss(include_background=include_background, alpha=cfg.get("alpha", 0.3),
+                               beta=cfg.get("beta", 0.7), exponent=cfg.get("exponent", 1.0))
+        except ValueError as e:
+            raise ValueError(f"'loss': {e}") from e
     weights = cfg.get("class_weights")
     if weights is not None:
         if not isinstance(weights, (list, tuple)):
@@ -290,6 +437,10 @@ def loss_from_config(cfg, num_classes: Optional[int] = None) -> torch.nn.Module:
         if num_classes is not None and len(weights) != num_classes:
             raise ValueError(f"'loss': 'class_weights' has {len(weights)} entries, 'num_classes' is {num_classes}")
     try:
+        if name == "DiceFocal":
+            return DiceFocalLoss(include_background=include_background, lambda_dice=cfg.get("lambda_dice", 1.0),
+                                 lambda_focal=cfg.get("lambda_focal", 1.0), gamma=cfg.get("gamma", 2.0),
+                                 weight=weights)
         return DiceCELoss(include_background=include_background,
                           lambda_dice=0.0 if name == "CE" else cfg.get("lambda_dice", 1.0),
                           lambda_ce=cfg.get("lambda_ce", 1.0), weight=weights)
