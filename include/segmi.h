@@ -711,6 +711,30 @@ int segmi_ensemble_select(const int32_t* const* labels_host, int models, const i
                           const int32_t* model_host, int pairs, int64_t n, int32_t* out,
                           void* stream);
 
+/* ---------------------------------------------------------------- STAPLE label fusion --- */
+/* Multi-label STAPLE (Warfield et al. 2004, as ITK's MultiLabelSTAPLEImageFilter) over `raters` (1 .. 16) label
+ * volumes of n < 2^31 voxels each, read in place as label_bytes in {1 (uint8), 2 (int16), 4 (int32)}, labels in
+ * 0 .. num_classes - 1 (2 .. 64 classes).  DESIGN.md section 22 is the definition: posteriors in fixed point
+ * (Q = 2^24), integer sums S[r][l][s], theta = S / T in f64, the E-step in f64 operation by operation, so the
+ * result is the same bits for every launch shape.  labels_host: HOST table of device pointers.  prior_host
+ * (nullable): HOST f64[num_classes], positive and finite, used as given; NULL = label frequencies over all
+ * raters.  Under a given prior so small that every product of a voxel's E-step rounds to 0, the voxel is dropped:
+ * q = 0 for every label, nothing added to sums, posterior 0, label 0.  Outputs on the device: out (dtype of the inputs), sums i64 [raters][L][L] of the last M-step, prior
+ * f64 [L], posterior (nullable) f32 [L][n] = q / Q of the last E-step.  info_host: HOST i32[4] = iterations,
+ * converged, rater index of an input label outside 0 .. L-1 (-1: none) and that label's value; when such a
+ * label exists it indexes no table, out and posterior are not written and the caller raises.  The stop flag
+ * stays on the device; the host reads the state back once per 16 iterations (ceil(iterations / 16)
+ * synchronisations per call, one more to fetch an offending label). */
+int64_t segmi_staple_workspace_bytes(int raters, int num_classes);
+/* "lds" when the per-workgroup S table of raters * L * L i64 fits the 48 KB LDS table, "global" when the
+ * passes add into the global table directly; "" for shapes segmi_staple refuses.  segmi_staple launches by
+ * the same choice. */
+const char* segmi_staple_table_name(int raters, int num_classes);
+int segmi_staple(const void* const* labels_host, int raters, int label_bytes, int64_t n, int num_classes,
+                 const double* prior_host, int max_iterations, double tolerance, void* out, int64_t* sums,
+                 double* prior, float* posterior, int32_t* info_host, void* workspace, size_t ws_bytes,
+                 void* stream);
+
 /* ---------------------------------------------------------------- evaluation ----------- */
 /* Segmentation evaluation (src/segmantic/seg/evaluation.py:5-125 and scripts/evaluate_segmentations.py).
  * Label volumes are read in place as label_bytes in {1 (uint8), 2 (int16), 4 (int32)}, [d][h][w]

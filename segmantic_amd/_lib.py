@@ -181,6 +181,9 @@ SIGNATURES = {
     "segmi_ensemble_mean": (_i, [_P, _P, _i, _i64, _P, _P]),
     "segmi_ensemble_vote": (_i, [_P, _i, _i64, _P, _P]),
     "segmi_ensemble_select": (_i, [_P, _i, _P, _P, _i, _i64, _P, _P]),
+    "segmi_staple_workspace_bytes": (_i64, [_i, _i]),
+    "segmi_staple_table_name": (C.c_char_p, [_i, _i]),
+    "segmi_staple": (_i, [_P, _i, _i, _i64, _i, _P, _i, _d, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "segmi_kspace_workspace": (_i64, [_i, _i, _i, _i]),
     "segmi_kspace_augment": (_i, [_P, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P]),
     "segmi_degrade_workspace": (_i64, [_i, _i, _i, _i, _i]),

@@ -141,8 +141,14 @@ def ensemble_predict(
     spacing: List[int] = typer.Option([], "--spacing", help="if specified, the image is first resampled"),
     gpu_ids: List[int] = [0],
     datalist_key: str = "test",
+    staple_iterations: int = typer.Option(100, "--staple-iterations", help="staple: most EM iterations"),
+    staple_tolerance: float = typer.Option(1e-5, "--staple-tolerance",
+                                           help="staple: stop when no confusion-matrix entry moves by this much"),
+    save_candidates: Path = typer.Option(None, "--save-candidates",
+                                         help="staple: write the most sensitive model per tissue to this yaml "
+                                              "(the --candidate-yaml of a later select_best run)"),
 ) -> None:
-    """Ensemble-based prediction (reference ``monai_unet_cli.py:212-264``)."""
+    """Ensemble-based prediction (reference ``monai_unet_cli.py:212-264``; ``-cm staple`` is this project's)."""
     datalist = load_decathlon_datalist(datalist_file, data_list_key=datalist_key)
     test_images = [Path(d["image"]) for d in datalist]
     test_labels = [Path(d["label"]) for d in datalist if "label" in d]
@@ -154,7 +160,8 @@ def ensemble_predict(
         model_files=sorted(f for f in models_dir.glob("*.ckpt")), test_images=test_images,
         test_labels=test_labels, tissue_dict=tissue_dict, output_dir=results_dir,
         combination_mode=combination_mode, candidate_per_tissue_path=candidate_per_tissue_path,
-        spacing=spacing, gpu_ids=gpu_ids)
+        spacing=spacing, gpu_ids=gpu_ids, staple_iterations=staple_iterations, staple_tolerance=staple_tolerance,
+        save_candidates=save_candidates)
 
 
 def main():

@@ -1135,6 +1135,78 @@ def ensemble_select(labels, tissue_model: dict, out) -> None:
                                     _stream()), "ensemble_select")
 
 
+# ------------------------------------------------------------------ STAPLE label fusion (staple.hip)
+STAPLE_MAX_RATERS = 16
+STAPLE_MAX_CLASSES = 64
+STAPLE_Q = 1 << 24            # fixed-point unit of the posteriors: sums / STAPLE_Q are expected voxel counts
+STAPLE_MIN_PRIOR = 1e-12      # smallest share of a caller-supplied prior entry in the prior's sum
+
+
+def staple_check_args(raters: int, num_classes, prior, max_iterations, tolerance):
+    """The argument checks of ``staple`` that need no tensor; returns the prior as a host f64 array or None."""
+    if not 1 <= int(raters) <= STAPLE_MAX_RATERS:
+        raise ValueError(f"labels: 1 .. {STAPLE_MAX_RATERS} raters, got {raters}")
+    if int(num_classes) != num_classes or not 2 <= int(num_classes) <= STAPLE_MAX_CLASSES:
+        raise ValueError(f"num_classes must be an integer in 2 .. {STAPLE_MAX_CLASSES}, got {num_classes}")
+    if int(max_iterations) != max_iterations or int(max_iterations) < 1:
+        raise ValueError(f"max_iterations must be an integer >= 1, got {max_iterations}")
+    if not (math.isfinite(float(tolerance)) and float(tolerance) >= 0.0):
+        raise ValueError(f"tolerance must be finite and >= 0, got {tolerance}")
+    if prior is None:
+        return None
+    p = np.ascontiguousarray(np.asarray(prior, dtype=np.float64))
+    if p.shape != (int(num_classes),) or not np.isfinite(p).all():
+        raise ValueError(f"prior must hold num_classes = {int(num_classes)} finite values")
+    total = float(p.sum())
+    if not total > 0.0 or not (p / total >= STAPLE_MIN_PRIOR).all():
+        raise ValueError(f"prior: every entry must be at least {STAPLE_MIN_PRIOR} of the prior's sum")
+    return p
+
+
+def staple_table_name(raters: int, num_classes: int) -> str:
+    """"lds" or "global": where the passes of ``staple`` accumulate S for this shape (the launch's own choice)"""
+    return lib.segmi_staple_table_name(int(raters), int(num_classes)).decode()
+
+
+def staple(labels, num_classes, *, prior=None, max_iterations=100, tolerance=1e-5, return_posterior=False):
+    """Multi-label STAPLE fusion of 1 .. 16 label volumes (device tensors of one dtype among uint8 / int16 / int32,
+    contiguous, of equal shape; labels in 0 .. num_classes - 1).  Returns (labels in the input dtype, sums int64
+    [R, L, L] of the last M-step, prior float64 [L], iterations, converged[, posterior float32 [L, *shape]]).
+    A label outside the range raises ValueError naming the rater and the value."""
+    labels = list(labels)
+    p = staple_check_args(len(labels), num_classes, prior, max_iterations, tolerance)
+    first = labels[0]
+    for r, t in enumerate(labels):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"labels[{r}] is not a tensor")
+        _require_device(t)
+        if t.dtype != first.dtype or t.shape != first.shape or t.device != first.device:
+            raise ValueError(f"labels[{r}]: {t.dtype} {tuple(t.shape)} differs from labels[0]: {first.dtype} "
+                             f"{tuple(first.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"labels[{r}] is not contiguous")
+    lb = label_bytes(first)
+    n = first.numel()
+    if n == 0 or n >= CC_MAX_VOXELS:
+        raise ValueError(f"labels hold 1 .. 2^31 - 1 voxels, got shape {tuple(first.shape)}")
+    R, L = len(labels), int(num_classes)
+    dev = first.device
+    out = torch.empty_like(first)
+    sums = torch.empty((R, L, L), dtype=torch.int64, device=dev)
+    prior_out = torch.empty(L, dtype=torch.float64, device=dev)
+    post = torch.empty((L,) + tuple(first.shape), dtype=torch.float32, device=dev) if return_posterior else None
+    ws = torch.empty(int(lib.segmi_staple_workspace_bytes(R, L)), dtype=torch.uint8, device=dev)
+    tab = (C.c_void_p * R)(*[t.data_ptr() for t in labels])
+    info = (C.c_int32 * 4)()
+    check(lib.segmi_staple(tab, R, lb, n, L, p.ctypes.data_as(C.c_void_p) if p is not None else None,
+                           int(max_iterations), float(tolerance), _ptr(out), _ptr(sums), _ptr(prior_out), _ptr(post),
+                           info, _ptr(ws), ws.numel(), _stream()), "staple")
+    if info[2] >= 0:
+        raise ValueError(f"staple: rater {info[2]} holds the label {info[3]}, outside 0 .. {L - 1}")
+    res = (out, sums, prior_out, int(info[0]), bool(info[1]))
+    return res + (post,) if return_posterior else res
+
+
 # ------------------------------------------------------------------ evaluation (distance.hip)
 def label_bytes(t: torch.Tensor) -> int:
     """label_bytes of a label volume read in place: uint8 -> 1, int16 -> 2, int32 -> 4."""

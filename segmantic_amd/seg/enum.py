@@ -6,3 +6,4 @@ class EnsembleCombination(str, Enum):
     mean = "mean"
     vote = "vote"
     select_best = "select_best"
+    staple = "staple"

@@ -978,18 +978,24 @@ def ensemble_creator(
     combination_mode="select_best",
     candidate_per_tissue_path: Optional[Path] = None,
     gpu_ids: List[int] = [],
+    staple_iterations: int = 100,
+    staple_tolerance: float = 1e-5,
+    save_candidates: Optional[Path] = None,
 ):
     """reference ``:848-1004``: every model predicts each volume with sliding windows of 96^3 at
     overlap 0.5 (``:840-842``); the predictions are combined on the device (``csrc/ensemble.hip``):
     ``mean`` (logits weighted by the ``val_dice`` in the checkpoint file name), ``vote`` (majority
     of the per-model arg-max labels) or ``select_best`` (per tissue, the labels of the model named
-    in ``candidate_per_tissue_path``); the result is carried back through the inverse
-    pre-processing and saved as ``<stem>.nii.gz``."""
+    in ``candidate_per_tissue_path``) or ``staple`` (multi-label STAPLE of the per-model arg-max labels,
+    ``csrc/staple.hip``; its posterior takes the place of the logits); the result is carried back through the
+    inverse pre-processing and saved as ``<stem>.nii.gz``.  ``staple`` also writes ``staple_performance.csv``
+    (sensitivity and PPV per model and tissue, pooled over the run's volumes) to ``output_dir`` and, with
+    ``save_candidates``, the per-tissue best model as the YAML a later ``select_best`` run loads."""
     from ..utils import config
     from .pipeline import PredictPipeline
 
     mode = getattr(combination_mode, "value", combination_mode)
-    if mode not in ("mean", "vote", "select_best"):
+    if mode not in ("mean", "vote", "select_best", "staple"):
         raise ValueError(f"unknown combination mode {combination_mode}")
     if mode == "select_best":
         if candidate_per_tissue_path is None:
@@ -1020,12 +1026,19 @@ def ensemble_creator(
     if mode == "select_best":
         name_model = config.load(config_file=Path(candidate_per_tissue_path))
         label_model = {int(tissue_dict[name]): int(idx) for name, idx in name_model.items()}
+    pooled = None                        # staple: S summed over the volumes
     saved = []
     with torch.no_grad():
         for i, img_path in enumerate(test_images):
             item = pipe.load(img_path, test_labels[i] if use_labels else None)
             x = item["image"][None]
-            if mode == "mean":
+            if mode == "staple":
+                labs = [_argmax_labels(inferer(x, m))[0, 0].contiguous() for m in models]
+                res = ops.staple(labs, num_classes, max_iterations=staple_iterations, tolerance=staple_tolerance,
+                                 return_posterior=True)
+                pooled = res[1].cpu() if pooled is None else pooled + res[1].cpu()
+                combined = res[5]
+            elif mode == "mean":
                 outs = [inferer(x, m).contiguous().clone() for m in models]      # [1,K,D,H,W] views
                 comb = torch.empty_like(outs[0])
                 ops.ensemble_mean(outs, weights, comb)
@@ -1041,6 +1054,15 @@ def ensemble_creator(
             label_vol = pipe.invert_and_discretize(combined, item)
             if output_dir:
                 saved.append(pipe.save(label_vol, item, output_dir))
+    if mode == "staple" and pooled is not None:
+        from . import staple as _staple
+        tissues = tissue_dict or {str(s): s for s in range(num_classes)}
+        if output_dir:
+            _staple.write_performance_csv(
+                _staple.performance_table(pooled.numpy(), [Path(p).name for p in model_files], tissues),
+                output_dir / "staple_performance.csv")
+        if save_candidates:
+            _staple.write_candidates(_staple.best_candidates(pooled.numpy(), tissues), save_candidates)
     return saved
 
 
