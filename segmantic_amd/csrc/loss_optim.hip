@@ -729,217 +729,236 @@ static int dice_dispatch_dt(int dtype, bool fwd, const DiceParams& p, hipStream_
 
 using namespace segmi;
 
-extern "C" {
-
 static inline int dice_real_chunks(const segmi_act* logits) {
   return (int)cdiv64((int64_t)logits->d * logits->h * logits->w, kDiceVox);
 }
 
-// chunks the caller must allocate: the real ones + a tail that holds the f64 stage-1 reduction
-// of reduce_fin.h (65 x [n][3][k] doubles), same scheme as the *_stats_rows() queries
+// ---- the one path of the four losses (LossMode): shared checks, DiceParams, launch
+// per LossMode: the partial rows its forward writes, and the rows its finalisation's LDS bound is computed from
+// (kTversky writes 3 rows and is held to the 4-row bound, so that one batch / class bound holds for every
+// configurable loss)
+struct DiceModeRows { int partial, lds; };
+static constexpr DiceModeRows kDiceModeRows[] = {{3, 3}, {4, 4}, {3, 4}, {4, 4}};
+
+static bool focal_gamma_ok(float gamma) { return gamma == 0.f || (gamma >= 1.f && gamma <= 5.f); }
+
+// the checks every entry point shares, the storage type first.  dlogits: the backward's (null in a forward);
+// ptrs: the entry point's other mandatory pointers are all there
+static int dice_check(const char* name, int dtype, const segmi_act* logits, const segmi_act* dlogits, bool ptrs) {
+  SEGMI_CHECK_ARG(dtype_ok(dtype), "%s: bad dtype", name);
+  SEGMI_CHECK_ARG(act_ok(logits) && ptrs, "%s: bad arguments", name);
+  SEGMI_CHECK_ARG(!dlogits || (act_ok(dlogits) && logits->n == dlogits->n && logits->d == dlogits->d &&
+                               logits->h == dlogits->h && logits->w == dlogits->w && logits->c == dlogits->c),
+                  "%s: bad arguments", name);
+  return SEGMI_OK;
+}
+
+static DiceParams dice_params(const segmi_act* logits, const float* labels) {
+  DiceParams p{};
+  p.logits = logits->data; p.labels = labels;
+  p.n = logits->n; p.k = logits->c; p.ld = logits->ld;
+  p.vox = (int64_t)logits->d * logits->h * logits->w;
+  p.chunks = dice_real_chunks(logits);
+  return p;
+}
+
+// kFocal with gamma = 0 IS Dice + cross-entropy and runs its kernels
+static int dice_launch(int mode, float gamma, int dtype, bool fwd, const DiceParams& p, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == kFocal && gamma == 0.f) mode = kDiceCE;
+  switch (mode) {
+    case kDice: return dice_dispatch_dt<kDice>(dtype, fwd, p, st);
+    case kFocal: return dice_dispatch_dt<kFocal>(dtype, fwd, p, st);
+    case kDiceCE: return dice_dispatch_dt<kDiceCE>(dtype, fwd, p, st);
+    default: return dice_dispatch_dt<kTversky>(dtype, fwd, p, st);
+  }
+}
+
+static void dice_set_fin(DiceParams& p, const DiceFin& f) { p.dfin = f; }
+static void dice_set_fin(DiceParams& p, const DiceCEFin& f) { p.cefin = f; }
+static void dice_set_fin(DiceParams& p, const TverskyFin& f) { p.tfin = f; }
+
+// the forward of `mode` after the entry point's own checks: the loss and the backward coefficients are written by
+// the last workgroup of the launch itself (fin_tail.h) -- rows = chunks, one row = [n][partial rows][k], folded in f64
+// and handed to `fin`
+template <class Fin>
+static int dice_fwd(const char* name, int mode, int dtype, const segmi_act* logits, const float* labels,
+                    float* partials, int include_background, float gamma, const Fin& fin, void* stream) {
+  SEGMI_CHECK_ARG(include_background || logits->c > 1, "%s: include_background = 0 needs more than one class", name);
+  DiceParams p = dice_params(logits, labels);
+  p.partials = partials;
+  p.gamma = gamma;
+  // the finalising workgroup holds one row of doubles in LDS (fin_tail_lds): 64 KB per workgroup
+  const DiceModeRows rows = kDiceModeRows[mode];
+  const size_t lds = fin_tail_lds(p.n * rows.lds * p.k, 256);
+  SEGMI_CHECK_ARG(lds <= 64 * 1024,
+                  "%s: batch %d x %d classes needs %zu bytes of LDS for the finalisation, the limit is 65536 "
+                  "(n * k <= %d)", name, p.n, p.k, lds, (int)((64 * 1024 / sizeof(double) - 4 * 256) / rows.lds));
+  p.ft = fin_tail_make(p.chunks, p.n * rows.partial * p.k, (unsigned)p.chunks * (unsigned)p.n);
+  dice_set_fin(p, fin);
+  return dice_launch(mode, gamma, dtype, true, p, stream);
+}
+
+// amp: the _amp entry points' loss scale on the device (it replaces grad_scale), null in the others
+static int dice_bwd(const char* name, int mode, int dtype, const segmi_act* logits, const float* labels,
+                    const float* coef, float gamma, float grad_scale, const float* amp, const segmi_act* dlogits,
+                    float* scratch, float* bias_grad, void* stream) {
+  if (int rc = dice_check(name, dtype, logits, dlogits, labels && coef && dlogits)) return rc;
+  SEGMI_CHECK_ARG(focal_gamma_ok(gamma), "%s: gamma must be 0 or lie in [1, 5] (got %g)", name, (double)gamma);
+  SEGMI_CHECK_ARG(!bias_grad || scratch, "%s: bias_grad needs the scratch buffer", name);
+  DiceParams p = dice_params(logits, labels);
+  p.coef = coef; p.dlogits = dlogits->data; p.ldd = dlogits->ld;
+  p.grad_scale = grad_scale;
+  p.amp = amp;
+  p.gamma = gamma;
+  if (bias_grad) {   // channel sums of the written gradient, folded by the last workgroup of the launch
+    p.bias_part = scratch;
+    p.ft = fin_tail_make(p.n * p.chunks, p.k, (unsigned)p.chunks * (unsigned)p.n);
+    p.cfin = ChanSumFin{p.k, bias_grad};
+  }
+  // the Tversky backward is the Dice backward on its coefficient pair
+  return dice_launch(mode == kTversky ? (int)kDice : mode, gamma, dtype, false, p, stream);
+}
+
+// the _amp entry points: the scale comes from amp[0]
+static int dice_bwd_amp(const char* name, int mode, int dtype, const segmi_act* logits, const float* labels,
+                        const float* coef, float gamma, const float* amp, const segmi_act* dlogits, float* scratch,
+                        float* bias_grad, void* stream) {
+  SEGMI_CHECK_ARG(amp, "%s: amp state missing", name);
+  return dice_bwd(name, mode, dtype, logits, labels, coef, gamma, 1.f, amp, dlogits, scratch, bias_grad, stream);
+}
+
+// ---- Dice + cross-entropy and Dice + focal: 4-row partials, 3-row coefficients, DiceCEFin.  kFocal: the fourth row
+// holds the focal sums and `lambda2` (named `lambda2_name` in messages) is lambda_focal
+static int dice_ce_fwd(const char* name, const char* lambda2_name, int mode, int dtype, const segmi_act* logits,
+                       const float* labels, float* partials, float* coef, float* loss, float smooth_nr,
+                       float smooth_dr, float lambda_dice, float lambda2, float gamma, int include_background,
+                       const float* class_weight, void* stream) {
+  if (int rc = dice_check(name, dtype, logits, nullptr, labels && partials && coef && loss)) return rc;
+  SEGMI_CHECK_ARG(focal_gamma_ok(gamma), "%s: gamma must be 0 or lie in [1, 5] (got %g)", name, (double)gamma);
+  SEGMI_CHECK_ARG(lambda_dice >= 0.f && lambda2 >= 0.f && __builtin_isfinite(lambda_dice) &&
+                      __builtin_isfinite(lambda2),
+                  "%s: lambda_dice / %s must be finite and >= 0 (got %g, %g)", name, lambda2_name,
+                  (double)lambda_dice, (double)lambda2);
+  return dice_fwd(name, mode, dtype, logits, labels, partials, include_background, gamma,
+                  DiceCEFin{logits->n, logits->c, smooth_nr, smooth_dr, lambda_dice, lambda2, include_background != 0,
+                            class_weight, coef, loss}, stream);
+}
+
+extern "C" {
+
+// chunks the caller must allocate: the real ones + a tail of 2 * kFinScratchRows + 1 rows.  The tail held the f64
+// stage-1 reduction of reduce_fin.h; since the FinTail hand-off nothing reads or writes it.  It stays in the count
+// only so that the buffers existing callers size by it remain large enough.
 int segmi_dice_chunks(const segmi_act* logits) {
   if (!logits) return 0;
   return dice_real_chunks(logits) + 2 * kFinScratchRows + 1;
 }
 
-int segmi_softmax_dice_fwd(int dtype, const segmi_act* logits, const float* labels,
-                           float* partials, float* coef, float* loss, float smooth_nr,
-                           float smooth_dr, void* stream) {
-  SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_dice_fwd: bad dtype");
-  SEGMI_CHECK_ARG(act_ok(logits) && labels && partials && coef && loss, "softmax_dice_fwd: bad arguments");
-  DiceParams p{};
-  p.logits = logits->data; p.labels = labels; p.partials = partials;
-  p.n = logits->n; p.k = logits->c; p.ld = logits->ld;
-  p.vox = (int64_t)logits->d * logits->h * logits->w;
-  p.chunks = dice_real_chunks(logits);
-  hipStream_t st = (hipStream_t)stream;
-  // the loss and the backward coefficients are written by the last workgroup of the launch itself
-  // (fin_tail.h): rows = chunks, one row = [n][3][k]
-  p.ft = fin_tail_make(p.chunks, p.n * 3 * p.k, (unsigned)p.chunks * (unsigned)p.n);
-  p.dfin = DiceFin{p.n, p.k, smooth_nr, smooth_dr, coef, loss};
-  return dice_dispatch_dt<kDice>(dtype, true, p, st);
-}
-
-static int dice_bwd(int mode, int dtype, const segmi_act* logits, const float* labels, const float* coef,
-                    float grad_scale, const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad,
-                    void* stream, float gamma = 0.f) {
-  SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_dice_bwd: bad dtype");
-  SEGMI_CHECK_ARG(act_ok(logits) && act_ok(dlogits) && labels && coef &&
-                      logits->n == dlogits->n && logits->d == dlogits->d &&
-                      logits->h == dlogits->h && logits->w == dlogits->w &&
-                      logits->c == dlogits->c, "softmax_dice_bwd: bad arguments");
-  DiceParams p{};
-  p.logits = logits->data; p.labels = labels; p.coef = coef; p.dlogits = dlogits->data;
-  p.n = logits->n; p.k = logits->c; p.ld = logits->ld; p.ldd = dlogits->ld;
-  p.vox = (int64_t)logits->d * logits->h * logits->w;
-  p.chunks = dice_real_chunks(logits);
-  p.grad_scale = grad_scale;
-  p.amp = amp;
-  p.gamma = gamma;
-  SEGMI_CHECK_ARG(!bias_grad || scratch, "softmax_dice_bwd: bias_grad needs the scratch buffer");
-  p.bias_part = bias_grad ? scratch : nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  if (bias_grad) {   // channel sums of the written gradient, folded by the last workgroup of the launch
-    p.ft = fin_tail_make(p.n * p.chunks, p.k, (unsigned)p.chunks * (unsigned)p.n);
-    p.cfin = ChanSumFin{p.k, bias_grad};
-  }
-  if (mode == kFocal) return dice_dispatch_dt<kFocal>(dtype, false, p, st);
-  return mode == kDiceCE ? dice_dispatch_dt<kDiceCE>(dtype, false, p, st) : dice_dispatch_dt<kDice>(dtype, false, p, st);
-}
-
-int segmi_softmax_dice_bwd(int dtype, const segmi_act* logits, const float* labels,
-                           const float* coef, float grad_scale, const segmi_act* dlogits,
-                           float* scratch, float* bias_grad, void* stream) {
-  return dice_bwd(kDice, dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
-}
-
-int segmi_softmax_dice_bwd_amp(int dtype, const segmi_act* logits, const float* labels,
-                               const float* coef, const float* amp, const segmi_act* dlogits,
-                               float* scratch, float* bias_grad, void* stream) {
-  SEGMI_CHECK_ARG(amp, "softmax_dice_bwd_amp: amp state missing");
-  return dice_bwd(kDice, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
-}
-
-// ---- Dice + cross-entropy: 4-row partials, 3-row coefficients
+// chunks of every other forward: the real ones
 int segmi_dice_ce_chunks(const segmi_act* logits) {
   if (!logits) return 0;
   return dice_real_chunks(logits);
 }
 
+// ---- Dice: 3-row partials, 2-row coefficients
+int segmi_softmax_dice_fwd(int dtype, const segmi_act* logits, const float* labels,
+                           float* partials, float* coef, float* loss, float smooth_nr,
+                           float smooth_dr, void* stream) {
+  const char* name = "softmax_dice_fwd";
+  if (int rc = dice_check(name, dtype, logits, nullptr, labels && partials && coef && loss)) return rc;
+  return dice_fwd(name, kDice, dtype, logits, labels, partials, 1, 0.f,
+                  DiceFin{logits->n, logits->c, smooth_nr, smooth_dr, coef, loss}, stream);
+}
+
+int segmi_softmax_dice_bwd(int dtype, const segmi_act* logits, const float* labels,
+                           const float* coef, float grad_scale, const segmi_act* dlogits,
+                           float* scratch, float* bias_grad, void* stream) {
+  return dice_bwd("softmax_dice_bwd", kDice, dtype, logits, labels, coef, 0.f, grad_scale, nullptr, dlogits, scratch,
+                  bias_grad, stream);
+}
+
+int segmi_softmax_dice_bwd_amp(int dtype, const segmi_act* logits, const float* labels,
+                               const float* coef, const float* amp, const segmi_act* dlogits,
+                               float* scratch, float* bias_grad, void* stream) {
+  return dice_bwd_amp("softmax_dice_bwd_amp", kDice, dtype, logits, labels, coef, 0.f, amp, dlogits, scratch,
+                      bias_grad, stream);
+}
+
+// ---- Dice + cross-entropy: 4-row partials, 3-row coefficients
 int segmi_softmax_dice_ce_fwd(int dtype, const segmi_act* logits, const float* labels, float* partials,
                               float* coef, float* loss, float smooth_nr, float smooth_dr, float lambda_dice,
                               float lambda_ce, int include_background, const float* class_weight, void* stream) {
-  SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_dice_ce_fwd: bad dtype");
-  SEGMI_CHECK_ARG(act_ok(logits) && labels && partials && coef && loss, "softmax_dice_ce_fwd: bad arguments");
-  SEGMI_CHECK_ARG(lambda_dice >= 0.f && lambda_ce >= 0.f && __builtin_isfinite(lambda_dice) &&
-                      __builtin_isfinite(lambda_ce),
-                  "softmax_dice_ce_fwd: lambda_dice / lambda_ce must be finite and >= 0 (got %g, %g)",
-                  (double)lambda_dice, (double)lambda_ce);
-  SEGMI_CHECK_ARG(include_background || logits->c > 1,
-                  "softmax_dice_ce_fwd: include_background = 0 needs more than one class");
-  DiceParams p{};
-  p.logits = logits->data; p.labels = labels; p.partials = partials;
-  p.n = logits->n; p.k = logits->c; p.ld = logits->ld;
-  p.vox = (int64_t)logits->d * logits->h * logits->w;
-  p.chunks = dice_real_chunks(logits);
-  // the finalising workgroup folds one [n][4][k] row of doubles in LDS (fin_tail_lds): 64 KB per workgroup
-  SEGMI_CHECK_ARG(fin_tail_lds(p.n * 4 * p.k, 256) <= 64 * 1024,
-                  "softmax_dice_ce_fwd: batch %d x %d classes needs %zu bytes of LDS for the finalisation, the "
-                  "limit is 65536 (n * k <= 1792)", p.n, p.k, fin_tail_lds(p.n * 4 * p.k, 256));
-  // rows = chunks, one row = [n][4][k]; the last workgroup forms W, the loss and the coefficients in f64
-  p.ft = fin_tail_make(p.chunks, p.n * 4 * p.k, (unsigned)p.chunks * (unsigned)p.n);
-  p.cefin = DiceCEFin{p.n, p.k, smooth_nr, smooth_dr, lambda_dice, lambda_ce, include_background != 0,
-                      class_weight, coef, loss};
-  return dice_dispatch_dt<kDiceCE>(dtype, true, p, (hipStream_t)stream);
+  return dice_ce_fwd("softmax_dice_ce_fwd", "lambda_ce", kDiceCE, dtype, logits, labels, partials, coef, loss,
+                     smooth_nr, smooth_dr, lambda_dice, lambda_ce, 0.f, include_background, class_weight, stream);
 }
 
 int segmi_softmax_dice_ce_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef,
                               float grad_scale, const segmi_act* dlogits, float* scratch, float* bias_grad,
                               void* stream) {
-  return dice_bwd(kDiceCE, dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
+  return dice_bwd("softmax_dice_ce_bwd", kDiceCE, dtype, logits, labels, coef, 0.f, grad_scale, nullptr, dlogits,
+                  scratch, bias_grad, stream);
 }
 
 int segmi_softmax_dice_ce_bwd_amp(int dtype, const segmi_act* logits, const float* labels, const float* coef,
                                   const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad,
                                   void* stream) {
-  SEGMI_CHECK_ARG(amp, "softmax_dice_ce_bwd_amp: amp state missing");
-  return dice_bwd(kDiceCE, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
+  return dice_bwd_amp("softmax_dice_ce_bwd_amp", kDiceCE, dtype, logits, labels, coef, 0.f, amp, dlogits, scratch,
+                      bias_grad, stream);
 }
 
 // ---- Tversky: the Dice forward with TverskyFin; the backward is the Dice backward on its coefficient pair
 int segmi_softmax_tversky_fwd(int dtype, const segmi_act* logits, const float* labels, float* partials, float* coef,
                               float* loss, float smooth_nr, float smooth_dr, float alpha, float beta, float exponent,
                               int include_background, void* stream) {
-  SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_tversky_fwd: bad dtype");
-  SEGMI_CHECK_ARG(act_ok(logits) && labels && partials && coef && loss, "softmax_tversky_fwd: bad arguments");
+  const char* name = "softmax_tversky_fwd";
+  if (int rc = dice_check(name, dtype, logits, nullptr, labels && partials && coef && loss)) return rc;
   SEGMI_CHECK_ARG(alpha >= 0.f && beta >= 0.f && __builtin_isfinite(alpha) && __builtin_isfinite(beta) &&
                       alpha + beta > 0.f,
-                  "softmax_tversky_fwd: alpha / beta must be finite and >= 0 with alpha + beta > 0 (got %g, %g)",
+                  "%s: alpha / beta must be finite and >= 0 with alpha + beta > 0 (got %g, %g)", name,
                   (double)alpha, (double)beta);
-  SEGMI_CHECK_ARG(exponent > 0.f && exponent <= 3.f, "softmax_tversky_fwd: exponent must lie in (0, 3] (got %g)",
+  SEGMI_CHECK_ARG(exponent > 0.f && exponent <= 3.f, "%s: exponent must lie in (0, 3] (got %g)", name,
                   (double)exponent);
-  SEGMI_CHECK_ARG(include_background || logits->c > 1,
-                  "softmax_tversky_fwd: include_background = 0 needs more than one class");
-  DiceParams p{};
-  p.logits = logits->data; p.labels = labels; p.partials = partials;
-  p.n = logits->n; p.k = logits->c; p.ld = logits->ld;
-  p.vox = (int64_t)logits->d * logits->h * logits->w;
-  p.chunks = dice_real_chunks(logits);
-  // the limit of the Dice + cross-entropy finalisation, so that one batch / class bound holds for every configurable loss
-  SEGMI_CHECK_ARG(fin_tail_lds(p.n * 4 * p.k, 256) <= 64 * 1024,
-                  "softmax_tversky_fwd: batch %d x %d classes is beyond the finalisation's LDS (n * k <= 1792)",
-                  p.n, p.k);
-  p.ft = fin_tail_make(p.chunks, p.n * 3 * p.k, (unsigned)p.chunks * (unsigned)p.n);
-  p.tfin = TverskyFin{p.n, p.k, smooth_nr, smooth_dr, alpha, beta, exponent, include_background != 0, coef, loss};
-  return dice_dispatch_dt<kTversky>(dtype, true, p, (hipStream_t)stream);
+  return dice_fwd(name, kTversky, dtype, logits, labels, partials, include_background, 0.f,
+                  TverskyFin{logits->n, logits->c, smooth_nr, smooth_dr, alpha, beta, exponent,
+                             include_background != 0, coef, loss}, stream);
 }
 
 int segmi_softmax_tversky_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef,
                               float grad_scale, const segmi_act* dlogits, float* scratch, float* bias_grad,
                               void* stream) {
-  return dice_bwd(kDice, dtype, logits, labels, coef, grad_scale, nullptr, dlogits, scratch, bias_grad, stream);
+  return dice_bwd("softmax_tversky_bwd", kTversky, dtype, logits, labels, coef, 0.f, grad_scale, nullptr, dlogits,
+                  scratch, bias_grad, stream);
 }
 
 int segmi_softmax_tversky_bwd_amp(int dtype, const segmi_act* logits, const float* labels, const float* coef,
                                   const float* amp, const segmi_act* dlogits, float* scratch, float* bias_grad,
                                   void* stream) {
-  SEGMI_CHECK_ARG(amp, "softmax_tversky_bwd_amp: amp state missing");
-  return dice_bwd(kDice, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch, bias_grad, stream);
+  return dice_bwd_amp("softmax_tversky_bwd_amp", kTversky, dtype, logits, labels, coef, 0.f, amp, dlogits, scratch,
+                      bias_grad, stream);
 }
 
-// ---- Dice + focal: the Dice + cross-entropy passes with the focal factor; gamma = 0 IS Dice + cross-entropy
-static bool focal_gamma_ok(float gamma) { return gamma == 0.f || (gamma >= 1.f && gamma <= 5.f); }
-
+// ---- Dice + focal: the Dice + cross-entropy passes with the focal factor
 int segmi_softmax_dice_focal_fwd(int dtype, const segmi_act* logits, const float* labels, float* partials,
                                  float* coef, float* loss, float smooth_nr, float smooth_dr, float lambda_dice,
                                  float lambda_focal, float gamma, int include_background, const float* class_weight,
                                  void* stream) {
-  SEGMI_CHECK_ARG(focal_gamma_ok(gamma), "softmax_dice_focal_fwd: gamma must be 0 or lie in [1, 5] (got %g)",
-                  (double)gamma);
-  if (gamma == 0.f)
-    return segmi_softmax_dice_ce_fwd(dtype, logits, labels, partials, coef, loss, smooth_nr, smooth_dr, lambda_dice,
-                                     lambda_focal, include_background, class_weight, stream);
-  SEGMI_CHECK_ARG(dtype_ok(dtype), "softmax_dice_focal_fwd: bad dtype");
-  SEGMI_CHECK_ARG(act_ok(logits) && labels && partials && coef && loss, "softmax_dice_focal_fwd: bad arguments");
-  SEGMI_CHECK_ARG(lambda_dice >= 0.f && lambda_focal >= 0.f && __builtin_isfinite(lambda_dice) &&
-                      __builtin_isfinite(lambda_focal),
-                  "softmax_dice_focal_fwd: lambda_dice / lambda_focal must be finite and >= 0 (got %g, %g)",
-                  (double)lambda_dice, (double)lambda_focal);
-  SEGMI_CHECK_ARG(include_background || logits->c > 1,
-                  "softmax_dice_focal_fwd: include_background = 0 needs more than one class");
-  DiceParams p{};
-  p.logits = logits->data; p.labels = labels; p.partials = partials;
-  p.n = logits->n; p.k = logits->c; p.ld = logits->ld;
-  p.vox = (int64_t)logits->d * logits->h * logits->w;
-  p.chunks = dice_real_chunks(logits);
-  p.gamma = gamma;
-  SEGMI_CHECK_ARG(fin_tail_lds(p.n * 4 * p.k, 256) <= 64 * 1024,
-                  "softmax_dice_focal_fwd: batch %d x %d classes needs %zu bytes of LDS for the finalisation, the "
-                  "limit is 65536 (n * k <= 1792)", p.n, p.k, fin_tail_lds(p.n * 4 * p.k, 256));
-  p.ft = fin_tail_make(p.chunks, p.n * 4 * p.k, (unsigned)p.chunks * (unsigned)p.n);
-  // the finalisation is the Dice + cross-entropy one: the fourth row holds the focal sums, lambda_focal is its lambda
-  p.cefin = DiceCEFin{p.n, p.k, smooth_nr, smooth_dr, lambda_dice, lambda_focal, include_background != 0,
-                      class_weight, coef, loss};
-  return dice_dispatch_dt<kFocal>(dtype, true, p, (hipStream_t)stream);
+  return dice_ce_fwd("softmax_dice_focal_fwd", "lambda_focal", kFocal, dtype, logits, labels, partials, coef, loss,
+                     smooth_nr, smooth_dr, lambda_dice, lambda_focal, gamma, include_background, class_weight, stream);
 }
 
 int segmi_softmax_dice_focal_bwd(int dtype, const segmi_act* logits, const float* labels, const float* coef,
                                  float gamma, float grad_scale, const segmi_act* dlogits, float* scratch,
                                  float* bias_grad, void* stream) {
-  SEGMI_CHECK_ARG(focal_gamma_ok(gamma), "softmax_dice_focal_bwd: gamma must be 0 or lie in [1, 5] (got %g)",
-                  (double)gamma);
-  return dice_bwd(gamma == 0.f ? (int)kDiceCE : (int)kFocal, dtype, logits, labels, coef, grad_scale, nullptr, dlogits,
-                  scratch, bias_grad, stream, gamma);
+  return dice_bwd("softmax_dice_focal_bwd", kFocal, dtype, logits, labels, coef, gamma, grad_scale, nullptr, dlogits,
+                  scratch, bias_grad, stream);
 }
 
 int segmi_softmax_dice_focal_bwd_amp(int dtype, const segmi_act* logits, const float* labels, const float* coef,
                                      float gamma, const float* amp, const segmi_act* dlogits, float* scratch,
                                      float* bias_grad, void* stream) {
-  SEGMI_CHECK_ARG(focal_gamma_ok(gamma), "softmax_dice_focal_bwd_amp: gamma must be 0 or lie in [1, 5] (got %g)",
-                  (double)gamma);
-  SEGMI_CHECK_ARG(amp, "softmax_dice_focal_bwd_amp: amp state missing");
-  return dice_bwd(gamma == 0.f ? (int)kDiceCE : (int)kFocal, dtype, logits, labels, coef, 1.f, amp, dlogits, scratch,
-                  bias_grad, stream, gamma);
+  return dice_bwd_amp("softmax_dice_focal_bwd_amp", kFocal, dtype, logits, labels, coef, gamma, amp, dlogits,
+                      scratch, bias_grad, stream);
 }
 
 int segmi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

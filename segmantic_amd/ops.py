@@ -520,114 +520,102 @@ def dice_chunks(logits) -> int:
     return int(lib.segmi_dice_chunks(C.byref(a)))
 
 
-def softmax_dice_fwd(logits, labels, partials, coef, loss, smooth_nr=1e-5, smooth_dr=1e-5):
+def dice_ce_chunks(logits) -> int:
+    """chunks of the partials buffer f32 [chunks, n, rows, k] of a forward (rows: 4 with a cross-entropy / focal
+    term, else 3)"""
     a = act(logits)
-    check(lib.segmi_softmax_dice_fwd(dtype_code(logits), C.byref(a), _ptr(labels),
-                                     _ptr(partials), _ptr(coef), _ptr(loss), smooth_nr,
-                                     smooth_dr, _stream()), "softmax_dice_fwd")
+    return int(lib.segmi_dice_ce_chunks(C.byref(a)))
+
+
+def _class_weight(class_weight, logits):
+    if class_weight is not None and (class_weight.dtype != torch.float32 or class_weight.numel() != logits.shape[4]
+                                     or not class_weight.is_contiguous()):
+        raise ValueError(f"class_weight must be a contiguous float32 tensor of {logits.shape[4]} entries")
+    return _ptr(class_weight)
+
+
+def _loss_fwd(name, logits, labels, partials, coef, loss, *params) -> None:
+    """``segmi_<name>``: ``params`` are the entry point's own arguments between ``loss`` and ``stream``"""
+    a = act(logits)
+    check(getattr(lib, "segmi_" + name)(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(partials), _ptr(coef),
+                                        _ptr(loss), *params, _stream()), name)
+
+
+def _loss_bwd(name, logits, labels, coef, extra, scale, dlogits, scratch, bias_grad) -> None:
+    """``segmi_<name>``: ``scale`` is the ``amp`` state tensor of an ``_amp`` entry point, else ``grad_scale``;
+    ``extra``: the entry point's own arguments in front of it"""
+    a, b = act(logits), act(dlogits)
+    scale = _ptr(scale) if name.endswith("_amp") else float(scale)
+    check(getattr(lib, "segmi_" + name)(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef), *extra, scale,
+                                        C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()), name)
+
+
+def softmax_dice_fwd(logits, labels, partials, coef, loss, smooth_nr=1e-5, smooth_dr=1e-5):
+    _loss_fwd("softmax_dice_fwd", logits, labels, partials, coef, loss, smooth_nr, smooth_dr)
 
 
 def softmax_dice_bwd(logits, labels, coef, grad_scale, dlogits, scratch=None, bias_grad=None) -> None:
     """bias_grad (f32[K], optional): channel sums of dlogits, folded into the same pass; `scratch`
     is then the forward's partials buffer."""
-    a, b = act(logits), act(dlogits)
-    check(lib.segmi_softmax_dice_bwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef),
-                                     float(grad_scale), C.byref(b), _ptr(scratch), _ptr(bias_grad),
-                                     _stream()),
-          "softmax_dice_bwd")
+    _loss_bwd("softmax_dice_bwd", logits, labels, coef, (), grad_scale, dlogits, scratch, bias_grad)
 
 
-def dice_ce_chunks(logits) -> int:
-    """chunks of the 4-row partials buffer f32 [chunks, n, 4, k] of the Dice + cross-entropy forward"""
-    a = act(logits)
-    return int(lib.segmi_dice_ce_chunks(C.byref(a)))
+def softmax_dice_bwd_amp(logits, labels, coef, amp, dlogits, scratch=None, bias_grad=None) -> None:
+    """softmax_dice_bwd with the loss scale read from ``amp[0]`` on the device (f32[3], see "dynamic loss scaling")."""
+    _loss_bwd("softmax_dice_bwd_amp", logits, labels, coef, (), amp, dlogits, scratch, bias_grad)
 
 
 def softmax_dice_ce_fwd(logits, labels, partials, coef, loss, smooth_nr=1e-5, smooth_dr=1e-5, lambda_dice=1.0,
                         lambda_ce=1.0, include_background=True, class_weight=None) -> None:
     """loss = lambda_dice * Dice + lambda_ce * CE (``segmi.h``); ``class_weight``: device f32[K] or None (ones);
     ``coef`` f32[n, 3, k] carries everything the backward needs."""
-    a = act(logits)
-    if class_weight is not None and (class_weight.dtype != torch.float32 or class_weight.numel() != logits.shape[4]
-                                     or not class_weight.is_contiguous()):
-        raise ValueError(f"class_weight must be a contiguous float32 tensor of {logits.shape[4]} entries")
-    check(lib.segmi_softmax_dice_ce_fwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(partials), _ptr(coef),
-                                        _ptr(loss), smooth_nr, smooth_dr, float(lambda_dice), float(lambda_ce),
-                                        int(bool(include_background)), _ptr(class_weight), _stream()),
-          "softmax_dice_ce_fwd")
+    _loss_fwd("softmax_dice_ce_fwd", logits, labels, partials, coef, loss, smooth_nr, smooth_dr, float(lambda_dice),
+              float(lambda_ce), int(bool(include_background)), _class_weight(class_weight, logits))
 
 
 def softmax_dice_ce_bwd(logits, labels, coef, grad_scale, dlogits, scratch=None, bias_grad=None) -> None:
     """as ``softmax_dice_bwd`` with the 3-row coefficients of ``softmax_dice_ce_fwd``"""
-    a, b = act(logits), act(dlogits)
-    check(lib.segmi_softmax_dice_ce_bwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef),
-                                        float(grad_scale), C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
-          "softmax_dice_ce_bwd")
+    _loss_bwd("softmax_dice_ce_bwd", logits, labels, coef, (), grad_scale, dlogits, scratch, bias_grad)
 
 
 def softmax_dice_ce_bwd_amp(logits, labels, coef, amp, dlogits, scratch=None, bias_grad=None) -> None:
     """softmax_dice_ce_bwd with the loss scale read from ``amp[0]`` on the device."""
-    a, b = act(logits), act(dlogits)
-    check(lib.segmi_softmax_dice_ce_bwd_amp(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef), _ptr(amp),
-                                            C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
-          "softmax_dice_ce_bwd_amp")
+    _loss_bwd("softmax_dice_ce_bwd_amp", logits, labels, coef, (), amp, dlogits, scratch, bias_grad)
 
 
 def softmax_tversky_fwd(logits, labels, partials, coef, loss, smooth_nr=1e-5, smooth_dr=1e-5, alpha=0.3, beta=0.7,
                         exponent=1.0, include_background=True) -> None:
     """loss = mean (1 - TI)^exponent (``segmi.h``); ``partials`` f32 [dice_ce_chunks, n, 3, k], ``coef`` f32 [n, 2, k]"""
-    a = act(logits)
-    check(lib.segmi_softmax_tversky_fwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(partials), _ptr(coef),
-                                        _ptr(loss), smooth_nr, smooth_dr, float(alpha), float(beta), float(exponent),
-                                        int(bool(include_background)), _stream()),
-          "softmax_tversky_fwd")
+    _loss_fwd("softmax_tversky_fwd", logits, labels, partials, coef, loss, smooth_nr, smooth_dr, float(alpha),
+              float(beta), float(exponent), int(bool(include_background)))
 
 
 def softmax_tversky_bwd(logits, labels, coef, grad_scale, dlogits, scratch=None, bias_grad=None) -> None:
     """as ``softmax_dice_bwd`` with the coefficient pair of ``softmax_tversky_fwd``"""
-    a, b = act(logits), act(dlogits)
-    check(lib.segmi_softmax_tversky_bwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef),
-                                        float(grad_scale), C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
-          "softmax_tversky_bwd")
+    _loss_bwd("softmax_tversky_bwd", logits, labels, coef, (), grad_scale, dlogits, scratch, bias_grad)
 
 
 def softmax_tversky_bwd_amp(logits, labels, coef, amp, dlogits, scratch=None, bias_grad=None) -> None:
     """softmax_tversky_bwd with the loss scale read from ``amp[0]`` on the device."""
-    a, b = act(logits), act(dlogits)
-    check(lib.segmi_softmax_tversky_bwd_amp(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef), _ptr(amp),
-                                            C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
-          "softmax_tversky_bwd_amp")
+    _loss_bwd("softmax_tversky_bwd_amp", logits, labels, coef, (), amp, dlogits, scratch, bias_grad)
 
 
 def softmax_dice_focal_fwd(logits, labels, partials, coef, loss, smooth_nr=1e-5, smooth_dr=1e-5, lambda_dice=1.0,
                            lambda_focal=1.0, gamma=2.0, include_background=True, class_weight=None) -> None:
     """loss = lambda_dice * Dice + lambda_focal * Focal (``segmi.h``); buffers as ``softmax_dice_ce_fwd``;
     ``gamma = 0`` runs the Dice + cross-entropy kernels."""
-    a = act(logits)
-    if class_weight is not None and (class_weight.dtype != torch.float32 or class_weight.numel() != logits.shape[4]
-                                     or not class_weight.is_contiguous()):
-        raise ValueError(f"class_weight must be a contiguous float32 tensor of {logits.shape[4]} entries")
-    check(lib.segmi_softmax_dice_focal_fwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(partials), _ptr(coef),
-                                           _ptr(loss), smooth_nr, smooth_dr, float(lambda_dice), float(lambda_focal),
-                                           float(gamma), int(bool(include_background)), _ptr(class_weight),
-                                           _stream()),
-          "softmax_dice_focal_fwd")
+    _loss_fwd("softmax_dice_focal_fwd", logits, labels, partials, coef, loss, smooth_nr, smooth_dr, float(lambda_dice),
+              float(lambda_focal), float(gamma), int(bool(include_background)), _class_weight(class_weight, logits))
 
 
 def softmax_dice_focal_bwd(logits, labels, coef, gamma, grad_scale, dlogits, scratch=None, bias_grad=None) -> None:
     """as ``softmax_dice_ce_bwd`` with the forward's ``gamma``"""
-    a, b = act(logits), act(dlogits)
-    check(lib.segmi_softmax_dice_focal_bwd(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef), float(gamma),
-                                           float(grad_scale), C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
-          "softmax_dice_focal_bwd")
+    _loss_bwd("softmax_dice_focal_bwd", logits, labels, coef, (float(gamma),), grad_scale, dlogits, scratch, bias_grad)
 
 
 def softmax_dice_focal_bwd_amp(logits, labels, coef, gamma, amp, dlogits, scratch=None, bias_grad=None) -> None:
     """softmax_dice_focal_bwd with the loss scale read from ``amp[0]`` on the device."""
-    a, b = act(logits), act(dlogits)
-    check(lib.segmi_softmax_dice_focal_bwd_amp(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef), float(gamma),
-                                               _ptr(amp), C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
-          "softmax_dice_focal_bwd_amp")
+    _loss_bwd("softmax_dice_focal_bwd_amp", logits, labels, coef, (float(gamma),), amp, dlogits, scratch, bias_grad)
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, beta1, beta2, eps,
@@ -652,14 +640,6 @@ def adabelief_step(param, grad, exp_avg, exp_avg_var, lr, beta1, beta2, eps, wei
 
 # ------------------------------------------------------------------ dynamic loss scaling
 # amp: f32[3] device tensor {scale, found_inf, skipped steps}; tracker: int32[1]; step: int64[1] (segmi.h)
-def softmax_dice_bwd_amp(logits, labels, coef, amp, dlogits, scratch=None, bias_grad=None) -> None:
-    """softmax_dice_bwd with the loss scale read from ``amp[0]`` on the device."""
-    a, b = act(logits), act(dlogits)
-    check(lib.segmi_softmax_dice_bwd_amp(dtype_code(logits), C.byref(a), _ptr(labels), _ptr(coef), _ptr(amp),
-                                         C.byref(b), _ptr(scratch), _ptr(bias_grad), _stream()),
-          "softmax_dice_bwd_amp")
-
-
 def amp_check_finite(grad, amp) -> None:
     check(lib.segmi_amp_check_finite(_ptr(grad), grad.numel(), _ptr(amp), _stream()), "amp_check_finite")
 

@@ -30,39 +30,70 @@ def as_ndhwc(t: torch.Tensor) -> torch.Tensor:
     return p if p.is_contiguous() else p.contiguous()
 
 
-class _DiceState:
-    """Scratch owned by one loss instance (reused across calls)."""
+class _LossState:
+    """Scratch owned by one loss instance (reused across calls).  ``rows`` / ``coef_rows``: the partial and
+    coefficient rows per (n, k) of the kernels it serves -- (3, 2) for Dice and Tversky, (4, 3) with a
+    cross-entropy or focal term."""
 
-    def __init__(self):
-        self.partials: Optional[torch.Tensor] = None
-        self.coef: Optional[torch.Tensor] = None
+    def __init__(self, rows: int = 3, coef_rows: int = 2):
+        self.rows, self.coef_rows = rows, coef_rows
+        self.partials: Optional[torch.Tensor] = None     # f32 [chunks, n, rows, k], the kernel's layout
+        self.coef: Optional[torch.Tensor] = None         # f32 [n, coef_rows, k]
         self.loss: Optional[torch.Tensor] = None
-        self.dlogits: Optional[torch.Tensor] = None
+        self.labels: Optional[torch.Tensor] = None       # the flattened labels of the last forward
+        self.gamma: Optional[float] = None               # DiceFocalLoss: the gamma of the last forward
+        self.weight: Optional[torch.Tensor] = None       # device copy of the class weights
+        self._weight_key = None
 
-    def ensure(self, logits: torch.Tensor):
-        n, k = logits.shape[0], logits.shape[4]
-        chunks = ops.dice_chunks(logits)
-        dev = logits.device
-        if self.partials is None or self.partials.shape != (n, chunks, 3, k) or self.partials.device != dev:
-            self.partials = torch.empty((n, chunks, 3, k), device=dev)
-            self.coef = torch.empty((n, 2, k), device=dev)
+    def prepare(self, logits: torch.Tensor, labels: torch.Tensor, include_background: bool = True,
+                weight: Optional[Sequence[float]] = None) -> torch.Tensor:
+        """Checks and buffers of one forward on NDHWC ``logits``; returns the flattened f32 labels."""
+        n, k, dev = logits.shape[0], logits.shape[4], logits.device
+        if weight is not None and len(weight) != k:
+            raise ValueError(f"'class_weights' has {len(weight)} entries, the logits have {k} classes")
+        if not include_background and k == 1:
+            raise ValueError("include_background=False needs more than one class")
+        lab = labels.to(dev, torch.float32).contiguous().view(-1)
+        if lab.numel() != logits.numel() // k:
+            raise ValueError("label volume does not match logits")
+        shape = (ops.dice_ce_chunks(logits), n, self.rows, k)
+        if self.partials is None or self.partials.shape != shape or self.partials.device != dev:
+            self.partials = torch.empty(shape, device=dev)
+            self.coef = torch.empty((n, self.coef_rows, k), device=dev)
+        # the device copy follows the values it was made from: a loss's ``weight`` may be edited between calls
+        key = None if weight is None else (tuple(float(v) for v in weight), dev)
+        if key != self._weight_key:
+            if key is not None and any(not math.isfinite(v) or v < 0.0 for v in key[0]):
+                raise ValueError(f"'class_weights' must be finite and >= 0 (got {list(key[0])})")
+            self.weight = None if weight is None else torch.tensor(key[0], dtype=torch.float32, device=dev)
+            self._weight_key = key
         # a fresh scalar per call: callers keep the returned loss tensor
         self.loss = torch.empty(1, device=dev)
+        self.labels = lab
+        return lab
 
 
-def dice_forward(state: _DiceState, logits_ndhwc: torch.Tensor, labels: torch.Tensor,
+def _backward(state: _LossState, bwd, bwd_amp, extra, logits_ndhwc: torch.Tensor, grad_scale: float,
+              out: Optional[torch.Tensor], bias_grad: Optional[torch.Tensor],
+              amp: Optional[torch.Tensor]) -> torch.Tensor:
+    """dlogits of the last forward on ``state`` through ``bwd`` (``bwd_amp`` when ``amp`` is given);
+    ``extra``: the backward op's own arguments in front of the scale."""
+    if out is None or out.shape != logits_ndhwc.shape or out.dtype != logits_ndhwc.dtype:
+        out = torch.empty_like(logits_ndhwc)
+    scratch = state.partials if bias_grad is not None else None
+    op, scale = (bwd, grad_scale) if amp is None else (bwd_amp, amp)
+    op(logits_ndhwc, state.labels, state.coef, *extra, scale, out, scratch=scratch, bias_grad=bias_grad)
+    return out
+
+
+def dice_forward(state: _LossState, logits_ndhwc: torch.Tensor, labels: torch.Tensor,
                  smooth_nr: float, smooth_dr: float) -> torch.Tensor:
-    lab = labels.to(logits_ndhwc.device, torch.float32).contiguous().view(-1)
-    if lab.numel() != logits_ndhwc.numel() // logits_ndhwc.shape[4]:
-        raise ValueError("label volume does not match logits")
-    state.ensure(logits_ndhwc)
-    ops.softmax_dice_fwd(logits_ndhwc, lab, state.partials, state.coef, state.loss, smooth_nr,
-                         smooth_dr)
-    state.labels = lab
+    lab = state.prepare(logits_ndhwc, labels)
+    ops.softmax_dice_fwd(logits_ndhwc, lab, state.partials, state.coef, state.loss, smooth_nr, smooth_dr)
     return state.loss.view(())
 
 
-def dice_backward(state: _DiceState, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
+def dice_backward(state: _LossState, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
                   out: Optional[torch.Tensor] = None,
                   bias_grad: Optional[torch.Tensor] = None,
                   amp: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -70,78 +101,8 @@ def dice_backward(state: _DiceState, logits_ndhwc: torch.Tensor, grad_scale: flo
     that produced the logits (saves that layer a pass over the gradient tensor).  ``amp`` (the f32[3]
     state of a ``GradScaler``): the gradient is scaled by the loss scale held there on the device
     (``grad_scale`` is then ignored)."""
-    if out is None or out.shape != logits_ndhwc.shape or out.dtype != logits_ndhwc.dtype:
-        out = torch.empty_like(logits_ndhwc)
-    scratch = state.partials if bias_grad is not None else None
-    if amp is not None:
-        ops.softmax_dice_bwd_amp(logits_ndhwc, state.labels, state.coef, amp, out, scratch=scratch,
-                                 bias_grad=bias_grad)
-    else:
-        ops.softmax_dice_bwd(logits_ndhwc, state.labels, state.coef, grad_scale, out, scratch=scratch,
-                             bias_grad=bias_grad)
-    return out
-
-
-class _DiceCEState:
-    """Scratch of the Dice + cross-entropy kernels (4-row partials, 3-row coefficients)."""
-
-    def __init__(self):
-        self.partials: Optional[torch.Tensor] = None
-        self.coef: Optional[torch.Tensor] = None
-        self.loss: Optional[torch.Tensor] = None
-        self.labels: Optional[torch.Tensor] = None
-        self.weight: Optional[torch.Tensor] = None
-        self._weight_key = None
-
-    def ensure(self, logits: torch.Tensor, weight: Optional[Sequence[float]]):
-        n, k = logits.shape[0], logits.shape[4]
-        chunks = ops.dice_ce_chunks(logits)
-        dev = logits.device
-        if self.partials is None or self.partials.shape != (chunks, n, 4, k) or self.partials.device != dev:
-            self.partials = torch.empty((chunks, n, 4, k), device=dev)      # the kernel's layout
-            self.coef = torch.empty((n, 3, k), device=dev)
-        # the device copy follows the values it was made from: ``DiceCELoss.weight`` may be edited between calls
-        key = None if weight is None else (tuple(float(v) for v in weight), dev)
-        if key != self._weight_key:
-            if key is not None and any(not math.isfinite(v) or v < 0.0 for v in key[0]):
-                raise ValueError(f"'class_weights' must be finite and >= 0 (got {list(key[0])})")
-            self.weight = None if weight is None else torch.tensor(key[0], dtype=torch.float32, device=dev)
-            self._weight_key = key
-        self.loss = torch.empty(1, device=dev)
-
-
-def dice_ce_forward(state: _DiceCEState, logits_ndhwc: torch.Tensor, labels: torch.Tensor, smooth_nr: float,
-                    smooth_dr: float, lambda_dice: float, lambda_ce: float, include_background: bool,
-                    weight: Optional[Sequence[float]]) -> torch.Tensor:
-    k = logits_ndhwc.shape[4]
-    if weight is not None and len(weight) != k:
-        raise ValueError(f"'class_weights' has {len(weight)} entries, the logits have {k} classes")
-    if not include_background and k == 1:
-        raise ValueError("include_background=False needs more than one class")
-    lab = labels.to(logits_ndhwc.device, torch.float32).contiguous().view(-1)
-    if lab.numel() != logits_ndhwc.numel() // k:
-        raise ValueError("label volume does not match logits")
-    state.ensure(logits_ndhwc, weight)
-    ops.softmax_dice_ce_fwd(logits_ndhwc, lab, state.partials, state.coef, state.loss, smooth_nr, smooth_dr,
-                            lambda_dice, lambda_ce, include_background, state.weight)
-    state.labels = lab
-    return state.loss.view(())
-
-
-def dice_ce_backward(state: _DiceCEState, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
-                     out: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
-                     amp: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``dice_backward`` for the Dice + cross-entropy coefficients (same ``bias_grad`` / ``amp`` meaning)."""
-    if out is None or out.shape != logits_ndhwc.shape or out.dtype != logits_ndhwc.dtype:
-        out = torch.empty_like(logits_ndhwc)
-    scratch = state.partials if bias_grad is not None else None
-    if amp is not None:
-        ops.softmax_dice_ce_bwd_amp(logits_ndhwc, state.labels, state.coef, amp, out, scratch=scratch,
-                                    bias_grad=bias_grad)
-    else:
-        ops.softmax_dice_ce_bwd(logits_ndhwc, state.labels, state.coef, grad_scale, out, scratch=scratch,
-                                bias_grad=bias_grad)
-    return out
+    return _backward(state, ops.softmax_dice_bwd, ops.softmax_dice_bwd_amp, (), logits_ndhwc, grad_scale, out,
+                     bias_grad, amp)
 
 
 class _LossFn(torch.autograd.Function):
@@ -163,15 +124,51 @@ class _LossFn(torch.autograd.Function):
         return (d if bool(gs == 1) else d * gs), None, None
 
 
+# the kernel families: forward op, backward op, _amp backward op, (partial rows, coefficient rows)
+_DICE = (ops.softmax_dice_fwd, ops.softmax_dice_bwd, ops.softmax_dice_bwd_amp, (3, 2))
+_DICE_CE = (ops.softmax_dice_ce_fwd, ops.softmax_dice_ce_bwd, ops.softmax_dice_ce_bwd_amp, (4, 3))
+_TVERSKY = (ops.softmax_tversky_fwd, ops.softmax_tversky_bwd, ops.softmax_tversky_bwd_amp, (3, 2))
+_DICE_FOCAL = (ops.softmax_dice_focal_fwd, ops.softmax_dice_focal_bwd, ops.softmax_dice_focal_bwd_amp, (4, 3))
+
+
 class _FusedLoss(torch.nn.Module):
-    """What the losses share: ``forward`` on logical [N,K,D,H,W] logits (autograd bridge or plain value)
-    over the subclass's ``forward_ndhwc`` / ``backward_ndhwc``."""
+    """What the losses share: ``forward`` on logical [N,K,D,H,W] logits (autograd bridge or plain value) over
+    ``forward_ndhwc`` / ``backward_ndhwc``, the scratch, and the backward.  A subclass validates its parameters,
+    binds its kernel family and writes ``forward_ndhwc``."""
+
+    def _bind(self, family, what: str, to_onehot_y: bool, softmax: bool) -> None:
+        """the subclass's kernel family and a scratch of its row counts"""
+        if not (to_onehot_y and softmax):
+            raise NotImplementedError(f"the HIP {what} kernels implement to_onehot_y=True, softmax=True")
+        self._fwd, self._bwd, self._bwd_amp, rows = family
+        self._state = _LossState(*rows)
 
     def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         """logits [N,K,D,H,W] (float32/bfloat16/float16), labels [N,1,D,H,W] integer-valued."""
         if logits.requires_grad and torch.is_grad_enabled():
             return _LossFn.apply(logits, labels, self)
         return self.forward_ndhwc(as_ndhwc(logits), labels).clone()
+
+    def _run_forward(self, logits_ndhwc: torch.Tensor, labels: torch.Tensor, *params, weight=None) -> torch.Tensor:
+        """the bound forward op on this loss's scratch; ``params``: the op's arguments behind ``loss`` (with
+        ``weight`` the device copy of the class weights is appended)"""
+        st = self._state
+        lab = st.prepare(logits_ndhwc, labels, self.include_background, weight)
+        if weight is not None:
+            params += (st.weight,)
+        self._fwd(logits_ndhwc, lab, st.partials, st.coef, st.loss, self.smooth_nr, self.smooth_dr, *params)
+        return st.loss.view(())
+
+    def _bwd_extra(self) -> tuple:
+        """the backward op's own arguments (in front of the scale)"""
+        return ()
+
+    def backward_ndhwc(self, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
+                       out: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
+                       amp: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dlogits of the last ``forward_ndhwc`` (see ``dice_backward`` for ``bias_grad`` / ``amp``)"""
+        return _backward(self._state, self._bwd, self._bwd_amp, self._bwd_extra(), logits_ndhwc, grad_scale, out,
+                         bias_grad, amp)
 
 
 def _check_lambda(name: str, v) -> float:
@@ -190,6 +187,16 @@ def _check_weight(weight) -> Optional[list]:
     return w
 
 
+def _check_range(name: str, v, ok, what: str) -> float:
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"'{name}' must be a number (got {v!r})") from None
+    if not (math.isfinite(v) and ok(v)):
+        raise ValueError(f"'{name}' must {what} (got {v})")
+    return v
+
+
 class DiceLoss(_FusedLoss):
     """Fused softmax + one-hot + Dice (MONAI defaults: include_background, smooth 1e-5, mean).
     ``include_background=False`` drops class 0 after the softmax (mean over N * (K - 1)); it runs on the
@@ -198,26 +205,15 @@ class DiceLoss(_FusedLoss):
     def __init__(self, to_onehot_y: bool = True, softmax: bool = True, smooth_nr: float = 1e-5,
                  smooth_dr: float = 1e-5, include_background: bool = True):
         super().__init__()
-        if not (to_onehot_y and softmax):
-            raise NotImplementedError("the HIP Dice kernel implements to_onehot_y=True, softmax=True "
-                                      "(the configuration segmantic uses)")
+        self._bind(_DICE if include_background else _DICE_CE, "Dice", to_onehot_y, softmax)
         self.smooth_nr, self.smooth_dr = smooth_nr, smooth_dr
         self.include_background = bool(include_background)
-        self._state = _DiceState() if self.include_background else _DiceCEState()
 
     def forward_ndhwc(self, logits_ndhwc: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         """NDHWC logits (K real classes; the row stride may be larger) -> 0-d loss on the device"""
         if self.include_background:
-            return dice_forward(self._state, logits_ndhwc, labels, self.smooth_nr, self.smooth_dr)
-        return dice_ce_forward(self._state, logits_ndhwc, labels, self.smooth_nr, self.smooth_dr, 1.0, 0.0,
-                               False, None)
-
-    def backward_ndhwc(self, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
-                       out: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
-                       amp: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """dlogits of the last ``forward_ndhwc`` (see ``dice_backward`` for ``bias_grad`` / ``amp``)"""
-        fn = dice_backward if self.include_background else dice_ce_backward
-        return fn(self._state, logits_ndhwc, grad_scale, out, bias_grad=bias_grad, amp=amp)
+            return self._run_forward(logits_ndhwc, labels)
+        return self._run_forward(logits_ndhwc, labels, 1.0, 0.0, False, None)
 
 
 class DiceCELoss(_FusedLoss):
@@ -236,53 +232,16 @@ class DiceCELoss(_FusedLoss):
                  lambda_dice: float = 1.0, lambda_ce: float = 1.0, weight=None, smooth_nr: float = 1e-5,
                  smooth_dr: float = 1e-5):
         super().__init__()
-        if not (to_onehot_y and softmax):
-            raise NotImplementedError("the HIP Dice + cross-entropy kernels implement to_onehot_y=True, "
-                                      "softmax=True")
+        self._bind(_DICE_CE, "Dice + cross-entropy", to_onehot_y, softmax)
         self.include_background = bool(include_background)
         self.lambda_dice = _check_lambda("lambda_dice", lambda_dice)
         self.lambda_ce = _check_lambda("lambda_ce", lambda_ce)
         self.weight = _check_weight(weight)
         self.smooth_nr, self.smooth_dr = smooth_nr, smooth_dr
-        self._state = _DiceCEState()
 
     def forward_ndhwc(self, logits_ndhwc: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        return dice_ce_forward(self._state, logits_ndhwc, labels, self.smooth_nr, self.smooth_dr,
-                               self.lambda_dice, self.lambda_ce, self.include_background, self.weight)
-
-    def backward_ndhwc(self, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
-                       out: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
-                       amp: Optional[torch.Tensor] = None) -> torch.Tensor:
-        return dice_ce_backward(self._state, logits_ndhwc, grad_scale, out, bias_grad=bias_grad, amp=amp)
-
-
-class _TverskyState:
-    """Scratch of the Tversky kernels (3-row partials in the kernel's layout, the Dice backward's coefficient pair)."""
-
-    def __init__(self):
-        self.partials: Optional[torch.Tensor] = None
-        self.coef: Optional[torch.Tensor] = None
-        self.loss: Optional[torch.Tensor] = None
-        self.labels: Optional[torch.Tensor] = None
-
-    def ensure(self, logits: torch.Tensor):
-        n, k = logits.shape[0], logits.shape[4]
-        chunks = ops.dice_ce_chunks(logits)
-        dev = logits.device
-        if self.partials is None or self.partials.shape != (chunks, n, 3, k) or self.partials.device != dev:
-            self.partials = torch.empty((chunks, n, 3, k), device=dev)
-            self.coef = torch.empty((n, 2, k), device=dev)
-        self.loss = torch.empty(1, device=dev)
-
-
-def _check_range(name: str, v, ok, what: str) -> float:
-    try:
-        v = float(v)
-    except (TypeError, ValueError):
-        raise ValueError(f"'{name}' must be a number (got {v!r})") from None
-    if not (math.isfinite(v) and ok(v)):
-        raise ValueError(f"'{name}' must {what} (got {v})")
-    return v
+        return self._run_forward(logits_ndhwc, labels, self.lambda_dice, self.lambda_ce, self.include_background,
+                                 weight=self.weight)
 
 
 class TverskyLoss(_FusedLoss):
@@ -296,8 +255,7 @@ class TverskyLoss(_FusedLoss):
                  alpha: float = 0.3, beta: float = 0.7, exponent: float = 1.0, smooth_nr: float = 1e-5,
                  smooth_dr: float = 1e-5):
         super().__init__()
-        if not (to_onehot_y and softmax):
-            raise NotImplementedError("the HIP Tversky kernels implement to_onehot_y=True, softmax=True")
+        self._bind(_TVERSKY, "Tversky", to_onehot_y, softmax)
         self.include_background = bool(include_background)
         self.alpha = _check_range("alpha", alpha, lambda v: v >= 0.0, "be finite and >= 0")
         self.beta = _check_range("beta", beta, lambda v: v >= 0.0, "be finite and >= 0")
@@ -305,36 +263,9 @@ class TverskyLoss(_FusedLoss):
             raise ValueError(f"'alpha' + 'beta' must be > 0 (got {self.alpha}, {self.beta})")
         self.exponent = _check_range("exponent", exponent, lambda v: 0.0 < v <= 3.0, "lie in (0, 3]")
         self.smooth_nr, self.smooth_dr = smooth_nr, smooth_dr
-        self._state = _TverskyState()
 
     def forward_ndhwc(self, logits_ndhwc: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        k = logits_ndhwc.shape[4]
-        if not self.include_background and k == 1:
-            raise ValueError("include_background=False needs more than one class")
-        lab = labels.to(logits_ndhwc.device, torch.float32).contiguous().view(-1)
-        if lab.numel() != logits_ndhwc.numel() // k:
-            raise ValueError("label volume does not match logits")
-        st = self._state
-        st.ensure(logits_ndhwc)
-        ops.softmax_tversky_fwd(logits_ndhwc, lab, st.partials, st.coef, st.loss, self.smooth_nr, self.smooth_dr,
-                                self.alpha, self.beta, self.exponent, self.include_background)
-        st.labels = lab
-        return st.loss.view(())
-
-    def backward_ndhwc(self, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
-                       out: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
-                       amp: Optional[torch.Tensor] = None) -> torch.Tensor:
-        st = self._state
-        if out is None or out.shape != logits_ndhwc.shape or out.dtype != logits_ndhwc.dtype:
-            out = torch.empty_like(logits_ndhwc)
-        scratch = st.partials if bias_grad is not None else None
-        if amp is not None:
-            ops.softmax_tversky_bwd_amp(logits_ndhwc, st.labels, st.coef, amp, out, scratch=scratch,
-                                        bias_grad=bias_grad)
-        else:
-            ops.softmax_tversky_bwd(logits_ndhwc, st.labels, st.coef, grad_scale, out, scratch=scratch,
-                                    bias_grad=bias_grad)
-        return out
+        return self._run_forward(logits_ndhwc, labels, self.alpha, self.beta, self.exponent, self.include_background)
 
 
 class DiceFocalLoss(_FusedLoss):
@@ -349,47 +280,22 @@ class DiceFocalLoss(_FusedLoss):
                  lambda_dice: float = 1.0, lambda_focal: float = 1.0, gamma: float = 2.0, weight=None,
                  smooth_nr: float = 1e-5, smooth_dr: float = 1e-5):
         super().__init__()
-        if not (to_onehot_y and softmax):
-            raise NotImplementedError("the HIP Dice + focal kernels implement to_onehot_y=True, softmax=True")
+        self._bind(_DICE_FOCAL, "Dice + focal", to_onehot_y, softmax)
         self.include_background = bool(include_background)
         self.lambda_dice = _check_lambda("lambda_dice", lambda_dice)
         self.lambda_focal = _check_lambda("lambda_focal", lambda_focal)
         self.gamma = _check_range("gamma", gamma, lambda v: v == 0.0 or 1.0 <= v <= 5.0, "be 0 or lie in [1, 5]")
         self.weight = _check_weight(weight)
         self.smooth_nr, self.smooth_dr = smooth_nr, smooth_dr
-        self._state = _DiceCEState()
 
     def forward_ndhwc(self, logits_ndhwc: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        k = logits_ndhwc.shape[4]
-        if self.weight is not None and len(self.weight) != k:
-            raise ValueError(f"'class_weights' has {len(self.weight)} entries, the logits have {k} classes")
-        if not self.include_background and k == 1:
-            raise ValueError("include_background=False needs more than one class")
-        lab = labels.to(logits_ndhwc.device, torch.float32).contiguous().view(-1)
-        if lab.numel() != logits_ndhwc.numel() // k:
-            raise ValueError("label volume does not match logits")
-        st = self._state
-        st.ensure(logits_ndhwc, self.weight)
-        ops.softmax_dice_focal_fwd(logits_ndhwc, lab, st.partials, st.coef, st.loss, self.smooth_nr, self.smooth_dr,
-                                   self.lambda_dice, self.lambda_focal, self.gamma, self.include_background, st.weight)
-        st.labels = lab
-        st.gamma = self.gamma           # the backward differentiates the forward that ran
-        return st.loss.view(())
+        loss = self._run_forward(logits_ndhwc, labels, self.lambda_dice, self.lambda_focal, self.gamma,
+                                 self.include_background, weight=self.weight)
+        self._state.gamma = self.gamma           # the backward differentiates the forward that ran
+        return loss
 
-    def backward_ndhwc(self, logits_ndhwc: torch.Tensor, grad_scale: float = 1.0,
-                       out: Optional[torch.Tensor] = None, bias_grad: Optional[torch.Tensor] = None,
-                       amp: Optional[torch.Tensor] = None) -> torch.Tensor:
-        st = self._state
-        if out is None or out.shape != logits_ndhwc.shape or out.dtype != logits_ndhwc.dtype:
-            out = torch.empty_like(logits_ndhwc)
-        scratch = st.partials if bias_grad is not None else None
-        if amp is not None:
-            ops.softmax_dice_focal_bwd_amp(logits_ndhwc, st.labels, st.coef, st.gamma, amp, out, scratch=scratch,
-                                           bias_grad=bias_grad)
-        else:
-            ops.softmax_dice_focal_bwd(logits_ndhwc, st.labels, st.coef, st.gamma, grad_scale, out, scratch=scratch,
-                                       bias_grad=bias_grad)
-        return out
+    def _bwd_extra(self) -> tuple:
+        return (self._state.gamma,)
 
 
 # ------------------------------------------------------------------ configuration

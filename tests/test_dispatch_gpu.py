@@ -157,7 +157,9 @@ DTYPE_ARGS = {
     "segmi_bn_act_bwd_apply_conv": (0,), "segmi_cast_copy": (0, 2), "segmi_nchw_to_ndhwc": (1,),
     "segmi_ndhwc_to_nchw": (0,), "segmi_softmax_dice_fwd": (0,), "segmi_softmax_dice_bwd": (0,),
     "segmi_softmax_dice_bwd_amp": (0,), "segmi_softmax_dice_ce_fwd": (0,), "segmi_softmax_dice_ce_bwd": (0,),
-    "segmi_softmax_dice_ce_bwd_amp": (0,), "segmi_sw_gather": (0, 5), "segmi_sw_scatter_add": (0,),
+    "segmi_softmax_dice_ce_bwd_amp": (0,), "segmi_softmax_tversky_fwd": (0,), "segmi_softmax_tversky_bwd": (0,),
+    "segmi_softmax_tversky_bwd_amp": (0,), "segmi_softmax_dice_focal_fwd": (0,), "segmi_softmax_dice_focal_bwd": (0,),
+    "segmi_softmax_dice_focal_bwd_amp": (0,), "segmi_sw_gather": (0, 5), "segmi_sw_scatter_add": (0,),
     "segmi_sw_blend": (0,), "segmi_argmax": (0,), "segmi_crop_patches": (5,), "segmi_warp_crop_patches": (6,),
     "segmi_elastic_warp_crop_patches": (10,),
 }

@@ -196,6 +196,11 @@ def test_bad_arguments_are_refused_before_any_launch():
         assert "gamma" in _lib.last_error()
         assert _lib.lib.segmi_softmax_dice_focal_bwd(0, a, p, p, gamma, 1.0, a, None, None, None) != 0
         assert "gamma" in _lib.last_error()
+    # the storage type is checked first: an unknown code with a bad gamma is reported as the type
+    assert fo(7, a, p, p, p, p, 1e-5, 1e-5, 1.0, 1.0, 0.5, 1, None, None) != 0
+    assert "dtype" in _lib.last_error()
+    assert _lib.lib.segmi_softmax_dice_focal_bwd(7, a, p, p, 0.5, 1.0, a, None, None, None) != 0
+    assert "dtype" in _lib.last_error()
     assert fo(0, a, p, p, p, p, 1e-5, 1e-5, -1.0, 1.0, 2.0, 1, None, None) != 0
     assert "lambda" in _lib.last_error()
     assert fo(0, a, p, p, p, p, 1e-5, 1e-5, -1.0, 1.0, 0.0, 1, None, None) != 0       # gamma = 0: the DiceCE checks

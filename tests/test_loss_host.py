@@ -126,6 +126,12 @@ def test_bad_arguments_are_refused_before_any_launch():
     big = _lib.Act(0x1000, 29, 2, 2, 2, 64, 64)                       # n * k = 1856 > 1792
     assert fwd(0, big, p, p, p, p, 1e-5, 1e-5, 1.0, 1.0, 1, None, None) != 0
     assert "LDS" in _lib.last_error()
+    # the Dice-only forward folds 3 rows: it refuses beyond its own bound, n * k <= 2389
+    huge = _lib.Act(0x1000, 38, 2, 2, 2, 64, 64)                      # n * k = 2432
+    assert _lib.lib.segmi_softmax_dice_fwd(0, huge, p, p, p, p, 1e-5, 1e-5, None) != 0
+    assert "LDS" in _lib.last_error() and "2389" in _lib.last_error()
+    assert _lib.lib.segmi_softmax_tversky_bwd(0, a, p, p, 1.0, a, None, p, None) != 0
+    assert "softmax_tversky_bwd" in _lib.last_error()                 # reported under the entry point called
     assert _lib.lib.segmi_softmax_dice_ce_bwd_amp(0, a, p, p, None, a, None, None, None) != 0
     assert "amp" in _lib.last_error()
     assert _lib.lib.segmi_softmax_dice_ce_bwd(0, a, p, p, 1.0, a, None, p, None) != 0      # bias_grad without scratch
@@ -174,7 +180,12 @@ def test_yaml_config_becomes_the_loss_object(tmp_path):
     net.optimizer = dict(Net.optimizer)
     assert "loss" not in Net.optimizer
     back = net.configure_loss()
-    assert type(back) is DiceLoss and back.include_background and type(back._state).__name__ == "_DiceState"
+    assert type(back) is DiceLoss and back.include_background
+    # ... bound to the Dice-only entry points and their 3-row / 2-row scratch, not to the _ce ones
+    from segmantic_amd import ops
+    assert (back._fwd, back._bwd, back._bwd_amp) == (ops.softmax_dice_fwd, ops.softmax_dice_bwd,
+                                                     ops.softmax_dice_bwd_amp)
+    assert (back._state.rows, back._state.coef_rows) == (3, 2) and back._state is not loss._state
     assert type(loss_from_config(None)) is DiceLoss
     # names
     ce = loss_from_config({"name": "CE", "class_weights": [1, 2, 3]}, 3)
