@@ -154,7 +154,12 @@ def keep_largest_connected_component(labels: ArrayLike, applied_labels: Optional
         if applied is None:
             mask = (t != 0).to(torch.uint8)
         else:
-            mask = torch.isin(t, torch.tensor(applied, dtype=t.dtype, device=dev)).to(torch.uint8)
+            # an applied label that the volume's storage type cannot hold is absent from the volume
+            info = torch.iinfo(t.dtype)
+            held = [v for v in applied if info.min <= v <= info.max]
+            if not held:
+                return _back(labels, t.clone())
+            mask = torch.isin(t, torch.tensor(held, dtype=t.dtype, device=dev)).to(torch.uint8)
         root = ops.cc_label(mask, c)
         out = ops.cc_keep_largest(t, root, ops.cc_sizes(root), None, False, int(num_components))
     return _back(labels, out)
