@@ -736,6 +736,39 @@ int segmi_staple(const void* const* labels_host, int raters, int label_bytes, in
                  double* prior, float* posterior, int32_t* info_host, void* workspace, size_t ws_bytes,
                  void* stream);
 
+/* ---------------------------------------------------------------- registration ---------- */
+/* Kernels of rigid / affine registration by mutual information (segmantic_amd/image/registration.py).  DESIGN.md
+ * section 23 is the definition.  Volumes are [z][y][x]; `pixel` as in segmi_resample3d (0 f32, 1 u8, 2 i16,
+ * 3 i32, 4 u16).
+ *
+ * Pyramid level: dst [sz/fz][sy/fy][sx/fx] f32 = mean of each fx * fy * fz block (tail samples dropped), the
+ * block summed in f64 with x innermost and z outermost, divided by the count, rounded to f32.  Factors 1 .. 8.
+ * Grid-stride under SEGMI_BIN_SHRINK_GRID_CAP workgroups of 256 (segmi_fixed_bins launches under the same cap). */
+#define SEGMI_BIN_SHRINK_GRID_CAP 2048
+int segmi_bin_shrink(int pixel, const void* src, int sx, int sy, int sz, int fx, int fy, int fz, float* dst,
+                     void* stream);
+/* out[e] = clamp(floor((image[e] - lo) * ((bins-1) / (hi-lo)) + 0.5), 0, bins-1) in f64, as u8; 255 ("ignore this
+ * sample") where mask_mean (nullable, f32, same extent) is below 0.5.  bins in {16, 32, 64}; hi > lo. */
+int segmi_fixed_bins(const float* image, const float* mask_mean, int64_t n, double lo, double hi, int bins,
+                     uint8_t* out, void* stream);
+/* Joint histograms out i64 [candidates][bins][bins] (fixed bin, moving bin) of 1 .. 32 candidates in one launch.
+ * index_maps_host: HOST f64 [candidates][12], fixed index (x,y,z,1) -> continuous moving index (x,y,z).  A fixed
+ * voxel with bin < bins counts for a candidate when 0 <= c <= n-1 on all three moving axes (no default value, no
+ * border clamp); the moving value is the f64 trilinear interpolation of segmi_resample3d; b = clamp((val - mlo) *
+ * mscale, 0, bins-1), i = min(floor(b), bins-2), q = floor((b - i) * 2^16 + 0.5); 2^16 - q goes to cell
+ * (fixed bin, i) and q to (fixed bin, i+1), so sum / 2^16 is the number of samples that counted.  Fixed bins
+ * of bins .. 254 are skipped as 255 is.  out is cleared by the call.
+ * Launch shape: at most SEGMI_JOINT_HIST_GRID_CAP workgroups of 256 stride over the fixed voxels, times one grid
+ * row per group of segmi_joint_histogram_group(bins) candidates (32 / 8 / 2 at 16 / 32 / 64 bins; 0 for any other
+ * bins): a workgroup holds one 32-bit LDS table per candidate of its group, shared by its four waves, and flushes
+ * it into out with device-scope integer atomics every 128 trips of its stride loop (at most 2^31 per counter). */
+#define SEGMI_JOINT_HIST_GRID_CAP 1024
+#define SEGMI_JOINT_HIST_MAX_CANDIDATES 32
+int segmi_joint_histogram_group(int bins);
+int segmi_joint_histogram(const uint8_t* fixed_bins, int fx, int fy, int fz, int pixel, const void* moving, int mx,
+                          int my, int mz, const double* index_maps_host, int candidates, int bins, double mlo,
+                          double mscale, int64_t* out, void* stream);
+
 /* ---------------------------------------------------------------- evaluation ----------- */
 /* Segmentation evaluation (src/segmantic/seg/evaluation.py:5-125 and scripts/evaluate_segmentations.py).
  * Label volumes are read in place as label_bytes in {1 (uint8), 2 (int16), 4 (int32)}, [d][h][w]

@@ -906,6 +906,102 @@ def resample3d_label_gaussian(src: torch.Tensor, out_size_zyx, index_map, sigma=
     return dst
 
 
+# ------------------------------------------------------------------ registration (registration.hip)
+JOINT_HIST_BINS = (16, 32, 64)
+JOINT_HIST_MAX_CANDIDATES = 32        # SEGMI_JOINT_HIST_MAX_CANDIDATES
+JOINT_HIST_GRID_CAP = 1024            # SEGMI_JOINT_HIST_GRID_CAP: workgroups of 256 per candidate group
+JOINT_HIST_UNIT = 1 << 16             # fixed-point weight of one sample: table sums / JOINT_HIST_UNIT count samples
+FIXED_BIN_IGNORE = 255
+
+
+def _pixel_volume(name: str, t: torch.Tensor) -> None:
+    _require_device(t)
+    if t.dim() != 3 or not t.is_contiguous() or t.numel() == 0:
+        raise ValueError(f"{name} expects a contiguous, non-empty [z,y,x] tensor, got shape {tuple(t.shape)}")
+    if t.dtype not in _PIXEL:
+        raise TypeError(f"{name}: unsupported pixel type {t.dtype}")
+
+
+def shrink_factors(shape_zyx, factor: int):
+    """Per-axis (z, y, x) block factors of the pyramid level ``factor``: the factor halved until the axis keeps
+    at least 8 blocks; an axis of extent 1 always gets 1."""
+    if factor not in (1, 2, 4, 8):
+        raise ValueError(f"a pyramid level is 1, 2, 4 or 8, got {factor!r}")
+    out = []
+    for n in shape_zyx:
+        f = int(factor)
+        while f > 1 and (int(n) == 1 or int(n) // f < 8):
+            f //= 2
+        out.append(f)
+    return tuple(out)
+
+
+def bin_shrink(src: torch.Tensor, factors_zyx) -> torch.Tensor:
+    """Block means of src [z,y,x] (any pixel type) as float32 [z // fz, y // fy, x // fx]: each block summed in
+    float64 (x innermost, z outermost), divided by its count; tail samples are dropped."""
+    _pixel_volume("bin_shrink", src)
+    fz, fy, fx = (int(v) for v in factors_zyx)
+    sz, sy, sx = src.shape
+    if min(fz, fy, fx) < 1 or max(fz, fy, fx) > 8 or fz > sz or fy > sy or fx > sx:
+        raise ValueError(f"bin_shrink: factors {tuple(factors_zyx)} must lie in 1 .. 8 and within {tuple(src.shape)}")
+    dst = torch.empty((sz // fz, sy // fy, sx // fx), dtype=torch.float32, device=src.device)
+    check(lib.segmi_bin_shrink(_PIXEL[src.dtype], _ptr(src), sx, sy, sz, fx, fy, fz, _ptr(dst), _stream()),
+          "bin_shrink")
+    return dst
+
+
+def fixed_bins(image: torch.Tensor, lo: float, hi: float, bins: int, mask_mean: Optional[torch.Tensor] = None):
+    """uint8 bin volume of a float32 level image: clamp(floor((v - lo) * ((bins-1)/(hi-lo)) + 0.5), 0, bins-1), and
+    ``FIXED_BIN_IGNORE`` where ``mask_mean`` (float32, same shape) is below 0.5."""
+    _pixel_volume("fixed_bins", image)
+    if image.dtype != torch.float32:
+        raise TypeError(f"fixed_bins: the level image is float32, not {image.dtype}")
+    if bins not in JOINT_HIST_BINS:
+        raise ValueError(f"bins must be one of {JOINT_HIST_BINS}, got {bins!r}")
+    if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+        raise ValueError(f"fixed_bins: constant or non-finite image (lo {lo}, hi {hi})")
+    if mask_mean is not None:
+        _pixel_volume("fixed_bins", mask_mean)
+        if mask_mean.dtype != torch.float32 or mask_mean.shape != image.shape or mask_mean.device != image.device:
+            raise ValueError("fixed_bins: mask_mean must be float32 of the image's shape")
+    out = torch.empty(image.shape, dtype=torch.uint8, device=image.device)
+    check(lib.segmi_fixed_bins(_ptr(image), _ptr(mask_mean), image.numel(), float(lo), float(hi), int(bins), _ptr(out),
+                               _stream()), "fixed_bins")
+    return out
+
+
+def joint_histogram_group(bins: int) -> int:
+    """candidates that one workgroup of ``joint_histogram`` holds in LDS at a time (0: bins not supported)"""
+    return int(lib.segmi_joint_histogram_group(int(bins)))
+
+
+def joint_histogram(fixed_bin: torch.Tensor, moving: torch.Tensor, index_maps, bins: int, mlo: float, mscale: float):
+    """int64 [T, bins, bins] joint histograms (fixed bin, moving bin) of the uint8 bin volume ``fixed_bin`` and
+    ``moving`` (any pixel type) under T <= 32 index maps [T, 3, 4] (fixed index -> continuous moving index), in one
+    launch; weights are fixed point, ``JOINT_HIST_UNIT`` per sample."""
+    _pixel_volume("joint_histogram", fixed_bin)
+    _pixel_volume("joint_histogram", moving)
+    if fixed_bin.dtype != torch.uint8:
+        raise TypeError(f"joint_histogram: fixed bins are uint8, not {fixed_bin.dtype}")
+    if moving.device != fixed_bin.device:
+        raise ValueError("joint_histogram: fixed bins and moving image live on different devices")
+    if bins not in JOINT_HIST_BINS:
+        raise ValueError(f"bins must be one of {JOINT_HIST_BINS}, got {bins!r}")
+    m = np.ascontiguousarray(np.asarray(index_maps, dtype=np.float64))
+    if m.ndim != 3 or m.shape[1:] != (3, 4) or not 1 <= m.shape[0] <= JOINT_HIST_MAX_CANDIDATES:
+        raise ValueError(f"index_maps must be [T, 3, 4] with 1 <= T <= {JOINT_HIST_MAX_CANDIDATES}, got {m.shape}")
+    if not (math.isfinite(mlo) and math.isfinite(mscale)):
+        raise ValueError(f"joint_histogram: mlo / mscale must be finite, got {mlo}, {mscale}")
+    T = m.shape[0]
+    out = torch.empty((T, bins, bins), dtype=torch.int64, device=fixed_bin.device)
+    fz, fy, fx = fixed_bin.shape
+    mz, my, mx = moving.shape
+    check(lib.segmi_joint_histogram(_ptr(fixed_bin), fx, fy, fz, _PIXEL[moving.dtype], _ptr(moving), mx, my, mz,
+                                    m.ctypes.data_as(C.c_void_p), T, int(bins), float(mlo), float(mscale), _ptr(out),
+                                    _stream()), "joint_histogram")
+    return out
+
+
 def normalize_intensity_(x: torch.Tensor) -> torch.Tensor:
     """in-place channel-wise (x-mean)/std of a contiguous f32 [C, ...] tensor."""
     _require_device(x)
