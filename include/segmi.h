@@ -769,6 +769,61 @@ int segmi_joint_histogram(const uint8_t* fixed_bins, int fx, int fy, int fz, int
                           int my, int mz, const double* index_maps_host, int candidates, int bins, double mlo,
                           double mscale, int64_t* out, void* stream);
 
+/* ---------------------------------------------------------------- deformable registration ---------- */
+/* Kernels of B-spline free-form deformable registration (segmantic_amd/image/registration.py, csrc/deformable.hip).
+ * DESIGN.md section 24 is the definition.  A control grid is DEVICE f64 [3][nz][ny][nx]: the displacement in mm
+ * along the fixed image's array axes, components in (x, y, z) order.  segmi_ffd_grid says where a launch's voxels
+ * sit in it: voxel j of an axis of the launch grid l is the full-resolution fixed index i = j f + 0.5 (f - 1) of an
+ * image of extent d (l f <= d, f in 1 .. 8), and the grid of n >= 4 points spans [0, d - 1] with n - 3 spans:
+ * t = (i (n - 3)) / (d - 1), k = min(floor(t), n - 4), cubic B-spline weights of t - k on points k .. k + 3 (an axis
+ * of extent 1: t = 0 and a zero displacement component).  At most SEGMI_FFD_MAX_CONTROL_POINTS points in all.
+ * index_map_host: HOST f64 [12], launch index (x,y,z,1) -> continuous moving index of the affine part;
+ * r_host: HOST f64 [9], row-major, a millimetre of displacement -> moving index units.  `pixel` as segmi_resample3d. */
+typedef struct {
+  int32_t lx, ly, lz; /* the launch's voxel grid */
+  int32_t dx, dy, dz; /* the full-resolution fixed extent */
+  int32_t fx, fy, fz; /* pyramid factors of the launch grid */
+  int32_t nx, ny, nz; /* control points */
+} segmi_ffd_grid;
+#define SEGMI_FFD_MAX_CONTROL_POINTS 32768
+#define SEGMI_FFD_MAX_CANDIDATES 8
+#define SEGMI_FFD_HIST_GRID_CAP 1024     /* workgroups of 256 striding over the voxels, per candidate group */
+#define SEGMI_FFD_GRADIENT_GRID_CAP 8    /* workgroups of 256 striding over the batches of ONE control cell */
+#define SEGMI_FFD_JACOBIAN_GRID_CAP 1024
+#define SEGMI_FFD_WARP_GRID_CAP 1024
+/* one sample adds at most 2^15 * 2^15 * 2^12 = 2^42 to an int64 gradient entry: 2^20 samples leave a bit to spare */
+#define SEGMI_FFD_GRADIENT_MAX_SUPPORT 1048576
+/* segmi_joint_histogram (same table, weights, inside test and LDS flush discipline) for 1 .. 8 candidate control
+ * grids control [candidates][3][nz][ny][nx]: sample position c = index_map (x,y,z,1) + R u.  With all-zero grids the
+ * table equals segmi_joint_histogram's of index_map bit for bit.  out i64 [candidates][bins][bins], cleared here. */
+int segmi_ffd_joint_histogram(const uint8_t* fixed_bins, const segmi_ffd_grid* grid, const double* control,
+                              int candidates, int pixel, const void* moving, int mx, int my, int mz,
+                              const double* index_map_host, const double* r_host, int bins, double mlo, double mscale,
+                              int64_t* out, void* stream);
+/* Integer gradient of the metric by the control values, out i64 [3][nz][ny][nx] (cleared here).  qd: DEVICE i32
+ * [bins][bins-1], |qd| <= 2^15.  Per counted sample whose bin coordinate b is not clamped (0 < b < bins-1):
+ * qd[fixed bin][floor(b)] * G_a * Wq goes to component a of each of the 64 support points, G_a =
+ * rint(clamp((sum_r g_r R[r][a]) * gscale, -1, 1) * 2^15) with g the derivative of the trilinear value by the moving
+ * index, Wq = rint(((w_z w_y) w_x) * 2^12).  One workgroup per control cell and batch stride; one 64-bit atomic per
+ * support point, component and workgroup.  Refuses a grid whose control point's support holds more than
+ * SEGMI_FFD_GRADIENT_MAX_SUPPORT voxels of the launch grid. */
+int segmi_ffd_gradient(const uint8_t* fixed_bins, const segmi_ffd_grid* grid, const double* control, int pixel,
+                       const void* moving, int mx, int my, int mz, const double* index_map_host, const double* r_host,
+                       int bins, double mlo, double mscale, double gscale, const int32_t* qd, int64_t* out,
+                       void* stream);
+/* det(I + du/ds) at every voxel of the launch grid, s in mm along the fixed array axes; inv_spacing_host: HOST f64
+ * [3] = 1 / control spacing in mm (0 on an axis of extent 1).  folded: DEVICE i64 [1], voxels with det <= 0;
+ * min_jacobian: DEVICE f64 [1]; det_map: nullable DEVICE f32 [lz][ly][lx]. */
+int segmi_ffd_jacobian(const segmi_ffd_grid* grid, const double* control, const double* inv_spacing_host,
+                       int64_t* folded, double* min_jacobian, float* det_map, void* stream);
+/* Resample moving onto the full-resolution fixed grid (factors 1, l = d) through the transform: position as in
+ * segmi_ffd_joint_histogram, then segmi_resample3d's inside test, linear (nearest = 0) or nearest (1, half up)
+ * taps, default value and output cast.  dst (nullable): the moving pixel type, [dz][dy][dx].  displacement
+ * (nullable): f32 [3][dz][dy][dx] = direction_host (HOST f64 [9], the fixed direction matrix) times u, in mm. */
+int segmi_ffd_warp(const segmi_ffd_grid* grid, const double* control, int pixel, const void* moving, int mx, int my,
+                   int mz, const double* index_map_host, const double* r_host, int nearest, double default_value,
+                   void* dst, const double* direction_host, float* displacement, void* stream);
+
 /* ---------------------------------------------------------------- evaluation ----------- */
 /* Segmentation evaluation (src/segmantic/seg/evaluation.py:5-125 and scripts/evaluate_segmentations.py).
  * Label volumes are read in place as label_bytes in {1 (uint8), 2 (int16), 4 (int32)}, [d][h][w]

@@ -52,6 +52,12 @@ class Windows(C.Structure):
                 ("offset", C.c_int64 * 32)]
 
 
+class FfdGrid(C.Structure):
+    """``segmi_ffd_grid``: launch grid, full-resolution extent, pyramid factors and control points, each (x, y, z)."""
+
+    _fields_ = [(k, C.c_int32) for k in ("lx", "ly", "lz", "dx", "dy", "dz", "fx", "fy", "fz", "nx", "ny", "nz")]
+
+
 class BnFin(C.Structure):
     """``segmi_bn_fin``: BatchNorm statistics finalised by the launch that produces the partial rows."""
 
@@ -188,6 +194,10 @@ SIGNATURES = {
     "segmi_fixed_bins": (_i, [_P, _P, _i64, _d, _d, _i, _P, _P]),
     "segmi_joint_histogram_group": (_i, [_i]),
     "segmi_joint_histogram": (_i, [_P, _i, _i, _i, _i, _P, _i, _i, _i, _P, _i, _i, _d, _d, _P, _P]),
+    "segmi_ffd_joint_histogram": (_i, [_P, _P, _P, _i, _i, _P, _i, _i, _i, _P, _P, _i, _d, _d, _P, _P]),
+    "segmi_ffd_gradient": (_i, [_P, _P, _P, _i, _P, _i, _i, _i, _P, _P, _i, _d, _d, _d, _P, _P, _P]),
+    "segmi_ffd_jacobian": (_i, [_P, _P, _P, _P, _P, _P, _P]),
+    "segmi_ffd_warp": (_i, [_P, _P, _i, _P, _i, _i, _i, _P, _P, _i, _d, _P, _P, _P, _P]),
     "segmi_kspace_workspace": (_i64, [_i, _i, _i, _i]),
     "segmi_kspace_augment": (_i, [_P, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P]),
     "segmi_degrade_workspace": (_i64, [_i, _i, _i, _i, _i]),

@@ -1002,6 +1002,166 @@ def joint_histogram(fixed_bin: torch.Tensor, moving: torch.Tensor, index_maps, b
     return out
 
 
+# ------------------------------------------------------------------ deformable registration (deformable.hip)
+FFD_MAX_CONTROL_POINTS = 32768        # SEGMI_FFD_MAX_CONTROL_POINTS
+FFD_MAX_CANDIDATES = 8                # SEGMI_FFD_MAX_CANDIDATES
+FFD_HIST_GRID_CAP = 1024              # SEGMI_FFD_HIST_GRID_CAP
+FFD_GRADIENT_GRID_CAP = 8             # SEGMI_FFD_GRADIENT_GRID_CAP: workgroups of 256 per control cell
+FFD_JACOBIAN_GRID_CAP = 1024          # SEGMI_FFD_JACOBIAN_GRID_CAP
+FFD_WARP_GRID_CAP = 1024              # SEGMI_FFD_WARP_GRID_CAP
+FFD_GRADIENT_MAX_SUPPORT = 1 << 20    # SEGMI_FFD_GRADIENT_MAX_SUPPORT: launch voxels under one control point
+FFD_QD_UNIT = 1 << 15                 # the derivative table and the image gradient are quantised to +- 2^15
+FFD_WEIGHT_UNIT = 1 << 12             # a B-spline tensor weight is quantised to 0 .. 2^12
+
+
+def _ffd_grid(name: str, level_zyx, full_zyx, factors_zyx, control: torch.Tensor, candidates: bool):
+    """the ``segmi_ffd_grid`` of a launch and its control tensor, checked: control is float64 [3, nz, ny, nx] (or
+    [T, 3, nz, ny, nx] with ``candidates``)"""
+    from ._lib import FfdGrid
+    _require_device(control)
+    want = 5 if candidates else 4
+    if control.dtype != torch.float64 or control.dim() != want or control.shape[-4] != 3 or not control.is_contiguous():
+        raise ValueError(f"{name}: the control grid is a contiguous float64 {'[T, ' if candidates else '['}3, nz, ny, nx] "
+                         f"tensor, got {control.dtype} {tuple(control.shape)}")
+    nz, ny, nx = (int(v) for v in control.shape[-3:])
+    if min(nz, ny, nx) < 4:
+        raise ValueError(f"{name}: a control grid has at least 4 points per axis, got (nz, ny, nx) = {(nz, ny, nx)}")
+    if nz * ny * nx > FFD_MAX_CONTROL_POINTS:
+        raise ValueError(f"{name}: {nz * ny * nx} control points, at most {FFD_MAX_CONTROL_POINTS}")
+    lz, ly, lx = (int(v) for v in level_zyx)
+    dz, dy, dx = (int(v) for v in full_zyx)
+    fz, fy, fx = (int(v) for v in factors_zyx)
+    if min(fz, fy, fx) < 1 or max(fz, fy, fx) > 8 or lz * fz > dz or ly * fy > dy or lx * fx > dx or min(lz, ly, lx) < 1:
+        raise ValueError(f"{name}: level grid {(lz, ly, lx)} with factors {(fz, fy, fx)} does not fit the fixed "
+                         f"extent {(dz, dy, dx)}")
+    return FfdGrid(lx, ly, lz, dx, dy, dz, fx, fy, fz, nx, ny, nz)
+
+
+def _ffd_maps(name: str, index_map, r):
+    m = np.ascontiguousarray(np.asarray(index_map, dtype=np.float64))
+    rr = np.ascontiguousarray(np.asarray(r, dtype=np.float64))
+    if m.shape != (3, 4) or rr.shape != (3, 3) or not (np.isfinite(m).all() and np.isfinite(rr).all()):
+        raise ValueError(f"{name}: index_map is a finite [3, 4] and r a finite [3, 3] matrix, got {m.shape}, {rr.shape}")
+    return m, rr
+
+
+def ffd_joint_histogram(fixed_bin: torch.Tensor, moving: torch.Tensor, control: torch.Tensor, full_zyx, factors_zyx,
+                        index_map, r, bins: int, mlo: float, mscale: float) -> torch.Tensor:
+    """int64 [T, bins, bins] joint histograms of ``fixed_bin`` (uint8 level volume) and ``moving`` under T <= 8
+    candidate control grids ``control`` float64 [T, 3, nz, ny, nx] (mm along the fixed array axes, components x, y, z)
+    in one launch.  ``full_zyx`` / ``factors_zyx``: the full-resolution fixed extent and the level's block factors;
+    ``index_map`` [3, 4]: level index -> moving index of the affine part; ``r`` [3, 3]: mm of displacement -> moving
+    index units.  All-zero grids give ``joint_histogram(fixed_bin, moving, [index_map], ...)`` bit for bit."""
+    _pixel_volume("ffd_joint_histogram", fixed_bin)
+    _pixel_volume("ffd_joint_histogram", moving)
+    if fixed_bin.dtype != torch.uint8:
+        raise TypeError(f"ffd_joint_histogram: fixed bins are uint8, not {fixed_bin.dtype}")
+    if moving.device != fixed_bin.device or control.device != fixed_bin.device:
+        raise ValueError("ffd_joint_histogram: fixed bins, moving image and control grid live on different devices")
+    if bins not in JOINT_HIST_BINS:
+        raise ValueError(f"bins must be one of {JOINT_HIST_BINS}, got {bins!r}")
+    g = _ffd_grid("ffd_joint_histogram", fixed_bin.shape, full_zyx, factors_zyx, control, True)
+    T = int(control.shape[0])
+    if not 1 <= T <= FFD_MAX_CANDIDATES:
+        raise ValueError(f"ffd_joint_histogram: 1 .. {FFD_MAX_CANDIDATES} candidate grids per call, got {T}")
+    m, rr = _ffd_maps("ffd_joint_histogram", index_map, r)
+    if not (math.isfinite(mlo) and math.isfinite(mscale)):
+        raise ValueError(f"ffd_joint_histogram: mlo / mscale must be finite, got {mlo}, {mscale}")
+    out = torch.empty((T, bins, bins), dtype=torch.int64, device=fixed_bin.device)
+    mz, my, mx = moving.shape
+    check(lib.segmi_ffd_joint_histogram(_ptr(fixed_bin), C.byref(g), _ptr(control), T, _PIXEL[moving.dtype],
+                                        _ptr(moving), mx, my, mz, m.ctypes.data_as(C.c_void_p),
+                                        rr.ctypes.data_as(C.c_void_p), int(bins), float(mlo), float(mscale), _ptr(out),
+                                        _stream()), "ffd_joint_histogram")
+    return out
+
+
+def ffd_gradient(fixed_bin: torch.Tensor, moving: torch.Tensor, control: torch.Tensor, full_zyx, factors_zyx,
+                 index_map, r, bins: int, mlo: float, mscale: float, gscale: float, qd: torch.Tensor) -> torch.Tensor:
+    """int64 [3, nz, ny, nx]: the integer gradient of the metric by the control values of ``control`` float64
+    [3, nz, ny, nx].  ``qd``: int32 [bins, bins - 1], the quantised derivative table (|qd| <= 2^15); ``gscale``
+    scales the image gradient into -1 .. 1.  Units: ``FFD_QD_UNIT`` ^ 2 * ``FFD_WEIGHT_UNIT`` = 2^42."""
+    _pixel_volume("ffd_gradient", fixed_bin)
+    _pixel_volume("ffd_gradient", moving)
+    if fixed_bin.dtype != torch.uint8:
+        raise TypeError(f"ffd_gradient: fixed bins are uint8, not {fixed_bin.dtype}")
+    if bins not in JOINT_HIST_BINS:
+        raise ValueError(f"bins must be one of {JOINT_HIST_BINS}, got {bins!r}")
+    _require_device(qd)
+    if qd.dtype != torch.int32 or tuple(qd.shape) != (bins, bins - 1) or not qd.is_contiguous():
+        raise ValueError(f"ffd_gradient: qd is a contiguous int32 [{bins}, {bins - 1}] tensor, got {qd.dtype} "
+                         f"{tuple(qd.shape)}")
+    if not {moving.device, control.device, qd.device} == {fixed_bin.device}:
+        raise ValueError("ffd_gradient: the tensors live on different devices")
+    g = _ffd_grid("ffd_gradient", fixed_bin.shape, full_zyx, factors_zyx, control, False)
+    support = 1
+    for l, n in zip(fixed_bin.shape, control.shape[-3:]):
+        support *= min(int(l), -(-4 * int(l) // (int(n) - 3)) + 1)
+    if support > FFD_GRADIENT_MAX_SUPPORT:
+        raise ValueError(f"ffd_gradient: {support} samples under one control point's support, at most "
+                         f"{FFD_GRADIENT_MAX_SUPPORT}: use more control points (a smaller grid_spacing)")
+    m, rr = _ffd_maps("ffd_gradient", index_map, r)
+    if not (math.isfinite(mlo) and math.isfinite(mscale) and math.isfinite(gscale)):
+        raise ValueError(f"ffd_gradient: mlo / mscale / gscale must be finite, got {mlo}, {mscale}, {gscale}")
+    out = torch.empty(tuple(control.shape), dtype=torch.int64, device=fixed_bin.device)
+    mz, my, mx = moving.shape
+    check(lib.segmi_ffd_gradient(_ptr(fixed_bin), C.byref(g), _ptr(control), _PIXEL[moving.dtype], _ptr(moving), mx,
+                                 my, mz, m.ctypes.data_as(C.c_void_p), rr.ctypes.data_as(C.c_void_p), int(bins),
+                                 float(mlo), float(mscale), float(gscale), _ptr(qd), _ptr(out), _stream()),
+          "ffd_gradient")
+    return out
+
+
+def ffd_jacobian(control: torch.Tensor, level_zyx, full_zyx, factors_zyx, inv_spacing_xyz, want_map: bool = False):
+    """(folded, min_jacobian, map): the number of voxels of the level grid where det(I + du/ds) <= 0, the smallest
+    determinant, and (``want_map``) the determinants as float32 [lz, ly, lx] (else None).  ``inv_spacing_xyz``:
+    1 / control spacing in mm per axis (x, y, z), 0 on an axis of extent 1.  The two numbers are device tensors
+    (int64 [1], float64 [1]): the caller reads them back."""
+    g = _ffd_grid("ffd_jacobian", level_zyx, full_zyx, factors_zyx, control, False)
+    ih = np.ascontiguousarray(np.asarray(inv_spacing_xyz, dtype=np.float64))
+    if ih.shape != (3,) or not np.isfinite(ih).all():
+        raise ValueError(f"ffd_jacobian: inv_spacing_xyz holds three finite numbers, got {inv_spacing_xyz!r}")
+    folded = torch.empty(1, dtype=torch.int64, device=control.device)
+    lowest = torch.empty(1, dtype=torch.float64, device=control.device)
+    dmap = (torch.empty(tuple(int(v) for v in level_zyx), dtype=torch.float32, device=control.device)
+            if want_map else None)
+    check(lib.segmi_ffd_jacobian(C.byref(g), _ptr(control), ih.ctypes.data_as(C.c_void_p), _ptr(folded), _ptr(lowest),
+                                 _ptr(dmap), _stream()), "ffd_jacobian")
+    return folded, lowest, dmap
+
+
+def ffd_warp(moving: Optional[torch.Tensor], control: torch.Tensor, full_zyx, index_map, r, nearest: bool = False,
+             default: float = 0.0, direction=None, want_displacement: bool = False):
+    """(warped, displacement): ``moving`` resampled onto the full-resolution fixed grid ``full_zyx`` through the
+    transform (its pixel type; None when ``moving`` is None), and (``want_displacement``) the dense displacement
+    float32 [3, z, y, x] in mm along the physical axes, ``direction`` [3, 3] being the fixed direction matrix."""
+    g = _ffd_grid("ffd_warp", full_zyx, full_zyx, (1, 1, 1), control, False)
+    if moving is None and not want_displacement:
+        raise ValueError("ffd_warp: neither a moving image nor a displacement field was asked for")
+    m, rr = _ffd_maps("ffd_warp", index_map, r)
+    mx = my = mz = 0
+    pixel, dst = 0, None
+    if moving is not None:
+        _pixel_volume("ffd_warp", moving)
+        if moving.device != control.device:
+            raise ValueError("ffd_warp: moving image and control grid live on different devices")
+        mz, my, mx = moving.shape
+        pixel = _PIXEL[moving.dtype]
+        dst = torch.empty(tuple(int(v) for v in full_zyx), dtype=moving.dtype, device=control.device)
+    dd, disp = None, None
+    if want_displacement:
+        dd = np.ascontiguousarray(np.asarray(direction, dtype=np.float64))
+        if dd.shape != (3, 3) or not np.isfinite(dd).all():
+            raise ValueError("ffd_warp: a displacement field needs the finite [3, 3] fixed direction matrix")
+        disp = torch.empty((3,) + tuple(int(v) for v in full_zyx), dtype=torch.float32, device=control.device)
+    if not math.isfinite(default):
+        raise ValueError(f"ffd_warp: default must be finite, got {default}")
+    check(lib.segmi_ffd_warp(C.byref(g), _ptr(control), pixel, _ptr(moving), mx, my, mz, m.ctypes.data_as(C.c_void_p),
+                             rr.ctypes.data_as(C.c_void_p), 1 if nearest else 0, float(default), _ptr(dst),
+                             None if dd is None else dd.ctypes.data_as(C.c_void_p), _ptr(disp), _stream()), "ffd_warp")
+    return dst, disp
+
+
 def normalize_intensity_(x: torch.Tensor) -> torch.Tensor:
     """in-place channel-wise (x-mean)/std of a contiguous f32 [C, ...] tensor."""
     _require_device(x)

@@ -1,0 +1,368 @@
+"""B-spline deformable registration on the GPU against the numpy restatement in
+tests/helpers/deformable_ref.py.  Every comparison is exact unless it says otherwise: the kernels' cross-lane sums
+are integers and every floating-point step is specified operation by operation."""
+import functools
+import importlib.util
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent / "helpers"))
+import deformable_ref as D  # noqa: E402
+import registration_ref as R  # noqa: E402
+
+from segmantic_amd import ops  # noqa: E402
+from segmantic_amd.image import processing as P  # noqa: E402
+from segmantic_amd.image import registration as reg  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ROOT = Path(__file__).resolve().parent.parent
+DEV = "cuda:0"
+F_SHAPE, M_SHAPE = (17, 19, 21), (20, 18, 23)           # fixed 21 x 19 x 17, moving 23 x 18 x 20 (x, y, z)
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _oblique_map():
+    """level index -> moving index: a small rotation about two axes, anisotropic scale, a shift"""
+    a = R.rot_z(0.07) @ R.rot_x(-0.05) @ np.diag([1.04, 0.93, 1.1])
+    m = np.zeros((3, 4))
+    m[:, :3] = a
+    m[:, 3] = (0.8, -0.4, 1.3)
+    return m
+
+
+R_MATRIX = R.rot_z(0.07) @ R.rot_x(-0.05) @ np.diag([0.9, 1.1, 1.0])
+
+
+@functools.lru_cache(maxsize=None)
+def _case(level=F_SHAPE, factors=(1, 1, 1), n_xyz=(7, 5, 6), T=3, bins=32, dtype="float32", amplitude=2.5, masked=True,
+          mshape=M_SHAPE, seed=3):
+    rng = np.random.default_rng(seed)
+    full = tuple(l * f + (1 if f > 1 and k != 1 else 0) for k, (l, f) in enumerate(zip(level, factors)))
+    fbin = rng.integers(0, bins, level).astype(np.uint8)
+    if masked:
+        fbin[rng.random(level) < 0.15] = D.IGNORE
+    # a smooth moving image: the gradient test needs samples off the bin edges, the histogram does not care
+    zz, yy, xx = np.meshgrid(*[np.arange(s, dtype=np.float64) for s in mshape], indexing="ij")
+    smooth = 60.0 * np.sin(0.31 * xx + 0.2) * np.cos(0.27 * yy) + 45.0 * np.sin(0.23 * zz + 0.11 * xx) + 4.0 * rng.normal(size=mshape)
+    if dtype == "float32":
+        mov = smooth.astype(np.float32)
+    else:
+        mov = np.rint(smooth * 20).astype(np.int16) if dtype == "int16" else np.rint(smooth + 120).clip(0, 255).astype(np.uint8)
+    phis = rng.uniform(-amplitude, amplitude, (T, 3) + tuple(reversed(n_xyz)))
+    m, r = _oblique_map(), R_MATRIX.copy()
+    if level[0] == 1:                                       # a 2-D image as a depth-1 volume: nothing moves along z
+        m[2] = (0.0, 0.0, 1.0, 0.0)
+        m[:2, 2] = 0.0
+        r[2, :] = 0.0
+        r[:, 2] = 0.0
+    mlo, mhi = float(mov.min()), float(mov.max())
+    return fbin, mov, phis, full, m, r, mlo, (bins - 1) / (mhi - mlo), mhi - mlo
+
+
+# ---------------------------------------------------------------------------- joint histogram
+@pytest.mark.parametrize("bins", [16, 32, 64])
+@pytest.mark.parametrize("dtype", ["float32", "int16"])
+def test_zero_grids_give_the_affine_joint_histogram(bins, dtype):
+    fbin, mov, phis, full, m, r, mlo, mscale, _ = _case(bins=bins, dtype=dtype, T=2)
+    zero = torch.zeros(phis.shape, dtype=torch.float64, device=DEV)
+    got = ops.ffd_joint_histogram(_dev(fbin), _dev(mov), zero, full, (1, 1, 1), m, r, bins, mlo, mscale)
+    want = ops.joint_histogram(_dev(fbin), _dev(mov), np.stack([m, m]), bins, mlo, mscale)
+    assert int(want.sum()) > 0 and torch.equal(got, want)
+
+
+@pytest.mark.parametrize("T", [1, 3, 8])
+@pytest.mark.parametrize("n_xyz", [(4, 4, 4), (7, 5, 6)])
+def test_joint_histogram_under_candidate_grids_equals_the_restatement(T, n_xyz):
+    fbin, mov, phis, full, m, r, mlo, mscale, _ = _case(n_xyz=n_xyz, T=T)
+    want = D.ffd_joint_histogram(fbin, mov, phis, full, (1, 1, 1), m, r, 32, mlo, mscale)
+    got = ops.ffd_joint_histogram(_dev(fbin), _dev(mov), _dev(phis), full, (1, 1, 1), m, r, 32, mlo, mscale)
+    assert np.array_equal(got.cpu().numpy(), want)
+    usable = int((fbin != D.IGNORE).sum())
+    counted = want.sum(axis=(1, 2)) // D.UNIT
+    assert (counted > 0).all() and (counted < usable).all()          # the field pushes some samples outside
+    assert len({t.tobytes() for t in want}) == T                     # the candidates differ
+
+
+def test_joint_histogram_at_a_pyramid_level_and_in_2d():
+    for kwargs in (dict(factors=(2, 2, 2), T=2), dict(level=(1, 19, 21), mshape=(1, 18, 23), n_xyz=(7, 5, 4), T=2),
+                   dict(factors=(1, 2, 4), n_xyz=(5, 4, 4), T=2, dtype="uint8", bins=16)):
+        fbin, mov, phis, full, m, r, mlo, mscale, _ = _case(**kwargs)
+        ff, bins = kwargs.get("factors", (1, 1, 1)), kwargs.get("bins", 32)
+        want = D.ffd_joint_histogram(fbin, mov, phis, full, ff, m, r, bins, mlo, mscale)
+        got = ops.ffd_joint_histogram(_dev(fbin), _dev(mov), _dev(phis), full, ff, m, r, bins, mlo, mscale)
+        assert want.sum() > 0 and np.array_equal(got.cpu().numpy(), want)
+        if max(ff) > 1:                                              # the 0.5 (F - 1) offset is seen
+            off = D.ffd_joint_histogram(fbin, mov, phis, full, ff, m, r, bins, mlo, mscale, fault="no_level_offset")
+            assert not np.array_equal(off, want)
+
+
+BIG = (41, 80, 81)                                                   # 265 680 voxels > 1024 * 256, ragged tail
+
+
+def test_joint_histogram_beyond_one_pass_of_its_grid():
+    assert np.prod(BIG) > ops.FFD_HIST_GRID_CAP * 256 and np.prod(BIG) % 256
+    fbin, mov, phis, full, m, r, mlo, mscale, _ = _case(level=BIG, n_xyz=(6, 5, 4), T=1, mshape=(44, 78, 85), seed=5)
+    want = D.ffd_joint_histogram(fbin, mov, phis, full, (1, 1, 1), m, r, 32, mlo, mscale)
+    got = ops.ffd_joint_histogram(_dev(fbin), _dev(mov), _dev(phis), full, (1, 1, 1), m, r, 32, mlo, mscale)
+    assert np.array_equal(got.cpu().numpy(), want)
+
+
+def test_joint_histogram_past_the_counter_flush_interval():
+    """SEGMI_FFD_HIST_GRID_CAP * 65 536 voxels plus a ragged remainder, every sample in one cell: each workgroup adds
+    more than 2^32 to one 32-bit LDS counter, which only the flush interval keeps exact.  The table is analytic."""
+    n = ops.FFD_HIST_GRID_CAP * 65536 + 12345
+    fbin = torch.full((1, 1, n), 5, dtype=torch.uint8, device=DEV)
+    mov = torch.full((1, 1, n), 3, dtype=torch.uint8, device=DEV)
+    ident = np.zeros((3, 4))
+    ident[0, 0] = ident[1, 1] = ident[2, 2] = 1.0
+    zero = torch.zeros((2, 3, 4, 4, 4), dtype=torch.float64, device=DEV)
+    got = ops.ffd_joint_histogram(fbin, mov, zero, (1, 1, n), (1, 1, 1), ident, np.eye(3), 16, 0.0, 1.0)
+    want = torch.zeros((2, 16, 16), dtype=torch.int64)
+    want[:, 5, 3] = n * D.UNIT
+    assert n * D.UNIT > (1 << 32) * ops.FFD_HIST_GRID_CAP and torch.equal(got.cpu(), want)
+
+
+# ---------------------------------------------------------------------------- gradient
+def _gradient_case(**kwargs):
+    fbin, mov, phis, full, m, r, mlo, mscale, mrange = _case(**kwargs)
+    ff, bins = kwargs.get("factors", (1, 1, 1)), kwargs.get("bins", 32)
+    hist = D.ffd_joint_histogram(fbin, mov, phis[:1], full, ff, m, r, bins, mlo, mscale)[0]
+    _, _, dmax, qd = D.derivative_table(hist, "nmi")
+    gscale = 1.0 / (mrange * float(np.abs(r).sum(axis=1).max()))
+    want = D.ffd_gradient(fbin, mov, phis[0], full, ff, m, r, bins, mlo, mscale, gscale, qd)
+    got = ops.ffd_gradient(_dev(fbin), _dev(mov), _dev(phis[0]), full, ff, m, r, bins, mlo, mscale, gscale, _dev(qd))
+    return want, got, (fbin, mov, phis, full, ff, m, r, bins, mlo, mscale, gscale, qd)
+
+
+@pytest.mark.parametrize("kwargs", [dict(), dict(n_xyz=(4, 4, 4)), dict(factors=(2, 2, 2), dtype="int16"),
+                                    dict(level=(1, 19, 21), mshape=(1, 18, 23), n_xyz=(7, 5, 4), dtype="uint8"),
+                                    dict(bins=64, n_xyz=(9, 8, 7))], ids=["7x5x6", "one-span", "level2-i16", "2d-u8", "64bins"])
+def test_gradient_equals_the_restatement(kwargs):
+    want, got, args = _gradient_case(**kwargs)
+    assert got.dtype == torch.int64 and np.array_equal(got.cpu().numpy(), want)
+    flat = kwargs.get("level", F_SHAPE)[0] == 1
+    # control points on the grid's corners take part (in 2-D the fourth z tap has the weight 0 at t = 0)
+    assert want[0, 0, 0, 0] != 0 and want[0, 2 if flat else -1, -1, -1] != 0
+    if flat:
+        assert not want[2].any()                                     # no z displacement in 2-D
+    fbin, mov, phis, full, ff, m, r, bins, mlo, mscale, gscale, qd = args
+    again = ops.ffd_gradient(_dev(fbin), _dev(mov), _dev(phis[0]), full, ff, m, r, bins, mlo, mscale, gscale, _dev(qd))
+    assert torch.equal(got, again)                                   # integer sums: the same bits every launch
+
+
+def test_gradient_of_a_support_without_samples_is_zero():
+    fbin, mov, phis, full, m, r, mlo, mscale, mrange = _case(n_xyz=(9, 5, 6))
+    fbin = fbin.copy()
+    fbin[:, :, 7:] = D.IGNORE                                # x >= 7 of 21: spans 2 .. 5 of 6 hold no sample
+    hist = D.ffd_joint_histogram(fbin, mov, phis[:1], full, (1, 1, 1), m, r, 32, mlo, mscale)[0]
+    _, _, _, qd = D.derivative_table(hist, "nmi")
+    gscale = 1.0 / (mrange * float(np.abs(r).sum(axis=1).max()))
+    want = D.ffd_gradient(fbin, mov, phis[0], full, (1, 1, 1), m, r, 32, mlo, mscale, gscale, qd)
+    got = ops.ffd_gradient(_dev(fbin), _dev(mov), _dev(phis[0]), full, (1, 1, 1), m, r, 32, mlo, mscale, gscale, _dev(qd))
+    assert np.array_equal(got.cpu().numpy(), want)
+    assert not want[:, :, :, 6:].any() and want[:, :, :, :4].any()
+
+
+def test_gradient_beyond_one_pass_over_a_cell():
+    """one span over 13^3 voxels: the cell holds 2197 > SEGMI_FFD_GRADIENT_GRID_CAP * 256 samples, with a ragged tail"""
+    assert 13 ** 3 > ops.FFD_GRADIENT_GRID_CAP * 256
+    want, got, _ = _gradient_case(level=(13, 13, 13), n_xyz=(4, 4, 4), mshape=(15, 14, 16), masked=False, amplitude=1.0)
+    assert want.any() and np.array_equal(got.cpu().numpy(), want)
+
+
+# ---------------------------------------------------------------------------- Jacobian
+def _inv_h(full, n_xyz, spacing=(0.9, 1.0, 1.2)):
+    return [0.0 if v == 0.0 else 1.0 / v for v in D.control_spacing(tuple(reversed(full)), spacing, n_xyz)]
+
+
+@pytest.mark.parametrize("kwargs", [dict(), dict(factors=(2, 2, 2)), dict(level=(1, 19, 21), n_xyz=(7, 5, 4)),
+                                    dict(level=BIG, n_xyz=(6, 5, 4))], ids=["7x5x6", "level2", "2d", "beyond-the-grid-cap"])
+def test_jacobian_equals_the_restatement(kwargs):
+    level, n_xyz, ff = kwargs.get("level", F_SHAPE), kwargs.get("n_xyz", (7, 5, 6)), kwargs.get("factors", (1, 1, 1))
+    _, _, phis, full, *_ = _case(**kwargs)
+    inv_h = _inv_h(full, n_xyz)
+    folded, lowest, dmap = D.jacobian(phis[0], level, full, ff, inv_h)
+    gf, gl, gm = ops.ffd_jacobian(_dev(phis[0]), level, full, ff, inv_h, want_map=True)
+    assert int(gf.item()) == folded == int((dmap <= 0).sum())
+    assert abs(float(gl.item()) - lowest) <= 1e-12 and np.abs(gm.cpu().numpy().astype(np.float64) - dmap).max() <= 1e-6
+    assert float(gl.item()) == lowest and np.array_equal(gm.cpu().numpy(), dmap.astype(np.float32))
+    for factor, folds in ((0.05, False), (8.0, True)):
+        scaled = phis[0] * factor
+        folded, lowest, _ = D.jacobian(scaled, level, full, ff, inv_h)
+        gf, gl, none = ops.ffd_jacobian(_dev(scaled), level, full, ff, inv_h)
+        assert none is None and int(gf.item()) == folded and float(gl.item()) == lowest and lowest < 1
+        assert (folded > 0) == (lowest <= 0)
+        if level != BIG:                                             # the wide spans of BIG take 8 x 2.5 mm without a fold
+            assert (folded > 0) == folds
+
+
+def test_a_fold_is_detected():
+    """an adjacent control difference of twice the control spacing along x"""
+    full, n_xyz = F_SHAPE, (7, 5, 6)
+    h = D.control_spacing(tuple(reversed(full)), (1.0, 1.0, 1.0), n_xyz)
+    phi = np.zeros((3, 6, 5, 7))
+    phi[0, :, :, 3] = 2.0 * h[0]
+    folded, lowest, _ = ops.ffd_jacobian(_dev(phi), full, full, (1, 1, 1), [1.0 / v for v in h])
+    assert int(folded.item()) > 0 and float(lowest.item()) < 0
+
+
+# ---------------------------------------------------------------------------- warp
+@pytest.mark.parametrize("dtype", ["float32", "uint8"])
+@pytest.mark.parametrize("nearest", [False, True])
+def test_warp_equals_the_restatement(dtype, nearest):
+    _, mov, phis, full, m, r, *_ = _case(dtype=dtype)
+    want = D.warp(mov, phis[0], full, m, r, nearest, default=7.0)
+    got, none = ops.ffd_warp(_dev(mov), _dev(phis[0]), full, m, r, nearest=nearest, default=7.0)
+    assert none is None and got.dtype == _dev(mov).dtype and np.array_equal(got.cpu().numpy(), want)
+    assert (want == 7).any() and (want != 7).any()                   # some voxels leave the moving image
+
+
+def test_warp_beyond_one_pass_of_its_grid_and_the_displacement_field():
+    _, mov, phis, full, m, r, *_ = _case(level=BIG, n_xyz=(6, 5, 4), T=1, mshape=(44, 78, 85), seed=5)
+    direction = R.rot_z(0.3) @ R.rot_y(-0.2)
+    got, disp = ops.ffd_warp(_dev(mov), _dev(phis[0]), full, m, r, direction=direction, want_displacement=True)
+    assert np.array_equal(got.cpu().numpy(), D.warp(mov, phis[0], full, m, r))
+    assert disp.dtype == torch.float32 and np.array_equal(disp.cpu().numpy(), D.displacement_field(phis[0], full, direction))
+    none, only = ops.ffd_warp(None, _dev(phis[0]), full, m, r, direction=direction, want_displacement=True)
+    assert none is None and torch.equal(only, disp)
+
+
+def test_the_zero_field_warps_as_apply_transform():
+    """``apply_transform`` forms its index map with contracted multiply-adds, this kernel with section 23's rounded
+    products, so the two positions can differ in the last bit for a general matrix.  They are the same numbers when
+    every product is exact: spacings, origins and matrix entries that are small dyadic rationals, as here."""
+    rng = np.random.default_rng(8)
+    moving = P.Image(rng.normal(size=(20, 18, 23)).astype(np.float32) * 50, (0.5, 1.0, 2.0), (-3.0, 1.5, 0.25))
+    fixed = P.Image(np.zeros(F_SHAPE, np.float32), (1.0, 0.5, 1.0), (0.5, -2.0, 1.0))
+    a = np.array([[0.0, -1.0, 0.0, 6.5], [1.25, 0.0, 0.0, 2.0], [0.0, 0.0, 0.75, 8.0], [0.0, 0.0, 0.0, 1.0]])
+    zero = reg.DeformableResult(np.zeros((3, 6, 5, 7)), a, reg._Geometry.of(fixed), "nmi", 0.0)
+    for nearest in (False, True):
+        want = P.apply_transform(moving, fixed, a, nearest)
+        got = reg.warp(moving, fixed, zero, nearest)
+        assert torch.equal(got.data, want.data) and got.spacing == fixed.spacing and got.origin == fixed.origin
+        assert (want.data != 0).float().mean() > 0.2
+
+
+# ---------------------------------------------------------------------------- end to end
+PHANTOM_SPACING = 8.0
+
+
+@functools.lru_cache(maxsize=None)
+def _phantom():
+    (f, m), truth = D.make_deformed_pair(D.smooth_field((6, 6, 6), 6.5, 1))
+    ref = D.register_deformable_ref(f, m, grid_spacing=PHANTOM_SPACING, levels=(2, 1), max_iterations=3)
+    return f, m, truth, ref
+
+
+def _image(g):
+    return P.Image(g.data, tuple(g.spacing), tuple(g.origin), tuple(g.direction.reshape(-1)))
+
+
+def test_register_deformable_gives_the_restatements_control_grid():
+    f, m, truth, ref = _phantom()
+    runs = [reg.register_deformable(_image(f), _image(m), grid_spacing=PHANTOM_SPACING, levels=(2, 1), max_iterations=3)
+            for _ in range(2)]
+    for got in runs:
+        assert got.control.tobytes() == ref.control.tobytes()
+        assert got.iterations == ref.iterations and got.evaluations == ref.evaluations and got.spans == ref.spans
+        assert got.level_values == ref.level_values and got.final_step == ref.final_step
+        assert got.accepted == ref.accepted and got.folded == ref.folded == 0 and got.min_jacobian == ref.min_jacobian
+    before, after = D.residual(truth, runs[0].control, f)
+    assert after < 0.5 * before
+    # the public helpers on the result
+    disp = reg.displacement_field(runs[0])
+    assert np.array_equal(disp.cpu().numpy(), D.displacement_field(ref.control, f.data.shape, np.eye(3)))
+    det = reg.jacobian_determinant(runs[0])
+    assert det.shape == f.data.shape and float(det.min()) == np.float32(ref.min_jacobian)
+    warped = reg.warp(_image(m), _image(f), runs[0])
+    lm_map = R.index_map(m, f, ref.affine)
+    assert np.array_equal(warped.data.cpu().numpy(), D.warp(m.data, ref.control, f.data.shape, lm_map, D.r_matrix(m, f, ref.affine)))
+
+
+def test_refusals_on_the_device():
+    fb, mv = torch.zeros((8, 8, 8), dtype=torch.uint8, device=DEV), torch.zeros((8, 8, 8), device=DEV)
+    ident = np.eye(3, 4)
+    grid = torch.zeros((1, 3, 4, 4, 4), dtype=torch.float64, device=DEV)
+    args = ((8, 8, 8), (1, 1, 1), ident, np.eye(3))
+    with pytest.raises(ValueError, match="bins"):
+        ops.ffd_joint_histogram(fb, mv, grid, *args, 20, 0.0, 1.0)
+    with pytest.raises(ValueError, match="candidate"):
+        ops.ffd_joint_histogram(fb, mv, grid.repeat(9, 1, 1, 1, 1), *args, 32, 0.0, 1.0)
+    with pytest.raises(ValueError, match="at least 4 points"):
+        ops.ffd_joint_histogram(fb, mv, grid[:, :, :3].contiguous(), *args, 32, 0.0, 1.0)
+    with pytest.raises(ValueError, match="control points"):
+        ops.ffd_jacobian(torch.zeros((3, 33, 32, 32), dtype=torch.float64, device=DEV), (8, 8, 8), (8, 8, 8), (1, 1, 1), [1, 1, 1])
+    with pytest.raises(ValueError, match="float64"):
+        ops.ffd_joint_histogram(fb, mv, grid.float(), *args, 32, 0.0, 1.0)
+    with pytest.raises(ValueError, match="does not fit"):
+        ops.ffd_joint_histogram(fb, mv, grid, (8, 8, 8), (2, 1, 1), ident, np.eye(3), 32, 0.0, 1.0)
+    with pytest.raises(ValueError, match="qd"):
+        ops.ffd_gradient(fb, mv, grid[0], *args, 32, 0.0, 1.0, 1.0, torch.zeros((32, 32), dtype=torch.int32, device=DEV))
+    # the C entries refuse on their own
+    from segmantic_amd._lib import FfdGrid, lib
+    import ctypes as C
+    g = FfdGrid(8, 8, 8, 8, 8, 8, 1, 1, 1, 4, 4, 3)
+    out = torch.zeros((1, 32, 32), dtype=torch.int64, device=DEV)
+    m, r = np.ascontiguousarray(ident), np.ascontiguousarray(np.eye(3))
+    call = lambda grid_, T, bins, pixel: lib.segmi_ffd_joint_histogram(  # noqa: E731
+        fb.data_ptr(), C.byref(grid_), grid.data_ptr(), T, pixel, mv.data_ptr(), 8, 8, 8, m.ctypes.data_as(C.c_void_p),
+        r.ctypes.data_as(C.c_void_p), bins, 0.0, 1.0, out.data_ptr(), None)
+    assert call(g, 1, 32, 0) != 0
+    ok = FfdGrid(8, 8, 8, 8, 8, 8, 1, 1, 1, 4, 4, 4)
+    assert call(ok, 9, 32, 0) != 0 and call(ok, 1, 48, 0) != 0 and call(ok, 1, 32, 9) != 0 and call(ok, 1, 32, 0) == 0
+    assert lib.segmi_ffd_jacobian(C.byref(ok), None, None, None, None, None, None) != 0
+
+
+# ---------------------------------------------------------------------------- multi-atlas segmentation
+def _load_script(name):
+    spec = importlib.util.spec_from_file_location(name, ROOT / "scripts" / f"{name}.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _dice(a, b):
+    scores = []
+    for k in range(1, int(max(a.max(), b.max())) + 1):
+        x, y = a == k, b == k
+        scores.append(2.0 * (x & y).sum() / max(1, x.sum() + y.sum()))
+    return float(np.mean(scores))
+
+
+def test_multi_atlas_segment_beats_every_affine_only_atlas(tmp_path):
+    """three 24^3 atlases, each the target's anatomy under its own smooth field: the fused B-spline-propagated labels
+    score a higher Dice against the target's labels than any atlas's labels carried by the affine registration alone"""
+    mas = _load_script("multi_atlas_segment")
+    size, spacing = (24, 24, 24), (2.0, 2.0, 2.0)
+    origin = R.centred_origin(size, spacing)
+    pts = R._points(size, spacing, origin)
+
+    def anatomy(p):
+        v = R.phantom(p)
+        return v, (v > 0.25).astype(np.uint8) + (v > 0.55).astype(np.uint8)
+
+    rng = np.random.default_rng(4)
+    tv, tl = anatomy(pts)
+    write = lambda arr, name: P.write_image(P.Image(arr, spacing, tuple(origin)), tmp_path / name) or tmp_path / name  # noqa: E731
+    target = write((tv + 0.01 * rng.standard_normal(tv.shape)).astype(np.float32), "target.nii.gz")
+    atlases = []
+    for k in range(3):
+        phi = D.smooth_field((5, 5, 5), 9.0, 20 + k)
+        u = D.field_at(phi, size, spacing, origin, pts)
+        av, al = anatomy(pts + u)
+        atlases.append((write(R.remap(av + 0.01 * rng.standard_normal(av.shape)).astype(np.float32), f"atlas{k}.nii.gz"),
+                        write(al, f"labels{k}.nii.gz")))
+    out = tmp_path / "fused.nii.gz"
+    report = mas.segment(target, out, atlases, grid_spacing=10.0, levels=(2, 1), max_iterations=8, keep_affine=True)
+    fused = P.read_image(out).numpy()
+    assert fused.shape == tl.shape and (tmp_path / "staple_performance.csv").exists()
+    fused_dice = _dice(fused, tl)
+    affine_dice = [_dice(a, tl) for a in report["affine_labels"]]
+    assert len(affine_dice) == 3 and all(fused_dice > d for d in affine_dice), (fused_dice, affine_dice)
