@@ -330,6 +330,17 @@ static inline const char* dtype_name(int dtype) { return dtype == SEGMI_BF16 ? "
     else SEGMI_CHECK_ARG(false, "unknown dtype code %d", (int)(dtype));            \
   } while (0)
 
+// F(P) with the pixel type of an image's `pixel` code; `what` (a string literal) names the entry point in the refusal
+#define SEGMI_BY_PIXEL(pixel, F, what)                                      \
+  switch (pixel) {                                                          \
+    case 0: F(float); break;                                                \
+    case 1: F(uint8_t); break;                                              \
+    case 2: F(int16_t); break;                                              \
+    case 3: F(int32_t); break;                                              \
+    case 4: F(uint16_t); break;                                             \
+    default: SEGMI_CHECK_ARG(false, what ": unknown pixel type %d", pixel); \
+  }
+
 // F(TS, TD, extra...) for a converting copy: f32 with any type, a 16-bit type with itself or with f32
 static inline bool dtype_pair_ok(int s, int d) {
   return dtype_ok(s) && dtype_ok(d) && (s == d || s == SEGMI_F32 || d == SEGMI_F32);

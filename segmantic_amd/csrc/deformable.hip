@@ -4,27 +4,16 @@
 // determinant of a grid, and the resampling of the moving image through the transform.  As in registration.hip
 // every sum that crosses lanes is an integer and everything else is float64 with every operation rounded on its own
 // (built with -ffp-contract=off), so a table, a gradient and a warped image are bit-equal to the numpy restatement.
-//
-// The sampling code of joint_hist_kernel (inside test, trilinear value, bin coordinate, fixed-point weights) is
-// restated here instead of shared through a header: registration.hip keeps its compiled code untouched.
-#include "common.h"
+// The histogram's table, the trilinear sample and the bin scatter are those of registration.hip (mi_sampling.h); the
+// warp ends in the resampler's tap (pixel_traits.h).
+#include "mi_sampling.h"
 #include "pixel_traits.h"
 
 namespace segmi {
 
 constexpr int kFfdMaxCandidates = SEGMI_FFD_MAX_CANDIDATES;
 constexpr int kFfdMaxPoints = SEGMI_FFD_MAX_CONTROL_POINTS;
-constexpr int kFfdLdsCounters = 8192;      // 32 KB of u32, as joint_hist_kernel: 32 / 8 / 2 candidates at 16 / 32 / 64 bins
-constexpr int kFfdFlushTrips = 128;        // 128 trips * 256 lanes * 2^16 = 2^31 < 2^32
 constexpr int64_t kFfdMaxSupport = (int64_t)SEGMI_FFD_GRADIENT_MAX_SUPPORT;
-
-typedef unsigned long long u64;
-
-static inline int ffd_hist_group(int bins) {
-  if (bins != 16 && bins != 32 && bins != 64) return 0;
-  const int g = kFfdLdsCounters / (bins * bins);
-  return g > kFfdMaxCandidates ? kFfdMaxCandidates : g;
-}
 
 // ------------------------------------------------------------------ the B-spline, axis by axis
 // span index k and fraction f of level voxel j: i = j F + 0.5 (F - 1), t = (i (n - 3)) / (dim - 1),
@@ -103,102 +92,43 @@ __device__ __forceinline__ double ffd_coord(const double* m, const double* r, do
 
 // ------------------------------------------------------------------ joint histogram under candidate grids
 struct FfdHistParams {
-  const uint8_t* fbin;
-  const void* mov;
+  HistParams h;                           // the fixed extent is the level grid g.lx x g.ly x g.lz
   const double* phi;                      // [T][3][nz][ny][nx]
-  u64* out;
   FfdGrid g;
-  int mx, my, mz, T, bins, group;
-  double mlo, mscale;
   double m[12], r[9];
 };
 
-__device__ __forceinline__ void ffd_hist_flush(unsigned* lds, u64* __restrict__ out, int entries) {
-  __syncthreads();
-  for (int e = threadIdx.x; e < entries; e += 256) {
-    const unsigned v = lds[e];
-    if (v) {
-      atomicAdd(&out[e], (u64)v);
-      lds[e] = 0;
-    }
+// coordinate policy of joint_hist_body: spans and weights once per voxel, the displacement under control grid t
+struct BsplineCoord {
+  const FfdHistParams& p;
+  struct Voxel {
+    double x, y, z, wx[4], wy[4], wz[4];
+    int64_t tap;                          // of the first support point in a component
+  };
+  __device__ __forceinline__ void voxel(int ix, int iy, int iz, Voxel& v) const {
+    const FfdGrid& g = p.g;
+    int kx, ky, kz;
+    double f;
+    v.x = (double)ix; v.y = (double)iy; v.z = (double)iz;
+    ffd_span(ix, g.fx, g.dx, g.nx, kx, f); ffd_weights(f, v.wx);
+    ffd_span(iy, g.fy, g.dy, g.ny, ky, f); ffd_weights(f, v.wy);
+    ffd_span(iz, g.fz, g.dz, g.nz, kz, f); ffd_weights(f, v.wz);
+    v.tap = ((int64_t)kz * g.ny + ky) * g.nx + kx;
   }
-  __syncthreads();
-}
+  __device__ __forceinline__ void at(const Voxel& v, int t, double& cx, double& cy, double& cz) const {
+    const FfdGrid& g = p.g;
+    const int64_t np = (int64_t)g.nx * g.ny * g.nz;
+    double u[3];
+    ffd_displacement(p.phi + (int64_t)t * 3 * np + v.tap, (int64_t)g.nx, (int64_t)g.nx * g.ny, np, v.wx, v.wy, v.wz, g, u);
+    cx = ffd_coord(p.m, p.r, v.x, v.y, v.z, u);
+    cy = ffd_coord(p.m + 4, p.r + 3, v.x, v.y, v.z, u);
+    cz = ffd_coord(p.m + 8, p.r + 6, v.x, v.y, v.z, u);
+  }
+};
 
 template <typename P>
 __global__ __launch_bounds__(256) void ffd_joint_hist_kernel(FfdHistParams p) {
-  __shared__ unsigned lds[kFfdLdsCounters];
-  const P* __restrict__ mov = (const P*)p.mov;
-  const FfdGrid g = p.g;
-  const int B = p.bins, BB = B * B;
-  const int t0 = blockIdx.y * p.group;
-  const int gcount = p.T - t0 < p.group ? p.T - t0 : p.group;
-  const int entries = gcount * BB;                       // <= kFfdLdsCounters by the choice of group
-  u64* __restrict__ out = p.out + (int64_t)t0 * BB;
-  for (int e = threadIdx.x; e < entries; e += 256) lds[e] = 0;
-  __syncthreads();
-
-  const int64_t np = (int64_t)g.nx * g.ny * g.nz;
-  const int64_t total = (int64_t)g.lx * g.ly * g.lz;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  const int64_t trips = (total + stride - 1) / stride;   // the same for every lane: the flushes hold barriers
-  const double hx = (double)(p.mx - 1), hy = (double)(p.my - 1), hz = (double)(p.mz - 1);
-  const double top = (double)(B - 1);
-  int since = 0;
-  for (int64_t trip = 0; trip < trips; ++trip) {
-    const int64_t e = trip * stride + blockIdx.x * 256ll + threadIdx.x;
-    int fb = 255;
-    if (e < total) fb = p.fbin[e];
-    if (fb < B) {
-      const int ix = (int)(e % g.lx), iy = (int)((e / g.lx) % g.ly), iz = (int)(e / ((int64_t)g.lx * g.ly));
-      const double x = (double)ix, y = (double)iy, z = (double)iz;
-      int kx, ky, kz;
-      double f, wx[4], wy[4], wz[4];
-      ffd_span(ix, g.fx, g.dx, g.nx, kx, f); ffd_weights(f, wx);
-      ffd_span(iy, g.fy, g.dy, g.ny, ky, f); ffd_weights(f, wy);
-      ffd_span(iz, g.fz, g.dz, g.nz, kz, f); ffd_weights(f, wz);
-      const int64_t tap = ((int64_t)kz * g.ny + ky) * g.nx + kx;
-      for (int c = 0; c < gcount; ++c) {
-        double u[3];
-        ffd_displacement(p.phi + (int64_t)(t0 + c) * 3 * np + tap, (int64_t)g.nx, (int64_t)g.nx * g.ny, np, wx, wy,
-                         wz, g, u);
-        const double cx = ffd_coord(p.m, p.r, x, y, z, u);
-        const double cy = ffd_coord(p.m + 4, p.r + 3, x, y, z, u);
-        const double cz = ffd_coord(p.m + 8, p.r + 6, x, y, z, u);
-        if (!(cx >= 0.0 && cx <= hx && cy >= 0.0 && cy <= hy && cz >= 0.0 && cz <= hz)) continue;
-        const double fx0 = floor(cx), fy0 = floor(cy), fz0 = floor(cz);
-        const int x0 = (int)fx0, y0 = (int)fy0, z0 = (int)fz0;
-        const double fx = cx - fx0, fy = cy - fy0, fz = cz - fz0;
-        const int x1 = x0 + 1 > p.mx - 1 ? p.mx - 1 : x0 + 1;
-        const int y1 = y0 + 1 > p.my - 1 ? p.my - 1 : y0 + 1;
-        const int z1 = z0 + 1 > p.mz - 1 ? p.mz - 1 : z0 + 1;
-        double val = 0.0;
-#pragma unroll
-        for (int corner = 0; corner < 8; ++corner) {
-          const int xi = (corner & 1) ? x1 : x0, yi = (corner & 2) ? y1 : y0, zi = (corner & 4) ? z1 : z0;
-          double w = (corner & 1) ? fx : 1.0 - fx;
-          w = w * ((corner & 2) ? fy : 1.0 - fy);
-          w = w * ((corner & 4) ? fz : 1.0 - fz);
-          val = val + w * (double)mov[((int64_t)zi * p.my + yi) * p.mx + xi];
-        }
-        double b = (val - p.mlo) * p.mscale;
-        b = b > 0.0 ? b : 0.0;                           // NaN -> 0: the cell index stays inside the table
-        b = b < top ? b : top;
-        int i = (int)floor(b);
-        i = i < B - 2 ? i : B - 2;
-        const double t = b - (double)i;
-        const unsigned q = (unsigned)(int)floor(t * 65536.0 + 0.5);
-        unsigned* cell = lds + c * BB + fb * B + i;
-        if (q != 65536u) atomicAdd(cell, 65536u - q);
-        if (q) atomicAdd(cell + 1, q);
-      }
-    }
-    if (++since == kFfdFlushTrips) {
-      ffd_hist_flush(lds, out, entries);
-      since = 0;
-    }
-  }
-  ffd_hist_flush(lds, out, entries);
+  joint_hist_body<P>(p.h, BsplineCoord{p});
 }
 
 // ------------------------------------------------------------------ gradient onto the control grid
@@ -267,7 +197,6 @@ __global__ __launch_bounds__(256) void ffd_gradient_kernel(FfdGradParams p) {
     sphi[comp][pt] = p.phi[comp * np + ((int64_t)(kz + (pt >> 4)) * g.ny + (ky + ((pt >> 2) & 3))) * g.nx + kx + (pt & 3)];
   }
   __syncthreads();
-  const double hx = (double)(p.mx - 1), hy = (double)(p.my - 1), hz = (double)(p.mz - 1);
   const double top = (double)(B - 1);
   const int wave = tid >> 6, lane = tid & 63;
   const int pc = lane >> 4, pb = (lane >> 2) & 3, pa = lane & 3;
@@ -292,28 +221,9 @@ __global__ __launch_bounds__(256) void ffd_gradient_kernel(FfdGradParams p) {
         const double cx = ffd_coord(p.m, p.r, x, y, z, u);
         const double cy = ffd_coord(p.m + 4, p.r + 3, x, y, z, u);
         const double cz = ffd_coord(p.m + 8, p.r + 6, x, y, z, u);
-        if (cx >= 0.0 && cx <= hx && cy >= 0.0 && cy <= hy && cz >= 0.0 && cz <= hz) {
-          const double fx0 = floor(cx), fy0 = floor(cy), fz0 = floor(cz);
-          const int x0 = (int)fx0, y0 = (int)fy0, z0 = (int)fz0;
-          const double fx = cx - fx0, fy = cy - fy0, fz = cz - fz0;
-          const int x1 = x0 + 1 > p.mx - 1 ? p.mx - 1 : x0 + 1;
-          const int y1 = y0 + 1 > p.my - 1 ? p.my - 1 : y0 + 1;
-          const int z1 = z0 + 1 > p.mz - 1 ? p.mz - 1 : z0 + 1;
-          // value and its derivatives by c_x, c_y, c_z, corner by corner in the histogram's corner order
-          double val = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
-#pragma unroll
-          for (int corner = 0; corner < 8; ++corner) {
-            const int xi = (corner & 1) ? x1 : x0, yi = (corner & 2) ? y1 : y0, zi = (corner & 4) ? z1 : z0;
-            const double v = (double)mov[((int64_t)zi * p.my + yi) * p.mx + xi];
-            const double ax = (corner & 1) ? fx : 1.0 - fx;
-            const double ay = (corner & 2) ? fy : 1.0 - fy;
-            const double az = (corner & 4) ? fz : 1.0 - fz;
-            val = val + ((ax * ay) * az) * v;
-            const double tx = (ay * az) * v, ty = (ax * az) * v, tz = (ax * ay) * v;
-            gx = (corner & 1) ? gx + tx : gx - tx;
-            gy = (corner & 2) ? gy + ty : gy - ty;
-            gz = (corner & 4) ? gz + tz : gz - tz;
-          }
+        if (mi_inside(p.mx, p.my, p.mz, cx, cy, cz)) {
+          double gc[3];                                   // the derivatives of the value by c_x, c_y, c_z
+          const double val = mi_sample<P, true>(mov, p.mx, p.my, p.mz, cx, cy, cz, gc);
           const double b = (val - p.mlo) * p.mscale;
           if (b > 0.0 && b < top) {                       // a clamped bin coordinate has no derivative
             const int i = (int)floor(b);                  // 0 .. B - 2
@@ -322,7 +232,7 @@ __global__ __launch_bounds__(256) void ffd_gradient_kernel(FfdGradParams p) {
             double d[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-              double s = ((gx * r[a] + gy * r[3 + a]) + gz * r[6 + a]) * p.gscale;
+              double s = ((gc[0] * r[a] + gc[1] * r[3 + a]) + gc[2] * r[6 + a]) * p.gscale;
               s = s > -1.0 ? s : -1.0;                    // NaN -> -1: stays a finite integer
               s = s < 1.0 ? s : 1.0;
               d[a] = rint(s * 32768.0);
@@ -486,39 +396,7 @@ __global__ __launch_bounds__(256) void ffd_warp_kernel(FfdWarpParams p) {
     const double cx = ffd_coord(p.m, p.r, x, y, z, u);
     const double cy = ffd_coord(p.m + 4, p.r + 3, x, y, z, u);
     const double cz = ffd_coord(p.m + 8, p.r + 6, x, y, z, u);
-    // from here on resample_kernel (image.hip): inside test, rounding, taps, default value, output cast
-    double val = p.defval;
-    const bool inside = cx >= -0.5 && cx < p.mx - 0.5 && cy >= -0.5 && cy < p.my - 0.5 && cz >= -0.5 && cz < p.mz - 0.5;
-    if (inside) {
-      if (p.nearest) {
-        int jx = (int)floor(cx + 0.5), jy = (int)floor(cy + 0.5), jz = (int)floor(cz + 0.5);
-        jx = jx < 0 ? 0 : (jx > p.mx - 1 ? p.mx - 1 : jx);
-        jy = jy < 0 ? 0 : (jy > p.my - 1 ? p.my - 1 : jy);
-        jz = jz < 0 ? 0 : (jz > p.mz - 1 ? p.mz - 1 : jz);
-        val = (double)src[((int64_t)jz * p.my + jy) * p.mx + jx];
-      } else {
-        const double fx0 = floor(cx), fy0 = floor(cy), fz0 = floor(cz);
-        const int bx = (int)fx0, by = (int)fy0, bz = (int)fz0;
-        double fx = cx - fx0, fy = cy - fy0, fz = cz - fz0;
-        if (bx < 0) fx = 0.0;
-        if (by < 0) fy = 0.0;
-        if (bz < 0) fz = 0.0;
-        const int x0 = bx < 0 ? 0 : bx, y0 = by < 0 ? 0 : by, z0 = bz < 0 ? 0 : bz;
-        const int x1 = bx + 1 > p.mx - 1 ? p.mx - 1 : (bx + 1 < 0 ? 0 : bx + 1);
-        const int y1 = by + 1 > p.my - 1 ? p.my - 1 : (by + 1 < 0 ? 0 : by + 1);
-        const int z1 = bz + 1 > p.mz - 1 ? p.mz - 1 : (bz + 1 < 0 ? 0 : bz + 1);
-        val = 0.0;
-#pragma unroll
-        for (int corner = 0; corner < 8; ++corner) {
-          const int xi = (corner & 1) ? x1 : x0, yi = (corner & 2) ? y1 : y0, zi = (corner & 4) ? z1 : z0;
-          double w = (corner & 1) ? fx : 1.0 - fx;
-          w = w * ((corner & 2) ? fy : 1.0 - fy);
-          w = w * ((corner & 4) ? fz : 1.0 - fz);
-          val = val + w * (double)src[((int64_t)zi * p.my + yi) * p.mx + xi];
-        }
-      }
-    }
-    dst[e] = PixelTraits<P>::cast(val);
+    dst[e] = resample_tap(src, p.mx, p.my, p.mz, cx, cy, cz, p.nearest ? 1 : 0, p.defval);
   }
 }
 
@@ -542,16 +420,6 @@ static int ffd_grid_check(const char* what, const segmi_ffd_grid* s, FfdGrid& g)
 
 using namespace segmi;
 
-#define SEGMI_FFD_BY_PIXEL(pixel, F, what)                               \
-  switch (pixel) {                                                       \
-    case 0: F(float); break;                                             \
-    case 1: F(uint8_t); break;                                           \
-    case 2: F(int16_t); break;                                           \
-    case 3: F(int32_t); break;                                           \
-    case 4: F(uint16_t); break;                                          \
-    default: SEGMI_CHECK_ARG(false, what ": unknown pixel type %d", pixel); \
-  }
-
 extern "C" {
 
 int segmi_ffd_joint_histogram(const uint8_t* fixed_bins, const segmi_ffd_grid* grid, const double* control,
@@ -564,7 +432,7 @@ int segmi_ffd_joint_histogram(const uint8_t* fixed_bins, const segmi_ffd_grid* g
   SEGMI_CHECK_ARG(mx > 0 && my > 0 && mz > 0, "ffd_joint_histogram: empty moving image");
   SEGMI_CHECK_ARG(candidates >= 1 && candidates <= kFfdMaxCandidates, "ffd_joint_histogram: 1 .. %d candidate grids per call, got %d",
                   kFfdMaxCandidates, candidates);
-  const int group = ffd_hist_group(bins);
+  const int group = hist_group(bins, kFfdMaxCandidates);
   SEGMI_CHECK_ARG(group > 0, "ffd_joint_histogram: bins must be 16, 32 or 64, got %d", bins);
   SEGMI_CHECK_ARG(pixel >= 0 && pixel <= 4, "ffd_joint_histogram: unknown pixel type %d", pixel);
   SEGMI_CHECK_ARG(mlo == mlo && mscale == mscale, "ffd_joint_histogram: mlo / mscale is NaN");
@@ -574,13 +442,13 @@ int segmi_ffd_joint_histogram(const uint8_t* fixed_bins, const segmi_ffd_grid* g
     return SEGMI_ELAUNCH;
   }
   FfdHistParams p{};
-  p.fbin = fixed_bins; p.mov = moving; p.phi = control; p.out = (u64*)out; p.g = g;
-  p.mx = mx; p.my = my; p.mz = mz; p.T = candidates; p.bins = bins; p.group = group; p.mlo = mlo; p.mscale = mscale;
+  p.h = HistParams{fixed_bins, moving, (u64*)out, g.lx, g.ly, g.lz, mx, my, mz, candidates, bins, group, mlo, mscale};
+  p.phi = control; p.g = g;
   for (int k = 0; k < 12; ++k) p.m[k] = index_map_host[k];
   for (int k = 0; k < 9; ++k) p.r[k] = r_host[k];
   const dim3 blocks(grid_1d((int64_t)g.lx * g.ly * g.lz, SEGMI_FFD_HIST_GRID_CAP), cdiv(candidates, group));
 #define LAUNCH(P) hipLaunchKernelGGL(ffd_joint_hist_kernel<P>, blocks, 256, 0, st, p)
-  SEGMI_FFD_BY_PIXEL(pixel, LAUNCH, "ffd_joint_histogram")
+  SEGMI_BY_PIXEL(pixel, LAUNCH, "ffd_joint_histogram")
 #undef LAUNCH
   SEGMI_LAUNCH_CHECK("ffd_joint_histogram");
   return SEGMI_OK;
@@ -594,7 +462,7 @@ int segmi_ffd_gradient(const uint8_t* fixed_bins, const segmi_ffd_grid* grid, co
   FfdGrid g;
   if (int rc = ffd_grid_check("ffd_gradient", grid, g)) return rc;
   SEGMI_CHECK_ARG(mx > 0 && my > 0 && mz > 0, "ffd_gradient: empty moving image");
-  SEGMI_CHECK_ARG(ffd_hist_group(bins) > 0, "ffd_gradient: bins must be 16, 32 or 64, got %d", bins);
+  SEGMI_CHECK_ARG(hist_group(bins, kFfdMaxCandidates) > 0, "ffd_gradient: bins must be 16, 32 or 64, got %d", bins);
   SEGMI_CHECK_ARG(pixel >= 0 && pixel <= 4, "ffd_gradient: unknown pixel type %d", pixel);
   SEGMI_CHECK_ARG(mlo == mlo && mscale == mscale && gscale == gscale, "ffd_gradient: mlo / mscale / gscale is NaN");
   // a control point's support is four spans per axis: at most ceil(4 l / spans) + 1 level voxels, and never more than l
@@ -628,7 +496,7 @@ int segmi_ffd_gradient(const uint8_t* fixed_bins, const segmi_ffd_grid* grid, co
   const dim3 blocks((unsigned)((g.nx - 3) * (g.ny - 3) * (g.nz - 3)),
                     (unsigned)(chunks > SEGMI_FFD_GRADIENT_GRID_CAP ? SEGMI_FFD_GRADIENT_GRID_CAP : chunks));
 #define LAUNCH(P) hipLaunchKernelGGL(ffd_gradient_kernel<P>, blocks, 256, 0, st, p)
-  SEGMI_FFD_BY_PIXEL(pixel, LAUNCH, "ffd_gradient")
+  SEGMI_BY_PIXEL(pixel, LAUNCH, "ffd_gradient")
 #undef LAUNCH
   SEGMI_LAUNCH_CHECK("ffd_gradient");
   return SEGMI_OK;
@@ -678,7 +546,7 @@ int segmi_ffd_warp(const segmi_ffd_grid* grid, const double* control, int pixel,
   hipStream_t st = (hipStream_t)stream;
   const int blocks = grid_1d((int64_t)g.lx * g.ly * g.lz, SEGMI_FFD_WARP_GRID_CAP);
 #define LAUNCH(P) hipLaunchKernelGGL(ffd_warp_kernel<P>, blocks, 256, 0, st, p)
-  SEGMI_FFD_BY_PIXEL(pixel, LAUNCH, "ffd_warp")
+  SEGMI_BY_PIXEL(pixel, LAUNCH, "ffd_warp")
 #undef LAUNCH
   SEGMI_LAUNCH_CHECK("ffd_warp");
   return SEGMI_OK;

@@ -32,45 +32,7 @@ __global__ void resample_kernel(ResampleParams p) {
       cy = cy < 0.0 ? 0.0 : (cy > p.sy - 1.0 ? p.sy - 1.0 : cy);
       cz = cz < 0.0 ? 0.0 : (cz > p.sz - 1.0 ? p.sz - 1.0 : cz);
     }
-    double val = p.defval;
-    const bool inside = cx >= -0.5 && cx < p.sx - 0.5 && cy >= -0.5 && cy < p.sy - 0.5 &&
-                        cz >= -0.5 && cz < p.sz - 0.5;
-    if (inside) {
-      if (p.interp & 1) {
-        // ITK rounds half up; bit 4 = round half to even (torch grid_sample "nearest" = nearbyint,
-        // what MONAI's Spacing(mode="nearest") ends in)
-        int ix, iy, iz;
-        if (p.interp & 4) { ix = (int)rint(cx); iy = (int)rint(cy); iz = (int)rint(cz); }
-        else { ix = (int)floor(cx + 0.5); iy = (int)floor(cy + 0.5); iz = (int)floor(cz + 0.5); }
-        ix = ix < 0 ? 0 : (ix > p.sx - 1 ? p.sx - 1 : ix);
-        iy = iy < 0 ? 0 : (iy > p.sy - 1 ? p.sy - 1 : iy);
-        iz = iz < 0 ? 0 : (iz > p.sz - 1 ? p.sz - 1 : iz);
-        val = (double)src[((int64_t)iz * p.sy + iy) * p.sx + ix];
-      } else {
-        const double fx0 = floor(cx), fy0 = floor(cy), fz0 = floor(cz);
-        int bx = (int)fx0, by = (int)fy0, bz = (int)fz0;
-        double fx = cx - fx0, fy = cy - fy0, fz = cz - fz0;
-        if (bx < 0) fx = 0.0;
-        if (by < 0) fy = 0.0;
-        if (bz < 0) fz = 0.0;
-        const int x0 = bx < 0 ? 0 : bx, y0 = by < 0 ? 0 : by, z0 = bz < 0 ? 0 : bz;
-        const int x1 = bx + 1 > p.sx - 1 ? p.sx - 1 : (bx + 1 < 0 ? 0 : bx + 1);
-        const int y1 = by + 1 > p.sy - 1 ? p.sy - 1 : (by + 1 < 0 ? 0 : by + 1);
-        const int z1 = bz + 1 > p.sz - 1 ? p.sz - 1 : (bz + 1 < 0 ? 0 : bz + 1);
-        // corner order and accumulation as oracle/resample_ref.py (bit d of the corner = dim d)
-        val = 0.0;
-#pragma unroll
-        for (int corner = 0; corner < 8; ++corner) {
-          const int xi = (corner & 1) ? x1 : x0, yi = (corner & 2) ? y1 : y0, zi = (corner & 4) ? z1 : z0;
-          // explicit round-to-nearest mul/add: no FMA contraction, same bits as the numpy oracle
-          double w = (corner & 1) ? fx : 1.0 - fx;
-          w = __dmul_rn(w, (corner & 2) ? fy : 1.0 - fy);
-          w = __dmul_rn(w, (corner & 4) ? fz : 1.0 - fz);
-          val = __dadd_rn(val, __dmul_rn(w, (double)src[((int64_t)zi * p.sy + yi) * p.sx + xi]));
-        }
-      }
-    }
-    dst[e] = PixelTraits<P>::cast(val);
+    dst[e] = resample_tap(src, p.sx, p.sy, p.sz, cx, cy, cz, p.interp, p.defval);
   }
 }
 
@@ -141,14 +103,9 @@ int segmi_resample3d(int pixel, const void* src, int sx, int sy, int sz, void* d
   const int64_t total = (int64_t)dx * dy * dz;
   const int grid = (int)(cdiv64(total, 256) > 8192 ? 8192 : cdiv64(total, 256));
   hipStream_t st = (hipStream_t)stream;
-  switch (pixel) {
-    case 0: hipLaunchKernelGGL(resample_kernel<float>, grid, 256, 0, st, p); break;
-    case 1: hipLaunchKernelGGL(resample_kernel<uint8_t>, grid, 256, 0, st, p); break;
-    case 2: hipLaunchKernelGGL(resample_kernel<int16_t>, grid, 256, 0, st, p); break;
-    case 3: hipLaunchKernelGGL(resample_kernel<int32_t>, grid, 256, 0, st, p); break;
-    case 4: hipLaunchKernelGGL(resample_kernel<uint16_t>, grid, 256, 0, st, p); break;
-    default: SEGMI_CHECK_ARG(false, "resample3d: unknown pixel type %d", pixel);
-  }
+#define LAUNCH(P) hipLaunchKernelGGL(resample_kernel<P>, grid, 256, 0, st, p)
+  SEGMI_BY_PIXEL(pixel, LAUNCH, "resample3d")
+#undef LAUNCH
   SEGMI_LAUNCH_CHECK("resample3d");
   return SEGMI_OK;
 }

@@ -379,19 +379,14 @@ int64_t segmi_bspline_workspace(int sx, int sy, int sz) {
 int segmi_bspline_prefilter(int pixel, const void* src, int sx, int sy, int sz, double* coef, void* stream) {
   SEGMI_CHECK_ARG(src && coef, "bspline_prefilter: null pointer");
   SEGMI_CHECK_ARG(hq_shape_ok(sx, sy, sz), "bspline_prefilter: empty image");
-  SEGMI_CHECK_ARG(pixel >= 0 && pixel <= 4, "bspline_prefilter: unknown pixel type %d", pixel);
   const int64_t rows = (int64_t)sy * sz, plane = (int64_t)sx * sy, nvox = plane * sz;
   SEGMI_CHECK_ARG(cdiv64(rows, 4) < (1ll << 31) && cdiv64(nvox, 256) < (1ll << 31), "bspline_prefilter: image too large");
   hipStream_t st = (hipStream_t)stream;
   const double z = sqrt(3.0) - 2.0;
   const int gx = (int)cdiv64(rows, 4);
-  switch (pixel) {
-    case 0: hipLaunchKernelGGL(bspline_x_kernel<float>, gx, 256, 0, st, (const float*)src, coef, sx, rows, z); break;
-    case 1: hipLaunchKernelGGL(bspline_x_kernel<uint8_t>, gx, 256, 0, st, (const uint8_t*)src, coef, sx, rows, z); break;
-    case 2: hipLaunchKernelGGL(bspline_x_kernel<int16_t>, gx, 256, 0, st, (const int16_t*)src, coef, sx, rows, z); break;
-    case 3: hipLaunchKernelGGL(bspline_x_kernel<int32_t>, gx, 256, 0, st, (const int32_t*)src, coef, sx, rows, z); break;
-    case 4: hipLaunchKernelGGL(bspline_x_kernel<uint16_t>, gx, 256, 0, st, (const uint16_t*)src, coef, sx, rows, z); break;
-  }
+#define LAUNCH(P) hipLaunchKernelGGL(bspline_x_kernel<P>, gx, 256, 0, st, (const P*)src, coef, sx, rows, z)
+  SEGMI_BY_PIXEL(pixel, LAUNCH, "bspline_prefilter")
+#undef LAUNCH
   if (sy > 1) {  // lines along y: one per (z, x)
     const int64_t lines = (int64_t)sx * sz;
     hipLaunchKernelGGL(bspline_line_kernel, (int)cdiv64(lines, 256), 256, 0, st, coef, sy, (int64_t)sx, (int64_t)sx,
@@ -413,14 +408,9 @@ int segmi_resample3d_bspline(const double* coef, int sx, int sy, int sz, int pix
   hq_fill(p, coef, sx, sy, sz, dst, dx, dy, dz, index_map_host, border, default_value);
   const int grid = grid_1d((int64_t)dx * dy * dz, SEGMI_RESAMPLE_HQ_GRID_CAP);
   hipStream_t st = (hipStream_t)stream;
-  switch (pixel) {
-    case 0: hipLaunchKernelGGL(bspline_eval_kernel<float>, grid, 256, 0, st, p); break;
-    case 1: hipLaunchKernelGGL(bspline_eval_kernel<uint8_t>, grid, 256, 0, st, p); break;
-    case 2: hipLaunchKernelGGL(bspline_eval_kernel<int16_t>, grid, 256, 0, st, p); break;
-    case 3: hipLaunchKernelGGL(bspline_eval_kernel<int32_t>, grid, 256, 0, st, p); break;
-    case 4: hipLaunchKernelGGL(bspline_eval_kernel<uint16_t>, grid, 256, 0, st, p); break;
-    default: SEGMI_CHECK_ARG(false, "resample3d_bspline: unknown pixel type %d", pixel);
-  }
+#define LAUNCH(P) hipLaunchKernelGGL(bspline_eval_kernel<P>, grid, 256, 0, st, p)
+  SEGMI_BY_PIXEL(pixel, LAUNCH, "resample3d_bspline")
+#undef LAUNCH
   SEGMI_LAUNCH_CHECK("resample3d_bspline");
   return SEGMI_OK;
 }
@@ -449,14 +439,9 @@ int segmi_resample3d_label_gaussian(int pixel, const void* src, int sx, int sy, 
   const size_t lds = (size_t)3 * p.taps * 256 * sizeof(int);
   const int grid = grid_1d((int64_t)dx * dy * dz, SEGMI_RESAMPLE_HQ_GRID_CAP);
   hipStream_t st = (hipStream_t)stream;
-  switch (pixel) {
-    case 0: hipLaunchKernelGGL(label_gaussian_kernel<float>, grid, 256, lds, st, p); break;
-    case 1: hipLaunchKernelGGL(label_gaussian_kernel<uint8_t>, grid, 256, lds, st, p); break;
-    case 2: hipLaunchKernelGGL(label_gaussian_kernel<int16_t>, grid, 256, lds, st, p); break;
-    case 3: hipLaunchKernelGGL(label_gaussian_kernel<int32_t>, grid, 256, lds, st, p); break;
-    case 4: hipLaunchKernelGGL(label_gaussian_kernel<uint16_t>, grid, 256, lds, st, p); break;
-    default: SEGMI_CHECK_ARG(false, "resample3d_label_gaussian: unknown pixel type %d", pixel);
-  }
+#define LAUNCH(P) hipLaunchKernelGGL(label_gaussian_kernel<P>, grid, 256, lds, st, p)
+  SEGMI_BY_PIXEL(pixel, LAUNCH, "resample3d_label_gaussian")
+#undef LAUNCH
   SEGMI_LAUNCH_CHECK("resample3d_label_gaussian");
   return SEGMI_OK;
 }

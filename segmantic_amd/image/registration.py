@@ -261,6 +261,38 @@ def _volume(image: Image, dev) -> torch.Tensor:
     return t.unsqueeze(0) if t.dim() == 2 else t
 
 
+def _device(device):
+    if not torch.cuda.is_available():
+        raise RuntimeError("segmantic_amd registration runs on an MI355X (no CPU path)")
+    return device or torch.device("cuda:0")
+
+
+def _prepare_level(fvol, mvol, mask, gf: _Geometry, gm: _Geometry, lv: int, bins: int):
+    """One pyramid level of a pair, as (ff, mf, fbin, mimg, mlo, mhi, mscale, usable, lgf, lgm): the shrink factors
+    (z, y, x) of fixed and moving, the fixed bin volume, the moving level image (the finest level reads the native
+    pixel type), its range and bin scale, the number of fixed samples that count, and the two level grids."""
+    from .. import ops
+    nd = len(gf.size)
+    ff = ops.shrink_factors(fvol.shape, lv)
+    mf = ops.shrink_factors(mvol.shape, lv)
+    fimg = ops.bin_shrink(fvol, ff)
+    mimg = mvol if lv == 1 else ops.bin_shrink(mvol, mf)
+    flo, fhi = float(fimg.min()), float(fimg.max())
+    mwide = mimg.to(torch.int32) if mimg.dtype == torch.uint16 else mimg
+    mlo, mhi = float(mwide.min()), float(mwide.max())
+    if not fhi > flo:
+        raise ValueError(f"fixed is constant at pyramid level {lv}: no intensity to register")
+    if not mhi > mlo:
+        raise ValueError(f"moving is constant at pyramid level {lv}: no intensity to register")
+    mmean = ops.bin_shrink(mask, ff) if mask is not None else None
+    fbin = ops.fixed_bins(fimg, flo, fhi, bins, mmean)
+    usable = int((fbin != IGNORE).sum())
+    if usable == 0:
+        raise ValueError(f"fixed_mask leaves no sample at pyramid level {lv}")
+    return (ff, mf, fbin, mimg, mlo, mhi, (bins - 1) / (mhi - mlo), usable,
+            level_geometry(gf, tuple(reversed(ff))[:nd]), level_geometry(gm, tuple(reversed(mf))[:nd]))
+
+
 # ---------------------------------------------------------------------------- the registration
 def register(fixed: Image, moving: Image, *, transform: str = "rigid", metric: str = "nmi", bins: int = 32,
              levels: Sequence[int] = (4, 2, 1), fixed_mask: Optional[Image] = None, initial=None,
@@ -273,9 +305,7 @@ def register(fixed: Image, moving: Image, *, transform: str = "rigid", metric: s
     nd, levels, m0 = _check(fixed, moving, transform, metric, bins, levels, fixed_mask, initial, min_overlap,
                             max_iterations)
     from .. import ops
-    if not torch.cuda.is_available():
-        raise RuntimeError("segmantic_amd registration runs on an MI355X (no CPU path)")
-    dev = device or (fixed.data.device if fixed.data.is_cuda else torch.device("cuda:0"))
+    dev = _device(device or (fixed.data.device if fixed.data.is_cuda else None))
     fvol, mvol = _volume(fixed, dev), _volume(moving, dev)
     mask = _volume(fixed_mask, dev) if fixed_mask is not None else None
     gf, gm = _Geometry.of(fixed), _Geometry.of(moving)
@@ -284,25 +314,7 @@ def register(fixed: Image, moving: Image, *, transform: str = "rigid", metric: s
     res = RegistrationResult(np.eye(nd + 1), q, transform, metric, float("-inf"), initial=m0)
     converged = True
     for lv in levels:
-        ff = ops.shrink_factors(fvol.shape, lv)          # (z, y, x)
-        mf = ops.shrink_factors(mvol.shape, lv)
-        fimg = ops.bin_shrink(fvol, ff)
-        mimg = mvol if lv == 1 else ops.bin_shrink(mvol, mf)   # the finest level reads the native pixel type
-        flo, fhi = float(fimg.min()), float(fimg.max())
-        mwide = mimg.to(torch.int32) if mimg.dtype == torch.uint16 else mimg
-        mlo, mhi = float(mwide.min()), float(mwide.max())
-        if not fhi > flo:
-            raise ValueError(f"fixed is constant at pyramid level {lv}: no intensity to register")
-        if not mhi > mlo:
-            raise ValueError(f"moving is constant at pyramid level {lv}: no intensity to register")
-        mmean = ops.bin_shrink(mask, ff) if mask is not None else None
-        fbin = ops.fixed_bins(fimg, flo, fhi, bins, mmean)
-        usable = int((fbin != IGNORE).sum())
-        if usable == 0:
-            raise ValueError(f"fixed_mask leaves no sample at pyramid level {lv}")
-        mscale = (bins - 1) / (mhi - mlo)
-        lgf = level_geometry(gf, tuple(reversed(ff))[:nd])
-        lgm = level_geometry(gm, tuple(reversed(mf))[:nd])
+        ff, _, fbin, mimg, mlo, mhi, mscale, usable, lgf, lgm = _prepare_level(fvol, mvol, mask, gf, gm, lv, bins)
 
         def evaluate(cands):
             maps = np.stack([processing._index_map(lgm, lgf.spacing, lgf.origin, lgf.direction,
@@ -514,9 +526,7 @@ def register_deformable(fixed: Image, moving: Image, *, initial=None, grid_spaci
     nd, levels, a0, lam, spans = _check_deformable(fixed, moving, initial, grid_spacing, levels, metric, bins,
                                                    regularisation, fixed_mask, min_overlap, max_iterations)
     from .. import ops
-    if not torch.cuda.is_available():
-        raise RuntimeError("segmantic_amd registration runs on an MI355X (no CPU path)")
-    dev = device or (fixed.data.device if fixed.data.is_cuda else torch.device("cuda:0"))
+    dev = _device(device or (fixed.data.device if fixed.data.is_cuda else None))
     fvol, mvol = _volume(fixed, dev), _volume(moving, dev)
     mask = _volume(fixed_mask, dev) if fixed_mask is not None else None
     gf, gm = _Geometry.of(fixed), _Geometry.of(moving)
@@ -529,25 +539,7 @@ def register_deformable(fixed: Image, moving: Image, *, initial=None, grid_spaci
     for lv, sp in zip(levels, spans):
         n_xyz = tuple(s + 3 for s in sp)
         phi = np.zeros((3,) + tuple(reversed(n_xyz))) if phi is None else refine_grid(phi, flat)
-        ff = ops.shrink_factors(fvol.shape, lv)
-        mf = ops.shrink_factors(mvol.shape, lv)
-        fimg = ops.bin_shrink(fvol, ff)
-        mimg = mvol if lv == 1 else ops.bin_shrink(mvol, mf)
-        flo, fhi = float(fimg.min()), float(fimg.max())
-        mwide = mimg.to(torch.int32) if mimg.dtype == torch.uint16 else mimg
-        mlo, mhi = float(mwide.min()), float(mwide.max())
-        if not fhi > flo:
-            raise ValueError(f"fixed is constant at pyramid level {lv}: no intensity to register")
-        if not mhi > mlo:
-            raise ValueError(f"moving is constant at pyramid level {lv}: no intensity to register")
-        mmean = ops.bin_shrink(mask, ff) if mask is not None else None
-        fbin = ops.fixed_bins(fimg, flo, fhi, bins, mmean)
-        usable = int((fbin != IGNORE).sum())
-        if usable == 0:
-            raise ValueError(f"fixed_mask leaves no sample at pyramid level {lv}")
-        mscale = (bins - 1) / (mhi - mlo)
-        lgf = level_geometry(gf, tuple(reversed(ff))[:nd])
-        lgm = level_geometry(gm, tuple(reversed(mf))[:nd])
+        ff, _, fbin, mimg, mlo, mhi, mscale, usable, lgf, lgm = _prepare_level(fvol, mvol, mask, gf, gm, lv, bins)
         m = processing._index_map(lgm, lgf.spacing, lgf.origin, lgf.direction, a0)
         r = _r_matrix(lgm, gf, a0)
         gscale = 1.0 / ((mhi - mlo) * float(np.abs(r).sum(axis=1).max()))
@@ -630,12 +622,6 @@ def _jacobian(result: DeformableResult, dev, want_map: bool):
     h = _control_spacing(size3, spacing3, tuple(reversed(result.control.shape[1:])))
     control = torch.from_numpy(np.ascontiguousarray(result.control, dtype=np.float64)).to(dev)
     return ops.ffd_jacobian(control, full, full, (1, 1, 1), [0.0 if v == 0.0 else 1.0 / v for v in h], want_map)
-
-
-def _device(device):
-    if not torch.cuda.is_available():
-        raise RuntimeError("segmantic_amd registration runs on an MI355X (no CPU path)")
-    return device or torch.device("cuda:0")
 
 
 def _same_grid(fixed: Image, g: _Geometry) -> bool:

@@ -250,6 +250,27 @@ def test_the_zero_field_warps_as_apply_transform():
         assert (want.data != 0).float().mean() > 0.2
 
 
+@pytest.mark.parametrize("mshape", [(5, 6, 7), (4, 5, 6)])
+@pytest.mark.parametrize("dtype,nearest", [("float32", True), ("uint8", True), ("int16", True), ("float32", False)])
+def test_the_zero_field_warps_at_half_coordinates_as_the_resampler(dtype, nearest, mshape):
+    """The warp and ``resample3d`` end in one shared tap.  The identity shifted by exactly 0.5 on every axis puts
+    every coordinate on a half: where half-up and half-even rounding part, and, for the moving volume of the fixed
+    grid's own extent, the last plane along each axis exactly on ``dim - 0.5``, the first position outside."""
+    full = (4, 5, 6)                                                  # the fixed grid 6 x 5 x 4 (x, y, z)
+    mov = np.arange(1, 1 + int(np.prod(mshape))).reshape(mshape).astype(dtype)   # distinct integers, none the default
+    m = np.concatenate([np.eye(3), np.full((3, 1), 0.5)], axis=1)
+    zero = np.zeros((3, 4, 4, 4))
+    got, _ = ops.ffd_warp(_dev(mov), _dev(zero), full, m, np.eye(3), nearest=nearest)
+    want = ops.resample3d(_dev(mov), full, m, nearest=nearest)
+    assert got.dtype == want.dtype and torch.equal(got, want)
+    assert np.array_equal(got.cpu().numpy(), D.warp(mov, zero, full, m, np.eye(3), nearest))
+    if mshape == full:
+        out = got.cpu().numpy()
+        assert (out[-1] == 0).all() and (out[:, -1] == 0).all() and (out[:, :, -1] == 0).all() and (out[:-1, :-1, :-1] != 0).all()
+    elif nearest:
+        assert np.array_equal(got.cpu().numpy(), mov[1:5, 1:6, 1:7])  # every half rounds up
+
+
 # ---------------------------------------------------------------------------- end to end
 PHANTOM_SPACING = 8.0
 
