@@ -146,6 +146,61 @@ __global__ void convt_direct_kernel(DirectParams p) {
 
 static inline bool mfma_ok(int cin, int cout) { return cin % 16 == 0 && cout % 16 == 0; }
 
+// what the MFMA kernels ask of the views: 16-byte aligned input rows, 4-element aligned output / residual rows
+static inline bool mfma_rows_aligned(int dtype, const segmi_act* in, const segmi_act* out) {
+  const int es = dtype_size(dtype);
+  return in->ld % (16 / es) == 0 && out->ld % 4 == 0 && ((uintptr_t)in->data % 16) == 0 &&
+         ((uintptr_t)out->data % (4 * es)) == 0;
+}
+static inline bool residual_rows_aligned(int dtype, const segmi_act* residual) {
+  return residual->ld % 4 == 0 && ((uintptr_t)residual->data % (4 * dtype_size(dtype))) == 0;
+}
+static inline bool residual_matches(const segmi_act* residual, const segmi_act* out) {
+  return act_ok(residual) && residual->n == out->n && residual->d == out->d && residual->h == out->h &&
+         residual->w == out->w && residual->c == out->c;
+}
+
+// the geometry ConvParams, ConvTParams and DirectParams have in common, from the views of a launch
+template <class P>
+static inline P geometry_params(const segmi_act* in, const segmi_act* out, const segmi_act* residual) {
+  P p{};
+  p.in = in->data; p.out = out->data;
+  p.res = residual ? residual->data : nullptr;
+  p.N = in->n; p.Di = in->d; p.Hi = in->h; p.Wi = in->w;
+  p.Do = out->d; p.Ho = out->h; p.Wo = out->w;
+  p.Cin = in->c; p.Cout = out->c; p.ldi = in->ld; p.ldo = out->ld;
+  p.ldr = residual ? residual->ld : 0;
+  return p;
+}
+// ... and what the two MFMA parameter blocks add to it
+template <class P>
+static inline P mfma_params(int dtype, const segmi_act* in, const segmi_act* out, const segmi_act* residual,
+                            const void* packed, const float* bias, const float* alpha, float* stats) {
+  P p = geometry_params<P>(in, out, residual);
+  p.wfrag = packed; p.bias = bias; p.alpha = alpha; p.stats = stats;
+  p.nchunks = in->c / pick_ck(dtype, in->c);
+  p.ntiles_total = out->c / 16;
+  return p;
+}
+static inline DirectParams direct_params(const segmi_act* in, const segmi_act* out, const segmi_act* residual,
+                                         const float* w, const float* bias, const float* alpha, int ks, int stride,
+                                         int kind) {
+  DirectParams p = geometry_params<DirectParams>(in, out, residual);
+  p.w = w; p.bias = bias; p.alpha = alpha; p.ks = ks; p.stride = stride; p.kind = kind;
+  return p;
+}
+
+// statistics behind a direct kernel: a pass over the written output, then the separate (small) finalisation
+// launch of the generic path over rows() partial rows.  `plain`: the launch had neither PReLU nor residual
+template <class Rows>
+static int direct_stats_tail(const char* name, bool plain, int dtype, const segmi_act* out, float* stats, Rows rows,
+                             const segmi_bn_fin* fin, hipStream_t st) {
+  SEGMI_CHECK_ARG(plain, "%s: fused statistics are taken before PReLU/residual", name);
+  const int rc = bn_stats_launch(dtype, out, stats, st);
+  if (rc != SEGMI_OK || !fin) return rc;
+  return bn_finalize_with(stats, rows(), out->c, fin, st);
+}
+
 static inline int out_extent(int in, int ks, int stride) {
   const int pad = (ks - 1) / 2;
   return (in + 2 * pad - ks) / stride + 1;
@@ -233,22 +288,13 @@ int segmi_conv3d_fwd_split_act(int dtype, const segmi_act* in, const segmi_act* 
   SEGMI_CHECK_ARG(in->n == out->n && out->d == out_extent(in->d, ksize, stride) &&
                       out->h == out_extent(in->h, ksize, stride) && out->w == out_extent(in->w, ksize, stride),
                   "conv3d_fwd_split_act: output extent does not match the input");
-  const int es = dtype_size(dtype);
-  SEGMI_CHECK_ARG(in->ld % (16 / es) == 0 && out->ld % 4 == 0 && ((uintptr_t)in->data % 16) == 0 &&
-                      ((uintptr_t)out->data % (4 * es)) == 0,
+  SEGMI_CHECK_ARG(mfma_rows_aligned(dtype, in, out),
                   "conv3d_fwd_split_act: MFMA path needs 16-byte aligned input rows");
-  ConvParams p{};
-  p.in = in->data; p.out = out->data; p.wfrag = packed; p.bias = bias; p.alpha = prelu_alpha;
-  p.N = in->n; p.Di = in->d; p.Hi = in->h; p.Wi = in->w;
-  p.Do = out->d; p.Ho = out->h; p.Wo = out->w;
-  p.Cin = in->c; p.Cout = out->c; p.ldi = in->ld; p.ldo = out->ld;
-  p.nchunks = in->c / pick_ck(dtype, in->c);
-  p.ntiles_total = out->c / 16;
+  ConvParams p = mfma_params<ConvParams>(dtype, in, out, nullptr, packed, bias, prelu_alpha, stats_partials);
   p.act_tiles = act_channels / 16;
   p.bias2 = bias_b;
   if (stats_partials) {
     // training: statistics (and their finalisation) of the first act_channels outputs only
-    p.stats = stats_partials;
     p.stats_tiles = act_channels / 16;
     if (stats_fin) { p.fin_on = 1; p.bfin = bn_fin_from(stats_fin, act_channels); }
   } else {
@@ -365,29 +411,14 @@ int segmi_conv3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, const
                       out->w == out_extent(in->w, ksize, stride),
                   "conv3d: output extent [%d,%d,%d,%d] does not match input [%d,%d,%d,%d] k%d s%d",
                   out->n, out->d, out->h, out->w, in->n, in->d, in->h, in->w, ksize, stride);
-  if (residual)
-    SEGMI_CHECK_ARG(act_ok(residual) && residual->n == out->n && residual->d == out->d &&
-                        residual->h == out->h && residual->w == out->w && residual->c == out->c,
-                    "conv3d: residual shape mismatch");
+  SEGMI_CHECK_ARG(!residual || residual_matches(residual, out), "conv3d: residual shape mismatch");
   hipStream_t st = (hipStream_t)stream;
-  const int es = dtype_size(dtype);
   if (mfma_ok(in->c, out->c)) {
     SEGMI_CHECK_ARG(packed, "conv3d: MFMA path needs a fragment-packed weight (segmi_wpack)");
-    SEGMI_CHECK_ARG(in->ld % (16 / es) == 0 && out->ld % 4 == 0 &&
-                        ((uintptr_t)in->data % 16) == 0 && ((uintptr_t)out->data % (4 * es)) == 0,
-                    "conv3d: MFMA path needs 16-byte aligned input rows");
-    if (residual)
-      SEGMI_CHECK_ARG(residual->ld % 4 == 0 && ((uintptr_t)residual->data % (4 * es)) == 0,
-                      "conv3d: residual rows must be 4-element aligned");
-    ConvParams p{};
-    p.in = in->data; p.out = out->data; p.wfrag = packed; p.bias = bias; p.alpha = prelu_alpha;
-    p.res = residual ? residual->data : nullptr; p.stats = stats_partials;
-    p.N = in->n; p.Di = in->d; p.Hi = in->h; p.Wi = in->w;
-    p.Do = out->d; p.Ho = out->h; p.Wo = out->w;
-    p.Cin = in->c; p.Cout = out->c; p.ldi = in->ld; p.ldo = out->ld;
-    p.ldr = residual ? residual->ld : 0;
-    p.nchunks = in->c / pick_ck(dtype, in->c);
-    p.ntiles_total = out->c / 16;
+    SEGMI_CHECK_ARG(mfma_rows_aligned(dtype, in, out), "conv3d: MFMA path needs 16-byte aligned input rows");
+    SEGMI_CHECK_ARG(!residual || residual_rows_aligned(dtype, residual),
+                    "conv3d: residual rows must be 4-element aligned");
+    ConvParams p = mfma_params<ConvParams>(dtype, in, out, residual, packed, bias, prelu_alpha, stats_partials);
     if (in_tf) { p.in_scale = in_tf->scale; p.in_shift = in_tf->shift; p.in_alpha = in_tf->prelu_alpha; }
     if (bn_bwd) {
       p.bx = bn_bwd->x->data; p.ldbx = bn_bwd->x->ld; p.bmean = bn_bwd->mean; p.binvstd = bn_bwd->invstd;
@@ -408,30 +439,19 @@ int segmi_conv3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, const
   SEGMI_CHECK_ARG(!(stats_partials && small_fwd_eligible(dtype, in, out, ksize) && w_kind != 0),
                   "conv3d: fused statistics on a small-Cin layer need the forward weight kind");
   if (small_fwd_eligible(dtype, in, out, ksize) && w_kind == 0 &&
-      (!residual || (residual->ld % 4 == 0 && ((uintptr_t)residual->data % (4 * es)) == 0))) {
+      (!residual || residual_rows_aligned(dtype, residual))) {
     SEGMI_CHECK_ARG(!stats_partials || (!prelu_alpha && !residual),
                     "conv3d: fused statistics are taken before PReLU/residual");
     return conv_small_fwd(dtype, in, out, w_src, bias, prelu_alpha, residual, stats_partials, stride,
                           st, nullptr, nullptr, nullptr, stats_fin);
   }
-  DirectParams p{};
-  p.in = in->data; p.out = out->data; p.w = w_src; p.bias = bias; p.alpha = prelu_alpha;
-  p.res = residual ? residual->data : nullptr;
-  p.N = in->n; p.Di = in->d; p.Hi = in->h; p.Wi = in->w; p.Do = out->d; p.Ho = out->h;
-  p.Wo = out->w; p.Cin = in->c; p.Cout = out->c; p.ldi = in->ld; p.ldo = out->ld;
-  p.ldr = residual ? residual->ld : 0; p.ks = ksize; p.stride = stride; p.kind = w_kind;
+  const DirectParams p = direct_params(in, out, residual, w_src, bias, prelu_alpha, ksize, stride, w_kind);
 #define DIRECT(T, KERN) hipLaunchKernelGGL(KERN<T>, grid_1d(act_voxels(out) * out->c, 8192), 256, 0, st, p)
   SEGMI_BY_DTYPE(dtype, DIRECT, conv_direct_kernel);
   SEGMI_LAUNCH_CHECK("conv3d_fwd(direct)");
-  if (stats_partials) {
-    SEGMI_CHECK_ARG(!prelu_alpha && !residual,
-                    "conv3d: fused statistics are taken before PReLU/residual");
-    const int rc = bn_stats_launch(dtype, out, stats_partials, st);
-    if (rc != SEGMI_OK || !stats_fin) return rc;
-    return bn_finalize_with(stats_partials, segmi_conv3d_stats_rows(dtype, in, out, ksize, stride), out->c,
-                            stats_fin, st);       // generic path: a separate (small) launch
-  }
-  return SEGMI_OK;
+  if (!stats_partials) return SEGMI_OK;
+  return direct_stats_tail("conv3d", !prelu_alpha && !residual, dtype, out, stats_partials,
+                           [&] { return segmi_conv3d_stats_rows(dtype, in, out, ksize, stride); }, stats_fin, st);
 }
 
 int segmi_convT3d_stats_rows(int dtype, const segmi_act* in, const segmi_act* out) {
@@ -453,50 +473,25 @@ int segmi_convT3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, cons
   for (int k = 0; k < 3; ++k)
     SEGMI_CHECK_ARG(dout[k] == 2 * di[k] || dout[k] == 2 * di[k] - 1,
                     "convT3d: output extent %d must be 2*in or 2*in-1 (in %d)", dout[k], di[k]);
-  if (residual)
-    SEGMI_CHECK_ARG(act_ok(residual) && residual->n == out->n && residual->d == out->d &&
-                        residual->h == out->h && residual->w == out->w && residual->c == out->c,
-                    "convT3d: residual shape mismatch");
+  SEGMI_CHECK_ARG(!residual || residual_matches(residual, out), "convT3d: residual shape mismatch");
   hipStream_t st = (hipStream_t)stream;
-  const int es = dtype_size(dtype);
   if (mfma_ok(in->c, out->c)) {
     SEGMI_CHECK_ARG(packed, "convT3d: MFMA path needs a kind-2 fragment pack (segmi_wpack)");
-    SEGMI_CHECK_ARG(in->ld % (16 / es) == 0 && out->ld % 4 == 0 &&
-                        ((uintptr_t)in->data % 16) == 0 && ((uintptr_t)out->data % (4 * es)) == 0,
-                    "convT3d: MFMA path needs 16-byte aligned input rows");
-    if (residual)
-      SEGMI_CHECK_ARG(residual->ld % 4 == 0 && ((uintptr_t)residual->data % (4 * es)) == 0,
-                      "convT3d: residual rows must be 4-element aligned");
-    ConvTParams p{};
-    p.in = in->data; p.out = out->data; p.wfrag = packed; p.bias = bias; p.alpha = prelu_alpha;
-    p.res = residual ? residual->data : nullptr; p.stats = stats_partials;
-    p.N = in->n; p.Di = in->d; p.Hi = in->h; p.Wi = in->w;
-    p.Do = out->d; p.Ho = out->h; p.Wo = out->w;
-    p.Cin = in->c; p.Cout = out->c; p.ldi = in->ld; p.ldo = out->ld;
-    p.ldr = residual ? residual->ld : 0;
-    p.nchunks = in->c / pick_ck(dtype, in->c);
-    p.ntiles_total = out->c / 16;
+    SEGMI_CHECK_ARG(mfma_rows_aligned(dtype, in, out), "convT3d: MFMA path needs 16-byte aligned input rows");
+    SEGMI_CHECK_ARG(!residual || residual_rows_aligned(dtype, residual),
+                    "convT3d: residual rows must be 4-element aligned");
+    ConvTParams p = mfma_params<ConvTParams>(dtype, in, out, residual, packed, bias, prelu_alpha, stats_partials);
     if (stats_fin) { p.fin_on = 1; p.bfin = bn_fin_from(stats_fin, out->c); }
     return convt_mfma_dt(dtype, p, st);
   }
   SEGMI_CHECK_ARG(w_src, "convT3d: direct path (channels not multiples of 16) needs w_src");
-  DirectParams p{};
-  p.in = in->data; p.out = out->data; p.w = w_src; p.bias = bias; p.alpha = prelu_alpha;
-  p.res = residual ? residual->data : nullptr;
-  p.N = in->n; p.Di = in->d; p.Hi = in->h; p.Wi = in->w; p.Do = out->d; p.Ho = out->h;
-  p.Wo = out->w; p.Cin = in->c; p.Cout = out->c; p.ldi = in->ld; p.ldo = out->ld;
-  p.ldr = residual ? residual->ld : 0; p.ks = 3; p.stride = 2; p.kind = 2;
+  const DirectParams p = direct_params(in, out, residual, w_src, bias, prelu_alpha, 3, 2, 2);
   SEGMI_BY_DTYPE(dtype, DIRECT, convt_direct_kernel);
 #undef DIRECT
   SEGMI_LAUNCH_CHECK("convT3d_fwd(direct)");
-  if (stats_partials) {
-    SEGMI_CHECK_ARG(!prelu_alpha && !residual,
-                    "convT3d: fused statistics are taken before PReLU/residual");
-    const int rc = bn_stats_launch(dtype, out, stats_partials, st);
-    if (rc != SEGMI_OK || !stats_fin) return rc;
-    return bn_finalize_with(stats_partials, segmi_convT3d_stats_rows(dtype, in, out), out->c, stats_fin, st);
-  }
-  return SEGMI_OK;
+  if (!stats_partials) return SEGMI_OK;
+  return direct_stats_tail("convT3d", !prelu_alpha && !residual, dtype, out, stats_partials,
+                           [&] { return segmi_convT3d_stats_rows(dtype, in, out); }, stats_fin, st);
 }
 
 }  // extern "C"

@@ -9,8 +9,7 @@
 // voxel: the epilogue (bias, BN statistics, PReLU, residual) stores 8 B (bf16) / 16 B (f32)
 // per lane, a fully coalesced NDHWC row per 4 lanes.
 #pragma once
-#include "common.h"
-#include "fin_tail.h"
+#include "conv_shared.h"
 
 namespace segmi {
 
@@ -327,17 +326,9 @@ static int launch_conv_cfg(ConvParams p, hipStream_t st) {
   // take the tickets of the finalisation
   const int stats_c = p.stats_tiles > 0 ? 16 * p.stats_tiles : p.Cout;
   const dim3 sgrid(grid.x, (unsigned)cdiv(stats_c / 16, NT));
-  const int lds = (int)fin_tail_arm(p, sgrid, 256, 2 * stats_c, lds0);
-  auto kern = conv_fwd_mfma_kernel<T, CK, KS, S, NT, TD, TH, TW>;
-  static bool attr_done = false;
-  if (!attr_done && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, grid, 256, lds, st, p);
-  SEGMI_LAUNCH_CHECK("conv3d_fwd(mfma)");
-  return SEGMI_OK;
+  const size_t lds = fin_tail_arm(p, sgrid, 256, 2 * stats_c, lds0);
+  return launch_wg256<conv_fwd_mfma_kernel<T, CK, KS, S, NT, TD, TH, TW>>(grid, lds, lds > 64 * 1024, st,
+                                                                         "conv3d_fwd(mfma)", p);
 }
 
 // tile selection per (KS, S): big tile when the output row is wide, small otherwise

@@ -244,17 +244,9 @@ static int launch_conv_ks_cfg(ConvParams p, hipStream_t st) {
   constexpr int red = 4 * 8 * NT * 64 * 16;
   constexpr int lds0 = G::LDS_BYTES > red ? G::LDS_BYTES : red;
   p.fin_on = p.fin_on && p.stats;
-  const int lds = (int)fin_tail_arm(p, grid, 256, 2 * p.Cout, lds0);
-  auto kern = conv_fwd_ks_kernel<T, CK, KS, S, NT, TD, TH, TW>;
-  static bool attr_done = false;
-  if (!attr_done && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, grid, 256, lds, st, p);
-  SEGMI_LAUNCH_CHECK("conv3d_fwd(mfma, k-split)");
-  return SEGMI_OK;
+  const size_t lds = fin_tail_arm(p, grid, 256, 2 * p.Cout, lds0);
+  return launch_wg256<conv_fwd_ks_kernel<T, CK, KS, S, NT, TD, TH, TW>>(grid, lds, lds > 64 * 1024, st,
+                                                                       "conv3d_fwd(mfma, k-split)", p);
 }
 
 // k-split tiles: 128 output voxels (8 voxel tiles) per workgroup, 16 output channels

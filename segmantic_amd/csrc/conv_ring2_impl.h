@@ -575,17 +575,9 @@ static int launch_conv_ring2_k(ConvParams p, hipStream_t st) {
   p.xcd = grid.x % 8 == 0;
   constexpr bool kStats = (MODE & 2) != 0, kBsum = MODE == 4;
   p.fin_on = p.fin_on && (kStats || kBsum);
-  (void)fin_tail_arm(p, grid, 256, (kBsum ? 3 : 2) * p.Cout, G::LDS_BYTES + 6 * CK * 4 + 4096);   // LDS: the ring is larger
-  auto kern = conv_ring2_kernel<T, CK, NT, MODE>;
-  static bool attr_done = false;
-  if (!attr_done && G::LDS_BYTES + 6 * CK * 4 + 4096 > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES + 6 * CK * 4 + 4096);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, grid, 256, G::LDS_BYTES + 6 * CK * 4 + 4096, st, p);
-  SEGMI_LAUNCH_CHECK("conv3d_fwd(ring2)");
-  return SEGMI_OK;
+  constexpr size_t lds = G::LDS_BYTES + 6 * CK * 4 + 4096;
+  (void)fin_tail_arm(p, grid, 256, (kBsum ? 3 : 2) * p.Cout, lds);   // LDS: the ring is larger
+  return launch_wg256<conv_ring2_kernel<T, CK, NT, MODE>>(grid, lds, lds > 64 * 1024, st, "conv3d_fwd(ring2)", p);
 }
 
 template <typename T, int CK, int NT>

@@ -456,27 +456,10 @@ __global__ __launch_bounds__(256, 2) void conv_ring3_kernel(ConvParams p) {
   }
 
   if constexpr (BSUM) {
-    float* red = reinterpret_cast<float*>(smem);  // [wave][3][16]  (ring no longer needed)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float a0 = row16_sum(bs0[e]);
-      const float a1 = row16_sum(bs1[e]);
-      const float a2 = row16_sum(bs2[e]);
-      if (r == 0) {
-        red[(wave * 3 + 0) * 16 + 4 * g + e] = a0;
-        red[(wave * 3 + 1) * 16 + 4 * g + e] = a1;
-        red[(wave * 3 + 2) * 16 + 4 * g + e] = a2;
-      }
-    }
-    __syncthreads();
-    if (tid < 48) {
-      const int which = tid / 16, ch = tid % 16;
-      float sacc = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) sacc += red[(w * 3 + which) * 16 + ch];
-      if (which == 1) sacc *= bprm[16 + ch];   // sum dz*(x - mean) -> sum dz*xhat
-      fin_store(&p.bpart[((int64_t)blockIdx.x * 3 + which) * p.Cout + nt0 * 16 + ch], sacc);
-    }
+    // the ring is no longer needed: its LDS takes the sums.  Row 1, sum dz*(x - mean), becomes sum dz*xhat by invstd
+    float* red = reinterpret_cast<float*>(smem);
+    wg_chan_rows_sum<1>(wave, 4 * g, r, red, bs0, bs1, bs2);
+    wg_chan_rows_put<3, 1, 1>(red, p.bpart, p.Cout, nt0 * 16, bprm + 16);
     fin_tail_run<BnBwdFin, 256, offsetof(ConvParams, ft), offsetof(ConvParams, bbfin)>(p.bpart, smem);
   }
   if (want_stats) {
@@ -523,16 +506,7 @@ static int launch_conv_ring3_k(ConvParams p, hipStream_t st) {
   constexpr bool kStats = (MODE & 2) != 0, kBsum = MODE == 4;
   p.fin_on = p.fin_on && (kStats || kBsum);
   (void)fin_tail_arm(p, grid, 256, (kBsum ? 3 : 2) * p.Cout, G::LDS_BYTES);   // LDS: the ring is larger than the tail's need
-  auto kern = conv_ring3_kernel<T, MODE>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              G::LDS_BYTES);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, grid, 256, G::LDS_BYTES, st, p);
-  SEGMI_LAUNCH_CHECK("conv3d_fwd(ring3)");
-  return SEGMI_OK;
+  return launch_wg256<conv_ring3_kernel<T, MODE>>(grid, G::LDS_BYTES, true, st, "conv3d_fwd(ring3)", p);
 }
 
 template <typename T>

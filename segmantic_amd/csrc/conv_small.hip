@@ -6,8 +6,7 @@
 //             / residual epilogue.
 //   wgrad   : MFMA with the voxel axis as K and (ci, tap) as N (see conv_small_wgrad_kernel);
 //             persistent workgroups, per-workgroup partial slabs (deterministic).
-#include "common.h"
-#include "fin_tail.h"
+#include "conv_shared.h"
 
 namespace segmi {
 
@@ -295,24 +294,9 @@ __global__ __launch_bounds__(256) void conv_small_fwd_kernel(SmallConvParams p) 
   }
   if (p.stats) {
     __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);  // [wave][2][16]
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float a0 = row16_sum(ssum[e]);
-      const float b0 = row16_sum(ssq[e]);
-      if (r == 0) {
-        red[(wave * 2 + 0) * 16 + 4 * g + e] = a0;
-        red[(wave * 2 + 1) * 16 + 4 * g + e] = b0;
-      }
-    }
-    __syncthreads();
-    if (tid < 32) {
-      const int which = tid / 16, ch = tid % 16;
-      float sacc = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) sacc += red[(w * 2 + which) * 16 + ch];
-      fin_store(&p.stats[((int64_t)blockIdx.x * 2 + which) * p.Cout + co0 + ch], sacc);
-    }
+    float* red = reinterpret_cast<float*>(smem);
+    wg_chan_rows_sum<1>(wave, 4 * g, r, red, ssum, ssq);
+    wg_chan_rows_put<2, 1>(red, p.stats, p.Cout, co0);
     fin_tail_run<BnFin, 256, offsetof(SmallConvParams, ft), offsetof(SmallConvParams, bfin)>(p.stats, smem);
   }
 }
@@ -575,15 +559,8 @@ static int launch_small_wgrad(const SmallWgradParams& p, int grid, hipStream_t s
   constexpr int stage = 256 * 16 * ES + CIN * 3 * ROWS * 16 * ES;
   constexpr int red = 4 * NTL * 64 * 4 * 4;
   constexpr int lds = stage > red ? stage : red;
-  static bool attr_set = false;
-  if (lds > 64 * 1024 && !attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_small_wgrad_kernel<T, S, CIN>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_small_wgrad_kernel<T, S, CIN>), dim3(grid, p.Cout / 16), 256, lds, st, p);
-  SEGMI_LAUNCH_CHECK("conv3d_wgrad(small-cin)");
-  return SEGMI_OK;
+  return launch_wg256<conv_small_wgrad_kernel<T, S, CIN>>(dim3(grid, p.Cout / 16), lds, lds > 64 * 1024, st,
+                                                          "conv3d_wgrad(small-cin)", p);
 }
 
 template <typename T, int S>

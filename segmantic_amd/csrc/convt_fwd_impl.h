@@ -10,8 +10,7 @@
 // reusing its weight fragments across the 4 voxel tiles.  D[co][vox] orientation and epilogue
 // as in conv_fwd_impl.h; voxel (z,y,x) of class (rd,rh,rw) lands at (2z+rd, 2y+rh, 2x+rw).
 #pragma once
-#include "common.h"
-#include "fin_tail.h"
+#include "conv_shared.h"
 
 namespace segmi {
 
@@ -310,26 +309,9 @@ __global__ __launch_bounds__(256) void convt_fwd_mfma_kernel(ConvTParams p) {
 
   if (p.stats) {
     __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);  // [wave][2][NT*16]
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float a = row16_sum(ssum[j][e]);
-        const float b = row16_sum(ssq[j][e]);
-        if (r == 0) {
-          red[(wave * 2 + 0) * NT * 16 + j * 16 + 4 * g + e] = a;
-          red[(wave * 2 + 1) * NT * 16 + j * 16 + 4 * g + e] = b;
-        }
-      }
-    __syncthreads();
-    if (tid < 2 * NT * 16) {
-      const int which = tid / (NT * 16), ch = tid % (NT * 16);
-      float sacc = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) sacc += red[(w * 2 + which) * NT * 16 + ch];
-      fin_store(&p.stats[((int64_t)blockIdx.x * 2 + which) * p.Cout + nt0 * 16 + ch], sacc);
-    }
+    float* red = reinterpret_cast<float*>(smem);
+    wg_chan_rows_sum<NT>(wave, 4 * g, r, red, ssum, ssq);
+    wg_chan_rows_put<2, NT>(red, p.stats, p.Cout, nt0 * 16);
     fin_tail_run<BnFin, 256, offsetof(ConvTParams, ft), offsetof(ConvTParams, bfin)>(p.stats, smem);
   }
 }
@@ -345,11 +327,9 @@ static int launch_convt_cfg(ConvTParams p, hipStream_t st) {
   dim3 grid((unsigned)nb, (unsigned)(p.Cout / (16 * NT)));
   constexpr int lds0 = G::LDS_BYTES > 4 * 2 * NT * 16 * 4 ? G::LDS_BYTES : 4 * 2 * NT * 16 * 4;
   p.fin_on = p.fin_on && p.stats;
-  const int lds = (int)fin_tail_arm(p, grid, 256, 2 * p.Cout, lds0);
+  const size_t lds = fin_tail_arm(p, grid, 256, 2 * p.Cout, lds0);
   SEGMI_CHECK_ARG(lds <= 64 * 1024, "convT3d: LDS budget");
-  hipLaunchKernelGGL((convt_fwd_mfma_kernel<T, CK, NT, TD, TH, TW>), grid, 256, lds, st, p);
-  SEGMI_LAUNCH_CHECK("convT3d_fwd(mfma)");
-  return SEGMI_OK;
+  return launch_wg256<convt_fwd_mfma_kernel<T, CK, NT, TD, TH, TW>>(grid, lds, false, st, "convT3d_fwd(mfma)", p);
 }
 
 template <typename T, int CK>

@@ -343,19 +343,12 @@ static int launch_convt_ps_cfg(ConvTParams p, hipStream_t st) {
   // 32-bit staging offsets inside one halo tile
   SEGMI_CHECK_ARG((int64_t)3 * p.Hi * p.Wi * p.ldi * G::ES < (1ll << 31),
                   "convT3d: input plane too large for the persistent kernel");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)convt_ps_kernel<T, NT, NCH>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-    attr_set = true;
-  }
   p.fin_on = p.fin_on && p.stats;
-  const size_t lds = fin_tail_arm(p, dim3((unsigned)cdiv(ntiles, per)), 256, 2 * p.Cout, G::LDS_BYTES);
+  const dim3 grid((unsigned)cdiv(ntiles, per));
+  const size_t lds = fin_tail_arm(p, grid, 256, 2 * p.Cout, G::LDS_BYTES);
   SEGMI_CHECK_ARG(lds == (size_t)G::LDS_BYTES, "convT3d: LDS budget");
-  hipLaunchKernelGGL((convt_ps_kernel<T, NT, NCH>), cdiv(ntiles, per), 256, G::LDS_BYTES, st, p,
-                     ntiles, per);
-  SEGMI_LAUNCH_CHECK("convT3d_fwd(persistent)");
-  return SEGMI_OK;
+  return launch_wg256<convt_ps_kernel<T, NT, NCH>>(grid, lds, true, st, "convT3d_fwd(persistent)", p, ntiles,
+                                                   per);
 }
 
 template <typename T>
