@@ -1,6 +1,9 @@
 """CPU oracle of the evaluation contract (segmantic_amd/seg/evaluation.py), written from the definitions:
 brute-force distance transforms for small sizes, a numpy separable exact transform (minimum over every
-parabola of a line, vectorised over lines) for 64^3 - 160^3, and the metrics as numpy restates them."""
+parabola of a line, vectorised over lines) for 64^3 - 160^3, and the metrics as numpy restates them.  For the direct
+calls of the csrc/distance.hip entry points: the label boxes, the unit-spacing passes restated with their float32
+roundings, the signed map over a box, the sampler's query values and exactly rounded sums, and the seeded faults
+(FAULTS) that tests/test_evaluation_limits_host.py shows the comparisons reject."""
 from __future__ import annotations
 
 import math
@@ -8,13 +11,27 @@ import math
 import numpy as np
 
 
-def contour(mask: np.ndarray) -> np.ndarray:
-    """foreground voxels with a background face neighbour (outside the image = background)"""
+FAULTS = ("no_z_faces", "outside_is_foreground", "no_sign", "no_clamp")
+
+
+def _fault(fault):
+    if fault is not None and fault not in FAULTS:
+        raise ValueError(f"unknown seeded fault {fault!r}")
+    return fault
+
+
+def contour(mask: np.ndarray, fault=None) -> np.ndarray:
+    """foreground voxels with a background face neighbour (outside the image = background).
+    Seeded faults (the host test shows that the comparisons reject them): "no_z_faces" never looks along the
+    first axis of a 3-D mask, "outside_is_foreground" takes a neighbour outside the image for foreground."""
+    fault = _fault(fault)
     m = mask.astype(bool)
     inner = m.copy()
     for ax in range(m.ndim):
+        if fault == "no_z_faces" and m.ndim == 3 and ax == 0:
+            continue
         pad = [(1, 1) if a == ax else (0, 0) for a in range(m.ndim)]
-        p = np.pad(m, pad, constant_values=False)
+        p = np.pad(m, pad, constant_values=fault == "outside_is_foreground")
         lo = [slice(None)] * m.ndim
         hi = [slice(None)] * m.ndim
         lo[ax] = slice(0, -2)
@@ -26,14 +43,17 @@ def contour(mask: np.ndarray) -> np.ndarray:
 def edt_sq_brute(feature: np.ndarray, spacing) -> np.ndarray:
     """squared distance of every voxel to the nearest True voxel of feature (f64; inf when none)"""
     sp = np.asarray(spacing, np.float64)
-    pts = np.argwhere(feature).astype(np.float64) * sp
-    grid = np.indices(feature.shape).reshape(feature.ndim, -1).T.astype(np.float64) * sp
+    pts = np.argwhere(feature).astype(np.float64)
+    grid = np.indices(feature.shape).reshape(feature.ndim, -1).T.astype(np.float64)
     if len(pts) == 0:
         return np.full(feature.shape, np.inf)
     out = np.empty(len(grid))
-    for s in range(0, len(grid), 4096):
-        g = grid[s:s + 4096]
-        out[s:s + 4096] = ((g[:, None, :] - pts[None, :, :]) ** 2).sum(-1).min(1)
+    step = max(1, min(4096, (1 << 22) // len(pts)))
+    for s in range(0, len(grid), step):
+        g = grid[s:s + step]
+        # index differences are exact; then one rounding each for the product with the spacing and its square
+        # and one per addition: at most (1 + 2^-53)^4 - 1 relative, all terms being non-negative
+        out[s:s + step] = (((g[:, None, :] - pts[None, :, :]) * sp) ** 2).sum(-1).min(1)
     return out.reshape(feature.shape)
 
 
@@ -50,6 +70,88 @@ def edt_sq_separable(feature: np.ndarray, spacing) -> np.ndarray:
             np.minimum(out, g[j][None] + w.reshape((n,) + (1,) * (g.ndim - 1)), out=out)
         g = np.moveaxis(out, 0, ax)
     return g
+
+
+def edt_sq_passes_f32(feature: np.ndarray) -> np.ndarray:
+    """The unit-spacing transform as csrc/distance.hip's integer path computes it: one pass per axis, each the exact
+    lower envelope D[i] = min_j g[j] + (i - j)^2 (brute force over the line; integers below 2^53 are exact in f64),
+    each rounded to float32 before the next pass reads it.  Below 2^24 nothing is rounded and this is the exact
+    transform; beyond, the later passes work on rounded heights."""
+    g = np.where(feature, 0.0, np.inf)
+    for ax in range(g.ndim):
+        g = np.moveaxis(g, ax, 0)
+        n = g.shape[0]
+        out = np.full_like(g, np.inf)
+        idx = np.arange(n, dtype=np.float64).reshape((n,) + (1,) * (g.ndim - 1))
+        for j in range(n):
+            if np.isfinite(g[j]).any():
+                np.minimum(out, g[j][None] + (idx - j) ** 2, out=out)
+        g = np.moveaxis(out.astype(np.float32).astype(np.float64), 0, ax)
+    return g.astype(np.float32)
+
+
+def box_slices(box, ndim=3):
+    """slices of a half-open z0 z1 y0 y1 x0 x1 box; a 2-D volume drops the z pair"""
+    sl = tuple(slice(int(box[2 * a]), int(box[2 * a + 1])) for a in range(3))
+    return sl[3 - ndim:]
+
+
+def signed_edt_sq(labels: np.ndarray, label: int, feature: int, spacing, box=None, fault=None):
+    """(f64 squared distances over the box, the sign bit each value carries) of ops.edt_sq: the feature set is the
+    label (feature 0) or contour(label) of the FULL volume (feature 1), cut to the box; distances are measured
+    inside the box; with feature 1 the label's voxels carry the sign bit ("no_sign": none does)."""
+    fault = _fault(fault)
+    m = labels == label
+    f = contour(m, fault) if feature else m
+    sl = box_slices(box, labels.ndim) if box is not None else tuple(slice(None) for _ in range(labels.ndim))
+    m, f = m[sl], f[sl]
+    sign = m if feature and fault != "no_sign" else np.zeros(m.shape, bool)
+    return edt_sq_brute(f, spacing), sign
+
+
+def query_values(dist: np.ndarray, labels: np.ndarray, label: int, query: int, box=None, fault=None) -> np.ndarray:
+    """the squared distances ops.edt_sample reads at its query voxels, in C order of the box, as float32:
+    ``dist`` is the signed map over the box (array order), the queries are contour(labels == label) of the full
+    volume (query 1, value |d|) or the label itself (query 0, d <= 0 -> 0; "no_clamp" leaves |d| there)."""
+    fault = _fault(fault)
+    m = labels == label
+    q = contour(m, fault) if query else m
+    if box is not None:
+        q = q[box_slices(box, labels.ndim)]
+    d = np.asarray(dist, np.float32)[q]
+    if query or fault == "no_clamp":
+        return np.abs(d)
+    return np.where(d <= 0, np.float32(0), d)
+
+
+def sample_stats(d2: np.ndarray):
+    """(count, sum, sum of squares, max) of sqrt(d2) in f64 with exactly rounded sums (math.fsum), and the bound
+    count * 2^-52 * sum|terms| that a sum of the same terms in any other order stays within"""
+    d2 = np.asarray(d2, np.float64)
+    n = d2.size
+    if n == 0:
+        return (0, 0.0, 0.0, 0.0), (0.0, 0.0)
+    d = np.sqrt(d2)
+    s, q = math.fsum(d.tolist()), math.fsum(d2.tolist())
+    return (n, s, q, float(d.max())), (n * 2.0 ** -52 * s, n * 2.0 ** -52 * q)
+
+
+def label_boxes(pred: np.ndarray, truth: np.ndarray, k: int):
+    """(int32 [k, 6] half-open z0 z1 y0 y1 x0 x1 of pred == c | truth == c, zeros when absent; int64 [k, 2] voxel
+    counts in pred and truth) of ops.label_boxes; labels outside 0 .. k-1 count for nothing.  2-D inputs are [y, x]
+    with z = 0."""
+    p3 = pred.reshape((1,) * (3 - pred.ndim) + pred.shape).astype(np.int64)
+    t3 = truth.reshape(p3.shape).astype(np.int64)
+    boxes = np.zeros((k, 6), np.int32)
+    counts = np.zeros((k, 2), np.int64)
+    for j, a in enumerate((p3, t3)):
+        v = a[(a >= 0) & (a < k)]
+        counts[:, j] = np.bincount(v, minlength=k)
+    for c in np.flatnonzero(counts.sum(1)):
+        at = np.argwhere((p3 == c) | (t3 == c))
+        lo, hi = at.min(0), at.max(0) + 1
+        boxes[c] = [lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]]
+    return boxes, counts
 
 
 def directed(query_pts: np.ndarray, dist_sq: np.ndarray) -> np.ndarray:
