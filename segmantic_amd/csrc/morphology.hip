@@ -16,7 +16,8 @@
 // parabola only when it is strictly lower) and the outermost pass runs along z, so z dominates y dominates x.
 // Arithmetic: with one spacing for all axes every comparison is i64 arithmetic on voxel counts (exact);
 // otherwise candidates are compared as the f64 value ((sz dz)^2 + (sy dy)^2) + (sx dx)^2, formed in that
-// order with no contraction, so candidates at mirrored offsets compare bit-equal.
+// order with no contraction, so candidates at mirrored offsets compare bit-equal.  P2 alone stays in i64
+// whenever sy == sx (thick slices): within a plane the voxel counts order the candidates exactly.
 #include "labelvol.h"
 
 namespace segmi {
@@ -385,13 +386,18 @@ int segmi_feature_transform(const void* labels, int label_bytes, int d, int h, i
   LV_BY_LABEL(label_bytes, P1);
 #undef P1
   const int g2 = (int)cdiv64((int64_t)p.bd * p.bw, 256), g3 = (int)cdiv64((int64_t)p.bh * p.bw, 256);
-  if (p.exact) {
+  // P2 only orders candidates of one plane: with sy == sx that order is the one of the voxel counts
+  // dy^2 + dx^2, whatever sz is.  In f64 the sums (sy dy)^2 + (sx dx)^2 of two offsets that are equally far
+  // (3, 4 against 5, 0) can differ in the last bit, and P2 would drop the candidate with the smaller raster
+  // index although the full distances P3 compares are bit-equal.
+  if (p.exact || p.sy == p.sx)
     hipLaunchKernelGGL(ft_p2_kernel<true>, g2, 256, 0, st, p);
-    hipLaunchKernelGGL(ft_p3_kernel<true>, g3, 256, 0, st, p);
-  } else {
+  else
     hipLaunchKernelGGL(ft_p2_kernel<false>, g2, 256, 0, st, p);
+  if (p.exact)
+    hipLaunchKernelGGL(ft_p3_kernel<true>, g3, 256, 0, st, p);
+  else
     hipLaunchKernelGGL(ft_p3_kernel<false>, g3, 256, 0, st, p);
-  }
   SEGMI_LAUNCH_CHECK("feature_transform");
   return SEGMI_OK;
 }

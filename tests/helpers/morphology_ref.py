@@ -1,8 +1,14 @@
 """CPU oracle of the morphology contract (segmantic_amd/seg/morphology.py), written from the definitions in
 float64 / int64 numpy: a brute-force nearest feature with the tie rule for small sizes, the separable form
 (x, then y, then z, every pass preferring the smaller coordinate) for 48^3 - 256^3, the six label operations
-composed exactly as defined, and the flag for voxels whose outcome hangs on rounding under unequal spacings."""
+composed exactly as defined, and the flag for voxels whose outcome hangs on rounding under unequal spacings.
+A third form of the nearest feature, ``nearest_envelope``, restates the three passes of the kernels step by step
+(with deliberate faults to choose from), and ``scattered`` / ``slab`` / ``staircase`` / ``cliff`` are inputs that
+produce ties in bulk, full-depth stacks and whole-stack pops."""
 from __future__ import annotations
+
+import contextlib
+from collections import namedtuple
 
 import numpy as np
 
@@ -92,14 +98,21 @@ def nearest_separable(feature: np.ndarray, spacing=None):
         better = val < best
         best = np.where(better, val, best)
         X = np.where(better, j, X)
-    # y: candidates are the row results of the same column
-    best = np.full(f.shape, big, vt)
+    # y: candidates are the row results of the same column.  With sy == sx the order within a plane is the
+    # one of the voxel counts, and is taken in integers whatever sz is (as the kernels do): the f64 sums of two
+    # equally far offsets (3, 4 against 5, 0) may differ in the last bit.
+    plane_exact = sy == sx
+    plane_big = np.iinfo(np.int64).max if plane_exact else np.inf
+    best = np.full(f.shape, plane_big, np.int64 if plane_exact else np.float64)
     Y = np.full(f.shape, -1, np.int64)
     X2 = np.full(f.shape, -1, np.int64)
     for j in range(h):
         xj = X[:, j:j + 1, :]
         ok = xj >= 0
-        val = np.where(ok, term(sy, yy - j) + term(sx, xx - xj), big)
+        if plane_exact:
+            val = np.where(ok, (yy - j) * (yy - j) + (xx - xj) * (xx - xj), plane_big)
+        else:
+            val = np.where(ok, term(sy, yy - j) + term(sx, xx - xj), plane_big)
         better = val < best
         best = np.where(better, val, best)
         Y = np.where(better, j, Y)
@@ -124,6 +137,127 @@ def nearest_separable(feature: np.ndarray, spacing=None):
     return index.reshape(feature.shape), dsq.reshape(feature.shape)
 
 
+ENVELOPE_FAULTS = ("fill_on_equal", "right_on_tie", "drop_hx")
+EnvelopeStats = namedtuple("EnvelopeStats", "depth2 depth3 pops2 pops3")   # deepest stack and most entries
+#                                                                            dropped by one newcomer, P2 and P3
+
+
+def _envelope_line(cand, sa, exact, fill_on_equal, drop_hx):
+    """One line of P2 / P3 as ``ft_envelope_line`` does it.  cand[q] is None or (hy, hx, payload): the two
+    height terms of the candidate found at position q (Python ints when exact, else floats, i.e. f64) and what
+    to hand on.  -> ([(position, payload, value) per sample] or None without a candidate, deepest stack, most
+    pops by one newcomer)."""
+    n = len(cand)
+    w2 = sa * sa
+    sv, sc = [], []
+    depth = pops = 0
+    for q in range(n):
+        c = cand[q]
+        if c is None:
+            continue
+        gq = c[0] + c[1]
+        step = 0
+        while len(sv) >= 2:
+            vb, va = sv[-1], sv[-2]
+            gb, ga = sc[-1][0] + sc[-1][1], sc[-2][0] + sc[-2][1]
+            qb, ba = q * q - vb * vb, vb * vb - va * va               # the position terms, in integers
+            if exact:
+                pop = ((gq - gb) + qb) * (vb - va) <= ((gb - ga) + ba) * (q - vb)
+            else:
+                pop = ((gq - gb) + w2 * float(qb)) * float(vb - va) <= ((gb - ga) + w2 * float(ba)) * float(q - vb)
+            if not pop:
+                break
+            sv.pop()
+            sc.pop()
+            step += 1
+        sv.append(q)
+        sc.append(c)
+        depth, pops = max(depth, len(sv)), max(pops, step)
+    if not sv:
+        return None, 0, 0
+
+    def value(t, k):
+        hy, hx, _ = sc[k]
+        if exact:
+            return (t - sv[k]) * (t - sv[k]) + hy + (0 if drop_hx else hx)
+        a = sa * float(t - sv[k])
+        v = a * a + hy
+        return v if drop_hx else v + hx
+
+    out = []
+    k = 0
+    for t in range(n):
+        c0 = value(t, k)
+        while k + 1 < len(sv):
+            c1 = value(t, k + 1)
+            if not (c1 <= c0 if fill_on_equal else c1 < c0):         # on only to a strictly lower parabola
+                break
+            k, c0 = k + 1, c1
+        out.append((sv[k], sc[k][2], c0))
+    return out, depth, pops
+
+
+def nearest_envelope(feature: np.ndarray, spacing=None, fault=None):
+    """The same result the way the kernels reach it.  P1: per row the nearest feature column at or left of x
+    and right of x, the left one on a tie.  P2 along y, P3 along z: the lower envelope with the kernels' pop
+    test ``((gq - gb) + w2 qb) (vb - va) <= ((gb - ga) + w2 ba) (q - vb)`` (i64 for equal spacings, and in P2
+    whenever sy == sx; else f64 with the position terms formed in integers), heights ``hy + hx``, values ``((sa dt)^2 + hy) + hx``, and a
+    fill that moves on only to a strictly lower value.  -> (index, squared distance, EnvelopeStats).
+
+    ``fault`` selects one deliberate error: "fill_on_equal" (the fill also moves on to an equal value),
+    "right_on_tie" (P1 keeps the right column on a tie), "drop_hx" (the x height left out of P3's value)."""
+    assert fault is None or fault in ENVELOPE_FAULTS, fault
+    sp3 = spacing3(spacing, feature.ndim)
+    sz, sy, sx = sp3
+    exact = sz == sy == sx
+    f = _as3(feature.astype(bool))
+    d, h, w = f.shape
+    fill_eq = fault == "fill_on_equal"
+    # P1
+    cols = np.arange(w)
+    left = np.maximum.accumulate(np.where(f, cols, -1), axis=2)
+    right = np.minimum.accumulate(np.where(f, cols, w)[..., ::-1], axis=2)[..., ::-1]
+    right = np.where(right == w, -1, right)
+    nearer = (right - cols <= cols - left) if fault == "right_on_tie" else (right - cols < cols - left)
+    X = np.where((right >= 0) & ((left < 0) | nearer), right, left)
+
+    def sq(s, delta, integers=exact):
+        if integers:
+            return delta * delta
+        t = s * float(delta)
+        return t * t
+
+    # P2: in integers also when only sy == sx
+    plane_exact = sy == sx
+    Y = np.full(f.shape, -1, np.int64)
+    X2 = np.full(f.shape, -1, np.int64)
+    depth2 = pops2 = 0
+    zero = 0 if plane_exact else 0.0
+    for z in range(d):
+        for x in range(w):
+            col = X[z, :, x].tolist()
+            cand = [None if c < 0 else (zero, sq(sx, x - c, plane_exact), c) for c in col]
+            out, dep, pop = _envelope_line(cand, sy, plane_exact, fill_eq, False)
+            depth2, pops2 = max(depth2, dep), max(pops2, pop)
+            if out is not None:
+                Y[z, :, x] = [o[0] for o in out]
+                X2[z, :, x] = [o[1] for o in out]
+    # P3
+    index = np.full(f.shape, -1, np.int32)
+    dsq = np.full(f.shape, np.inf)
+    depth3 = pops3 = 0
+    for y in range(h):
+        for x in range(w):
+            ys, xs = Y[:, y, x].tolist(), X2[:, y, x].tolist()
+            cand = [None if yy < 0 else (sq(sy, y - yy), sq(sx, x - xx), (yy, xx)) for yy, xx in zip(ys, xs)]
+            out, dep, pop = _envelope_line(cand, sz, exact, fill_eq, fault == "drop_hx")
+            depth3, pops3 = max(depth3, dep), max(pops3, pop)
+            if out is not None:
+                index[:, y, x] = [(o[0] * h + o[1][0]) * w + o[1][1] for o in out]
+                dsq[:, y, x] = [float(o[2]) * (sx * sx) if exact else o[2] for o in out]
+    return index.reshape(feature.shape), dsq.reshape(feature.shape), EnvelopeStats(depth2, depth3, pops2, pops3)
+
+
 def index_planes(index: np.ndarray) -> np.ndarray:
     """linear indices -> int32 [ndim, ...] coordinates (scipy's return_indices layout), -1 where there is none"""
     shape = index.shape
@@ -139,8 +273,22 @@ def distance_transform_edt(img, sampling=None, nearest=nearest_separable):
     return np.sqrt(dsq), dsq, index
 
 
+_within = np.less_equal      # the closed ball; ``radius_open`` swaps in the open one
+
+
+@contextlib.contextmanager
+def radius_open():
+    """the deliberate fault of the label operations: inside this block a radius reaches ``<`` instead of ``<=``"""
+    global _within
+    _within = np.less
+    try:
+        yield
+    finally:
+        _within = np.less_equal
+
+
 def _gather(labels, index, dsq, r2):
-    take = (labels == 0) & (index >= 0) & (dsq <= r2)
+    take = (labels == 0) & (index >= 0) & _within(dsq, r2)
     out = labels.copy()
     out[take] = labels.reshape(-1)[index[take]]
     return out
@@ -190,7 +338,7 @@ def erode_labels(labels, radius, spacing=None, applied_labels=None, nearest=near
             sl = tuple(slice(max(int(lo) - 1, 0), int(hi) + 2) for lo, hi in zip(pts.min(0), pts.max(0)))
         _, dsq = nearest(labels[sl] != L, spacing)
         sub = out[sl]
-        sub[mask[sl] & (dsq <= radius_sq(radius))] = 0
+        sub[mask[sl] & _within(dsq, radius_sq(radius))] = 0
     return out
 
 
@@ -241,7 +389,79 @@ def ambiguous(feature: np.ndarray, outcome=None, spacing=None, radius=None, k: i
     return flag.reshape(feature.shape)
 
 
+def near_tie(feature: np.ndarray, spacing=None, k: int = 16) -> np.ndarray:
+    """bool per voxel: two different features among the k nearest have squared distances that differ by a
+    relative amount in (0, REL], the smaller one being the minimum: which of them is nearest hangs on rounding.
+    Exact ties are not flagged (the tie rule decides them)."""
+    return ambiguous(feature, np.arange(feature.size, dtype=np.int64).reshape(feature.shape), spacing, None, k)
+
+
+def on_radius(dsq: np.ndarray, radius) -> np.ndarray:
+    """bool per voxel: the squared distance equals radius^2 exactly, the one point where <= and < differ"""
+    return np.asarray(dsq) == radius_sq(radius)
+
+
+def features_at_minimum(feature: np.ndarray, spacing=None) -> np.ndarray:
+    """int per voxel: how many features lie at exactly the smallest squared distance (brute force)"""
+    sp3 = spacing3(spacing, feature.ndim)
+    f = _as3(feature.astype(bool))
+    pts = np.argwhere(f)
+    count = np.zeros(f.size, np.int64)
+    if len(pts):
+        grid = np.indices(f.shape).reshape(3, -1).T
+        step = max(1, (1 << 22) // len(pts))
+        for s in range(0, len(grid), step):
+            g = grid[s:s + step]
+            d2 = dist_sq(g[:, None, 0] - pts[None, :, 0], g[:, None, 1] - pts[None, :, 1],
+                         g[:, None, 2] - pts[None, :, 2], sp3)
+            count[s:s + step] = (d2 == d2.min(axis=1, keepdims=True)).sum(axis=1)
+    return count.reshape(feature.shape)
+
+
 # ------------------------------------------------------------------ seeded inputs
+def scattered(shape, density: float, seed: int, n_labels: int, dtype=np.uint8) -> np.ndarray:
+    """a label map whose non-zero voxels are random single points (a share ``density`` of the voxels) with
+    random labels 1 .. n_labels: many features, most voxels between several of them"""
+    rs = np.random.RandomState(seed)
+    points = rs.random_sample(shape) < density
+    values = rs.randint(1, n_labels + 1, size=shape)
+    return np.where(points, values, 0).astype(dtype)
+
+
+def slab(shape, x0: int, x1: int, seed: int, n_labels: int, dtype=np.uint8) -> np.ndarray:
+    """every voxel with x0 <= x < x1 is labelled (random labels): every row hands a candidate to every line of
+    P2 and P3, all of one line equally high, so no parabola is ever dropped and the stack grows to the line's
+    length"""
+    rs = np.random.RandomState(seed)
+    out = np.zeros(shape, dtype)
+    out[..., x0:x1] = rs.randint(1, n_labels + 1, size=out[..., x0:x1].shape)
+    return out
+
+
+def staircase(shape, step: int = 3, dtype=np.uint8) -> np.ndarray:
+    """one labelled voxel per row at x = step * y (rows whose step leaves the array stay empty), the same in
+    every z plane; the label is 1 + y % 5.  Along y the heights are a quadratic in y, so every parabola stays
+    on the envelope: a full-depth stack of unequal heights."""
+    out = np.zeros(shape, dtype)
+    h, w = shape[-2], shape[-1]
+    for y in range(h):
+        if step * y < w:
+            out[..., y, step * y] = 1 + y % 5
+    return out
+
+
+def cliff(shape, dtype=np.uint8) -> np.ndarray:
+    """column x = 0 is labelled 1 everywhere, and the last voxel of the volume (last plane, last row, last
+    column) is labelled 2.  In the last plane the line of P2 at the last column stacks h - 1 equally high
+    parabolas and the last row's candidate, of height 0, drops all of them but the lowest entry in one step;
+    the line of P3 through the last row and column does the same along z."""
+    out = np.zeros(shape, dtype)
+    out[..., 0] = 1
+    out[(-1,) * len(shape)] = 2
+    return out
+
+
+
 def ellipsoids(shape, n_labels: int, seed: int, lo: float = 3.0, hi: float = 9.0, margin: float = 6.0,
                dtype=np.uint8, values=None) -> np.ndarray:
     """a label map of n_labels seeded ellipsoids (label i + 1, or values[i]); later ones overwrite earlier"""
