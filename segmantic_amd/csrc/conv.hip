@@ -2,7 +2,6 @@
 // kernels used when a channel count is not a multiple of 16 (first layer Cin=1, K=3 heads,
 // tiny test networks).
 #include "conv_fwd_impl.h"
-#include "conv_ring_impl.h"
 #include "conv_ks_impl.h"
 #include "convt_ps_impl.h"
 #include "conv_bnbwd_impl.h"
@@ -12,41 +11,38 @@ namespace segmi {
 int conv_s2_bnbwd_bf16(const ConvBnBwdParams& p, hipStream_t st);
 int conv_s2_bnbwd_f16(const ConvBnBwdParams& p, hipStream_t st);
 
-int conv_mfma_f32(const ConvParams& p, int ksize, int stride, hipStream_t st);
-int conv_mfma_bf16(const ConvParams& p, int ksize, int stride, hipStream_t st);
-int conv_mfma_f16(const ConvParams& p, int ksize, int stride, hipStream_t st);
-int convt_mfma_f32(const ConvTParams& p, hipStream_t st);
-int convt_mfma_bf16(const ConvTParams& p, hipStream_t st);
-int convt_mfma_f16(const ConvTParams& p, hipStream_t st);
+int conv_mfma_f32(const ConvParams& p, const ConvPlan& pl, int ksize, int stride, hipStream_t st);
+int conv_mfma_bf16(const ConvParams& p, const ConvPlan& pl, int ksize, int stride, hipStream_t st);
+int conv_mfma_f16(const ConvParams& p, const ConvPlan& pl, int ksize, int stride, hipStream_t st);
+int convt_mfma_f32(const ConvTParams& p, const ConvTPlan& pl, hipStream_t st);
+int convt_mfma_bf16(const ConvTParams& p, const ConvTPlan& pl, hipStream_t st);
+int convt_mfma_f16(const ConvTParams& p, const ConvTPlan& pl, hipStream_t st);
 // the MFMA families by storage format: one translation unit and one function name per type, so the choice
 // is spelled out here instead of going through SEGMI_BY_DTYPE; it fails closed all the same
-static inline int conv_mfma_dt(int dtype, const ConvParams& p, int ksize, int stride, hipStream_t st) {
-  if (dtype == SEGMI_F32) return conv_mfma_f32(p, ksize, stride, st);
-  if (dtype == SEGMI_F16) return conv_mfma_f16(p, ksize, stride, st);
+static inline int conv_mfma_dt(int dtype, const ConvParams& p, const ConvPlan& pl, int ksize, int stride, hipStream_t st) {
+  if (dtype == SEGMI_F32) return conv_mfma_f32(p, pl, ksize, stride, st);
+  if (dtype == SEGMI_F16) return conv_mfma_f16(p, pl, ksize, stride, st);
   SEGMI_CHECK_ARG(dtype == SEGMI_BF16, "conv3d: unknown dtype code %d", dtype);
-  return conv_mfma_bf16(p, ksize, stride, st);
+  return conv_mfma_bf16(p, pl, ksize, stride, st);
 }
-static inline int convt_mfma_dt(int dtype, const ConvTParams& p, hipStream_t st) {
-  if (dtype == SEGMI_F32) return convt_mfma_f32(p, st);
-  if (dtype == SEGMI_F16) return convt_mfma_f16(p, st);
+static inline int convt_mfma_dt(int dtype, const ConvTParams& p, const ConvTPlan& pl, hipStream_t st) {
+  if (dtype == SEGMI_F32) return convt_mfma_f32(p, pl, st);
+  if (dtype == SEGMI_F16) return convt_mfma_f16(p, pl, st);
   SEGMI_CHECK_ARG(dtype == SEGMI_BF16, "convT3d: unknown dtype code %d", dtype);
-  return convt_mfma_bf16(p, st);
+  return convt_mfma_bf16(p, pl, st);
 }
 int bn_stats_launch(int dtype, const segmi_act* x, float* partials, hipStream_t st, const BiasFin* bias_fin = nullptr);
-int bn_stats_rows_for(const segmi_act* x);
 int stats_reserve_rows();
 // the separate finalisation launch with a segmi_bn_fin's arguments (generic / direct paths)
 static inline int bn_finalize_with(const float* partials, int rows, int c, const segmi_bn_fin* f, hipStream_t st) {
   return segmi_bn_finalize(partials, rows, c, f->count, f->gamma, f->beta, f->running_mean, f->running_var,
                            f->momentum, f->eps, f->mean, f->invstd, f->scale, f->shift, st);
 }
-bool conv_small_ok(int cin, int cout, int ksize);
-int conv_small_fwd(int dtype, const segmi_act* in, const segmi_act* out, const float* w,
+int conv_small_fwd(int dtype, const ConvPlan& pl, const segmi_act* in, const segmi_act* out, const float* w,
                    const float* bias, const float* alpha, const segmi_act* res, float* stats,
                    int stride, hipStream_t st, const segmi_act* out2 = nullptr,
                    const float* w2 = nullptr, const float* bias2 = nullptr,
                    const segmi_bn_fin* fin = nullptr, const segmi_windows* win = nullptr);
-int conv_small_fwd_rows(const segmi_act* out);
 
 struct DirectParams {
   const void* in;
@@ -144,8 +140,6 @@ __global__ void convt_direct_kernel(DirectParams p) {
   }
 }
 
-static inline bool mfma_ok(int cin, int cout) { return cin % 16 == 0 && cout % 16 == 0; }
-
 // what the MFMA kernels ask of the views: 16-byte aligned input rows, 4-element aligned output / residual rows
 static inline bool mfma_rows_aligned(int dtype, const segmi_act* in, const segmi_act* out) {
   const int es = dtype_size(dtype);
@@ -191,14 +185,13 @@ static inline DirectParams direct_params(const segmi_act* in, const segmi_act* o
 }
 
 // statistics behind a direct kernel: a pass over the written output, then the separate (small) finalisation
-// launch of the generic path over rows() partial rows.  `plain`: the launch had neither PReLU nor residual
-template <class Rows>
-static int direct_stats_tail(const char* name, bool plain, int dtype, const segmi_act* out, float* stats, Rows rows,
+// launch of the generic path over the table's `rows` partial rows.  `plain`: the launch had neither PReLU nor residual
+static int direct_stats_tail(const char* name, bool plain, int dtype, const segmi_act* out, float* stats, int rows,
                              const segmi_bn_fin* fin, hipStream_t st) {
   SEGMI_CHECK_ARG(plain, "%s: fused statistics are taken before PReLU/residual", name);
   const int rc = bn_stats_launch(dtype, out, stats, st);
   if (rc != SEGMI_OK || !fin) return rc;
-  return bn_finalize_with(stats, rows(), out->c, fin, st);
+  return bn_finalize_with(stats, rows, out->c, fin, st);
 }
 
 static inline int out_extent(int in, int ks, int stride) {
@@ -210,11 +203,9 @@ static inline int out_extent(int in, int ks, int stride) {
 
 using namespace segmi;
 
-// the first-layer kernel (conv_small.hip) takes the layer: shared by the launch and the rows query
-static inline bool small_fwd_eligible(int dtype, const segmi_act* in, const segmi_act* out, int ksize) {
-  const int es = dtype_size(dtype);
-  return conv_small_ok(in->c, out->c, ksize) && out->ld % 4 == 0 &&
-         ((uintptr_t)out->data % (4 * es)) == 0;
+// what a query reads: the plan of the layer with the ring3 / ring2 choice made for rows as wide as the output's
+static inline ConvPlan query_plan(int dtype, const segmi_act* in, const segmi_act* out, int ksize, int stride) {
+  return conv_plan(dtype, in, out, ksize, stride, out->ld, out->ld);
 }
 
 extern "C" {
@@ -222,22 +213,15 @@ extern "C" {
 int segmi_conv3d_stats_rows(int dtype, const segmi_act* in, const segmi_act* out, int ksize,
                             int stride) {
   if (!in || !out) return 0;
-  if (mfma_ok(in->c, out->c)) {
-    if (conv_ring_ok(dtype, in->c, ksize, stride, out))
-      return conv_ring_rows(dtype, in->c, out) + stats_reserve_rows();
-    if (conv_ks_ok(dtype, in->c, ksize, stride)) return conv_ks_rows(out) + stats_reserve_rows();
-    return conv_mfma_rows(out, stride) + stats_reserve_rows();
-  }
-  if (small_fwd_eligible(dtype, in, out, ksize)) return conv_small_fwd_rows(out) + stats_reserve_rows();
-  return bn_stats_rows_for(out) + stats_reserve_rows();
+  return query_plan(dtype, in, out, ksize, stride).grid_x + stats_reserve_rows();
 }
 
 int segmi_conv3d_pair_ok(int dtype, const segmi_act* in, const segmi_act* out_a,
                          const segmi_act* out_b) {
   if (!act_ok(in) || !act_ok(out_a) || !act_ok(out_b)) return 0;
   if (!dtype_ok(dtype)) return 0;
-  return !mfma_ok(in->c, out_a->c) && small_fwd_eligible(dtype, in, out_a, 3) &&
-         small_fwd_eligible(dtype, in, out_b, 3) && out_a->c == out_b->c && out_a->n == out_b->n &&
+  return query_plan(dtype, in, out_a, 3, 1).family == kConvSmallCin &&
+         query_plan(dtype, in, out_b, 3, 1).family == kConvSmallCin && out_a->c == out_b->c && out_a->n == out_b->n &&
          out_a->d == out_b->d && out_a->h == out_b->h && out_a->w == out_b->w;
 }
 
@@ -265,7 +249,7 @@ int segmi_conv3d_fwd_pair(int dtype, const segmi_act* in, const segmi_act* out_a
                   "conv3d_fwd_pair: output extent does not match the input");
   SEGMI_CHECK_ARG(!(stats_partials_a && prelu_alpha_a),
                   "conv3d_fwd_pair: fused statistics are taken before PReLU");
-  return conv_small_fwd(dtype, in, out_a, w_a, bias_a, prelu_alpha_a, nullptr, stats_partials_a,
+  return conv_small_fwd(dtype, query_plan(dtype, in, out_a, 3, stride), in, out_a, w_a, bias_a, prelu_alpha_a, nullptr, stats_partials_a,
                         stride, (hipStream_t)stream, out_b, w_b, bias_b, stats_fin_a, windows);
 }
 
@@ -273,8 +257,7 @@ int segmi_conv3d_split_act_ok(int dtype, const segmi_act* in, const segmi_act* o
                               int stride) {
   if (!act_ok(in) || !act_ok(out) || !dtype_ok(dtype)) return 0;
   // the tile kernel must take the layer (it is the one that honours act_tiles): k3 stride 2 MFMA
-  return mfma_ok(in->c, out->c) && ksize == 3 && stride == 2 && !conv_ks_ok(dtype, in->c, ksize, stride) &&
-         !conv_ring_ok(dtype, in->c, ksize, stride, out);
+  return query_plan(dtype, in, out, ksize, stride).split_act;
 }
 
 int segmi_conv3d_fwd_split_act(int dtype, const segmi_act* in, const segmi_act* out, const void* packed,
@@ -301,48 +284,28 @@ int segmi_conv3d_fwd_split_act(int dtype, const segmi_act* in, const segmi_act* 
     SEGMI_CHECK_ARG(!stats_fin, "conv3d_fwd_split_act: stats_fin needs stats_partials");
   }
   hipStream_t st = (hipStream_t)stream;
-  return conv_mfma_dt(dtype, p, ksize, stride, st);
+  return conv_mfma_dt(dtype, p, conv_plan(dtype, in, out, ksize, stride, 0, 0), ksize, stride, st);
 }
 
 const char* segmi_conv3d_fwd_kernel_name(int dtype, const segmi_act* in, const segmi_act* out,
                                          int ksize, int stride) {
   static thread_local char buf[96];
   if (!act_ok(in) || !act_ok(out)) return "invalid";
-  const char* dt = dtype_name(dtype);
-  if (mfma_ok(in->c, out->c)) {
-    const int ck = pick_ck(dtype, in->c);
-    if (conv_ring_ok(dtype, in->c, ksize, stride, out)) {
-      if (conv_ring3_shape_ok(in->c, out->c, in->data, out->data, in->d, in->h, in->w, in->ld, out->d, out->h, out->w, out->ld,
-                              out->ld, out->ld))
-        snprintf(buf, sizeof buf, "conv_ring3_kernel<%s, CK=16> (LDS-DMA ring)", dt);
-      else
-        snprintf(buf, sizeof buf, "conv_ring2_kernel<%s, CK=%d, NT=%d>", dt, ck,
-                 ck == 32 && (out->c / 16) % 2 == 0 ? 2 : 1);
-    }
-    else if (conv_ks_ok(dtype, in->c, ksize, stride))
-      snprintf(buf, sizeof buf, "conv_fwd_ks_kernel<%s, k%d s%d>", dt, ksize, stride);
-    else
-      snprintf(buf, sizeof buf, "conv_fwd_mfma_kernel<%s, CK=%d, k%d s%d>", dt, ck, ksize, stride);
-    return buf;
-  }
-  if (small_fwd_eligible(dtype, in, out, ksize)) snprintf(buf, sizeof buf, "conv_small_fwd_kernel<%s>", dt);
-  else snprintf(buf, sizeof buf, "conv_direct_kernel<%s>", dt);
-  return buf;
+  return conv_plan_name(query_plan(dtype, in, out, ksize, stride), dtype, ksize, stride, buf, sizeof buf);
 }
 
 int segmi_conv3d_in_affine_ok(int dtype, const segmi_act* in, const segmi_act* out, int ksize,
                               int stride) {
   if (!act_ok(in) || !act_ok(out) || !dtype_h16(dtype) || !mfma_ok(in->c, out->c)) return 0;
   // forward: the bf16 / fp16 z-marching ring; weight gradient: the MFMA kernel (any channel blocking)
-  return ksize == 3 && stride == 1 && conv_ring_ok(dtype, in->c, ksize, stride, out) ? 1 : 0;
+  return query_plan(dtype, in, out, ksize, stride).in_affine ? 1 : 0;
 }
 
 int segmi_conv3d_bn_bwd_sums_ok(int dtype, const segmi_act* in, const segmi_act* out, int ksize,
                                 int stride) {
   if (!act_ok(in) || !act_ok(out) || !dtype_h16(dtype)) return 0;
-  // the ring kernels' MODE 4: 16 -> 16 (conv_ring3 / conv_ring2<bf16, 16, 1>) and 32 -> 32 (conv_ring2<bf16, 32, 2>)
-  return ((in->c == 16 && out->c == 16) || (in->c == 32 && out->c == 32)) && ksize == 3 && stride == 1 &&
-                 conv_ring_ok(dtype, in->c, ksize, stride, out) ? 1 : 0;
+  // the ring kernels' MODE 4: 16 -> 16 (conv_ring3 / conv_ring2<bf16, 16, 1>) and 32 -> 32 (conv_ring2<bf16, 32, 1>)
+  return query_plan(dtype, in, out, ksize, stride).bn_bwd_sums ? 1 : 0;
 }
 
 int segmi_bn_act_bwd_apply_conv_ok(int dtype, const segmi_act* dy, const segmi_act* x, const segmi_act* dx,
@@ -413,6 +376,7 @@ int segmi_conv3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, const
                   out->n, out->d, out->h, out->w, in->n, in->d, in->h, in->w, ksize, stride);
   SEGMI_CHECK_ARG(!residual || residual_matches(residual, out), "conv3d: residual shape mismatch");
   hipStream_t st = (hipStream_t)stream;
+  const ConvPlan pl = conv_plan(dtype, in, out, ksize, stride, residual ? residual->ld : 0, bn_bwd ? bn_bwd->x->ld : 0);
   if (mfma_ok(in->c, out->c)) {
     SEGMI_CHECK_ARG(packed, "conv3d: MFMA path needs a fragment-packed weight (segmi_wpack)");
     SEGMI_CHECK_ARG(mfma_rows_aligned(dtype, in, out), "conv3d: MFMA path needs 16-byte aligned input rows");
@@ -432,17 +396,17 @@ int segmi_conv3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, const
       }
     }
     if (stats_fin) { p.fin_on = 1; p.bfin = bn_fin_from(stats_fin, out->c); }
-    return conv_mfma_dt(dtype, p, ksize, stride, st);
+    return conv_mfma_dt(dtype, p, pl, ksize, stride, st);
   }
   SEGMI_CHECK_ARG(w_src, "conv3d: direct path (channels not multiples of 16) needs w_src");
   SEGMI_CHECK_ARG(w_kind == 0 || w_kind == 1, "conv3d: bad w_kind %d", w_kind);
-  SEGMI_CHECK_ARG(!(stats_partials && small_fwd_eligible(dtype, in, out, ksize) && w_kind != 0),
+  SEGMI_CHECK_ARG(!(stats_partials && pl.family == kConvSmallCin && w_kind != 0),
                   "conv3d: fused statistics on a small-Cin layer need the forward weight kind");
-  if (small_fwd_eligible(dtype, in, out, ksize) && w_kind == 0 &&
+  if (pl.family == kConvSmallCin && w_kind == 0 &&
       (!residual || residual_rows_aligned(dtype, residual))) {
     SEGMI_CHECK_ARG(!stats_partials || (!prelu_alpha && !residual),
                     "conv3d: fused statistics are taken before PReLU/residual");
-    return conv_small_fwd(dtype, in, out, w_src, bias, prelu_alpha, residual, stats_partials, stride,
+    return conv_small_fwd(dtype, pl, in, out, w_src, bias, prelu_alpha, residual, stats_partials, stride,
                           st, nullptr, nullptr, nullptr, stats_fin);
   }
   const DirectParams p = direct_params(in, out, residual, w_src, bias, prelu_alpha, ksize, stride, w_kind);
@@ -451,13 +415,12 @@ int segmi_conv3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, const
   SEGMI_LAUNCH_CHECK("conv3d_fwd(direct)");
   if (!stats_partials) return SEGMI_OK;
   return direct_stats_tail("conv3d", !prelu_alpha && !residual, dtype, out, stats_partials,
-                           [&] { return segmi_conv3d_stats_rows(dtype, in, out, ksize, stride); }, stats_fin, st);
+                           pl.grid_x + stats_reserve_rows(), stats_fin, st);
 }
 
 int segmi_convT3d_stats_rows(int dtype, const segmi_act* in, const segmi_act* out) {
   if (!in || !out) return 0;
-  if (mfma_ok(in->c, out->c)) return convt_mfma_rows(dtype, in, out->c) + stats_reserve_rows();
-  return bn_stats_rows_for(out) + stats_reserve_rows();
+  return convt_plan(dtype, in, out).grid_x + stats_reserve_rows();
 }
 
 int segmi_convT3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, const void* packed,
@@ -482,7 +445,7 @@ int segmi_convT3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, cons
                     "convT3d: residual rows must be 4-element aligned");
     ConvTParams p = mfma_params<ConvTParams>(dtype, in, out, residual, packed, bias, prelu_alpha, stats_partials);
     if (stats_fin) { p.fin_on = 1; p.bfin = bn_fin_from(stats_fin, out->c); }
-    return convt_mfma_dt(dtype, p, st);
+    return convt_mfma_dt(dtype, p, convt_plan(dtype, in, out), st);
   }
   SEGMI_CHECK_ARG(w_src, "convT3d: direct path (channels not multiples of 16) needs w_src");
   const DirectParams p = direct_params(in, out, residual, w_src, bias, prelu_alpha, 3, 2, 2);
@@ -491,7 +454,7 @@ int segmi_convT3d_fwd(int dtype, const segmi_act* in, const segmi_act* out, cons
   SEGMI_LAUNCH_CHECK("convT3d_fwd(direct)");
   if (!stats_partials) return SEGMI_OK;
   return direct_stats_tail("convT3d", !prelu_alpha && !residual, dtype, out, stats_partials,
-                           [&] { return segmi_convT3d_stats_rows(dtype, in, out); }, stats_fin, st);
+                           convt_plan(dtype, in, out).grid_x + stats_reserve_rows(), stats_fin, st);
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 // per lane, a fully coalesced NDHWC row per 4 lanes.
 #pragma once
 #include "conv_shared.h"
+#include "conv_plan.h"
 
 namespace segmi {
 
@@ -312,14 +313,12 @@ __global__ __launch_bounds__(256) void conv_fwd_mfma_kernel(ConvParams p) {
 }
 
 template <typename T, int CK, int KS, int S, int NT, int TD, int TH, int TW>
-static int launch_conv_cfg(ConvParams p, hipStream_t st) {
+static int launch_conv_cfg(ConvParams p, const ConvPlan& pl, hipStream_t st) {
   using G = ConvGeom<T, CK, KS, S, TD, TH, TW>;
-  p.tz = cdiv(p.Do, TD);
-  p.ty = cdiv(p.Ho, TH);
-  p.tx = cdiv(p.Wo, TW);
-  const int64_t nb = (int64_t)p.N * p.tz * p.ty * p.tx;
-  SEGMI_CHECK_ARG(nb < (1ll << 31), "conv3d: too many tiles");
-  dim3 grid((unsigned)nb, (unsigned)(p.Cout / (16 * NT)));
+  p.tz = pl.tz; p.ty = pl.ty; p.tx = pl.tx;
+  SEGMI_CHECK_ARG(TD == pl.td && TH == pl.th && TW == pl.tw && pl.grid_x > 0 && (int64_t)p.N * p.tz * p.ty * p.tx == pl.grid_x,
+                  "conv3d: too many tiles, or the tile kernel's grid is not the planned one");
+  dim3 grid((unsigned)pl.grid_x, (unsigned)(p.Cout / (16 * NT)));
   constexpr int lds0 = G::LDS_BYTES > 4 * 2 * NT * 16 * 4 ? G::LDS_BYTES : 4 * 2 * NT * 16 * 4;
   p.fin_on = p.fin_on && p.stats;
   // statistics of the first stats_tiles channel tiles only (training pair): those workgroups write the rows and
@@ -331,58 +330,29 @@ static int launch_conv_cfg(ConvParams p, hipStream_t st) {
                                                                          "conv3d_fwd(mfma)", p);
 }
 
-// tile selection per (KS, S): big tile when the output row is wide, small otherwise
-template <typename T, int CK, int KS, int S, int NT>
-static int launch_conv_tiles(const ConvParams& p, hipStream_t st) {
-  const bool wide = p.Wo > 8;
-  if constexpr (S == 1) {
-    if (wide) return launch_conv_cfg<T, CK, KS, S, NT, 4, 8, 16>(p, st);
-    return launch_conv_cfg<T, CK, KS, S, NT, 4, 4, 8>(p, st);
-  } else {
-    if (wide) return launch_conv_cfg<T, CK, KS, S, NT, 2, 4, 16>(p, st);
-    return launch_conv_cfg<T, CK, KS, S, NT, 2, 4, 8>(p, st);
-  }
-}
-
-template <typename T, int CK, int KS, int S>
-static int launch_conv_nt(const ConvParams& p, hipStream_t st) {
-  const int nt = p.Cout / 16;
-  // output-channel tiles per workgroup: as many as divide Cout (input tile reuse), but fewer
-  // when the launch would not fill the chip (deep levels: 8^3 .. 16^3 voxels)
-  const bool wide = p.Wo > 8;
-  const int td = S == 1 ? 4 : 2, th = S == 1 ? (wide ? 8 : 4) : 4, tw = wide ? 16 : 8;
-  const int64_t tiles = (int64_t)p.N * cdiv(p.Do, td) * cdiv(p.Ho, th) * cdiv(p.Wo, tw);
-  int sel = nt % 4 == 0 ? 4 : (nt % 2 == 0 ? 2 : 1);
-  while (sel > 1 && tiles * (nt / sel) < 512) sel /= 2;
-  if (sel == 4) return launch_conv_tiles<T, CK, KS, S, 4>(p, st);
-  if (sel == 2) return launch_conv_tiles<T, CK, KS, S, 2>(p, st);
-  return launch_conv_tiles<T, CK, KS, S, 1>(p, st);
-}
-
+// the tile kernel's instantiation of a plan: channel chunk, (k, s), output tiles per workgroup, tile width (the
+// tile's shape follows from stride and width: conv_tile_shape)
+constexpr int conv_tile_key(int ck, int ks, int s, int nt, int tw) { return (((ck * 4 + ks) * 4 + s) * 8 + nt) * 32 + tw; }
 template <typename T>
-static int launch_conv_mfma_t(const ConvParams& p, int ksize, int stride, hipStream_t st) {
-  constexpr int dt = DtypeOf<T>::value;
-  const int ck = pick_ck(dt, p.Cin);
-  if constexpr (sizeof(T) == 2) {
-    if (ck == 32) {
-      if (ksize == 3 && stride == 1) return launch_conv_nt<T, 32, 3, 1>(p, st);
-      if (ksize == 3 && stride == 2) return launch_conv_nt<T, 32, 3, 2>(p, st);
-      if (ksize == 1 && stride == 1) return launch_conv_nt<T, 32, 1, 1>(p, st);
-    }
+static int launch_conv_tile(const ConvParams& p, const ConvPlan& pl, int ksize, int stride, hipStream_t st) {
+#define TILE_W(CK, KS, S, NT, WIDE)                                                \
+  case conv_tile_key(CK, KS, S, NT, conv_tile_shape(S, WIDE).tw): {                \
+    constexpr Tile3 t = conv_tile_shape(S, WIDE);                                  \
+    return launch_conv_cfg<T, CK, KS, S, NT, t.td, t.th, t.tw>(p, pl, st);         \
   }
-  if (ksize == 3 && stride == 1) return launch_conv_nt<T, 16, 3, 1>(p, st);
-  if (ksize == 3 && stride == 2) return launch_conv_nt<T, 16, 3, 2>(p, st);
-  if (ksize == 1 && stride == 1) return launch_conv_nt<T, 16, 1, 1>(p, st);
+#define TILE_NT(CK, KS, S, NT) TILE_W(CK, KS, S, NT, true) TILE_W(CK, KS, S, NT, false)
+#define TILE_KS(CK, KS, S) TILE_NT(CK, KS, S, 1) TILE_NT(CK, KS, S, 2) TILE_NT(CK, KS, S, 4)
+#define TILE_CK(CK) TILE_KS(CK, 3, 1) TILE_KS(CK, 3, 2) TILE_KS(CK, 1, 1)
+  const int key = conv_tile_key(pl.ck, ksize, stride, pl.nt, pl.tw);
+  if constexpr (sizeof(T) == 2) {
+    switch (key) { TILE_CK(32) }
+  }
+  switch (key) { TILE_CK(16) }
+#undef TILE_CK
+#undef TILE_KS
+#undef TILE_NT
+#undef TILE_W
   SEGMI_UNSUPPORTED("conv3d: unsupported ksize/stride %d/%d", ksize, stride);
-}
-
-// stats rows of the MFMA path (= spatial workgroups)
-static inline int conv_mfma_rows(const segmi_act* out, int stride) {
-  const bool wide = out->w > 8;
-  int td, th, tw;
-  if (stride == 1) { td = 4; th = wide ? 8 : 4; tw = wide ? 16 : 8; }
-  else { td = 2; th = 4; tw = wide ? 16 : 8; }
-  return out->n * cdiv(out->d, td) * cdiv(out->h, th) * cdiv(out->w, tw);
 }
 
 }  // namespace segmi

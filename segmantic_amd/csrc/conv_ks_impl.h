@@ -233,14 +233,12 @@ __global__ __launch_bounds__(256) void conv_fwd_ks_kernel(ConvParams p) {
 }
 
 template <typename T, int CK, int KS, int S, int NT, int TD, int TH, int TW>
-static int launch_conv_ks_cfg(ConvParams p, hipStream_t st) {
+static int launch_conv_ks_cfg(ConvParams p, const ConvPlan& pl, hipStream_t st) {
   using G = ConvGeom<T, CK, KS, S, TD, TH, TW>;
-  p.tz = cdiv(p.Do, TD);
-  p.ty = cdiv(p.Ho, TH);
-  p.tx = cdiv(p.Wo, TW);
-  const int64_t nb = (int64_t)p.N * p.tz * p.ty * p.tx;
-  SEGMI_CHECK_ARG(nb < (1ll << 31), "conv3d: too many tiles");
-  dim3 grid((unsigned)nb, (unsigned)(p.Cout / (16 * NT)));
+  p.tz = pl.tz; p.ty = pl.ty; p.tx = pl.tx;
+  SEGMI_CHECK_ARG(TD == pl.td && TH == pl.th && TW == pl.tw && pl.grid_x > 0 && (int64_t)p.N * p.tz * p.ty * p.tx == pl.grid_x,
+                  "conv3d: too many tiles, or the k-split kernel's grid is not the planned one");
+  dim3 grid((unsigned)pl.grid_x, (unsigned)(p.Cout / (16 * NT)));
   constexpr int red = 4 * 8 * NT * 64 * 16;
   constexpr int lds0 = G::LDS_BYTES > red ? G::LDS_BYTES : red;
   p.fin_on = p.fin_on && p.stats;
@@ -249,34 +247,17 @@ static int launch_conv_ks_cfg(ConvParams p, hipStream_t st) {
                                                                        "conv3d_fwd(mfma, k-split)", p);
 }
 
-// k-split tiles: 128 output voxels (8 voxel tiles) per workgroup, 16 output channels
-static inline int conv_ks_rows(const segmi_act* out) {
-  const bool wide = out->w > 8;
-  const int td = wide ? 2 : 4, th = 4, tw = wide ? 16 : 8;
-  return out->n * cdiv(out->d, td) * cdiv(out->h, th) * cdiv(out->w, tw);
-}
-// Layers the k-split kernel takes: k3 s1 with at least one channel chunk (single-chunk layers
-// included) of one-k-step-per-tap width.  Measured with cold caches (scripts/conv_microbench.py,
-// batch 8): 128->128 @16^3 99 -> 56 us, 256->256 @8^3 60 -> 36 us, 256->128 @16^3 181 -> 98 us, 64->64 @32^3 119 -> 114 us;
-// stride 2 does not gain (86 -> 97 us) and stays on conv_fwd_impl.h.
-static inline bool conv_ks_ok(int dtype, int cin, int ksize, int stride) {
-  if (ksize != 3 || stride != 1) return false;
-  const int ck = pick_ck(dtype, cin);
-  const int spt = ck / (dtype == SEGMI_F32 ? 4 : 8);
-  return spt == 4 && cin >= ck;
-}
-
+// the k-split kernel's instantiation of a plan: output tiles per workgroup x tile width (conv_ks_tile_shape)
 template <typename T, int CK>
-static int launch_conv_ks_t(const ConvParams& p, hipStream_t st) {
-  const segmi_act o{nullptr, p.N, p.Do, p.Ho, p.Wo, p.Cout, p.Cout};
-  const int nt = p.Cout / 16;
-  // two output tiles per workgroup (input fragment reuse) unless that leaves < 512 workgroups
-  const bool two = nt % 2 == 0 && (int64_t)conv_ks_rows(&o) * (nt / 2) >= 512;
-  const bool wide = p.Wo > 8;
-  if (two) return wide ? launch_conv_ks_cfg<T, CK, 3, 1, 2, 2, 4, 16>(p, st)
-                       : launch_conv_ks_cfg<T, CK, 3, 1, 2, 4, 4, 8>(p, st);
-  return wide ? launch_conv_ks_cfg<T, CK, 3, 1, 1, 2, 4, 16>(p, st)
-              : launch_conv_ks_cfg<T, CK, 3, 1, 1, 4, 4, 8>(p, st);
+static int launch_conv_ks(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
+#define KS_CASE(NT, WIDE)                                                          \
+  case NT * 32 + conv_ks_tile_shape(WIDE).tw: {                                    \
+    constexpr Tile3 t = conv_ks_tile_shape(WIDE);                                  \
+    return launch_conv_ks_cfg<T, CK, 3, 1, NT, t.td, t.th, t.tw>(p, pl, st);       \
+  }
+  switch (pl.nt * 32 + pl.tw) { KS_CASE(2, true) KS_CASE(2, false) KS_CASE(1, true) KS_CASE(1, false) }
+#undef KS_CASE
+  SEGMI_UNSUPPORTED("conv3d: no k-split kernel of %d output tiles per workgroup", pl.nt);
 }
 
 }  // namespace segmi

@@ -554,24 +554,24 @@ __global__ __launch_bounds__(256, CK == 16 ? 2 : 1) void conv_ring2_kernel(ConvP
 }
 
 template <typename T, int CK, int NT, int MODE>
-static int launch_conv_ring2_k(ConvParams p, hipStream_t st) {
+static int launch_conv_ring2_k(ConvParams p, const ConvPlan& pl, hipStream_t st) {
   using G = RingGeom<T, CK>;
-  constexpr int dt = DtypeOf<T>::value;
-  p.tz = conv_ring_zsplit(dt, p.Cin, 3, 1, p.N, p.Do, p.Ho, p.Wo);
-  p.ty = cdiv(p.Ho, G::TH);
-  p.tx = cdiv(p.Wo, G::TW);
+  static_assert(G::TD == kRingTile.td && G::TH == kRingTile.th && G::TW == kRingTile.tw, "the plan's ring tile");
+  p.tz = pl.zsplit; p.ty = pl.ty; p.tx = pl.tx;
   // 32-bit byte offsets inside one input / output plane
-  SEGMI_CHECK_ARG((int64_t)p.Hi * p.Wi * p.ldi * 2 < (1ll << 31) && (int64_t)p.Ho * p.Wo * p.ldo < (1ll << 31) &&
-                      (int64_t)p.Ho * p.Wo * (p.ldr > 0 ? p.ldr : 1) < (1ll << 31),
+  SEGMI_CHECK_ARG((int64_t)p.Hi * p.Wi * p.ldi * 2 < kOffsetLimit && (int64_t)p.Ho * p.Wo * p.ldo < kOffsetLimit &&
+                      (int64_t)p.Ho * p.Wo * (p.ldr > 0 ? p.ldr : 1) < kOffsetLimit,
                   "conv3d: plane too large for the ring kernel's 32-bit offsets");
   // plane index x plane size as a 32-bit product: one sample of every operand below 2^31 (bytes for
   // the input, elements for the others)
-  SEGMI_CHECK_ARG((int64_t)(p.Di + 8) * p.Hi * p.Wi * p.ldi * 2 < (1ll << 31) &&
-                      (int64_t)(p.Do + 4) * p.Ho * p.Wo * p.ldo < (1ll << 31) &&
-                      (int64_t)(p.Do + 4) * p.Ho * p.Wo * (p.ldr > 0 ? p.ldr : 1) < (1ll << 31) &&
-                      (int64_t)(p.Do + 4) * p.Ho * p.Wo * (p.ldbx > 0 ? p.ldbx : 1) < (1ll << 31),
+  SEGMI_CHECK_ARG((int64_t)(p.Di + 8) * p.Hi * p.Wi * p.ldi * 2 < kOffsetLimit &&
+                      (int64_t)(p.Do + 4) * p.Ho * p.Wo * p.ldo < kOffsetLimit &&
+                      (int64_t)(p.Do + 4) * p.Ho * p.Wo * (p.ldr > 0 ? p.ldr : 1) < kOffsetLimit &&
+                      (int64_t)(p.Do + 4) * p.Ho * p.Wo * (p.ldbx > 0 ? p.ldbx : 1) < kOffsetLimit,
                   "conv3d: sample too large for the ring kernel's 32-bit plane offsets");
-  dim3 grid((unsigned)(p.N * p.ty * p.tx * p.tz), (unsigned)(p.Cout / (16 * NT)));
+  SEGMI_CHECK_ARG(pl.grid_x > 0 && (int64_t)p.N * p.ty * p.tx * p.tz == pl.grid_x,
+                  "conv3d: the ring kernel's grid is not the planned one");
+  dim3 grid((unsigned)pl.grid_x, (unsigned)(p.Cout / (16 * NT)));
   p.xcd = grid.x % 8 == 0;
   constexpr bool kStats = (MODE & 2) != 0, kBsum = MODE == 4;
   p.fin_on = p.fin_on && (kStats || kBsum);
@@ -580,33 +580,20 @@ static int launch_conv_ring2_k(ConvParams p, hipStream_t st) {
   return launch_wg256<conv_ring2_kernel<T, CK, NT, MODE>>(grid, lds, lds > 64 * 1024, st, "conv3d_fwd(ring2)", p);
 }
 
-template <typename T, int CK, int NT>
-static int launch_conv_ring2_cfg(const ConvParams& p, hipStream_t st) {
-  if constexpr (NT == 1) {
-    // MODE 4 (BatchNorm-backward sums in the input-gradient launch): 16 -> 16, and 32 -> 32 (BASELINE config 4's
-    // full-resolution layers, round 4) as two 16-channel output tiles on grid.y -- with both tiles in one workgroup
-    // (NT = 2: 216 weight registers + the sums) the variant spills 96 registers and the step got slower
-    if (p.bpart && !p.alpha && !p.stats) return launch_conv_ring2_k<T, CK, NT, 4>(p, st);
-  }
-  switch ((p.alpha ? 1 : 0) | (p.stats ? 2 : 0)) {
-    case 0: return launch_conv_ring2_k<T, CK, NT, 0>(p, st);
-    case 1: return launch_conv_ring2_k<T, CK, NT, 1>(p, st);
-    case 2: return launch_conv_ring2_k<T, CK, NT, 2>(p, st);
-    default: return launch_conv_ring2_k<T, CK, NT, 3>(p, st);
-  }
-}
-
-// bf16 / fp16 ring layers: 16 -> 16*m and 32 -> 32*m
+// bf16 / fp16 ring layers, 16 -> 16*m and 32 -> 32*m: channel chunk x output tiles per workgroup x MODE
 template <typename T>
-static int launch_conv_ring2(const ConvParams& p, hipStream_t st) {
-  const int ck = pick_ck(DtypeOf<T>::value, p.Cin);
-  const int nt = p.Cout / 16;
-  if (ck == 32) {
-    const bool sums = p.bpart && !p.alpha && !p.stats;
-    if (nt % 2 == 0 && !sums) return launch_conv_ring2_cfg<T, 32, 2>(p, st);
-    return launch_conv_ring2_cfg<T, 32, 1>(p, st);
+static int launch_conv_ring2(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
+  const int mode = conv_ring_mode(pl, p.bpart, p.alpha, p.stats), nt = mode == 4 ? 1 : pl.nt;
+#define RING2(CK, NT, MODE) case (CK * 4 + NT) * 8 + MODE: return launch_conv_ring2_k<T, CK, NT, MODE>(p, pl, st);
+#define RING2_MODES(CK, NT) RING2(CK, NT, 0) RING2(CK, NT, 1) RING2(CK, NT, 2) RING2(CK, NT, 3)
+  switch ((pl.ck * 4 + nt) * 8 + mode) {
+    RING2_MODES(16, 1) RING2(16, 1, 4)
+    RING2_MODES(32, 1) RING2(32, 1, 4)
+    RING2_MODES(32, 2)
   }
-  return launch_conv_ring2_cfg<T, 16, 1>(p, st);
+#undef RING2_MODES
+#undef RING2
+  SEGMI_UNSUPPORTED("conv3d: no ring2 kernel of CK %d, %d output tiles, MODE %d", pl.ck, pl.nt, mode);
 }
 
 }  // namespace segmi

@@ -485,23 +485,20 @@ __global__ __launch_bounds__(256, 2) void conv_ring3_kernel(ConvParams p) {
   }
 }
 
-static inline bool conv_ring3_ok(const ConvParams& p) {
-  return conv_ring3_shape_ok(p.Cin, p.Cout, p.in, p.out, p.Di, p.Hi, p.Wi, p.ldi, p.Do, p.Ho, p.Wo, p.ldo, p.ldr, p.ldbx);
-}
-
 template <typename T, int MODE>
-static int launch_conv_ring3_k(ConvParams p, hipStream_t st) {
+static int launch_conv_ring3_k(ConvParams p, const ConvPlan& pl, hipStream_t st) {
   using G = Ring3Geom;
-  p.tz = conv_ring_zsplit(DtypeOf<T>::value, p.Cin, 3, 1, p.N, p.Do, p.Ho, p.Wo);
+  static_assert(G::TH == kRingTile.th && G::TW == kRingTile.tw, "the plan's ring tile");
+  p.tz = pl.zsplit; p.ty = pl.ty; p.tx = pl.tx;
+  SEGMI_CHECK_ARG(pl.grid_x > 0 && (int64_t)p.N * p.ty * p.tx * p.tz == pl.grid_x,
+                  "conv3d: the ring kernel's grid is not the planned one");
+  dim3 grid((unsigned)pl.grid_x, (unsigned)(p.Cout / 16));
   // ring2's XCD-aware column map (XCD k walks the k-th eighth of the columns: neighbours' halos meet in one L2) is used
   // for launches of at most one round of workgroups (<= 512: the 64^3 layers -- inference 41.4 vs 42.3 ms per volume
   // with / without) and NOT for larger ones: on the full-resolution 8 x 128^3 launch (1024 workgroups, two rounds) it
   // costs 10 % (0.300 -> 0.270 ms inside the training step, step 5.11 -> 5.02 ms, alternating runs; memory-only
   // probe 289 -> 228 us).  The halo re-reads it saves there were Infinity-Cache hits, and a CU's vector-memory
   // pipe -- the bound of this kernel -- does not care where a line comes from.
-  p.ty = cdiv(p.Ho, G::TH);
-  p.tx = cdiv(p.Wo, G::TW);
-  dim3 grid((unsigned)(p.N * p.ty * p.tx * p.tz), (unsigned)(p.Cout / 16));
   p.xcd = grid.x <= 512 && grid.x % 8 == 0;
   constexpr bool kStats = (MODE & 2) != 0, kBsum = MODE == 4;
   p.fin_on = p.fin_on && (kStats || kBsum);
@@ -510,13 +507,13 @@ static int launch_conv_ring3_k(ConvParams p, hipStream_t st) {
 }
 
 template <typename T>
-static int launch_conv_ring3(const ConvParams& p, hipStream_t st) {
-  if (p.bpart && !p.alpha && !p.stats && p.Cout == 16) return launch_conv_ring3_k<T, 4>(p, st);
-  switch ((p.alpha ? 1 : 0) | (p.stats ? 2 : 0)) {
-    case 0: return launch_conv_ring3_k<T, 0>(p, st);
-    case 1: return launch_conv_ring3_k<T, 1>(p, st);
-    case 2: return launch_conv_ring3_k<T, 2>(p, st);
-    default: return launch_conv_ring3_k<T, 3>(p, st);
+static int launch_conv_ring3(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
+  switch (conv_ring_mode(pl, p.bpart, p.alpha, p.stats)) {
+    case 0: return launch_conv_ring3_k<T, 0>(p, pl, st);
+    case 1: return launch_conv_ring3_k<T, 1>(p, pl, st);
+    case 2: return launch_conv_ring3_k<T, 2>(p, pl, st);
+    case 3: return launch_conv_ring3_k<T, 3>(p, pl, st);
+    default: return launch_conv_ring3_k<T, 4>(p, pl, st);
   }
 }
 

@@ -1,5 +1,5 @@
-// conv_ring_impl.h -- geometry and plan of the persistent "z-marching" MFMA Conv3d forward for the
-// full-resolution layers (k3, stride 1, Cin = one chunk); the kernel itself is conv_ring2_impl.h.
+// conv_ring_impl.h -- geometry of the persistent "z-marching" MFMA Conv3d forward for the
+// full-resolution layers (k3, stride 1, Cin = one chunk); the kernel itself is conv_ring2_impl.h, the plan (z-split, ring3 or ring2) conv_plan.h.
 // (The first formulation -- one output plane x 8 rows per wave, described below -- needed one 1-KiB
 // LDS fragment per MFMA and spilled in its f32 and 32-channel variants; bf16 layers run ring2, f32
 // layers the K-split / tile kernels, which are 6 % faster there than the spilling ring was.)
@@ -62,49 +62,6 @@ template <> struct Raw4<f16_t> {
     return f32x4{H16<f16_t>::lo(o[0]), H16<f16_t>::hi(o[0]), H16<f16_t>::lo(o[1]), H16<f16_t>::hi(o[1])};
   }
 };
-
-
-// Plan: columns = N * ceil(H/8) * ceil(W/16); each column is cut into `zsplit` z-segments so that
-// >= ~512 workgroups exist, as long as every segment keeps >= 4 steps (else the 2-plane prologue
-// overhead and the lost pipelining make the tile-at-a-time kernel the better choice).
-// Returns zsplit, or 0 when the ring kernel should not be used.
-static inline int conv_ring_zsplit(int dtype, int cin, int ksize, int stride, int N, int Do, int Ho,
-                                   int Wo) {
-  if (!(ksize == 3 && stride == 1 && cin == pick_ck(dtype, cin) && Wo > 8)) return 0;
-  if (!dtype_h16(dtype)) return 0;
-  // the kernel addresses one sample with 32-bit "plane index x plane size" products (bytes for the
-  // input, elements for the others); rows may be strided views (ld up to 4 x cin in this engine: skip
-  // buffers, padded class axis).  Larger samples take the tile / K-split kernels (64-bit addressing)
-  // -- every eligibility predicate (in_affine_ok, bn_bwd_sums_ok, stats_rows, kernel_name) follows.
-  if ((int64_t)(Do + 8) * Ho * Wo * (4 * cin) * 2 >= (1ll << 31)) return 0;
-  const int columns = N * cdiv(Ho, 8) * cdiv(Wo, 16);
-  const int steps = cdiv(Do, 4);
-  int zs = 512 / columns;
-  if (zs < 1) zs = 1;
-  if (zs > steps / 4) zs = steps / 4;
-  if (zs < 1) return 0;
-  if (columns * zs < 256) return 0;
-  return zs;
-}
-// ring3 (conv_ring3_impl.h: LDS-DMA staging) takes a ring layer when it has 16 input channels, 16-byte aligned
-// input and output rows, and every operand sample stays below 2^31 BYTES (its out-of-range marker 2^31 + a plane offset must
-// not wrap); ring2 takes the others (top conv inside the training step: 0.295 ms on ring3, 0.313 on ring2).
-static inline bool conv_ring3_shape_ok(int cin, int cout, const void* in, const void* out, int Di, int Hi, int Wi, int ldi, int Do,
-                                       int Ho, int Wo, int ldo, int ldr, int ldbx) {
-  if (cin != 16 || cout % 16 != 0) return false;
-  const int64_t lim = 1ll << 31;
-  return (int64_t)(Di + 8) * Hi * Wi * ldi * 2 < lim && (int64_t)(Do + 4) * Ho * Wo * ldo * 2 < lim &&
-         (int64_t)(Do + 4) * Ho * Wo * (ldr > 0 ? ldr : 1) * 2 < lim &&
-         (int64_t)(Do + 4) * Ho * Wo * (ldbx > 0 ? ldbx : 1) * 2 < lim && ((uintptr_t)in % 16) == 0 && ldi % 8 == 0 &&
-         ((uintptr_t)out % 16) == 0 && ldo % 8 == 0;          // 16-byte DMA pieces and 16-byte stores
-}
-static inline bool conv_ring_ok(int dtype, int cin, int ksize, int stride, const segmi_act* out) {
-  return conv_ring_zsplit(dtype, cin, ksize, stride, out->n, out->d, out->h, out->w) > 0;
-}
-static inline int conv_ring_rows(int dtype, int cin, const segmi_act* out) {
-  return out->n * cdiv(out->h, 8) * cdiv(out->w, 16) *
-         conv_ring_zsplit(dtype, cin, 3, 1, out->n, out->d, out->h, out->w);
-}
 
 
 }  // namespace segmi

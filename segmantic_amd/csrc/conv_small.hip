@@ -7,6 +7,7 @@
 //   wgrad   : MFMA with the voxel axis as K and (ci, tap) as N (see conv_small_wgrad_kernel);
 //             persistent workgroups, per-workgroup partial slabs (deterministic).
 #include "conv_shared.h"
+#include "conv_plan.h"
 
 namespace segmi {
 
@@ -479,15 +480,6 @@ __global__ __launch_bounds__(256) void conv_small_wgrad_kernel(SmallWgradParams 
   }
 }
 
-bool conv_small_ok(int cin, int cout, int ksize) {
-  return ksize == 3 && cin >= 1 && cin <= 4 && (cout == 16 || cout == 32);
-}
-
-// partial-statistics rows of the small-Cin forward (= spatial workgroups)
-int conv_small_fwd_rows(const segmi_act* out) {
-  return out->n * cdiv(out->d, 4) * cdiv(out->h, 8) * cdiv(out->w, 16);
-}
-
 template <typename T, int S, int CIN, bool PAIR>
 static int launch_small_fwd_k(SmallConvParams p, hipStream_t st) {
   constexpr int HD = 3 * S + 3, HH = 7 * S + 3, HW = 15 * S + 3, XW = (HW + 6) / 4 * 4;
@@ -520,7 +512,7 @@ static int launch_small_fwd_cin(const SmallConvParams& p, int cin, hipStream_t s
   }
 }
 
-int conv_small_fwd(int dtype, const segmi_act* in, const segmi_act* out, const float* w,
+int conv_small_fwd(int dtype, const ConvPlan& pl, const segmi_act* in, const segmi_act* out, const float* w,
                    const float* bias, const float* alpha, const segmi_act* res, float* stats,
                    int stride, hipStream_t st, const segmi_act* out2, const float* w2,
                    const float* bias2, const segmi_bn_fin* fin, const segmi_windows* win) {
@@ -538,17 +530,13 @@ int conv_small_fwd(int dtype, const segmi_act* in, const segmi_act* out, const f
   p.res = res ? res->data : nullptr; p.ldr = res ? res->ld : 0; p.stats = stats;
   p.N = in->n; p.Di = in->d; p.Hi = in->h; p.Wi = in->w; p.Do = out->d; p.Ho = out->h; p.Wo = out->w;
   p.Cout = out->c; p.ldi = in->ld; p.ldo = out->ld;
-  p.tz = cdiv(out->d, 4); p.ty = cdiv(out->h, 8); p.tx = cdiv(out->w, 16);
-  SEGMI_CHECK_ARG((int64_t)p.N * p.tz * p.ty * p.tx < (1ll << 31), "conv3d: too many tiles");
+  p.tz = pl.tz; p.ty = pl.ty; p.tx = pl.tx;
+  SEGMI_CHECK_ARG(pl.family == kConvSmallCin && pl.grid_x > 0 && (int64_t)p.N * p.tz * p.ty * p.tx == pl.grid_x,
+                  "conv3d: too many tiles, or the small-Cin kernel's grid is not the planned one");
 #define SMALL_FWD(T) \
   return stride == 2 ? launch_small_fwd_cin<T, 2>(p, in->c, st) : launch_small_fwd_cin<T, 1>(p, in->c, st)
   SEGMI_BY_DTYPE(dtype, SMALL_FWD);
 #undef SMALL_FWD
-}
-
-int conv_small_wgrad_slabs(const segmi_act* dy) {
-  const int nt = dy->n * cdiv(dy->d, 2) * cdiv(dy->h, 8) * cdiv(dy->w, 16);
-  return nt < 1024 ? nt : 1024;
 }
 
 template <typename T, int S, int CIN>
@@ -573,15 +561,15 @@ static int launch_small_wgrad_cin(const SmallWgradParams& p, int cin, int grid, 
   }
 }
 
-int conv_small_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float* partials,
+int conv_small_wgrad(int dtype, const WgradPlan& pl, const segmi_act* x, const segmi_act* dy, float* partials,
                      int stride, hipStream_t st) {
   SmallWgradParams p{};
   p.x = x->data; p.dy = dy->data; p.partials = partials;
   p.N = x->n; p.Dx = x->d; p.Hx = x->h; p.Wx = x->w; p.Dy = dy->d; p.Hy = dy->h; p.Wy = dy->w;
   p.Cout = dy->c; p.ldx = x->ld; p.ldy = dy->ld;
-  p.tz = cdiv(dy->d, 2); p.ty = cdiv(dy->h, 8); p.tx = cdiv(dy->w, 16);
+  p.tz = cdiv(dy->d, pl.td); p.ty = cdiv(dy->h, pl.th); p.tx = cdiv(dy->w, pl.tw);
   p.ntiles = dy->n * p.tz * p.ty * p.tx;
-  const int grid = conv_small_wgrad_slabs(dy);
+  const int grid = pl.gx;
 #define SMALL_WGRAD(T) \
   return stride == 2 ? launch_small_wgrad_cin<T, 2>(p, x->c, grid, st) : launch_small_wgrad_cin<T, 1>(p, x->c, grid, st)
   SEGMI_BY_DTYPE(dtype, SMALL_WGRAD);

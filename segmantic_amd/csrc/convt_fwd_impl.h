@@ -11,6 +11,7 @@
 // as in conv_fwd_impl.h; voxel (z,y,x) of class (rd,rh,rw) lands at (2z+rd, 2y+rh, 2x+rw).
 #pragma once
 #include "conv_shared.h"
+#include "conv_plan.h"
 
 namespace segmi {
 
@@ -317,14 +318,12 @@ __global__ __launch_bounds__(256) void convt_fwd_mfma_kernel(ConvTParams p) {
 }
 
 template <typename T, int CK, int NT, int TD, int TH, int TW>
-static int launch_convt_cfg(ConvTParams p, hipStream_t st) {
+static int launch_convt_cfg(ConvTParams p, const ConvTPlan& pl, hipStream_t st) {
   using G = ConvTGeom<T, CK, TD, TH, TW>;
-  p.tz = cdiv(p.Di, TD);
-  p.ty = cdiv(p.Hi, TH);
-  p.tx = cdiv(p.Wi, TW);
-  const int64_t nb = (int64_t)p.N * p.tz * p.ty * p.tx;
-  SEGMI_CHECK_ARG(nb < (1ll << 31), "convT3d: too many tiles");
-  dim3 grid((unsigned)nb, (unsigned)(p.Cout / (16 * NT)));
+  p.tz = pl.tz; p.ty = pl.ty; p.tx = pl.tx;
+  SEGMI_CHECK_ARG(TD == pl.td && TH == pl.th && TW == pl.tw && pl.grid_x > 0 && (int64_t)p.N * p.tz * p.ty * p.tx == pl.grid_x,
+                  "convT3d: too many tiles, or the tile kernel's grid is not the planned one");
+  dim3 grid((unsigned)pl.grid_x, (unsigned)(p.Cout / (16 * NT)));
   constexpr int lds0 = G::LDS_BYTES > 4 * 2 * NT * 16 * 4 ? G::LDS_BYTES : 4 * 2 * NT * 16 * 4;
   p.fin_on = p.fin_on && p.stats;
   const size_t lds = fin_tail_arm(p, grid, 256, 2 * p.Cout, lds0);
@@ -332,39 +331,29 @@ static int launch_convt_cfg(ConvTParams p, hipStream_t st) {
   return launch_wg256<convt_fwd_mfma_kernel<T, CK, NT, TD, TH, TW>>(grid, lds, false, st, "convT3d_fwd(mfma)", p);
 }
 
-template <typename T, int CK>
-static int launch_convt_nt(const ConvTParams& p, hipStream_t st) {
-  const bool wide = p.Wi > 8;
-  const int nt = p.Cout / 16;
-  if (nt % 2 == 0) {
-    if (wide) return launch_convt_cfg<T, CK, 2, 2, 2, 16>(p, st);
-    return launch_convt_cfg<T, CK, 2, 2, 4, 8>(p, st);
-  }
-  if (wide) return launch_convt_cfg<T, CK, 1, 2, 2, 16>(p, st);
-  return launch_convt_cfg<T, CK, 1, 2, 4, 8>(p, st);
-}
-
+// the tile kernel's instantiation of a plan: channel chunk x output tiles per workgroup x tile width (convt_tile_shape)
 template <typename T>
-static int launch_convt_mfma_t(ConvTParams p, hipStream_t st) {
-  constexpr int dt = DtypeOf<T>::value;
-  const int ck = pick_ck(dt, p.Cin);
-  const PackGeom g = pack_geom(dt, p.Cin, p.Cout, 1);
+static int launch_convt_tile(ConvTParams p, const ConvTPlan& pl, hipStream_t st) {
+  const PackGeom g = pack_geom(DtypeOf<T>::value, p.Cin, p.Cout, 1);
   int64_t off = 0;
   for (int c = 0; c < 8; ++c) {
     p.class_off[c] = off;
     off += (int64_t)g.nchunks * ((ct_ntaps(c) * g.SPT + 3) / 4) * g.ntiles * 1024;
   }
-  if constexpr (sizeof(T) == 2) {
-    if (ck == 32) return launch_convt_nt<T, 32>(p, st);
+#define CT_W(CK, NT, WIDE)                                                         \
+  case (CK * 4 + NT) * 32 + convt_tile_shape(WIDE).tw: {                           \
+    constexpr Tile3 t = convt_tile_shape(WIDE);                                    \
+    return launch_convt_cfg<T, CK, NT, t.td, t.th, t.tw>(p, pl, st);               \
   }
-  return launch_convt_nt<T, 16>(p, st);
-}
-
-static inline int convt_tile_rows(int dtype, const segmi_act* in) {
-  const bool wide = in->w > 8;
-  const int td = 2, th = wide ? 2 : 4, tw = wide ? 16 : 8;
-  (void)dtype;
-  return in->n * cdiv(in->d, td) * cdiv(in->h, th) * cdiv(in->w, tw);
+#define CT_CK(CK) CT_W(CK, 2, true) CT_W(CK, 2, false) CT_W(CK, 1, true) CT_W(CK, 1, false)
+  const int key = (pl.ck * 4 + pl.nt) * 32 + pl.tw;
+  if constexpr (sizeof(T) == 2) {
+    switch (key) { CT_CK(32) }
+  }
+  switch (key) { CT_CK(16) }
+#undef CT_CK
+#undef CT_W
+  SEGMI_UNSUPPORTED("convT3d: no tile kernel of CK %d, %d output tiles per workgroup", pl.ck, pl.nt);
 }
 
 }  // namespace segmi

@@ -18,32 +18,6 @@
 
 namespace segmi {
 
-constexpr int kCtPsMaxTiles = 16;     // tiles per workgroup (upper bound)
-constexpr int kCtPsTargetWgs = 1024;  // workgroups wanted before tiles are grouped
-
-static inline int convt_ps_tiles(const int n, const int di, const int hi, const int wi) {
-  return n * cdiv(di, 2) * cdiv(hi, 2) * cdiv(wi, 16);
-}
-static inline int convt_ps_per_wg(int ntiles) {
-  int per = ntiles / kCtPsTargetWgs;
-  return per < 1 ? 1 : (per > kCtPsMaxTiles ? kCtPsMaxTiles : per);
-}
-static inline int convt_ps_grid(int ntiles) { return cdiv(ntiles, convt_ps_per_wg(ntiles)); }
-// layers the persistent kernel takes (everything else: convt_fwd_impl.h)
-static inline bool convt_ps_ok(int dtype, int cin, int cout, int wi) {
-  const int ck = dtype == SEGMI_F32 ? 16 : 32;
-  if (cin % ck || cout % 16 || wi < 16) return false;
-  const int nch = cin / ck, nt = cout / 16;
-  return (nt == 1 && nch <= 2) || (nt == 2 && nch == 1 && dtype_h16(dtype));
-}
-
-// partial-statistics rows the MFMA transposed-conv path writes (one per workgroup)
-static inline int convt_mfma_rows(int dtype, const segmi_act* in, int cout) {
-  if (convt_ps_ok(dtype, in->c, cout, in->w))
-    return convt_ps_grid(convt_ps_tiles(in->n, in->d, in->h, in->w));
-  return convt_tile_rows(dtype, in);
-}
-
 constexpr int ctps_class_off(int cls, int nch, int nt) {
   int o = 0;
   for (int p = 0; p < cls; ++p) o += nch * ct_ntaps_c(p) * nt * 1024;
@@ -332,36 +306,36 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void convt_ps_kernel(ConvTPar
 }
 
 template <typename T, int NT, int NCH>
-static int launch_convt_ps_cfg(ConvTParams p, hipStream_t st) {
+static int launch_convt_ps_cfg(ConvTParams p, const ConvTPlan& pl, hipStream_t st) {
   using G = CtPsGeom<T, NT, NCH>;
-  p.tz = cdiv(p.Di, 2);
-  p.ty = cdiv(p.Hi, 2);
-  p.tx = cdiv(p.Wi, 16);
-  const int64_t nt64 = (int64_t)p.N * p.tz * p.ty * p.tx;
-  SEGMI_CHECK_ARG(nt64 < (1ll << 31), "convT3d: too many tiles");
-  const int ntiles = (int)nt64, per = convt_ps_per_wg(ntiles);
+  p.tz = pl.tz; p.ty = pl.ty; p.tx = pl.tx;
+  const int ntiles = (int)pl.tiles, per = pl.tiles_per_wg;
+  SEGMI_CHECK_ARG(pl.family == kConvTPersistent && pl.tiles < kOffsetLimit && (int64_t)p.N * p.tz * p.ty * p.tx == pl.tiles &&
+                      pl.grid_x > 0 && cdiv(ntiles, per) == pl.grid_x,
+                  "convT3d: too many tiles, or the persistent kernel's grid is not the planned one");
   // 32-bit staging offsets inside one halo tile
-  SEGMI_CHECK_ARG((int64_t)3 * p.Hi * p.Wi * p.ldi * G::ES < (1ll << 31),
+  SEGMI_CHECK_ARG((int64_t)3 * p.Hi * p.Wi * p.ldi * G::ES < kOffsetLimit,
                   "convT3d: input plane too large for the persistent kernel");
   p.fin_on = p.fin_on && p.stats;
-  const dim3 grid((unsigned)cdiv(ntiles, per));
+  const dim3 grid((unsigned)pl.grid_x);
   const size_t lds = fin_tail_arm(p, grid, 256, 2 * p.Cout, G::LDS_BYTES);
   SEGMI_CHECK_ARG(lds == (size_t)G::LDS_BYTES, "convT3d: LDS budget");
   return launch_wg256<convt_ps_kernel<T, NT, NCH>>(grid, lds, true, st, "convT3d_fwd(persistent)", p, ntiles,
                                                    per);
 }
 
+// the persistent kernel's instantiation of a plan: output tiles x channel chunks of the layer
 template <typename T>
-static int launch_convt_ps_t(const ConvTParams& p, hipStream_t st) {
-  constexpr int CK = sizeof(T) == 2 ? 32 : 16;
-  const int nch = p.Cin / CK, nt = p.Cout / 16;
-  SEGMI_CHECK_ARG((nt == 1 && (nch == 1 || nch == 2)) || (nt == 2 && nch == 1),
-                  "convT3d: persistent kernel misuse");
+static int launch_convt_ps(const ConvTParams& p, const ConvTPlan& pl, hipStream_t st) {
+  const int key = pl.nt * 10 + p.Cin / pl.ck;
   if constexpr (sizeof(T) == 2) {
-    if (nt == 2) return launch_convt_ps_cfg<T, 2, 1>(p, st);
+    if (key == 21) return launch_convt_ps_cfg<T, 2, 1>(p, pl, st);
   }
-  if (nch == 1) return launch_convt_ps_cfg<T, 1, 1>(p, st);
-  return launch_convt_ps_cfg<T, 1, 2>(p, st);
+  switch (key) {
+    case 11: return launch_convt_ps_cfg<T, 1, 1>(p, pl, st);
+    case 12: return launch_convt_ps_cfg<T, 1, 2>(p, pl, st);
+  }
+  SEGMI_UNSUPPORTED("convT3d: persistent kernel misuse");
 }
 
 }  // namespace segmi

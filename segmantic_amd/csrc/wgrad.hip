@@ -19,17 +19,12 @@ int wgrad_cus(int cus) {
   if (env) return env;
   return cus > 0 ? clamp_cus(cus) : 256;
 }
-}  // namespace segmi
-namespace segmi {
 
-int wgrad_mfma_f32(const WgradParams& p, int ksize, int stride, int ct, int gx, hipStream_t st);
-int wgrad_mfma_bf16(const WgradParams& p, int ksize, int stride, int ct, int gx, hipStream_t st);
-int wgrad_mfma_f16(const WgradParams& p, int ksize, int stride, int ct, int gx, hipStream_t st);
+int wgrad_mfma_f32(const WgradParams& p, const WgradPlan& pl, int ksize, int stride, hipStream_t st);
+int wgrad_mfma_bf16(const WgradParams& p, const WgradPlan& pl, int ksize, int stride, hipStream_t st);
+int wgrad_mfma_f16(const WgradParams& p, const WgradPlan& pl, int ksize, int stride, hipStream_t st);
 int bn_stats_launch(int dtype, const segmi_act* x, float* partials, hipStream_t st, const BiasFin* bias_fin = nullptr);
-int bn_stats_rows_for(const segmi_act* x);
-bool conv_small_ok(int cin, int cout, int ksize);
-int conv_small_wgrad_slabs(const segmi_act* dy);
-int conv_small_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float* partials,
+int conv_small_wgrad(int dtype, const WgradPlan& pl, const segmi_act* x, const segmi_act* dy, float* partials,
                      int stride, hipStream_t st);
 
 struct WgDirectParams {
@@ -141,55 +136,7 @@ __global__ __launch_bounds__(1024) void slab_reduce_fused_kernel(const float* __
 }
 
 
-static inline bool aligned_rows(const segmi_act* a, int dtype) {
-  const int es = dtype_size(dtype);
-  return a->ld % (16 / es) == 0 && ((uintptr_t)a->data % 16) == 0;
-}
-static inline bool wg_mfma_ok(int dtype, const segmi_act* x, const segmi_act* dy, int ksize) {
-  return x->c % 16 == 0 && dy->c % 16 == 0 && aligned_rows(x, dtype) && aligned_rows(dy, dtype) &&
-         (ksize == 3 || ksize == 1);
-}
-static inline bool wg_small_ok(int dtype, const segmi_act* x, const segmi_act* dy, int ksize) {
-  const int es = dtype_size(dtype);
-  (void)es;
-  return conv_small_ok(x->c, dy->c, ksize) && aligned_rows(dy, dtype);
-}
-static inline int wg_direct_blocks(const segmi_act* dy) {
-  const int64_t b = cdiv64(act_voxels(dy), 512);
-  return (int)(b > 1024 ? 1024 : b);
-}
 static inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
-// The wave-specialised kernel addresses each operand through ONE buffer descriptor (32-bit offsets, < 4 GiB).  A
-// layer that misses it only for that (160^3 x 32 channels x batch 8 inside a 64-channel skip buffer = 4.2 GB) is
-// cut along the batch into 2 / 4 / 8 parts that fit: one launch per part, each with its own slabs, one reduce.
-static inline segmi_act batch_part(const segmi_act* a, int parts, int i, int dtype) {
-  segmi_act s = *a;
-  s.n = a->n / parts;
-  s.data = (char*)a->data + (int64_t)i * s.n * a->d * a->h * a->w * a->ld * dtype_size(dtype);
-  return s;
-}
-static inline int wg_batch_parts(int dtype, const segmi_act* x, const segmi_act* dy, int ksize, int stride, int cus) {
-  if (!wg_mfma_ok(dtype, x, dy, ksize) || wgrad_ws_gx(dtype, x, dy, ksize, stride, cus) > 0) return 1;
-  const int64_t lim = 0xfff00000ll;
-  if (act_voxels(x) * x->ld * 2 < lim && act_voxels(dy) * dy->ld * 2 < lim) return 1;   // not the size that keeps it out
-  for (int parts = 2; parts <= 8 && parts <= x->n; parts *= 2) {
-    if (x->n % parts) break;
-    const segmi_act xs = batch_part(x, parts, 0, dtype), ys = batch_part(dy, parts, 0, dtype);
-    if (wgrad_ws_gx(dtype, &xs, &ys, ksize, stride, cus) > 0) return parts;
-  }
-  return 1;
-}
-static inline int wg_slabs(int dtype, const segmi_act* x, const segmi_act* dy, int ksize,
-                           int stride, int cus) {
-  const int parts = wg_batch_parts(dtype, x, dy, ksize, stride, cus);
-  if (parts > 1) {
-    const segmi_act xs = batch_part(x, parts, 0, dtype), ys = batch_part(dy, parts, 0, dtype);
-    return parts * wgrad_gx(dtype, &xs, &ys, ksize, stride, cus);
-  }
-  if (wg_mfma_ok(dtype, x, dy, ksize)) return wgrad_gx(dtype, x, dy, ksize, stride, cus);
-  if (wg_small_ok(dtype, x, dy, ksize)) return conv_small_wgrad_slabs(dy);
-  return wg_direct_blocks(dy);
-}
 
 }  // namespace segmi
 
@@ -203,7 +150,7 @@ int64_t segmi_conv3d_wgrad_workspace(int dtype, const segmi_act* x, const segmi_
                                      int ksize, int stride, int cus) {
   if (!x || !dy) return 0;
   const int64_t nout = (int64_t)x->c * dy->c * ksize * ksize * ksize;
-  const int slabs = wg_slabs(dtype, x, dy, ksize, stride, cus);
+  const int slabs = wgrad_plan(dtype, x, dy, ksize, stride, cus).slabs;
   const int64_t bias = ((int64_t)bn_stats_rows_for(dy) + 2 * kFinScratchRows + 1) * 2 * dy->c * 4;  // + f64 tail
   return align256(slabs * nout * 4) + align256((int64_t)kSlabGroups * nout * 4) + align256(bias);
 }
@@ -221,8 +168,7 @@ int segmi_conv3d_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float
                        float* db, int ksize, int stride, void* workspace,
                        const segmi_in_affine* in_tf, int cus, void* stream) {
   if (in_tf)
-    SEGMI_CHECK_ARG(in_tf->scale && in_tf->shift && dtype_h16(dtype) && act_ok(x) && act_ok(dy) &&
-                        wg_mfma_ok(dtype, x, dy, ksize),
+    SEGMI_CHECK_ARG(in_tf->scale && in_tf->shift && dtype_h16(dtype),
                     "wgrad: an input transform needs the bf16 / fp16 MFMA kernel");
   SEGMI_CHECK_ARG(dtype_ok(dtype), "wgrad: bad dtype");
   SEGMI_CHECK_ARG(act_ok(x) && act_ok(dy) && dw && workspace, "wgrad: bad arguments");
@@ -236,26 +182,24 @@ int segmi_conv3d_wgrad(int dtype, const segmi_act* x, const segmi_act* dy, float
   hipStream_t st = (hipStream_t)stream;
   const int64_t nout = (int64_t)x->c * dy->c * ksize * ksize * ksize;
   float* partials = (float*)workspace;
-  const int slabs = wg_slabs(dtype, x, dy, ksize, stride, cus);
-  if (wg_mfma_ok(dtype, x, dy, ksize)) {
-    const int parts = wg_batch_parts(dtype, x, dy, ksize, stride, cus);
-    for (int part = 0; part < parts; ++part) {
-      const segmi_act xs = batch_part(x, parts, part, dtype), ys = batch_part(dy, parts, part, dtype);
-      const int gx = slabs / parts;
+  const WgradPlan pl = wgrad_plan(dtype, x, dy, ksize, stride, cus);
+  SEGMI_CHECK_ARG(!in_tf || pl.path <= kWgradMfma, "wgrad: an input transform needs the bf16 / fp16 MFMA kernel");
+  const int slabs = pl.slabs;
+  if (pl.path <= kWgradMfma) {
+    for (int part = 0; part < pl.parts; ++part) {
+      const segmi_act xs = batch_part(x, pl.parts, part, dtype), ys = batch_part(dy, pl.parts, part, dtype);
       WgradParams p{};
-      p.x = xs.data; p.dy = ys.data; p.partials = partials + (int64_t)part * gx * nout;
+      p.x = xs.data; p.dy = ys.data; p.partials = partials + (int64_t)part * pl.gx * nout;
       p.N = xs.n; p.Dx = x->d; p.Hx = x->h; p.Wx = x->w; p.Dy = dy->d; p.Hy = dy->h; p.Wy = dy->w;
       p.Cin = x->c; p.Cout = dy->c; p.ldx = x->ld; p.ldy = dy->ld;
       if (in_tf) { p.in_scale = in_tf->scale; p.in_shift = in_tf->shift; p.in_alpha = in_tf->prelu_alpha; }
-      const int ct = wgrad_ct(dtype, ys.c);
-      const bool ws = wgrad_ws_gx(dtype, &xs, &ys, ksize, stride, cus) > 0;
-      const int rc = dtype == SEGMI_F32   ? wgrad_mfma_f32(p, ksize, stride, ct, gx, st)
-                     : dtype == SEGMI_F16 ? wgrad_mfma_f16(p, ksize, stride, ws ? -ct : ct, gx, st)
-                                          : wgrad_mfma_bf16(p, ksize, stride, ws ? -ct : ct, gx, st);
+      const int rc = dtype == SEGMI_F32   ? wgrad_mfma_f32(p, pl, ksize, stride, st)
+                     : dtype == SEGMI_F16 ? wgrad_mfma_f16(p, pl, ksize, stride, st)
+                                          : wgrad_mfma_bf16(p, pl, ksize, stride, st);
       if (rc) return rc;
     }
-  } else if (wg_small_ok(dtype, x, dy, ksize)) {
-    const int rc = conv_small_wgrad(dtype, x, dy, partials, stride, st);
+  } else if (pl.path == kWgradSmallCin) {
+    const int rc = conv_small_wgrad(dtype, pl, x, dy, partials, stride, st);
     if (rc) return rc;
   } else {
     WgDirectParams p{};

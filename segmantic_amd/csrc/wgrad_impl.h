@@ -22,6 +22,7 @@
 // rate (2 ds_read_b64_tr_b16 per operand, ~2.4 clk each, 2.3 per MFMA).
 #pragma once
 #include "common.h"
+#include "conv_plan.h"
 
 namespace segmi {
 
@@ -326,100 +327,33 @@ static int launch_wgrad_cfg(WgradParams p, int gx_hint, hipStream_t st) {
   return SEGMI_OK;
 }
 
-// how many voxel-range workgroups (= partial slabs) the MFMA path uses
-static inline int wgrad_tiles(const segmi_act* dy, int stride, bool one_block) {
-  const bool wide = dy->w > 8;
-  int td, th, tw;
-  if (stride == 1) { td = wide && !one_block ? 2 : 4; th = 8; tw = wide ? 16 : 8; }
-  else { td = 2; th = wide ? 4 : 8; tw = wide ? 16 : 8; }
-  return dy->n * cdiv(dy->d, td) * cdiv(dy->h, th) * cdiv(dy->w, tw);
-}
-// channel blocking of one workgroup, encoded 10*CTO + CTI (16-channel tiles of dY x of X).
-// bf16 / fp16 only: 2 output tiles share one staging of X when the output channels allow it (4x1
-// measured slower: 360 VGPRs).  Layers with >= 32 input and output channels took the 2 x 2 tile
-// (220 VGPRs, one workgroup per CU) until round 4; with the 2 x 1 tile (the wave-specialised kernel
-// where the layer has the tiles for it, wgrad_mfma_kernel's 2 x 1 form elsewhere) the training step
-// went 4.98 -> 4.75 ms and the 160^3 / 32-label step at batch 4 11.1 -> 9.9 ms, alternating runs (the
-// operand read twice costs less than the 2 x 2 tile's occupancy).
-static inline int wgrad_ct(int dtype, int cout) {
-  return dtype_h16(dtype) && cout % 32 == 0 ? 21 : 11;
-}
-// CUs the weight-gradient kernels size their grids for (the `cus` argument of segmi_conv3d_wgrad and of its
-// workspace query; SEGMI_WGRAD_CUS overrides).  These
-// kernels hold a CU exclusively (one 768-thread or 400-register workgroup per CU), so with one workgroup on
-// EVERY CU the dependent chain of the main stream gets no CU until they retire; sized for half the chip the two
-// streams really run side by side (5.55 -> 5.28 ms per training step, round 3).
-int wgrad_cus(int cus);
-// ---- wave-specialised kernel (wgrad_ws_impl.h): bf16 k3 layers whose two tile buffers fit one CU
-// and that have enough tiles per workgroup for its pipeline to matter.  Encodes the choice made by
-// the launcher (wgrad_mfma_bf16) so that the workspace query sizes the same number of slabs.
-static inline int wgrad_ws_gx(int dtype, const segmi_act* x, const segmi_act* dy, int ksize, int stride, int cus) {
-  if (!dtype_h16(dtype) || ksize != 3) return 0;
-  const int ct = wgrad_ct(dtype, dy->c);
-  const int cto = ct / 10, cti = ct % 10;
-  const int chunks = (x->c / (16 * cti)) * (dy->c / (16 * cto));
-  int gx = wgrad_cus(cus) / chunks / 8 * 8;        // one 768-thread workgroup per CU, a multiple of the 8 XCDs
-  if (gx < 8) return 0;
-  // the tile shapes of launch_wgrad_ws (must match)
-  const bool wide = dy->w > 8;
-  int td, th, tw;
-  if (stride == 1) { td = ct == 11 ? 4 : (wide ? 2 : 4); th = 8; tw = wide ? 16 : 8; }
-  else { td = 2; th = wide ? 4 : 8; tw = wide ? 16 : 8; }
-  const int64_t nt = (int64_t)dy->n * cdiv(dy->d, td) * cdiv(dy->h, th) * cdiv(dy->w, tw);
-  // raw buffer loads: 32-bit offsets / num_records over each tensor
-  if (act_voxels(x) * x->ld * 2 >= 0xfff00000ll || act_voxels(dy) * dy->ld * 2 >= 0xfff00000ll) return 0;
-  return nt >= 4 * (int64_t)gx ? gx : 0;           // at least 4 tiles per workgroup
-}
-static inline int wgrad_gx(int dtype, const segmi_act* x, const segmi_act* dy, int ksize, int stride, int cus_arg) {
-  const int ws = wgrad_ws_gx(dtype, x, dy, ksize, stride, cus_arg);
-  if (ws > 0) return ws;
-  const int ct = wgrad_ct(dtype, dy->c);
-  const int cto = ct / 10, cti = ct % 10;
-  const int chunks = (x->c / (16 * cti)) * (dy->c / (16 * cto));
-  // workgroups wanted = a multiple of the 256 CUs; one per CU once the kernel holds > 1 channel
-  // tile (200-400 VGPRs, 55-110 KB slabs).  Measured on MI355X: 1x1 blocks
-  // 704/508/540/608 us at 256/512/1024/2048 workgroups, 2x2 blocks 125/198/348 us at 256/512/1024.
-  const int cus = wgrad_cus(cus_arg);
-  const int target = cto * cti == 1 ? 2 * cus : cus;
-  int gx = target / chunks;
-  if (gx < 1) gx = 1;
-  const int nt = wgrad_tiles(dy, stride, cto * cti == 1);
-  return gx < nt ? gx : nt;
-}
-
-#define WG_CFG(KS, S, CTO, CTI)                                                         \
-  do {                                                                                   \
-    if (S == 1 || KS == 1)                                                               \
-      return wide ? launch_wgrad_cfg<T, KS, 1, CTO, CTI, 2, 8, 16>(p, gx, st)            \
-                  : launch_wgrad_cfg<T, KS, 1, CTO, CTI, 4, 8, 8>(p, gx, st);            \
-    return wide ? launch_wgrad_cfg<T, KS, S, CTO, CTI, 2, 4, 16>(p, gx, st)              \
-                : launch_wgrad_cfg<T, KS, S, CTO, CTI, 2, 8, 8>(p, gx, st);              \
-  } while (0)
+// the MFMA kernel's instantiation of a plan: (k, s), channel blocking, dY tile (wgrad_tile_shape)
+constexpr int wgrad_key(int ks, int s, int ct, Tile3 t) { return ((((ks * 4 + s) * 32 + ct) * 8 + t.td) * 16 + t.th) * 32 + t.tw; }
+#define WG_CASE(LAUNCH, KS, S, CTO, CTI, TD, TH, TW) \
+  case wgrad_key(KS, S, 10 * CTO + CTI, Tile3{TD, TH, TW}): return LAUNCH<T, KS, S, CTO, CTI, TD, TH, TW>(p, pl.gx, st);
+#define WG_W(LAUNCH, KS, S, CTO, CTI, WIDE)                                     \
+  WG_CASE(LAUNCH, KS, S, CTO, CTI, wgrad_tile_shape(KS, S, 10 * CTO + CTI, WIDE).td, \
+          wgrad_tile_shape(KS, S, 10 * CTO + CTI, WIDE).th, wgrad_tile_shape(KS, S, 10 * CTO + CTI, WIDE).tw)
+#define WG_PLANNED(LAUNCH, KS, S, CTO, CTI) WG_W(LAUNCH, KS, S, CTO, CTI, true) WG_W(LAUNCH, KS, S, CTO, CTI, false)
+// Shapes no plan picks (the stride-2 tiles on a stride-1 block, the 2-plane tile on the k3 16 x 16 block).  The library
+// has carried these instantiations since before the plan existed; they are listed so that its kernels stay what they were.
+#define WG_UNPLANNED_S1(KS, CTO, CTI) \
+  WG_CASE(launch_wgrad_cfg, KS, 1, CTO, CTI, 2, 4, 16) WG_CASE(launch_wgrad_cfg, KS, 1, CTO, CTI, 2, 8, 8)
 
 template <typename T>
-static int launch_wgrad_mfma_t(const WgradParams& p, int ksize, int stride, int ct, int gx,
-                               hipStream_t st) {
-  const bool wide = p.Wy > 8;
-  if (ksize == 1) {
-    if constexpr (sizeof(T) == 2) {
-      if (ct == 21) WG_CFG(1, 1, 2, 1);
-    }
-    WG_CFG(1, 1, 1, 1);
-  }
+static int launch_wgrad_mfma(const WgradParams& p, const WgradPlan& pl, int ksize, int stride, hipStream_t st) {
+  const int key = wgrad_key(ksize, stride, pl.ct, Tile3{pl.td, pl.th, pl.tw});
   if constexpr (sizeof(T) == 2) {
-    if (stride == 1) {
-      if (ct == 21) WG_CFG(3, 1, 2, 1);
-    } else {
-      if (ct == 21) WG_CFG(3, 2, 2, 1);
+    switch (key) {
+      WG_PLANNED(launch_wgrad_cfg, 1, 1, 2, 1) WG_PLANNED(launch_wgrad_cfg, 3, 1, 2, 1) WG_PLANNED(launch_wgrad_cfg, 3, 2, 2, 1)
+      WG_UNPLANNED_S1(1, 2, 1) WG_UNPLANNED_S1(3, 2, 1)
     }
   }
-  // 16 x 16 channel block (144 VGPRs, 50 KB of LDS): 4 output planes per tile halve the per-tile
-  // overhead (barriers, tile decode, LDS commit) and take the X halo from 2.8x to 2.1x
-  if (stride == 1)
-    return wide ? launch_wgrad_cfg<T, 3, 1, 1, 1, 4, 8, 16>(p, gx, st)
-                : launch_wgrad_cfg<T, 3, 1, 1, 1, 4, 8, 8>(p, gx, st);
-  WG_CFG(3, 2, 1, 1);
+  switch (key) {
+    WG_PLANNED(launch_wgrad_cfg, 1, 1, 1, 1) WG_PLANNED(launch_wgrad_cfg, 3, 1, 1, 1) WG_PLANNED(launch_wgrad_cfg, 3, 2, 1, 1)
+    WG_UNPLANNED_S1(1, 1, 1) WG_CASE(launch_wgrad_cfg, 3, 1, 1, 1, 2, 8, 16)
+  }
+  SEGMI_UNSUPPORTED("conv3d_wgrad: no MFMA kernel for k%d s%d, channel blocking %d", ksize, stride, pl.ct);
 }
-#undef WG_CFG
 
 }  // namespace segmi

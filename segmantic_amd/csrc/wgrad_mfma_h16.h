@@ -5,25 +5,19 @@
 #include "wgrad_ws_impl.h"
 namespace segmi {
 
-// ct < 0: the wave-specialised kernel was chosen (wgrad_ws_gx); tile shapes as listed there
+// the wave-specialised kernel's instantiation of a plan: stride, channel blocking, dY tile
 template <typename T>
-static int launch_wgrad_ws(const WgradParams& p, int stride, int ct, int gx, hipStream_t st) {
-  const bool wide = p.Wy > 8;
-  if (stride == 1) {
-    if (ct == 11) return wide ? launch_wgrad_ws_cfg<T, 3, 1, 1, 1, 4, 8, 16>(p, gx, st)
-                              : launch_wgrad_ws_cfg<T, 3, 1, 1, 1, 4, 8, 8>(p, gx, st);
-    return wide ? launch_wgrad_ws_cfg<T, 3, 1, 2, 1, 2, 8, 16>(p, gx, st)
-                : launch_wgrad_ws_cfg<T, 3, 1, 2, 1, 4, 8, 8>(p, gx, st);
+static int launch_wgrad_ws(const WgradParams& p, const WgradPlan& pl, int stride, hipStream_t st) {
+  switch (wgrad_key(3, stride, pl.ct, Tile3{pl.td, pl.th, pl.tw})) {
+    WG_PLANNED(launch_wgrad_ws_cfg, 3, 1, 1, 1) WG_PLANNED(launch_wgrad_ws_cfg, 3, 1, 2, 1)
+    WG_PLANNED(launch_wgrad_ws_cfg, 3, 2, 1, 1) WG_PLANNED(launch_wgrad_ws_cfg, 3, 2, 2, 1)
   }
-  if (ct == 11) return wide ? launch_wgrad_ws_cfg<T, 3, 2, 1, 1, 2, 4, 16>(p, gx, st)
-                            : launch_wgrad_ws_cfg<T, 3, 2, 1, 1, 2, 8, 8>(p, gx, st);
-  return wide ? launch_wgrad_ws_cfg<T, 3, 2, 2, 1, 2, 4, 16>(p, gx, st)
-              : launch_wgrad_ws_cfg<T, 3, 2, 2, 1, 2, 8, 8>(p, gx, st);
+  SEGMI_UNSUPPORTED("conv3d_wgrad: no wave-specialised kernel for s%d, channel blocking %d", stride, pl.ct);
 }
 
 template <typename T>
-static int wgrad_mfma_h16(const WgradParams& p, int ksize, int stride, int ct, int gx, hipStream_t st) {
-  if (ct < 0) return launch_wgrad_ws<T>(p, stride, -ct, gx, st);
-  return launch_wgrad_mfma_t<T>(p, ksize, stride, ct, gx, st);
+static int wgrad_mfma_h16(const WgradParams& p, const WgradPlan& pl, int ksize, int stride, hipStream_t st) {
+  if (pl.path == kWgradWaveSpecialised) return launch_wgrad_ws<T>(p, pl, stride, st);
+  return launch_wgrad_mfma<T>(p, pl, ksize, stride, st);
 }
 }  // namespace segmi

@@ -313,8 +313,8 @@ UNREACHABLE = {
         "convolutions only, which are not k3 layers",
     "conv3d_split_act_ok=False":
         "both call sites (_train_pair, _merged_eval) ask only for MFMA k3 stride-2 pairs, and for those the predicate "
-        "is true by construction: conv_ks_ok and conv_ring_ok, its two exclusions, are stride-1 only.  The engine's "
-        "own guards in front of it (non-MFMA, carried, no residual convolution) do go both ways",
+        "is true by construction: the k-split and ring families (conv_plan.h), its two exclusions, are stride-1 "
+        "only.  The engine's own guards in front of it (non-MFMA, carried, no residual convolution) do go both ways",
 }
 
 

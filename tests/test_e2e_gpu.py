@@ -657,7 +657,7 @@ def test_full_size_c4_160_k32_training_step_bf16():
     top = eng.levels["upru"]["units"][-1][0]
     assert (top.cin, top.cout) == (32, 32)
     from segmantic_amd import ops
-    # ... i.e. the z-marching ring kernel <bf16, 32 channels> (this query == conv_ring_ok in conv.hip)
+    # ... i.e. the z-marching ring kernel <bf16, 32 channels> (this query == a ring family in conv_plan.h)
     assert ops.conv3d_in_affine_ok(logits, logits, 3, 1)
     for _ in range(4):
         l2 = float(net.training_step({"image": x, "label": lab})["loss"].cpu())
