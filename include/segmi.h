@@ -736,6 +736,36 @@ int segmi_staple(const void* const* labels_host, int raters, int label_bytes, in
                  double* prior, float* posterior, int32_t* info_host, void* workspace, size_t ws_bytes,
                  void* stream);
 
+/* ---------------------------------------------------------------- patch-based label fusion ---------- */
+/* Intensity-weighted fusion of `atlases` (1 .. 16) atlases on the grid of a target of [d][h][w] voxels, d*h*w < 2^31
+ * (2-D: d == 1).  DESIGN.md section 25 is the definition: 8-bit intensities, integer patch distances, the weight a
+ * lookup in a caller-supplied table, integer scores, so the result is the same bits for every launch shape.
+ *
+ * segmi_quantise_u8: dst[i] = clamp(floor((src[i] - (float)lo) * scale + 0.5f), 0, 255) in float32, every operation
+ * rounded on its own, scale = (float)(255.0 / (hi - lo)); NaN gives 0.  lo < hi, both finite, scale finite.
+ *
+ * segmi_patch_fusion: target_q u8 [d][h][w]; atlas_q_host / atlas_labels_host: HOST tables of device pointers to the
+ * quantised atlas images (u8) and the label maps (label_bytes in {1 (uint8), 2 (int16), 4 (int32)}, labels in
+ * 0 .. num_classes - 1, 2 .. 64 classes).  patch_radius / search_radius: HOST i32[3] (z, y, x), each 0 .. 3; on an
+ * axis of extent 1 both are taken as 0.  adaptive 1: den = max(smallest distance among the voxel's candidates,
+ * npatch * h2); adaptive 0: den = npatch * h2; h2 in 1 .. 65025.  table: DEVICE u32[1024], entries above 65536 are
+ * read as 65536.  Outputs on the device: out (dtype of the label maps), and the nullable best u32 [d][h][w] (the
+ * winner's score), total u32 [d][h][w] (the sum of the scores) and scores u32 [num_classes][d][h][w].  info_host:
+ * HOST i32[2] = atlas index of an input label outside 0 .. num_classes - 1 (-1: none; the first such voxel, then the
+ * first atlas) and that label's value; when such a label exists no output is written and the caller raises.  One
+ * synchronisation per call (one more to fetch an offending label). */
+int segmi_quantise_u8(const float* src, int64_t n, double lo, double hi, uint8_t* dst, void* stream);
+int64_t segmi_patch_fusion_workspace_bytes(int atlases, int num_classes);
+/* "lds_scores_tile_8x8x8" when the score table of the classes fits next to the staged tiles of an 8 x 8 x 8 tile
+ * (num_classes <= 18), "lds_scores_tile_2x8x8" above; "" for arguments segmi_patch_fusion refuses.
+ * segmi_patch_fusion launches by the same choice. */
+const char* segmi_patch_fusion_variant_name(int num_classes, const int32_t* patch_radius, const int32_t* search_radius);
+int segmi_patch_fusion(const uint8_t* target_q, const void* const* atlas_q_host, const void* const* atlas_labels_host,
+                       int atlases, int label_bytes, int d, int h, int w, int num_classes, const int32_t* patch_radius,
+                       const int32_t* search_radius, int adaptive, int h2, const uint32_t* table, void* out,
+                       uint32_t* best, uint32_t* total, uint32_t* scores, int32_t* info_host, void* workspace,
+                       size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- registration ---------- */
 /* Kernels of rigid / affine registration by mutual information (segmantic_amd/image/registration.py).  DESIGN.md
  * section 23 is the definition.  Volumes are [z][y][x]; `pixel` as in segmi_resample3d (0 f32, 1 u8, 2 i16,

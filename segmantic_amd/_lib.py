@@ -190,6 +190,11 @@ SIGNATURES = {
     "segmi_staple_workspace_bytes": (_i64, [_i, _i]),
     "segmi_staple_table_name": (C.c_char_p, [_i, _i]),
     "segmi_staple": (_i, [_P, _i, _i, _i64, _i, _P, _i, _d, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "segmi_quantise_u8": (_i, [_P, _i64, _d, _d, _P, _P]),
+    "segmi_patch_fusion_workspace_bytes": (_i64, [_i, _i]),
+    "segmi_patch_fusion_variant_name": (C.c_char_p, [_i, _P, _P]),
+    "segmi_patch_fusion": (_i, [_P, _P, _P, _i, _i, _i, _i, _i, _i, _P, _P, _i, _i, _P, _P, _P, _P, _P, _P, _P,
+                                C.c_size_t, _P]),
     "segmi_bin_shrink": (_i, [_i, _P, _i, _i, _i, _i, _i, _i, _P, _P]),
     "segmi_fixed_bins": (_i, [_P, _P, _i64, _d, _d, _i, _P, _P]),
     "segmi_joint_histogram_group": (_i, [_i]),

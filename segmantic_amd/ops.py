@@ -1443,6 +1443,158 @@ def staple(labels, num_classes, *, prior=None, max_iterations=100, tolerance=1e-
     return res + (post,) if return_posterior else res
 
 
+# ------------------------------------------------------------------ patch-based label fusion (patch_fusion.hip)
+PF_MAX_ATLASES = 16
+PF_MAX_CLASSES = 64
+PF_MAX_RADIUS = 3
+PF_MAX_H2 = 65025             # 255^2: squared 8-bit quanta per patch voxel
+PF_TABLE_ENTRIES = 1024
+PF_MAX_WEIGHT = 65536
+
+
+def pf_radius(radius, name: str) -> tuple:
+    """a radius given as one integer or one per axis (z, y, x) -> (z, y, x), each in 0 .. 3"""
+    r = (radius,) * 3 if isinstance(radius, (int, np.integer)) and not isinstance(radius, bool) else tuple(
+        radius if hasattr(radius, "__len__") else (radius,))
+    if len(r) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in r):
+        raise ValueError(f"{name} must be one integer or three (z, y, x), got {radius!r}")
+    if any(not 0 <= int(v) <= PF_MAX_RADIUS for v in r):
+        raise ValueError(f"{name}: every component must lie in 0 .. {PF_MAX_RADIUS}, got {radius!r}")
+    return tuple(int(v) for v in r)
+
+
+def pf_check_args(atlases: int, num_classes, patch_radius, search_radius, h2, min_h2):
+    """The argument checks of ``patch_fusion`` that need no tensor; returns (rp, rs, adaptive, h2 or min_h2)."""
+    if not 1 <= int(atlases) <= PF_MAX_ATLASES:
+        raise ValueError(f"1 .. {PF_MAX_ATLASES} atlases, got {atlases}")
+    if isinstance(num_classes, bool) or int(num_classes) != num_classes or not 2 <= int(num_classes) <= PF_MAX_CLASSES:
+        raise ValueError(f"num_classes must be an integer in 2 .. {PF_MAX_CLASSES}, got {num_classes}")
+    rp, rs = pf_radius(patch_radius, "patch_radius"), pf_radius(search_radius, "search_radius")
+    name, v = ("min_h2", min_h2) if h2 is None else ("h2", h2)
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= PF_MAX_H2:
+        raise ValueError(f"{name} must be an integer in 1 .. {PF_MAX_H2}, got {v!r}")
+    return rp, rs, h2 is None, int(v)
+
+
+def quantise_range_check(lo, hi) -> tuple:
+    lo, hi = float(lo), float(hi)
+    if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+        raise ValueError(f"quantise_u8: lo < hi, both finite, got ({lo}, {hi})")
+    if not math.isfinite(float(np.float32(255.0 / (hi - lo)))):
+        raise ValueError(f"quantise_u8: the range ({lo}, {hi}) is too narrow for float32")
+    return lo, hi
+
+
+def quantise_u8(image: torch.Tensor, lo, hi) -> torch.Tensor:
+    """uint8 tensor of the shape of ``image`` (float32, contiguous, on the device):
+    clamp(floor((v - lo) * scale + 0.5), 0, 255) in float32, scale = float32(255 / (hi - lo)); NaN gives 0."""
+    lo, hi = quantise_range_check(lo, hi)
+    _require_device(image)
+    if image.dtype != torch.float32 or not image.is_contiguous():
+        raise ValueError(f"quantise_u8: a contiguous float32 tensor expected, got {image.dtype}")
+    n = image.numel()
+    if n == 0 or n >= CC_MAX_VOXELS:
+        raise ValueError(f"quantise_u8: 1 .. 2^31 - 1 elements, got shape {tuple(image.shape)}")
+    out = torch.empty(image.shape, dtype=torch.uint8, device=image.device)
+    check(lib.segmi_quantise_u8(_ptr(image), n, lo, hi, _ptr(out), _stream()), "quantise_u8")
+    return out
+
+
+def patch_fusion_table(beta=1.0) -> np.ndarray:
+    """The weight table of ``patch_fusion``: W[k] = floor(65536 * exp(-k / (64 * beta)) + 0.5), k = 0 .. 1023, in
+    float64 numpy, as uint32.  k counts 64ths of the bandwidth, so W[64] is the weight at D = den for beta = 1."""
+    if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)) or \
+            not (math.isfinite(float(beta)) and float(beta) > 0.0):
+        raise ValueError(f"beta must be finite and positive, got {beta!r}")
+    k = np.arange(PF_TABLE_ENTRIES, dtype=np.float64)
+    return np.floor(65536.0 * np.exp(-k / (64.0 * float(beta))) + 0.5).astype(np.uint32)
+
+
+def pf_check_table(table) -> None:
+    """a host table: 1024 integers in 0 .. 65536 with W[0] >= 1"""
+    t = np.asarray(table)
+    if t.shape != (PF_TABLE_ENTRIES,) or t.dtype.kind not in "iu":
+        raise ValueError(f"table must hold {PF_TABLE_ENTRIES} integers, got {t.dtype} {t.shape}")
+    if int(t.min()) < 0 or int(t.max()) > PF_MAX_WEIGHT or int(t[0]) < 1:
+        raise ValueError(f"table: entries in 0 .. {PF_MAX_WEIGHT} with table[0] >= 1")
+
+
+def patch_fusion_variant_name(num_classes: int, patch_radius=1, search_radius=2) -> str:
+    """which form of the fusion kernel ``patch_fusion`` launches for these arguments (the launch's own choice)"""
+    rp = (C.c_int32 * 3)(*pf_radius(patch_radius, "patch_radius"))
+    rs = (C.c_int32 * 3)(*pf_radius(search_radius, "search_radius"))
+    return lib.segmi_patch_fusion_variant_name(int(num_classes), rp, rs).decode()
+
+
+def patch_fusion(target_q, atlas_q, atlas_labels, num_classes, *, patch_radius=1, search_radius=2, table, h2=None,
+                 min_h2=4, return_scores=False, return_confidence=False):
+    """Patch-based label fusion (DESIGN.md section 25).  ``target_q``: uint8 [d, h, w] or [h, w] on the device;
+    ``atlas_q``: 1 .. 16 uint8 tensors and ``atlas_labels`` as many label maps (one dtype among uint8 / int16 /
+    int32, labels in 0 .. num_classes - 1), all contiguous and of the target's shape.  ``table``: 1024 weights
+    (numpy integers, checked, or a uint32 / int32 device tensor, taken as it is).  ``h2``: fixed bandwidth
+    den = npatch * h2; None: adaptive with the floor npatch * min_h2.  Returns labels in the dtype of the label maps,
+    then (best, total) uint32-valued int32 tensors with ``return_confidence`` and scores [K, *shape] with
+    ``return_scores``.  A label outside the range raises ValueError naming the atlas and the value."""
+    atlas_q, atlas_labels = list(atlas_q), list(atlas_labels)
+    if len(atlas_q) != len(atlas_labels):
+        raise ValueError(f"{len(atlas_q)} atlas images for {len(atlas_labels)} label maps")
+    rp, rs, adaptive, hv = pf_check_args(len(atlas_q), num_classes, patch_radius, search_radius, h2, min_h2)
+    if not isinstance(table, torch.Tensor):
+        pf_check_table(table)
+    if not isinstance(target_q, torch.Tensor):
+        raise TypeError("target_q is not a tensor")
+    _require_device(target_q)
+    if target_q.dtype != torch.uint8 or target_q.dim() not in (2, 3) or not target_q.is_contiguous():
+        raise ValueError(f"target_q: a contiguous uint8 [d, h, w] or [h, w] tensor expected, got {target_q.dtype} "
+                         f"{tuple(target_q.shape)}")
+    n = target_q.numel()
+    if n == 0 or n >= CC_MAX_VOXELS:
+        raise ValueError(f"target_q holds 1 .. 2^31 - 1 voxels, got shape {tuple(target_q.shape)}")
+    for a, (q, l) in enumerate(zip(atlas_q, atlas_labels)):
+        for what, t in ((f"atlas_q[{a}]", q), (f"atlas_labels[{a}]", l)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{what} is not a tensor")
+            _require_device(t)
+            if t.shape != target_q.shape or t.device != target_q.device or not t.is_contiguous():
+                raise ValueError(f"{what}: contiguous, of shape {tuple(target_q.shape)} on {target_q.device} expected, "
+                                 f"got {tuple(t.shape)} on {t.device}")
+        if q.dtype != torch.uint8:
+            raise ValueError(f"atlas_q[{a}] is {q.dtype}, not uint8")
+        if l.dtype != atlas_labels[0].dtype:
+            raise ValueError(f"atlas_labels[{a}] is {l.dtype}, atlas_labels[0] is {atlas_labels[0].dtype}")
+    lb = label_bytes(atlas_labels[0])
+    dev = target_q.device
+    if isinstance(table, torch.Tensor):
+        _require_device(table)
+        if table.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or table.numel() != PF_TABLE_ENTRIES or not table.is_contiguous():
+            raise ValueError(f"table: {PF_TABLE_ENTRIES} contiguous int32 / uint32 entries expected")
+        tab = table
+    else:
+        tab = torch.from_numpy(np.ascontiguousarray(np.asarray(table).astype(np.int32))).to(dev)
+    A, K = len(atlas_q), int(num_classes)
+    d, h, w = ((1,) + tuple(target_q.shape))[-3:]
+    out = torch.empty_like(atlas_labels[0])
+    conf = return_confidence
+    best = torch.empty(target_q.shape, dtype=torch.int32, device=dev) if conf else None
+    total = torch.empty(target_q.shape, dtype=torch.int32, device=dev) if conf else None
+    scores = torch.empty((K,) + tuple(target_q.shape), dtype=torch.int32, device=dev) if return_scores else None
+    ws = torch.empty(int(lib.segmi_patch_fusion_workspace_bytes(A, K)), dtype=torch.uint8, device=dev)
+    qt = (C.c_void_p * A)(*[t.data_ptr() for t in atlas_q])
+    lt = (C.c_void_p * A)(*[t.data_ptr() for t in atlas_labels])
+    info = (C.c_int32 * 2)()
+    check(lib.segmi_patch_fusion(_ptr(target_q), qt, lt, A, lb, d, h, w, K, (C.c_int32 * 3)(*rp), (C.c_int32 * 3)(*rs),
+                                 int(adaptive), hv, _ptr(tab), _ptr(out), _ptr(best), _ptr(total), _ptr(scores), info,
+                                 _ptr(ws), ws.numel(), _stream()), "patch_fusion")
+    if info[0] >= 0:
+        raise ValueError(f"patch_fusion: atlas {info[0]} holds the label {info[1]}, outside 0 .. {K - 1}")
+    res = (out,)
+    if conf:
+        res += (best, total)
+    if return_scores:
+        res += (scores,)
+    return res if len(res) > 1 else out
+
+
 # ------------------------------------------------------------------ evaluation (distance.hip)
 def label_bytes(t: torch.Tensor) -> int:
     """label_bytes of a label volume read in place: uint8 -> 1, int16 -> 2, int32 -> 4."""
