@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -298,11 +298,78 @@ class _BN:
         return self._eval[1], self._eval[2]
 
 
+class _SubSaved(NamedTuple):
+    """what a training forward keeps of one subunit"""
+    x: torch.Tensor                    # the conv's forward input ...
+    r: Optional[torch.Tensor]          # ... its raw output, the BatchNorm's input (None: conv-only subunit)
+    in_tf: Optional[tuple]             # (scale, shift, alpha) the conv applied to x while staging it, or None
+
+
+class _UnitSaved(NamedTuple):
+    x: torch.Tensor                    # the residual unit's input
+    subs: List[_SubSaved]
+
+
+class _LevelSaved(NamedTuple):
+    cat: torch.Tensor                  # [skip | sub-level output]: the transposed conv's input
+    u: torch.Tensor                    # its raw output
+
+
 class UNetEngine:
     """Execution plan for one ``UNetParams`` on one MI355X."""
 
     eps = 1e-5
     momentum = 0.1
+
+    # ------------------------------------------------------------------ schedule flags
+    # Each fused-off / serial setting is the reference of a bit-identity test (tests/test_e2e_gpu.py).
+    #
+    # SEGMI_SERIAL=1 keeps every kernel on one stream (per-kernel profiling without co-running work)
+    overlap_wgrad = os.environ.get("SEGMI_SERIAL", "0") != "1"
+    # CUs the weight-gradient kernels size their grids for while they run on the side stream (the `cus` argument of
+    # segmi_conv3d_wgrad; SEGMI_WGRAD_CUS overrides).  Their workgroups hold a CU exclusively (768 threads or ~400
+    # registers each): one per CU on all 256 and the main chain's kernels wait for a CU to retire -- "overlap" was
+    # then mostly alternation.  Sized for half the chip both streams run: 5.55 -> 5.28 ms per step (160: 5.40,
+    # 96: 5.53, 64: 5.93).  The deferred / carried schedule puts these kernels beside the latency-bound levels of the
+    # main chain, which need CUs, not bandwidth.
+    wgrad_cus_overlap = 128
+    # Single-GPU training_step: the weight gradients of the two full-resolution decoder convolutions (0.73 ms of
+    # HBM-bound persistent kernels, 1.6 GB) are carried over the end of the step: beside the backward's own
+    # bandwidth-bound kernels they only stretch it (backward 2.30 ms alone, 3.79 ms with all weight gradients beside
+    # it, 4.13 ms serial: the overlap buys 0.34 ms), beside the NEXT step's forward -- whose 64^3 .. 8^3 levels are
+    # latency-bound and leave the memory system idle -- they are nearly free.  Their layers are the last ones a
+    # forward reaches, so there is ~1 ms of slack: the weight-gradient stream runs them, then the optimiser on the
+    # arena suffix [carry_lo, n) and the re-pack of the two layers, and records `_tail_ev`; the next forward waits for
+    # it in front of the top transposed convolution.  Same arithmetic in the same order per parameter: bit-identical
+    # weights.  SEGMI_CARRY_TOP_WGRAD=0: everything inside the step.
+    carry_top_wgrad = os.environ.get("SEGMI_CARRY_TOP_WGRAD", "1") != "0"
+    # how many of the upper levels' up paths are carried (1 = the full-resolution decoder only).  With 1 the
+    # weight-gradient stream was still ~0.2 ms behind when the main chain reached the optimiser (the 64^3 decoder's
+    # weight gradients sat in front of the first encoder layers', which the next forward needs first); with the 64^3
+    # up path carried too the step went 5.02 -> 4.91 ms (alternating runs); 3: 4.99, 4: 5.25.
+    carry_levels = int(os.environ.get("SEGMI_CARRY_LEVELS", "2"))
+    # BatchNorm-apply + PReLU folded into the consumer conv's staging where the kernels allow it (segmi_in_affine);
+    # SEGMI_FUSE_BN=0 keeps the separate pass
+    fuse_bn_apply = os.environ.get("SEGMI_FUSE_BN", "1") != "0"
+    # BatchNorm-backward reduction in the epilogue of the input-gradient launch that produces its operand
+    # (segmi_bn_bwd_sums); SEGMI_FUSE_BN_BWD=0 keeps the separate two-tensor pass
+    fuse_bn_bwd = os.environ.get("SEGMI_FUSE_BN_BWD", "1") != "0"
+    # BatchNorm / PReLU backward of the small (<= 32 MB) tensors as one launch with a grid-wide hand-off instead of
+    # reduce -> apply (SEGMI_FUSE_BN_BWD_SMALL=0: two launches)
+    fuse_bn_bwd_small = os.environ.get("SEGMI_FUSE_BN_BWD_SMALL", "1") != "0"
+    # decoder levels: the BatchNorm-backward apply of the up layer rides in the stride-2 convolution that consumes it
+    # (the transposed convolution's input gradient; csrc/conv_bnbwd_impl.h): du is written once for the weight
+    # gradient instead of written + read.  SEGMI_FUSE_APPLY_CONV=0: two launches.
+    fuse_apply_conv = os.environ.get("SEGMI_FUSE_APPLY_CONV", "1") != "0"
+    # inference: subunit 0 + residual convolution of an MFMA encoder unit as one split-activation launch
+    # (SEGMI_MERGE_PAIRS=0: two launches)
+    merge_eval_pairs = os.environ.get("SEGMI_MERGE_PAIRS", "1") != "0"
+    # inference: transposed conv + conv-only unit of the full-resolution decoder as one launch (csrc/dectop.hip): the
+    # 16-channel full-resolution tensor between them never reaches HBM (218 -> 84 MB per 128^3 patch).  Bit-identical
+    # to the two launches; 46-49 us against 58 per patch, the 512^3 benchmark gains 8-9 % (22.9 vs 21.0 volumes/s,
+    # same process order, one box).  SEGMI_FUSE_EVAL_TOP=0 restores the two launches.
+    fuse_eval_top = os.environ.get("SEGMI_FUSE_EVAL_TOP", "1") != "0"
+    eval_top_fused = False      # set once an eval forward took the fused decoder-top launch (bench.py labels its roofline)
 
     def __init__(self, params: UNetParams, device: torch.device, dtype: torch.dtype):
         if params.dimensions not in (2, 3):
@@ -326,7 +393,10 @@ class UNetEngine:
         self._bufs: Dict[str, torch.Tensor] = {}
         self._scratch: Dict[str, torch.Tensor] = {}
         self._lane = 0
-        self._saved: Dict[str, torch.Tensor] = {}
+        self._saved: Dict[str, _UnitSaved] = {}           # residual-unit prefix -> what its backward reads
+        self._saved_levels: Dict[str, _LevelSaved] = {}   # level prefix -> its up path's
+        self._merged_packs: Dict[str, tuple] = {}         # unit prefix -> (weights version, pack, bias) of _merged_eval
+        self._dectop_pack: Optional[tuple] = None         # (weights version, fragments, bias, slope in [0, 1]) of the dectop launch
         self.timings: Dict[str, list] = {}
         self._carry_convs: set = set()
         self.fixed_slope = torch.full((1,), FIXED_SLOPE.get(params.act, 0.0), dtype=torch.float32,
@@ -538,35 +608,44 @@ class UNetEngine:
             bn = None if conv_only else _BN(self, f"{prefix}.conv.unit{su}.adn", cout)
             units.append((conv, bn))
             sc, ss = cout, 1
-        res = None
+        res = share = None
         if stride != 1 or cin != cout:
             res = _Conv(self, f"{prefix}.residual", cin, cout, 3 if stride != 1 else 1, stride)
-            c0, bn0 = units[0]
-            if (len(units) >= 2 and bn0 is not None and c0.mfma and res.mfma and c0.k == 3 and res.k == 3
-                    and c0.stride == res.stride == 2):
-                c0.pair_with = res
-        return {"prefix": prefix, "units": units, "res": res, "cin": cin, "cout": cout,
-                "stride": stride}
+            # Subunit 0 and the residual convolution read the same input with the same channels and stride; where
+            # both are k3 (a strided unit) and a second subunit consumes subunit 0's BatchNorm, the two can be ONE
+            # launch: "split" = segmi_conv3d_fwd_split_act over a pack with both weight sets (MFMA layers), "pair" =
+            # segmi_conv3d_fwd_pair (the small-Cin first layer).  Whether a launch takes the views of a given call is
+            # the kernels' business (ops.conv3d_split_act_ok / conv3d_pair_ok).  Training, as two launches of the
+            # tile-at-a-time kernel: 54 + 54 us (16 -> 32 at 64^3, batch 8), 44 + 44 and 14 + 24 one and two levels
+            # down; as one launch each 4.64 vs 4.72 ms per step.
+            if res.k == 3 and subunits >= 2 and units[0][1] is not None:
+                share = "split" if res.mfma else "pair"
+            if share == "split":
+                units[0][0].pair_with = res
+        return {"prefix": prefix, "units": units, "res": res, "stride": stride, "share": share}
 
     def _make_level(self, prefix, inc, outc, chs, sts, is_top):
         p = prefix  # e.g. "" , "1.submodule." ...
         c, s = chs[0], sts[0]
-        lvl = {"prefix": p, "c": c, "stride": s, "is_top": is_top, "inc": inc, "outc": outc}
+        lvl = {"prefix": p, "c": c, "stride": s, "is_top": is_top, "outc": outc}
         lvl["down"] = self._make_ru(p + "0", inc, c, s, 2)
         if len(chs) > 2:
             lvl["sub"] = self._make_level(p + "1.submodule.", c, c, chs[1:], sts[1:], False)
             lvl["bottom"] = None
             upc = 2 * c
-            lvl["subc"] = c
         else:
             lvl["sub"] = None
             lvl["bottom"] = self._make_ru(p + "1.submodule", c, chs[1], 1, 2)
             upc = c + chs[1]
-            lvl["subc"] = chs[1]
         lvl["upc"] = upc
         lvl["upconv"] = _Conv(self, p + "2.0.conv", upc, outc, 3, s, transposed=True)
         lvl["upbn"] = _BN(self, p + "2.0.adn", outc)
-        lvl["upru"] = self._make_ru(p + "2.1", outc, outc, 1, 1, last_conv_only=is_top)
+        upru = lvl["upru"] = self._make_ru(p + "2.1", outc, outc, 1, 1, last_conv_only=is_top)
+        # conv-only unit with an identity residual (the top of the net): its conv, the weight gradient and the
+        # in-kernel residual are the only readers of act(bn(u)), so they can apply it themselves ...
+        lvl["top_identity"] = upru["res"] is None and upru["units"][0][1] is None
+        # ... and in inference the 32 -> 16 transposed conv and the 16 -> 16 unit can be one launch (csrc/dectop.hip)
+        lvl["dectop"] = is_top and lvl["top_identity"] and (upc, outc) == (32, 16)
         if s != 2:
             raise NotImplementedError("segmantic_amd: the up path implements stride-2 levels")
         return lvl
@@ -603,15 +682,17 @@ class UNetEngine:
 
     # ------------------------------------------------------------------ primitive steps
     def _pair_ok(self, ru, x, out, dst_name, oshape) -> bool:
-        """subunit 0 + residual convolution of a small-Cin unit can share one launch
-        (segmi_conv3d_fwd_pair): two or more subunits, both k3 with the same stride"""
-        units, rc = ru["units"], ru["res"]
-        if len(units) < 2 or units[0][1] is None or rc is None:
-            return False
-        c0 = units[0][0]
-        if c0.mfma or rc.mfma or c0.k != 3 or rc.k != 3 or c0.stride != rc.stride or c0.cout != rc.cout:
-            return False
-        return ops.conv3d_pair_ok(x, self._buf(dst_name, oshape + (c0.cout,)), out)
+        """subunit 0 + residual convolution of a small-Cin unit share one launch (segmi_conv3d_fwd_pair) on these views"""
+        return ru["share"] == "pair" and ops.conv3d_pair_ok(x, self._buf(dst_name, oshape + (ru["res"].cout,)), out)
+
+    def _split_buf(self, ru, x, name, oshape):
+        """the [.., 2c] buffer that subunit 0 + residual convolution of an MFMA unit write as one launch
+        (segmi_conv3d_fwd_split_act; consumers read the halves as channel-slice views), or None"""
+        if ru["share"] != "split":
+            return None
+        rc = ru["res"]
+        m = self._buf(f"{ru['prefix']}.{name}", oshape + (2 * rc.cout,))
+        return m if ops.conv3d_split_act_ok(x, m, 3, rc.stride) else None
 
     def _tf_ok(self, x, y, conv: _Conv) -> bool:
         """the BatchNorm-apply + PReLU that would produce ``conv``'s input can be done by the conv
@@ -620,51 +701,22 @@ class UNetEngine:
                 and not conv.transposed and conv.k == 3 and conv.stride == 1 and conv.mfma
                 and ops.conv3d_in_affine_ok(x, y, 3, 1))
 
-    merge_eval_pairs = os.environ.get("SEGMI_MERGE_PAIRS", "1") != "0"
-    eval_top_fused = False      # set once an eval forward took the fused decoder-top launch (bench.py labels its roofline)
-    # inference: transposed conv + conv-only unit of the full-resolution decoder as one launch
-    # (csrc/dectop.hip): the 16-channel full-resolution tensor between them never reaches HBM (218 -> 84 MB
-    # per 128^3 patch).  Bit-identical to the two launches.  Round 2's version lost (69 vs 59 us per patch);
-    # with the producers re-tiled as 16 base voxels x 8 parity classes (round 3) it takes 46-49 us against
-    # 58 and the 512^3 benchmark gains 8-9 % (22.9 vs 21.0 volumes/s, same process order, one box).
-    # SEGMI_FUSE_EVAL_TOP=0 restores the two launches.
-    fuse_eval_top = os.environ.get("SEGMI_FUSE_EVAL_TOP", "1") != "0"
-
-    # Training: the stride-2 first subunit and the residual convolution of an encoder unit read the same input; as
-    # two launches of the tile-at-a-time kernel they cost 54 + 54 us (16 -> 32 at 64^3, batch 8), 44 + 44 and 14 + 24
-    # one and two levels down.  The eval pairing with BatchNorm statistics on the first half (round 4) runs them as
-    # one launch each (4.64 vs 4.72 ms per step as two launches).
-    def _train_pair(self, ru, x, oshape):
-        """the [.., 2c] buffer of the merged first subunit + residual convolution (training), or None"""
-        c0 = ru["units"][0][0]
-        if c0.pair_with is None or c0 in self._carry_convs:
-            return None
-        m = self._buf(f"{ru['prefix']}.tm", oshape + (2 * c0.cout,))
-        return m if ops.conv3d_split_act_ok(x, m, 3, c0.stride) else None
-
     def _merged_eval(self, ru, x, oshape):
-        """(pack, bias, buffer) of the merged subunit-0 + residual convolution of a unit (inference,
-        MFMA layers, segmi_conv3d_fwd_split_act), or None.  The pack concatenates the BatchNorm-folded
-        subunit-0 weight and the residual weight along the output channels; cached per weight version."""
-        units, rc = ru["units"], ru["res"]
-        if not self.merge_eval_pairs or rc is None or len(units) < 2 or units[0][1] is None:
+        """(pack, bias, buffer) of the merged subunit-0 + residual convolution of a unit (inference), or None.  The pack
+        concatenates the BatchNorm-folded subunit-0 weight and the residual weight along the output channels; cached
+        per weight version."""
+        m = self._split_buf(ru, x, "merged", oshape) if self.merge_eval_pairs else None
+        if m is None:
             return None
-        c0, bn0 = units[0]
-        if not (c0.mfma and rc.mfma and c0.k == 3 and rc.k == 3 and c0.stride == rc.stride
-                and c0.cout == rc.cout and c0.cin == rc.cin and not c0.transposed):
-            return None
-        m = self._buf(f"{ru['prefix']}.merged", oshape + (2 * c0.cout,))
-        if not ops.conv3d_split_act_ok(x, m, 3, c0.stride):
-            return None
-        hit = ru.get("_merged")
+        hit = self._merged_packs.get(ru["prefix"])
         if hit is None or hit[0] != self.weights_version:
+            (c0, bn0), rc = ru["units"][0], ru["res"]
             sc, sh = bn0.eval_affine()
             w_cat = torch.cat([c0.w, rc.w], 0).contiguous()
             scale = torch.cat([sc, torch.ones_like(sc)])
             bias = torch.cat([torch.addcmul(sh, c0.b, sc), rc.b]).contiguous()
             pack = ops.wpack(self.dtype, 0, w_cat, c0.cin, 2 * c0.cout, 3, scale=scale)
-            hit = (self.weights_version, pack, bias)
-            ru["_merged"] = hit
+            hit = self._merged_packs[ru["prefix"]] = (self.weights_version, pack, bias)
         return hit[1], hit[2], m
 
     def _conv_train(self, conv: _Conv, x, y, bn: Optional[_BN], in_tf=None):
@@ -764,11 +816,6 @@ class UNetEngine:
         count = x_raw.shape[0] * x_raw.shape[1] * x_raw.shape[2] * x_raw.shape[3]
         return (count, bn.g_gamma, bn.g_beta, bn.g_alpha, bn.coef)
 
-    # decoder levels: the BatchNorm-backward apply of the up layer rides in the stride-2 convolution that
-    # consumes it (the transposed convolution's input gradient; csrc/conv_bnbwd_impl.h): du is written once
-    # for the weight gradient instead of written + read.  SEGMI_FUSE_APPLY_CONV=0: two launches (A/B).
-    fuse_apply_conv = os.environ.get("SEGMI_FUSE_APPLY_CONV", "1") != "0"
-
     def _bn_bwd(self, bn: _BN, dy, x_raw, dx, sums_rows: int = 0, then_conv=None) -> bool:
         """``sums_rows`` > 0: the reduction's partial rows were written and finalised by the launch that
         produced dy (``_dgrad(..., bsum=)``); only the apply remains.  ``then_conv`` = (conv, out): the
@@ -800,94 +847,54 @@ class UNetEngine:
     # ------------------------------------------------------------------ residual unit
     def _ru_fwd_train(self, ru, x, out, in_tf=None):
         """``in_tf``: x is the RAW output of the producer conv and (scale, shift, alpha) its pending
-        BatchNorm-apply + PReLU, which the first unit's conv applies on the fly (only for a unit
-        whose sole consumers of x are that conv, its weight gradient and an in-kernel identity
+        BatchNorm-apply + PReLU, which the first subunit's conv applies on the fly (only for a unit without a
+        residual convolution whose sole consumers of x are that conv, its weight gradient and an in-kernel identity
         residual -- see ``_level_fwd``)."""
-        pre = ru["prefix"]
-        n, d, h, w = self._down_shape(x.shape, ru["stride"])
-        cur = x
-        nun = len(ru["units"])
-        saved = {"x": x}
-        # residual branch straight into `out` (read back as the epilogue residual of the last unit)
-        paired = False
-        tpair = None
-        if ru["res"] is not None:
-            rc = ru["res"]
-            paired = self._pair_ok(ru, x, out, f"{pre}.r0", (n, d, h, w))
-            if not paired and in_tf is None:
-                tpair = self._train_pair(ru, x, (n, d, h, w))
-            if not paired and tpair is None:
-                ops.conv3d_fwd(x, out, rc.fwd_pack(), rc.w, 0, rc.b, rc.k, rc.stride)
+        pre, units, rc = ru["prefix"], ru["units"], ru["res"]
+        oshape = self._down_shape(x.shape, ru["stride"])
+        # residual branch: x itself, or the residual convolution straight into `out` (read back as the epilogue
+        # residual of the last subunit) -- in a launch of its own, or in subunit 0's (pair / split)
+        resid, paired, split = x, False, None
+        if rc is not None:
             resid = out
-        else:
-            resid = x
-        for i, (conv, bn) in enumerate(ru["units"]):
-            last = i == nun - 1
-            if i == 0 and tpair is not None:
-                # MFMA layers: subunit 0 (+ its statistics) and the residual convolution as ONE launch with 2c
-                # outputs -- one staging of x instead of two; consumers read the halves as channel-slice views
-                m = tpair
-                r, resid = m[..., :conv.cout], m[..., conv.cout:]
-                rows = ops.conv3d_stats_rows(x, m, conv.k, conv.stride)
-                stats = self._fstat(rows, conv.cout)
-                self._timed(conv.prefix + ":fwd", ops.conv3d_fwd_split_act, x, m, conv.pair_pack(), conv.b, None,
-                            conv.cout, conv.k, conv.stride, bias_b=ru["res"].b, stats=stats,
-                            stats_fin=self._stats_fin(bn, r))
-                saved[f"in{i}"] = cur
-                saved[f"r{i}"] = r
-                nconv = ru["units"][i + 1][0]
-                if self._tf_ok(r, r, nconv) and nconv.cin == conv.cout and nconv.cout == conv.cout:
-                    in_tf = (bn.scale, bn.shift, bn.alpha)
-                    cur = r
-                else:
-                    a = self._buf(f"{pre}.a{i}", (n, d, h, w, conv.cout))
-                    ops.bn_act_fwd(r, a, bn.scale, bn.shift, bn.alpha, dropout=bn.drop())
-                    cur = a
-                continue
-            if i == 0 and paired:
-                # first layer: subunit 0 and the residual convolution share one staging of x
-                r = self._buf(f"{pre}.r{i}", (n, d, h, w, conv.cout))
-                rows = ops.conv3d_stats_rows(x, r, conv.k, conv.stride)
-                stats = self._fstat(rows, conv.cout)
-                rc = ru["res"]
-                self._timed(conv.prefix + ":fwd", ops.conv3d_fwd_pair, x, r, conv.w, conv.b, out,
-                            rc.w, rc.b, conv.stride, stats_a=stats, stats_fin_a=self._stats_fin(bn, r))
-                saved[f"in{i}"] = cur
-                saved[f"r{i}"] = r
-                nconv = ru["units"][i + 1][0]
-                if self._tf_ok(r, r, nconv) and nconv.cin == conv.cout and nconv.cout == conv.cout:
-                    in_tf = (bn.scale, bn.shift, bn.alpha)
-                    cur = r
-                else:
-                    a = self._buf(f"{pre}.a{i}", (n, d, h, w, conv.cout))
-                    ops.bn_act_fwd(r, a, bn.scale, bn.shift, bn.alpha, dropout=bn.drop())
-                    cur = a
-                continue
+            paired = self._pair_ok(ru, x, out, f"{pre}.r0", oshape)
+            split = None if paired else self._split_buf(ru, x, "tm", oshape)
+            if not paired and split is None:
+                ops.conv3d_fwd(x, out, rc.fwd_pack(), rc.w, 0, rc.b, rc.k, rc.stride)
+        saved = _UnitSaved(x, [])
+        cur = x
+        for i, (conv, bn) in enumerate(units):
             if bn is None:
-                # conv-only last unit (top of the net): out = conv(cur) + residual
+                # conv-only last subunit (top of the net): out = conv(cur) + residual
                 self._timed(conv.prefix + ":fwd", ops.conv3d_fwd, cur, out, conv.fwd_pack(), conv.w,
                             0, conv.b, conv.k, conv.stride, residual=resid, in_tf=in_tf)
-                saved[f"in{i}"] = cur
-                saved[f"tf{i}"] = in_tf
+                saved.subs.append(_SubSaved(cur, None, in_tf))
                 break
-            r = self._buf(f"{pre}.r{i}", (n, d, h, w, conv.cout))
-            self._conv_train(conv, cur, r, bn, in_tf=in_tf)
-            saved[f"in{i}"] = cur
-            saved[f"r{i}"] = r
-            saved[f"tf{i}"] = in_tf
-            in_tf = None
-            if last:
-                ops.bn_act_fwd(r, out, bn.scale, bn.shift, bn.alpha, residual=resid, dropout=bn.drop())
+            # r = raw conv output, with the statistics of its BatchNorm finalised by the same launch
+            if i == 0 and split is not None:
+                r, resid = split[..., :conv.cout], split[..., conv.cout:]
+                stats = self._fstat(ops.conv3d_stats_rows(x, split, conv.k, conv.stride), conv.cout)
+                self._timed(conv.prefix + ":fwd", ops.conv3d_fwd_split_act, x, split, conv.pair_pack(), conv.b, None,
+                            conv.cout, conv.k, conv.stride, bias_b=rc.b, stats=stats, stats_fin=self._stats_fin(bn, r))
+            elif i == 0 and paired:
+                r = self._buf(f"{pre}.r0", oshape + (conv.cout,))
+                stats = self._fstat(ops.conv3d_stats_rows(x, r, conv.k, conv.stride), conv.cout)
+                self._timed(conv.prefix + ":fwd", ops.conv3d_fwd_pair, x, r, conv.w, conv.b, out,
+                            rc.w, rc.b, conv.stride, stats_a=stats, stats_fin_a=self._stats_fin(bn, r))
             else:
-                nconv = ru["units"][i + 1][0]
-                if self._tf_ok(r, r, nconv) and nconv.cin == conv.cout and nconv.cout == conv.cout:
-                    # the next unit's conv (and its weight gradient) normalise r on the fly
-                    in_tf = (bn.scale, bn.shift, bn.alpha)
-                    cur = r
-                else:
-                    a = self._buf(f"{pre}.a{i}", (n, d, h, w, conv.cout))
-                    ops.bn_act_fwd(r, a, bn.scale, bn.shift, bn.alpha, dropout=bn.drop())
-                    cur = a
+                r = self._buf(f"{pre}.r{i}", oshape + (conv.cout,))
+                self._conv_train(conv, cur, r, bn, in_tf=in_tf)
+            saved.subs.append(_SubSaved(cur, r, in_tf))
+            in_tf = None
+            if i == len(units) - 1:
+                ops.bn_act_fwd(r, out, bn.scale, bn.shift, bn.alpha, residual=resid, dropout=bn.drop())
+            elif self._tf_ok(r, r, units[i + 1][0]):
+                # the next subunit's conv (and its weight gradient) normalise r on the fly
+                in_tf = (bn.scale, bn.shift, bn.alpha)
+                cur = r
+            else:
+                cur = self._buf(f"{pre}.a{i}", oshape + (conv.cout,))
+                ops.bn_act_fwd(r, cur, bn.scale, bn.shift, bn.alpha, dropout=bn.drop())
         self._saved[pre] = saved
 
     def _ru_bwd(self, ru, dout, dx=None, extra=None, dx_bn=None):
@@ -896,114 +903,93 @@ class UNetEngine:
         ``dx_bn`` = (bn, x_raw): dx is the output gradient of that BatchNorm; when the unit's last
         launch into dx can carry the reduction of its backward, the partial-row count is returned
         (else 0)."""
-        pre = ru["prefix"]
+        pre, units, rc = ru["prefix"], ru["units"], ru["res"]
         sv = self._saved[pre]
-        x = sv["x"]
-        nun = len(ru["units"])
-        rc = ru["res"]
         # the residual conv's input gradient depends only on dout: it goes into dx first, the first
-        # unit's dgrad accumulates on top of it
+        # subunit's dgrad accumulates on top of it
         if rc is not None and dx is not None:
             self._dgrad(rc, dout, dx, residual=extra)
         g = dout            # gradient flowing back through the conv branch
         g_rows = 0          # > 0: the launch that wrote g also wrote the next BatchNorm's reduction rows
-        for i in range(nun - 1, -1, -1):
-            conv, bn = ru["units"][i]
-            xin = sv[f"in{i}"]
+        for i in range(len(units) - 1, -1, -1):
+            conv, bn = units[i]
+            sub = sv.subs[i]
             if bn is not None:
-                r = sv[f"r{i}"]
-                dr = self._buf(f"{pre}.dr{i}", r.shape)
-                self._bn_bwd(bn, g, r, dr, sums_rows=g_rows)
+                dr = self._buf(f"{pre}.dr{i}", sub.r.shape)
+                self._bn_bwd(bn, g, sub.r, dr, sums_rows=g_rows)
             else:
                 dr = g
             g_rows = 0
-            self._wgrad(conv, xin, dr, need_bias=bn is None and conv is not self._top_bias_conv,
-                        in_tf=sv.get(f"tf{i}"))
+            self._wgrad(conv, sub.x, dr, need_bias=bn is None and conv is not self._top_bias_conv, in_tf=sub.in_tf)
             if i > 0:
-                da = self._buf(f"{pre}.da{i - 1}", xin.shape)
-                pbn = ru["units"][i - 1][1]
-                if self._bsum_ok(conv, dr, da, pbn):
-                    g_rows = self._dgrad(conv, dr, da, bsum=(pbn, sv[f"r{i - 1}"]))
+                g = self._buf(f"{pre}.da{i - 1}", sub.x.shape)
+                pbn = units[i - 1][1]
+                if self._bsum_ok(conv, dr, g, pbn):
+                    g_rows = self._dgrad(conv, dr, g, bsum=(pbn, sv.subs[i - 1].r))
                 else:
-                    self._dgrad(conv, dr, da)
-                g = da
-            else:
-                first_dr = dr
+                    self._dgrad(conv, dr, g)
         if rc is not None:
-            self._wgrad(rc, x, dout)
+            self._wgrad(rc, sv.x, dout)
         # every parameter gradient of this unit (and of everything after it in the arena) is final
         self._grads_ready(self.param_offsets[f"model.{pre}.conv.unit0.conv.weight"][0])
         if dx is None:
             return 0
-        conv0 = ru["units"][0][0]
-        bsum = dx_bn if dx_bn is not None and self._bsum_ok(conv0, first_dr, dx, dx_bn[0]) else None
-        if rc is not None:
-            return self._dgrad(conv0, first_dr, dx, residual=dx, bsum=bsum) or 0
-        # identity residual: dx = dgrad(conv0) + dout (+ extra)
-        if extra is not None:
+        conv0 = units[0][0]
+        bsum = dx_bn if dx_bn is not None and self._bsum_ok(conv0, dr, dx, dx_bn[0]) else None
+        # dx = dgrad(conv0, dr) + the residual branch's gradient: already in dx behind a residual convolution; dout
+        # (+ extra) for an identity residual
+        resid = dx if rc is not None else dout
+        if rc is None and extra is not None:
             ops.add(dout, extra, dx)
-            return self._dgrad(conv0, first_dr, dx, residual=dx, bsum=bsum) or 0
-        return self._dgrad(conv0, first_dr, dx, residual=dout, bsum=bsum) or 0
+            resid = dx
+        return self._dgrad(conv0, dr, dx, residual=resid, bsum=bsum) or 0
 
     def _ru_fwd_eval(self, ru, x, out):
-        pre = ru["prefix"]
-        n, d, h, w = self._down_shape(x.shape, ru["stride"])
-        paired = False
-        merged = None
-        if ru["res"] is not None:
-            rc = ru["res"]
-            paired = self._pair_ok(ru, x, out, f"{pre}.ea0", (n, d, h, w))
+        pre, units, rc = ru["prefix"], ru["units"], ru["res"]
+        oshape = self._down_shape(x.shape, ru["stride"])
+        resid, paired, merged = x, False, None
+        if rc is not None:
+            resid = out
+            paired = self._pair_ok(ru, x, out, f"{pre}.ea0", oshape)
             if isinstance(x, ops.WindowBatch) and not paired:
                 raise RuntimeError("window views need the first-layer pair kernel (window_views_ok said yes?)")
-            merged = None if paired else self._merged_eval(ru, x, (n, d, h, w))
+            merged = None if paired else self._merged_eval(ru, x, oshape)
             if not paired and merged is None:
                 ops.conv3d_fwd(x, out, rc.fwd_pack(), rc.w, 0, rc.b, rc.k, rc.stride)
-            resid = out
-        else:
-            resid = x
         cur = x
-        nun = len(ru["units"])
-        for i, (conv, bn) in enumerate(ru["units"]):
-            last = i == nun - 1
-            if i == 0 and merged is not None:
-                # subunit 0 and the residual convolution as ONE launch with 2c outputs (one staging of
-                # x); consumers read the halves as channel-slice views
-                pack, bias, m = merged
-                ops.conv3d_fwd_split_act(x, m, pack, bias, bn.alpha, conv.cout, 3, conv.stride)
-                cur, resid = m[..., :conv.cout], m[..., conv.cout:]
-                continue
-            if i == 0 and paired:
-                sc, sh = bn.eval_affine()
-                _, wsrc, bias = conv.folded(sc, sh)
-                dst = self._buf(f"{pre}.ea{i}", (n, d, h, w, conv.cout))
-                rc = ru["res"]
-                ops.conv3d_fwd_pair(x, dst, wsrc, bias, out, rc.w, rc.b, conv.stride,
-                                    prelu_alpha_a=bn.alpha)
-                cur = dst
-                continue
+        for i, (conv, bn) in enumerate(units):
+            last = i == len(units) - 1
             if bn is None:
                 self._timed(conv.prefix + ":fwd", ops.conv3d_fwd, cur, out, conv.fwd_pack(), conv.w, 0,
                             conv.b, conv.k, conv.stride, residual=resid)
                 break
-            sc, sh = bn.eval_affine()
-            pack, wsrc, bias = conv.folded(sc, sh)
-            dst = out if last else self._buf(f"{pre}.ea{i}", (n, d, h, w, conv.cout))
-            ops.conv3d_fwd(cur, dst, pack, wsrc, 0, bias, conv.k, conv.stride,
-                           prelu_alpha=bn.alpha, residual=resid if last else None)
+            if i == 0 and merged is not None:
+                pack, bias, m = merged
+                ops.conv3d_fwd_split_act(x, m, pack, bias, bn.alpha, conv.cout, 3, conv.stride)
+                cur, resid = m[..., :conv.cout], m[..., conv.cout:]
+                continue
+            # BatchNorm folded into the weights and bias, PReLU (and the last subunit's residual) in the epilogue
+            pack, wsrc, bias = conv.folded(*bn.eval_affine())
+            dst = out if last else self._buf(f"{pre}.ea{i}", oshape + (conv.cout,))
+            if i == 0 and paired:
+                ops.conv3d_fwd_pair(x, dst, wsrc, bias, out, rc.w, rc.b, conv.stride, prelu_alpha_a=bn.alpha)
+            else:
+                ops.conv3d_fwd(cur, dst, pack, wsrc, 0, bias, conv.k, conv.stride,
+                               prelu_alpha=bn.alpha, residual=resid if last else None)
             cur = dst
 
     # ------------------------------------------------------------------ levels
     def _level_fwd(self, lvl, x, out, train: bool):
         p = lvl["prefix"]
         n, d, h, w = self._down_shape(x.shape, lvl["stride"])
-        c, upc, subc = lvl["c"], lvl["upc"], lvl["subc"]
+        c = lvl["c"]
         tag = "t" if train else "e"
         if (train and id(lvl) in self._carry_lvls and self.carry_top_wgrad and self.grad_hook is None
                 and self.overlap_wgrad):
             # the carried transposed-conv weight gradient of the LAST step may still be reading the last
             # step's skip buffer: alternate between two
             tag = "t" + str(self._fwd_parity)
-        cat = self._buf(f"{p}cat.{tag}", (n, d, h, w, upc))
+        cat = self._buf(f"{p}cat.{tag}", (n, d, h, w, lvl["upc"]))
         down_out = cat[..., :c]
         sub_out = cat[..., c:]
         ru_fwd = self._ru_fwd_train if train else self._ru_fwd_eval
@@ -1012,56 +998,45 @@ class UNetEngine:
             self._level_fwd(lvl["sub"], down_out, sub_out, train)
         else:
             ru_fwd(lvl["bottom"], down_out, sub_out)
-        up, ubn = lvl["upconv"], lvl["upbn"]
-        oshape = (x.shape[0], x.shape[1], x.shape[2], x.shape[3], lvl["outc"])
+        up, ubn, upru = lvl["upconv"], lvl["upbn"], lvl["upru"]
+        oshape = tuple(x.shape[:4]) + (lvl["outc"],)
         if train:
             if id(lvl) in self._carry_lvls:
                 self.sync_weights()        # parameters of the carried layers, and their readers of u / scale / shift
             u = self._buf(f"{p}u", oshape)
             self._conv_train(up, cat, u, ubn)
-            upru = lvl["upru"]
-            conv0, bn0 = upru["units"][0]
-            if (bn0 is None and upru["res"] is None and conv0.cin == conv0.cout == lvl["outc"]
-                    and self._tf_ok(u, out, conv0)):
-                # conv-only unit with an identity residual (the top of the net): its conv, the weight
-                # gradient and the in-kernel residual are the only readers of act(bn(u)) -- they
-                # apply it themselves, the normalised tensor is never written
-                self._saved[p + "up"] = {"cat": cat, "u": u}
+            self._saved_levels[p] = _LevelSaved(cat, u)
+            if lvl["top_identity"] and self._tf_ok(u, out, upru["units"][0][0]):
+                # the normalised tensor is never written: the unit's readers apply act(bn(u)) themselves
                 self._ru_fwd_train(upru, u, out, in_tf=(ubn.scale, ubn.shift, ubn.alpha))
             else:
                 au = self._buf(f"{p}au.t", oshape)
                 ops.bn_act_fwd(u, au, ubn.scale, ubn.shift, ubn.alpha, dropout=ubn.drop())
-                self._saved[p + "up"] = {"cat": cat, "u": u}
                 self._ru_fwd_train(upru, au, out)
-        else:
-            sc, sh = ubn.eval_affine()
-            upru = lvl["upru"]
-            conv0, bn0 = upru["units"][0]
-            if (self.fuse_eval_top and lvl["is_top"] and self.dtype in _HALF and bn0 is None
-                    and upru["res"] is None and up.cin == 32 and up.cout == 16 and conv0.cin == conv0.cout == 16
-                    and ops.dectop_ok(cat, out)):
-                # the full-resolution decoder as ONE launch: the 16-channel tensor between the
-                # transposed conv and the conv-only unit never reaches HBM (csrc/dectop.hip)
-                hit = lvl.get("_dectop")
-                if hit is None or hit[0] != self.weights_version:
-                    # (one host read of the slope per weights version: the kernel's PReLU fast path)
-                    a = float(ubn.alpha.reshape(-1)[0])
-                    hit = (self.weights_version, ops.dectop_up_frag(up.w, sc, self.dtype), torch.addcmul(sh, up.b, sc),
-                           0.0 <= a <= 1.0)
-                    lvl["_dectop"] = hit
-                self._timed(conv0.prefix + ":fwd", ops.dectop_fwd, cat, out, hit[1], hit[2], ubn.alpha,
-                            conv0.fwd_pack(), conv0.b, alpha_in_unit_range=hit[3])
-                self.eval_top_fused = True
-                return
-            au = self._buf(f"{p}au.e", oshape)
-            pack, wsrc, bias = up.folded(sc, sh)
-            ops.convT3d_fwd(cat, au, pack, wsrc, bias, prelu_alpha=ubn.alpha)
-            self._ru_fwd_eval(lvl["upru"], au, out)
+            return
+        sc, sh = ubn.eval_affine()
+        if self.fuse_eval_top and lvl["dectop"] and self.dtype in _HALF and ops.dectop_ok(cat, out):
+            # the full-resolution decoder as ONE launch: the 16-channel tensor between the
+            # transposed conv and the conv-only unit never reaches HBM (csrc/dectop.hip)
+            conv0 = upru["units"][0][0]
+            hit = self._dectop_pack
+            if hit is None or hit[0] != self.weights_version:
+                # (one host read of the slope per weights version: the kernel's PReLU fast path)
+                a = float(ubn.alpha.reshape(-1)[0])
+                hit = self._dectop_pack = (self.weights_version, ops.dectop_up_frag(up.w, sc, self.dtype),
+                                           torch.addcmul(sh, up.b, sc), 0.0 <= a <= 1.0)
+            self._timed(conv0.prefix + ":fwd", ops.dectop_fwd, cat, out, hit[1], hit[2], ubn.alpha,
+                        conv0.fwd_pack(), conv0.b, alpha_in_unit_range=hit[3])
+            self.eval_top_fused = True
+            return
+        au = self._buf(f"{p}au.e", oshape)
+        pack, wsrc, bias = up.folded(sc, sh)
+        ops.convT3d_fwd(cat, au, pack, wsrc, bias, prelu_alpha=ubn.alpha)
+        self._ru_fwd_eval(upru, au, out)
 
     def _level_bwd(self, lvl, dout, dx=None, extra=None):
         p = lvl["prefix"]
-        sv = self._saved[p + "up"]
-        cat, u = sv["cat"], sv["u"]
+        cat, u = self._saved_levels[p]
         c = lvl["c"]
         dau = self._buf(f"{p}dau", u.shape)
         rows = self._ru_bwd(lvl["upru"], dout, dx=dau, dx_bn=(lvl["upbn"], u))
@@ -1126,14 +1101,8 @@ class UNetEngine:
         (``ops.WindowBatch`` -> ``segmi_windows``): single input channel, 3-D, the small-Cin pair kernel
         (subunit 0 + residual convolution in one launch) takes the unit, windows in the compute dtype"""
         ru = self.levels["down"]
-        units, rc = ru["units"], ru["res"]
-        if self.net.in_channels != 1 or self.net.dimensions != 3 or dtype != self.dtype:
-            return False
-        if len(units) < 2 or units[0][1] is None or rc is None:
-            return False
-        c0 = units[0][0]
-        return (not c0.mfma and not rc.mfma and c0.k == 3 and rc.k == 3 and c0.stride == rc.stride
-                and c0.cout == rc.cout and c0.cout in (16, 32))
+        return (self.net.in_channels == 1 and self.net.dimensions == 3 and dtype == self.dtype
+                and ru["share"] == "pair" and ru["res"].cout in (16, 32))
 
     def forward(self, x: torch.Tensor, train: Optional[bool] = None,
                 out: Optional[torch.Tensor] = None, lane: int = 0) -> torch.Tensor:
@@ -1176,6 +1145,7 @@ class UNetEngine:
             self._fwd_parity ^= 1
             self._repack_async()
             self._saved.clear()
+            self._saved_levels.clear()
             self._nbt_flat += 1        # every BatchNorm runs exactly once per training forward
             self._drop_step += 1       # fresh dropout masks for this step (shared by its backward)
         self._level_fwd(self.levels, xin, logits, train)
@@ -1231,22 +1201,6 @@ class UNetEngine:
                 self._wgrad(conv, x, dy, need_bias=need_bias, in_tf=in_tf)
         return carried
 
-    # Single-GPU training_step: the weight gradients of the two full-resolution decoder convolutions
-    # (0.73 ms of HBM-bound persistent kernels, 1.6 GB) are carried over the end of the step: beside the
-    # backward's own bandwidth-bound kernels they only stretch it (backward 2.30 ms alone, 3.79 ms with
-    # all weight gradients beside it, 4.13 ms serial: the overlap buys 0.34 ms), beside the NEXT step's
-    # forward -- whose 64^3 .. 8^3 levels are latency-bound and leave the memory system idle -- they are
-    # nearly free.  Their layers are the last ones a forward reaches, so there is ~1 ms of slack: the
-    # weight-gradient stream runs them, then the optimiser on the arena suffix [carry_lo, n) and the
-    # re-pack of the two layers, and records `_tail_ev`; the next forward waits for it in front of the
-    # top transposed convolution.  Same arithmetic in the same order per parameter: bit-identical weights
-    # (tests/test_e2e_gpu.py).  SEGMI_CARRY_TOP_WGRAD=0: everything inside the step, as before.
-    carry_top_wgrad = os.environ.get("SEGMI_CARRY_TOP_WGRAD", "1") != "0"
-    # how many of the upper levels' up paths are carried (1 = the full-resolution decoder only).  Round 4: 2 -- the
-    # weight-gradient stream was still ~0.2 ms behind when the main chain reached the optimiser (the 64^3 decoder's
-    # weight gradients sat in front of the first encoder layers', which the next forward needs first); with the
-    # 64^3 up path carried too the step went 5.02 -> 4.91 ms (alternating runs); 3: 4.99, 4: 5.25.
-    carry_levels = int(os.environ.get("SEGMI_CARRY_LEVELS", "2"))
     _carry_open = False
     _carried: list = []
     _tail_ev = None
@@ -1298,37 +1252,17 @@ class UNetEngine:
     # callable(lo_offset, events): gradients at arena offsets >= lo are final once the main stream's
     # current point and `events` (side-stream weight gradients) have been reached
     grad_hook = None
-    # SEGMI_SERIAL=1 keeps every kernel on one stream (per-kernel profiling without co-running work)
-    overlap_wgrad = os.environ.get("SEGMI_SERIAL", "0") != "1"
     _side = None
-    # CUs the weight-gradient kernels size their grids for while they run on the side stream
-    # (the `cus` argument of segmi_conv3d_wgrad; SEGMI_WGRAD_CUS overrides).  Their workgroups hold a CU exclusively (768 threads
-    # or ~400 registers each): one per CU on all 256 and the main chain's kernels wait for a CU to retire --
-    # "overlap" was then mostly alternation.  Sized for half the chip both streams run: 5.55 -> 5.28 ms per
-    # step (160: 5.40, 96: 5.53, 64: 5.93; `gpurun_out/r3/wcus_ab2.txt`).  Round 2 measured the same knob
-    # neutral; what changed is that the deferred / carried schedule now puts these kernels beside the
-    # latency-bound levels of the main chain, which need CUs, not bandwidth.
-    wgrad_cus_overlap = 128
-
     def _side_stream(self):
         if self._side is None:
             self._side = streams.shared_stream(self.device, streams.WGRAD)
         return self._side
 
-    # BatchNorm-apply + PReLU folded into the consumer conv's staging where the kernels allow it
-    # (segmi_in_affine); SEGMI_FUSE_BN=0 keeps the separate pass for A/B measurements
-    fuse_bn_apply = os.environ.get("SEGMI_FUSE_BN", "1") != "0"
-    # BatchNorm / PReLU backward of the small (<= 32 MB) tensors as one launch with a grid-wide hand-off
-    # instead of reduce -> apply (SEGMI_FUSE_BN_BWD_SMALL=0: two launches)
-    fuse_bn_bwd_small = os.environ.get("SEGMI_FUSE_BN_BWD_SMALL", "1") != "0"
-
     def fused_bn_max_wgs(self) -> int:
         """workgroups the one-launch BatchNorm backward may hold: the CUs the weight-gradient stream's budget
         leaves free (0 = the device's capacity when nothing CU-exclusive runs beside it)"""
         return max(8, 256 - ops.wgrad_cus(self.wgrad_cus_overlap)) if self.overlap_wgrad else 0
-    # BatchNorm-backward reduction in the epilogue of the input-gradient launch that produces its
-    # operand (segmi_bn_bwd_sums); SEGMI_FUSE_BN_BWD=0 keeps the separate two-tensor pass (A/B)
-    fuse_bn_bwd = os.environ.get("SEGMI_FUSE_BN_BWD", "1") != "0"
+
     def _join_side(self):
         """main stream waits for every weight-gradient kernel issued so far"""
         if self._side is not None:

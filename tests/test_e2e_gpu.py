@@ -559,8 +559,7 @@ def test_fused_bn_apply_training_step_is_bit_identical_to_the_separate_pass():
         eng.fuse_bn_apply = fuse
         res = net.training_step({"image": img.to(DEV), "label": lab.to(DEV)})
         torch.cuda.synchronize()
-        fused_layers = sum(1 for sv in eng._saved.values() for k, v in sv.items()
-                           if k.startswith("tf") and v is not None)
+        fused_layers = sum(1 for unit in eng._saved.values() for sub in unit.subs if sub.in_tf is not None)
         results.append((eng._bufs["logits.t"].clone(), float(res["loss"].cpu()), eng.flat_grad.clone(),
                         eng.flat.clone(), fused_layers))
     (la, lossa, ga, wa, na), (lb, lossb, gb, wb, nb) = results
