@@ -14,8 +14,21 @@
 
 namespace segmi {
 
-template <typename T, int CK, int KS, int S, int NT, int TD, int TH, int TW>
-__global__ __launch_bounds__(256) void conv_fwd_ks_kernel(ConvParams p) {
+// Residency (workgroups per CU = waves per SIMD).  LDS: max(halo image, 24 KB * NT of exchange area), so 48 KB
+// at NT = 2 and the halo image (28 - 34 KB) at NT = 1.  Registers: left to itself under __launch_bounds__(256)
+// the allocator spends them freely and lands on 2 waves (1 for the several-chunk forms at NT = 2), so it is
+// held to a wave count.  One chunk: 3 at NT = 2 (acc 64 + weights 56 + staging 28 leave no room for a fourth),
+// 4 at NT = 1.  Several chunks (a second weight set): 2.  The narrow tile at NT = 2 with several chunks spills
+// 29 registers under that budget and is left alone (298 registers, 1 wave; the parent form had 250): no
+// layer of the UNet engine takes it.
+constexpr int conv_ks_waves(bool one, int nt, int tw) {
+  return one ? (nt == 2 ? 3 : 4) : (nt == 2 && tw == 8 ? 1 : 2);
+}
+template <int W> struct KsWave { static constexpr int value = W; };
+
+template <typename T, int CK, int KS, int S, int NT, int TD, int TH, int TW, bool ONE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(conv_ks_waves(ONE, NT, TW))))
+void conv_fwd_ks_kernel(ConvParams p) {
   using G = ConvGeom<T, CK, KS, S, TD, TH, TW>;
   static_assert(G::SPT == 4, "k-split kernel: one k-step per tap");
   static_assert(G::NVT == 8, "k-split kernel: 8 voxel tiles per workgroup");
@@ -75,11 +88,19 @@ __global__ __launch_bounds__(256) void conv_fwd_ks_kernel(ConvParams p) {
       }
     }
   };
+  // the staged halo image -> LDS rows
+  auto commit = [&]() {
+#pragma unroll
+    for (int k = 0; k < NLD; ++k) {
+      const int i = tid + 256 * k;
+      if (i < NCH) *reinterpret_cast<frag_t*>(smem + (i / G::CPR) * G::ROWB + (i % G::CPR) * 16) = stg[k];
+    }
+  };
   // this wave's weight fragments of a chunk (k-steps wave, wave+4, ...): all fetched at once, one
   // chunk ahead, so a cold L2 costs one exposed latency per kernel instead of one per k-step
   const char* wb0 = (const char*)p.wfrag + (int64_t)nt0 * 1024 + lane * 16;
-  frag_t wcur[NSW][NT], wnxt[NSW][NT];
-  auto fetch_w = [&](int c, frag_t (&dst)[NSW][NT]) {
+  frag_t wcur[NSW][NT];
+  auto fetch_w = [&](int c, auto& dst) {
 #pragma unroll
     for (int si = 0; si < NSW; ++si) {
       int s = wave + 4 * si;
@@ -90,58 +111,102 @@ __global__ __launch_bounds__(256) void conv_fwd_ks_kernel(ConvParams p) {
             wb0 + (((int64_t)c * G::NSTEP + s) * p.ntiles_total + j) * 1024);
     }
   };
-  fetch(0);
-  fetch_w(0, wcur);
-  for (int c = 0; c < p.nchunks; ++c) {
-    if (c > 0) __syncthreads();
+  // k-step si of this wave on the halo image
+  auto kstep = [&](int si) {
+    const int s = wave + 4 * si;
+    if (s < G::NSTEP) {
 #pragma unroll
-    for (int k = 0; k < NLD; ++k) {
-      const int i = tid + 256 * k;
-      if (i < NCH) *reinterpret_cast<frag_t*>(smem + (i / G::CPR) * G::ROWB + (i % G::CPR) * 16) = stg[k];
-    }
-    __syncthreads();
-    if (c + 1 < p.nchunks) {
-      fetch(c + 1);
-      fetch_w(c + 1, wnxt);
-    }
+      for (int i = 0; i < 8; ++i) {
+        const frag_t a = *reinterpret_cast<const frag_t*>(smem + vaddr[i] + tapoff[si]);
 #pragma unroll
-    for (int si = 0; si < NSW; ++si) {
-      const int s = wave + 4 * si;
-      if (s < G::NSTEP) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const frag_t a = *reinterpret_cast<const frag_t*>(smem + vaddr[i] + tapoff[si]);
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = mma16<T>(wcur[si][j], a, acc[i][j]);
-        }
+        for (int j = 0; j < NT; ++j) acc[i][j] = mma16<T>(wcur[si][j], a, acc[i][j]);
       }
     }
+  };
+  fetch(0);
+  fetch_w(0, wcur);
+  if constexpr (ONE) {
+    // one channel chunk: no next-chunk registers, no chunk loop
+    commit();
+    __syncthreads();
 #pragma unroll
-    for (int si = 0; si < NSW; ++si)
+    for (int si = 0; si < NSW; ++si) kstep(si);
+    __syncthreads();   // the exchange below overwrites the halo image
+  } else {
+    // one halo image, two barriers per chunk, the next chunk's halo and weights fetched behind the
+    // second one.  (Two halo images with one barrier per chunk and the loads issued a chunk earlier
+    // were built and measured: not faster on any layer, see DESIGN.md.)
+    frag_t wnxt[NSW][NT];
+    for (int c = 0; c < p.nchunks; ++c) {
+      if (c > 0) __syncthreads();
+      commit();
+      __syncthreads();
+      if (c + 1 < p.nchunks) {
+        fetch(c + 1);
+        fetch_w(c + 1, wnxt);
+      }
 #pragma unroll
-      for (int j = 0; j < NT; ++j) wcur[si][j] = wnxt[si][j];
+      for (int si = 0; si < NSW; ++si) kstep(si);
+#pragma unroll
+      for (int si = 0; si < NSW; ++si)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) wcur[si][j] = wnxt[si][j];
+    }
+    __syncthreads();   // the exchange below overwrites the halo image
   }
 
-  // ---- fixed-order sum of the 4 waves' partial accumulators: red[wave][tile][NT][lane]
-  __syncthreads();
+  // ---- fixed-order sum of the 4 waves' partial accumulators.  Wave w finishes voxel tiles 2w, 2w+1:
+  // it keeps its own partial sums of those in registers and passes the other six tiles through LDS,
+  // red[owner][k][tile of the owner][NT][lane] with k the writer's rank among the owner's 3 foreign
+  // waves.  The area starts at smem: the halo image is dead behind the barrier above.  `wave` is
+  // uniform, so each phase branches once to the copy written for that wave: every register index
+  // and LDS slot is a constant (a select over the 8 tiles costs 16 more live registers).
   f32x4* red = reinterpret_cast<f32x4*>(smem);
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) red[((wave * 8 + i) * NT + j) * 64 + lane] = acc[i][j];
-  __syncthreads();
   f32x4 fin[2][NT];
+  auto put = [&](auto wc) {
+    constexpr int w = decltype(wc)::value;
 #pragma unroll
-  for (int ii = 0; ii < 2; ++ii)
+    for (int d = 0; d < 4; ++d) {
+      if (d == w) continue;
+      const int k = w < d ? w : w - 1;
 #pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int i = wave * 2 + ii;
-      f32x4 v = red[((0 * 8 + i) * NT + j) * 64 + lane];
-      v += red[((1 * 8 + i) * NT + j) * 64 + lane];
-      v += red[((2 * 8 + i) * NT + j) * 64 + lane];
-      v += red[((3 * 8 + i) * NT + j) * 64 + lane];
-      fin[ii][j] = v;
+      for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) red[(((d * 3 + k) * 2 + ii) * NT + j) * 64 + lane] = acc[2 * d + ii][j];
     }
+  };
+  auto get = [&](auto wc) {
+    constexpr int w = decltype(wc)::value;
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        // wave order 0 + 1 + 2 + 3, the own partial at position w
+        f32x4 part[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+          part[s] = s == w ? acc[2 * w + ii][j]
+                           : red[(((w * 3 + (s < w ? s : s - 1)) * 2 + ii) * NT + j) * 64 + lane];
+        f32x4 v = part[0];
+        v += part[1];
+        v += part[2];
+        v += part[3];
+        fin[ii][j] = v;
+      }
+  };
+  switch (wave) {
+    case 0: put(KsWave<0>{}); break;
+    case 1: put(KsWave<1>{}); break;
+    case 2: put(KsWave<2>{}); break;
+    default: put(KsWave<3>{});
+  }
+  __syncthreads();
+  switch (wave) {
+    case 0: get(KsWave<0>{}); break;
+    case 1: get(KsWave<1>{}); break;
+    case 2: get(KsWave<2>{}); break;
+    default: get(KsWave<3>{});
+  }
 
   // ---- epilogue (as conv_fwd_impl.h): wave w owns voxel tiles 2w, 2w+1
   f32x4 bias4[NT];
@@ -232,19 +297,26 @@ __global__ __launch_bounds__(256) void conv_fwd_ks_kernel(ConvParams p) {
   }
 }
 
-template <typename T, int CK, int KS, int S, int NT, int TD, int TH, int TW>
-static int launch_conv_ks_cfg(ConvParams p, const ConvPlan& pl, hipStream_t st) {
+template <typename T, int CK, int KS, int S, int NT, int TD, int TH, int TW, bool ONE>
+static int launch_conv_ks_one(ConvParams p, const ConvPlan& pl, hipStream_t st) {
   using G = ConvGeom<T, CK, KS, S, TD, TH, TW>;
   p.tz = pl.tz; p.ty = pl.ty; p.tx = pl.tx;
   SEGMI_CHECK_ARG(TD == pl.td && TH == pl.th && TW == pl.tw && pl.grid_x > 0 && (int64_t)p.N * p.tz * p.ty * p.tx == pl.grid_x,
                   "conv3d: too many tiles, or the k-split kernel's grid is not the planned one");
   dim3 grid((unsigned)pl.grid_x, (unsigned)(p.Cout / (16 * NT)));
-  constexpr int red = 4 * 8 * NT * 64 * 16;
+  constexpr int red = 4 * 3 * 2 * NT * 64 * 16;                 // 6 foreign tiles per wave
   constexpr int lds0 = G::LDS_BYTES > red ? G::LDS_BYTES : red;
   p.fin_on = p.fin_on && p.stats;
   const size_t lds = fin_tail_arm(p, grid, 256, 2 * p.Cout, lds0);
-  return launch_wg256<conv_fwd_ks_kernel<T, CK, KS, S, NT, TD, TH, TW>>(grid, lds, lds > 64 * 1024, st,
-                                                                       "conv3d_fwd(mfma, k-split)", p);
+  return launch_wg256<conv_fwd_ks_kernel<T, CK, KS, S, NT, TD, TH, TW, ONE>>(grid, lds, lds > 64 * 1024, st,
+                                                                            "conv3d_fwd(mfma, k-split)", p);
+}
+
+// a layer of one channel chunk takes the form without next-chunk registers and chunk loop
+template <typename T, int CK, int KS, int S, int NT, int TD, int TH, int TW>
+static int launch_conv_ks_cfg(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
+  return p.nchunks == 1 ? launch_conv_ks_one<T, CK, KS, S, NT, TD, TH, TW, true>(p, pl, st)
+                        : launch_conv_ks_one<T, CK, KS, S, NT, TD, TH, TW, false>(p, pl, st);
 }
 
 // the k-split kernel's instantiation of a plan: output tiles per workgroup x tile width (conv_ks_tile_shape)
