@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 
 from segmantic_amd import ops  # noqa: E402
 from tests.helpers import lowp_bounds as lb  # noqa: E402
+from tests.helpers.reduce_cases import drop_mask as _drop_mask  # noqa: E402
 
 DEV = "cuda:0"
 F32_RTOL = 2e-5      # f32 path: relative to max |ref|
@@ -719,19 +720,6 @@ def test_bn_prelu_fwd_bwd(dtype, c):
     assert relerr(from_ndhwc(dxd), xq.grad) < (1e-4 if dtype == torch.float32 else 1.5e-2)
     bn_bwd_bound(dtype, from_ndhwc(dxd), q(dy, dtype), q(x, dtype), mean.cpu(), invstd.cpu(), gamma, beta, float(alpha),
                  coef.cpu())
-
-
-def _drop_mask(numel, p, seed):
-    """numpy restatement of norm_act.hip drop_mult (keep -> 1/(1-p), drop -> 0) over element indices."""
-    e = np.arange(numel, dtype=np.uint64)
-    h = ((e & 0xFFFFFFFF) * 0x9E3779B1) & 0xFFFFFFFF
-    h ^= np.uint64(seed)
-    h ^= ((e >> np.uint64(32)) * 0x85EBCA77) & 0xFFFFFFFF
-    h ^= h >> np.uint64(16); h = (h * 0x7FEB352D) & 0xFFFFFFFF
-    h ^= h >> np.uint64(15); h = (h * 0x846CA68B) & 0xFFFFFFFF
-    h ^= h >> np.uint64(16)
-    keep = (h >> np.uint64(8)) >= np.uint64(int(np.float32(p) * np.float32(16777216.0)))
-    return keep.astype(np.float32) / (1.0 - p)
 
 
 @pytest.mark.parametrize("c", [3, 16, 64])
